@@ -11,7 +11,12 @@ evaluation itself needs no collective).
 itself (fresh children, before anything touches the GPU), one per GPU, backend "nccl" (= RCCL);
 under `python -m torch.distributed.run --nproc-per-node N bench.py --gpus N` it is one of the ranks.
 
-Prints ONE JSON line on rank 0 (contract in the task statement) with, besides the contract keys:
+A plain run sets up, warms up, times exactly --steps steps and prints ONE JSON line on rank 0 with the contract keys
+(metric, value, unit, higher_is_better, dtype, ms_per_step, ...) and the workload's config.  `--dump-outputs DIR`
+writes what the last timed step computed -- logL, gradient and status of every chain of the ladder, in chain order --
+as DIR/<name>.npy (float64).  The inputs come from fixed seeds (synth.py: chain parameters, and the spectrum as seeded
+chi^2 noise on the library's model of the true parameters), so runs with the same arguments see the same inputs and
+two builds can be compared output for output.  `--full` adds, after the timed steps:
   roofline        -- dominant kernel (tamcmc_eval_kernel<grad>): algorithmic bytes (16 B x Nx x chains per launch)
                      over its mean duration from HIP events on the launch stream, against 8 TB/s; `bound` names the
                      roof that actually binds (fp64 VALU issue) and `valu` the fraction of it in use, with the core
@@ -54,13 +59,17 @@ def parse_args(argv=None):
     ap.add_argument("--warmup", type=int, default=500)
     ap.add_argument("--chains", type=int, default=64, help="chains per GPU")
     ap.add_argument("--nx", type=int, default=100000)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true", help="also the secondary figures (roofline, logL_only, host_path, ensemble, "
+                    "sampler legs, cpu_baseline); a plain run times the headline step only")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write the last step's logL / grad / status "
+                    "of every chain as DIR/<name>.npy (float64)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--cpu-seconds", type=float, default=12.0)
-    ap.add_argument("--no-sampler", action="store_true", help="skip the end-to-end sampler legs")
+    ap.add_argument("--no-sampler", action="store_true", help="with --full: skip the end-to-end sampler legs")
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend for N>1 (nccl = RCCL; gloo only to rehearse on one GPU)")
     ap.add_argument("--force-dist", action="store_true", help="rehearsal: initialise torch.distributed even for one rank (checks the RCCL path on a one-GPU box)")
     ap.add_argument("--single-device", action="store_true", help="rehearsal: every rank uses cuda:0 (with --backend gloo)")
-    ap.add_argument("--no-ensemble", action="store_true", help="skip the C5 ensemble leg")
+    ap.add_argument("--no-ensemble", action="store_true", help="with --full: skip the C5 ensemble leg")
     ap.add_argument("--ensemble-stars", type=int, default=32, help="stars of the ensemble leg (BASELINE C5: 32), spread over the ranks")
     ap.add_argument("--strict-exit", action="store_true", help="exit with code 3 (after printing the line) when the sharded sampler leg hit its deadline; "
                     "by default the line carries the error and the exit code stays 0, so that a stuck exchange cannot cost the measurement")
@@ -103,6 +112,8 @@ def main():
     args = parse_args()
     if args.gpus < 1:
         sys.exit("bench.py: --gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        sys.exit("bench.py: --steps must be >= 1 and --warmup >= 0")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(spawn_ranks(args, sys.argv[1:]))
     run_rank(args)
@@ -194,18 +205,46 @@ def run_rank(args):
         ghz, sec = acc.clock_probe_end()
         return ghz
 
-    # HIP events around every 4th eval launch of the timed region (an event pair costs ~3 us of stream time: around every
-    # launch it took 5 % off `value`)
+    # --full: HIP events around every 4th eval launch of the timed region, for `roofline` (an event pair costs ~3 us of
+    # stream time: around every launch it took 5 % off `value`); a plain run times the steps alone
     ev_stride = 4 if args.steps >= 8 else 1
     prewarm(True)
     for _ in range(args.warmup):
         step(True)
-    acc.profile(ev_stride)
+    if args.full:
+        acc.profile(ev_stride)
     dt = timed(args.steps, True)
-    k_ms, k_n = acc.kernel_time()
-    acc.profile(False)
+    if args.full:
+        k_ms, k_n = acc.kernel_time()
+        acc.profile(False)
     assert int(d_status.abs().sum().item()) == 0, "a chain reported a non-zero status"
     assert bool(torch.isfinite(d_logL).all()) and bool(torch.isfinite(d_grad).all())
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"logL": d_logL, "grad": d_grad, "status": d_status}, dist, rank, world, comm_dev)
+
+    value = total_chains * args.steps / dt
+    geo = acc.geometry()
+
+    def headline():
+        return {
+            "metric": METRIC, "value": round(value, 1), "unit": "chain-steps/s (model+logL+grad)", "n_gpus": world,
+            "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(dt / args.steps * 1e3, 4),
+            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f64", "data": "synthetic",
+            "config": {"workload": "C2: model_MS_Global_a1etaa3_HarveyLike (id 2), 21 modes l=0..2, 56 params, "
+                                   f"{args.nx} bins, {nchains} chains per GPU, trunc_c=20, logL + gradient over "
+                                   f"{nvars} variables, params resident in HBM",
+                       "chains_total": total_chains, "geometry_logL": geo,
+                       "prewarm_ms": PREWARM_MS},
+        }
+
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(headline()), flush=True)
+        acc.close()
+        if dist is not None:
+            dist.destroy_process_group()
+        return
+
     ghz_g = clock_under_load(max(args.steps, 100), True)
 
     # secondary: likelihood only (what the reference's sampler actually evaluates per step)
@@ -218,9 +257,7 @@ def run_rank(args):
     acc.profile(False)
     ghz_l = clock_under_load(max(args.steps, 100), False)
 
-    value = total_chains * args.steps / dt
     value_l = total_chains * args.steps / dt_l
-    geo = acc.geometry()
     bytes_per_launch = 16.0 * args.nx * nchains               # B_alg = 16 Nx per chain-step
     k_avg_s = (k_ms / max(k_n, 1)) * 1e-3
     kl_avg_s = (kl_ms / max(kl_n, 1)) * 1e-3
@@ -341,20 +378,13 @@ def run_rank(args):
     cpu = None
     out = None
     if rank == 0:
-        out = {
-            "metric": METRIC, "value": round(value, 1), "unit": "chain-steps/s (model+logL+grad)", "n_gpus": world,
-            "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(dt / args.steps * 1e3, 4),
-            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f64", "data": "synthetic",
-            "config": {"workload": "C2: model_MS_Global_a1etaa3_HarveyLike (id 2), 21 modes l=0..2, 56 params, "
-                                   f"{args.nx} bins, {nchains} chains per GPU, trunc_c=20, logL + gradient over "
-                                   f"{nvars} variables, params resident in HBM",
-                       "chains_total": total_chains, "geometry_logL": geo,
-                       "prewarm_ms": PREWARM_MS},
+        out = headline()
+        out.update({
             "logL_only": {"value": round(value_l, 1), "unit": "chain-steps/s (model+logL)",
                           "ms_per_step": round(dt_l / args.steps * 1e3, 4)},
             "host_path": host_path, "ensemble": ensemble, "sampler": sampler_rate, "sampler_sharded": None, "roofline": roofline,
             "cpu_baseline": cpu,
-        }
+        })
 
     # ---- sharded sampler: 64 N chains over the N ranks, PT every iteration, boundary pairs between neighbours.
     # Guarded by a deadline: a stuck exchange must not cost the line above (rank 0 prints it and every rank leaves).
@@ -406,6 +436,37 @@ def run_rank(args):
     acc.close()
     if dist is not None:
         dist.destroy_process_group()
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(dirname, arrays, dist, rank, world, comm_dev):
+    """--dump-outputs: every rank's rows of each array gathered in rank order (= the chain order of the ladder) and
+    written by rank 0 as DIR/<name>.npy in float64.  Past DUMP_LIMIT_BYTES in all, a fixed seeded sample of the chains
+    is kept, and their indices go to DIR/chain_index.npy."""
+    import numpy as np
+    import torch
+    host = {}
+    for name, t in arrays.items():
+        if dist is not None:
+            src = t.to(comm_dev) if comm_dev is not None else t.cpu()
+            parts = [torch.empty_like(src) for _ in range(world)]
+            dist.all_gather(parts, src)
+            t = torch.cat(parts)
+        host[name] = t.cpu().numpy().astype(np.float64)
+    if rank != 0:
+        return
+    n = next(iter(host.values())).shape[0]
+    row_bytes = sum(a.nbytes for a in host.values()) // n
+    if n * row_bytes > DUMP_LIMIT_BYTES:
+        rows = (DUMP_LIMIT_BYTES - 4096) // (row_bytes + 8)          # 4 KiB for the .npy headers
+        keep = np.sort(np.random.default_rng(0).choice(n, rows, replace=False))
+        host = {name: a[keep] for name, a in host.items()}
+        host["chain_index"] = keep.astype(np.float64)
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in host.items():
+        np.save(os.path.join(dirname, name + ".npy"), a)
 
 
 def ensemble_leg(args, w, m_true, dist, rank, world, local, dev, comm_dev, stream):

@@ -119,3 +119,13 @@ def test_bench_refuses_a_rank_count_that_does_not_match():
     assert r.returncode != 0 and "WORLD_SIZE=3" in r.stderr and r.stdout.strip() == ""
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "0"], capture_output=True, text=True, timeout=300)
     assert r.returncode != 0
+
+
+def test_bench_refuses_a_run_without_timed_steps():
+    """ms_per_step is the timed time over --steps: zero steps (or negative warm-up) is refused before any GPU work."""
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    for bad in (["--steps", "0"], ["--warmup", "-1"]):
+        r = subprocess.run([sys.executable, os.path.join(root, "bench.py")] + bad, capture_output=True, text=True, timeout=300)
+        assert r.returncode != 0 and "--steps must be >= 1" in r.stderr and r.stdout.strip() == "", bad
