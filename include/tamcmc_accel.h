@@ -32,9 +32,9 @@
  *   TAMCMC_FUSED=0                    one-tile grids: prologue and evaluation as two launches instead of one
  *   TAMCMC_BG_EXACT=1                 Harvey background by exp() per bin instead of the per-cell polynomial
  *   TAMCMC_TAIL="frac,su2" | 0        gradient launch on long grids: 8-unit tiles for frac % of the units, su2-unit tiles for the
- *                                     rest (default "85,4"; 0: all tiles alike); TAMCMC_TAIL_L the same for the likelihood launch (default off)
+ *                                     rest (default "85,4"; 0: all tiles alike)
  *   TAMCMC_GATE_PATIENCE=n            polls (~2 us each) before the gate of an armed batch gives up (default 2^21: ~4 s; tests)
- * (tamcmc_sampler.h: TAMCMC_SAMPLER_THREADS, TAMCMC_SAMPLER_TIMING, TAMCMC_SAMPLER_PIPELINE, TAMCMC_SAMPLER_ARM, TAMCMC_SAMPLER_ARRIVE.)
+ * (tamcmc_sampler.h: TAMCMC_SAMPLER_THREADS, TAMCMC_SAMPLER_TIMING, TAMCMC_SAMPLER_ARM, TAMCMC_SAMPLER_ARRIVE.)
  *
  * Threading: one ctx = one device + one stream; calls on one ctx must be serialised by the caller;
  * different ctx objects (other GPUs, other stars) may be driven concurrently from different threads.
@@ -136,7 +136,6 @@ int tamcmc_eval_batch_device(tamcmc_ctx *ctx, int32_t Nchains, int32_t Nparams,
 int tamcmc_eval_batch_begin(tamcmc_ctx *ctx, int32_t Nchains, int32_t Nparams, const double *params, const double *Tcoefs);
 int tamcmc_eval_batch_end(tamcmc_ctx *ctx, int32_t Nchains, double *logL, int32_t *status);
 
-#define TAMCMC_MAX_PARTS 4
 /* Armed batch -- for a host loop whose next parameters depend on the results of the batch in flight (a sampler):
  * _arm puts the launches of the NEXT likelihood-only batch into the stream behind a one-wave gate kernel, while the
  * current batch is still being evaluated (allowed between _begin / _fire and _end of a batch of the same size; the
@@ -158,19 +157,9 @@ int tamcmc_eval_batch_poll(const tamcmc_ctx *ctx, int32_t chain, double *logL, i
 int tamcmc_eval_batch_fire(tamcmc_ctx *ctx, int32_t Nchains, int32_t Nparams, const double *params, const double *Tcoefs);
 int tamcmc_eval_batch_disarm(tamcmc_ctx *ctx);
 
-/* The same in up to TAMCMC_MAX_PARTS PARTS that may be in flight together (part = 0 .. 3; every part but 0 runs on a stream
- * of its own): chains
- * [first, first + Nchains) of the context's numbering -- the ranges of parts in flight must not overlap; with several
- * spectra resident `first` also indexes the chain -> spectrum map.  For a sampler that splits its chains in parts
- * and handles one part's results on the host while the GPU evaluates the others (chains are independent inside an
- * iteration, MALA.cpp:632-655).  params / Tcoefs point at the part's first row / entry.  A chain's result is bit for
- * bit that of tamcmc_eval_batch (tests/test_parity_gpu.py).  tamcmc_ctx_reserve sizes the context's buffers for Nchains
- * chains in total beforehand: they are never reallocated under a part in flight (a begin that would need to returns
- * TAMCMC_E_INVALID).  No whole-batch call may be made while a part is in flight. */
+/* Sizes the context's buffers for batches of up to Nchains chains ahead of _arm, which never reallocates under a batch in
+ * flight (refused while a batch is in flight or armed). */
 int tamcmc_ctx_reserve(tamcmc_ctx *ctx, int32_t Nchains);
-int tamcmc_eval_batch_begin_part(tamcmc_ctx *ctx, int32_t part, int32_t first, int32_t Nchains, int32_t Nparams,
-                                 const double *params, const double *Tcoefs);
-int tamcmc_eval_batch_end_part(tamcmc_ctx *ctx, int32_t part, double *logL, int32_t *status);
 
 /* Replaces: Model_def::call_model_explicit (model_def.cpp:199-208) as used by tools/getmodel.cpp:111.
  * One params row -> model spectrum (Nx doubles, host).  *status gets the TAMCMC_CHAIN_* code. */

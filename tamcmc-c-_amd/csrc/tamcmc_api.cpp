@@ -81,14 +81,6 @@ struct tamcmc_ctx {
     uint32_t *h_gate = nullptr, *dv_gate = nullptr;   // pinned word the gate kernel watches
     uint32_t gate_seq = 0;         // value that opens the gate of the armed batch
     int gate_patience = 1 << 21;   // polls (~2 us each) before the gate gives up; TAMCMC_GATE_PATIENCE (tests)
-    // tamcmc_eval_batch_begin_part / _end_part: two sub-batches of the context's chains in flight at once, part 1 on a
-    // stream of its own; a part's rows of every per-chain buffer start at its first chain
-    hipStream_t part_streams[TAMCMC_MAX_PARTS] = {};      // [0] unused (part 0 runs on the context stream), created on demand
-    int part_first[TAMCMC_MAX_PARTS] = {}, part_n[TAMCMC_MAX_PARTS] = {};
-    bool part_ev_recorded[TAMCMC_MAX_PARTS] = {};
-    hipEvent_t part_ev[TAMCMC_MAX_PARTS] = {};
-    // (an armed batch counts: nothing but _fire / _disarm / _end may touch the context while launches wait behind a gate)
-    bool parts_busy() const { if (armed) return true; for (int n : part_n) if (n) return true; return false; }
     // variables
     int Nvars = 0;
     int32_t *d_relax = nullptr;
@@ -204,7 +196,6 @@ static int ensure_capacity(tamcmc_ctx *c, int Nchains, bool grad)
     const int cap = Nchains > c->cap ? Nchains : c->cap;
     const bool g = grad || c->cap_grad;
     TM_HIP(hipStreamSynchronize(c->stream));
-    for (hipStream_t ps : c->part_streams) if (ps) TM_HIP(hipStreamSynchronize(ps));
     free_batch(c);
     const size_t n = (size_t)cap;
     const size_t nm = (size_t)(c->L.n_mult > 0 ? c->L.n_mult : 1);
@@ -335,21 +326,6 @@ extern "C" int tamcmc_ctx_create(tamcmc_ctx **out, int device_id, int model_case
                 }
             }
         }
-        // the same for the likelihood launch (experiment: TAMCMC_TAIL_L="frac,su2"; off by default)
-        c->cost_l.t1 = 0;
-        {
-            const char *e = getenv("TAMCMC_TAIL_L");
-            int frac = 0, su2 = 0;
-            if (e && sscanf(e, "%d,%d", &frac, &su2) == 2 && frac >= 1 && frac <= 99 && su2 >= 1 && su2 <= TM_TILE_MAXU &&
-                c->units >= 70 && !c->equal_cost && !getenv("TAMCMC_TILES")) {
-                const int t1 = (int)(((long long)c->units * frac / 100 + TM_TILE_MAXU / 2) / TM_TILE_MAXU);
-                const int rest = c->units - t1 * TM_TILE_MAXU;
-                if (t1 >= 1 && rest > 0) {
-                    c->cost_l.t1 = t1; c->cost_l.su1 = TM_TILE_MAXU; c->cost_l.su2 = su2;
-                    c->tiles_l = t1 + (rest + su2 - 1) / su2;
-                }
-            }
-        }
         // the balancer's guarantee is TM_TILE_MAXU units per tile; equal-length likelihood tiles may be longer
         c->cost_l.pad = (c->equal_cost && (long long)c->tiles_l * TM_TILE_MAXU > c->units) ? TM_TILE_MAXU : TM_TILE_MAXU_L;
     }
@@ -393,8 +369,6 @@ extern "C" int tamcmc_ctx_destroy(tamcmc_ctx *c)
     if (c->probe_stream) { (void)hipStreamSynchronize(c->probe_stream); (void)hipStreamDestroy(c->probe_stream); }
     (void)hipHostFree(c->h_probe);
     if (c->ev_done) (void)hipEventDestroy(c->ev_done);
-    for (hipStream_t ps : c->part_streams) if (ps) { (void)hipStreamSynchronize(ps); (void)hipStreamDestroy(ps); }
-    for (hipEvent_t e : c->part_ev) if (e) (void)hipEventDestroy(e);
     for (hipEvent_t e : c->ev) (void)hipEventDestroy(e);
     if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
     delete c;
@@ -577,43 +551,33 @@ static int pick_tiles(const tamcmc_ctx *c, int /*Nchains*/, bool grad)
     return grad ? c->tiles_g : c->tiles_l;
 }
 
-// Enqueue setup -> eval (-> backward) for device-resident inputs.
-// base / stream: the sub-batch starts at chain `base` of the context's per-chain buffers (0 for a whole batch) and runs
-// on `stream` (the context stream for a whole batch).
+// Enqueue setup -> eval (-> backward) for device-resident inputs on the context stream.
 static int enqueue(tamcmc_ctx *c, int Nchains, const double *d_params, const double *d_T, double *d_logL,
-                   double *d_grad, int32_t *d_status, const int32_t *d_rows, double *d_model, int base = 0, hipStream_t stream = nullptr)
+                   double *d_grad, int32_t *d_status, const int32_t *d_rows, double *d_model)
 {
     const bool grad = d_grad != nullptr;
-    if (stream == nullptr) stream = c->stream;
+    const hipStream_t stream = c->stream;
     // several spectra resident: every chain of the batch must have been told which one it is fitted to (a batch longer
     // than the map used to fall back to spectrum 0 for all chains -- silently the wrong data)
-    if (c->nspec > 1 && (c->d_spec == nullptr || base + Nchains > c->spec_n)) return TAMCMC_E_INVALID;
+    if (c->nspec > 1 && (c->d_spec == nullptr || Nchains > c->spec_n)) return TAMCMC_E_INVALID;
     const int units = c->units, cells = c->cells;
     const int tiles = pick_tiles(c, Nchains, grad);
     if (!grad) c->last_tiles = tiles;
-    const size_t b = (size_t)base, nmx = (size_t)(c->L.n_mult > 0 ? c->L.n_mult : 1);
-    TmMult *const p_mult = c->d_mult + b * nmx;
-    TmNoise *const p_noise = c->d_noise + b;
-    TmCellRec *const p_cell = c->d_cell + b * cells;
-    TmTileHdr *const p_thdr = c->d_thdr + b * tiles;
-    TmActive *const p_tidx = c->d_tidx + b * tiles * nmx;
-    double *const p_wt = c->d_wt + b * 2, *const p_part = c->d_part + b * tiles * 4;
-    int32_t *const p_order = c->d_order + b * tiles, *const p_ticket = c->d_ticket + b;
-    double *const p_gmult = grad ? c->d_gmult + b * tiles * nmx * TM_GSLOTS : nullptr;
-    double *const p_gnoise = grad ? c->d_gnoise + b * tiles * 2 * TM_NSLOTS : nullptr;
-    double *const p_hser = grad ? c->d_hser + b * cells * TM_MAXH * TM_HSER : nullptr;
-    void *const p_chain_rec = grad ? (void *)((char *)c->d_chain_rec + b * tm_sizeof_chain_rec()) : nullptr;
-    void *const p_aux = grad ? (void *)((char *)c->d_aux + b * nmx * tm_sizeof_aux()) : nullptr;
+    double *const p_gmult = grad ? c->d_gmult : nullptr;
+    double *const p_gnoise = grad ? c->d_gnoise : nullptr;
+    double *const p_hser = grad ? c->d_hser : nullptr;
+    void *const p_chain_rec = grad ? c->d_chain_rec : nullptr;
+    void *const p_aux = grad ? c->d_aux : nullptr;
     TmEvalArgs a{};
     a.x2 = c->d_x2; a.y = c->d_y; a.lx = c->d_lx; a.isig2 = c->d_isig2;
-    a.spec = (c->nspec > 1) ? c->d_spec + b : nullptr;
-    a.mult = p_mult; a.noise = p_noise; a.cell = p_cell; a.thdr = p_thdr; a.tidx = p_tidx; a.wt = p_wt;
-    a.part = p_part; a.gmult = p_gmult; a.gnoise = p_gnoise;
+    a.spec = (c->nspec > 1) ? c->d_spec : nullptr;
+    a.mult = c->d_mult; a.noise = c->d_noise; a.cell = c->d_cell; a.thdr = c->d_thdr; a.tidx = c->d_tidx; a.wt = c->d_wt;
+    a.part = c->d_part; a.gmult = p_gmult; a.gnoise = p_gnoise;
     a.row_of_chain = d_rows; a.model_out = d_model;
-    a.ticket = grad ? nullptr : p_ticket; a.logL = d_logL; a.status = d_status;
+    a.ticket = grad ? nullptr : c->d_ticket; a.logL = d_logL; a.status = d_status;
     a.Nx = c->L.Nx; a.n_mult = c->L.n_mult; a.tiles = tiles; a.cells = cells; a.likelihood_case = c->L.likelihood_case;
     a.like_p = c->L.like_p;
-    a.order = p_order; a.order_mode = (tiles <= 65535) ? c->order_mode : 0; a.prio = c->prio;
+    a.order = c->d_order; a.order_mode = (tiles <= 65535) ? c->order_mode : 0; a.prio = c->prio;
     a.generic = (c->L.likelihood_case != 0 || c->L.family == TM_FAM_GAUSS || d_rows != nullptr) ? 1 : 0;
     if (tiles == 1 && a.order_mode == 2) a.order_mode = 1;     // nothing to rank
     a.tile_magic = ((1ULL << 40) + (unsigned long long)tiles - 1) / (unsigned long long)tiles;
@@ -621,9 +585,9 @@ static int enqueue(tamcmc_ctx *c, int Nchains, const double *d_params, const dou
     const bool fused = (tiles == 1) && c->fuse != 0 && units <= TM_TILE_MAXU;   // (TAMCMC_TILES=1 on a 9..16-unit grid: two launches)
     int rc = 0;
     if (!fused) {
-        rc = tm_launch_setup(c->L, Nchains, d_params, d_T, p_wt, c->d_lx, units, cells, tiles, c->equal_cost, grad ? c->cost_g : c->cost_l,
-                             p_mult, p_noise, p_cell, p_thdr, p_tidx, p_chain_rec, p_aux,
-                             p_hser, a.order_mode == 2 ? p_order : nullptr, stream);
+        rc = tm_launch_setup(c->L, Nchains, d_params, d_T, c->d_wt, c->d_lx, units, cells, tiles, c->equal_cost, grad ? c->cost_g : c->cost_l,
+                             c->d_mult, c->d_noise, c->d_cell, c->d_thdr, c->d_tidx, p_chain_rec, p_aux,
+                             p_hser, a.order_mode == 2 ? c->d_order : nullptr, stream);
         if (rc != 0) { snprintf(g_hip_err, sizeof(g_hip_err), "setup launch -> %s", hipGetErrorString((hipError_t)rc)); return TAMCMC_E_HIP; }
     }
     const bool timed = c->profile && (c->profile_count++ % c->profile_stride == 0);
@@ -646,7 +610,7 @@ static int enqueue(tamcmc_ctx *c, int Nchains, const double *d_params, const dou
     }
     if (rc != 0) {
         snprintf(g_hip_err, sizeof(g_hip_err), "eval launch -> %s", hipGetErrorString((hipError_t)rc));
-        (void)hipMemsetAsync(p_ticket, 0, (size_t)Nchains * sizeof(int32_t), stream);   // arrival counters back to zero
+        (void)hipMemsetAsync(c->d_ticket, 0, (size_t)Nchains * sizeof(int32_t), stream);   // arrival counters back to zero
         return TAMCMC_E_HIP;
     }
     if (timed) {
@@ -656,8 +620,8 @@ static int enqueue(tamcmc_ctx *c, int Nchains, const double *d_params, const dou
     if (!grad) {
         // finalize happens inside the eval launch (last-arriving workgroup per chain)
     } else {
-        rc = tm_launch_backward(c->L, Nchains, units, cells, tiles, tm_setup_balances(units, tiles, c->equal_cost, (grad ? c->cost_g : c->cost_l).pad), c->cost_g, d_params, p_wt, p_chain_rec, p_aux, p_noise, p_part,
-                                p_gmult, p_gnoise, p_cell, p_thdr, p_hser, c->Nvars, c->d_relax, d_grad, d_logL, d_status,
+        rc = tm_launch_backward(c->L, Nchains, units, cells, tiles, tm_setup_balances(units, tiles, c->equal_cost, (grad ? c->cost_g : c->cost_l).pad), c->cost_g, d_params, c->d_wt, p_chain_rec, p_aux, c->d_noise, c->d_part,
+                                p_gmult, p_gnoise, c->d_cell, c->d_thdr, p_hser, c->Nvars, c->d_relax, d_grad, d_logL, d_status,
                                 stream);
         if (rc != 0) { snprintf(g_hip_err, sizeof(g_hip_err), "backward launch -> %s", hipGetErrorString((hipError_t)rc)); return TAMCMC_E_HIP; }
     }
@@ -676,7 +640,7 @@ extern "C" int tamcmc_eval_batch_device(tamcmc_ctx *c, int32_t Nchains, int32_t 
 {
     if (c && c->armed) return TAMCMC_E_INVALID;     // launches wait behind a gate: only _fire / _end / _disarm / destroy (tamcmc_accel.h)
     if (!c || Nchains < 1 || !d_params || !d_Tcoefs || !d_logL) return TAMCMC_E_INVALID;
-    if (Nparams != c->L.Nparams || c->parts_busy()) return TAMCMC_E_INVALID;
+    if (Nparams != c->L.Nparams) return TAMCMC_E_INVALID;
     if (d_grad) { int rc = grad_supported(c); if (rc != TAMCMC_OK) return rc; }
     TM_HIP(hipSetDevice(c->device));
     int rc = ensure_capacity(c, Nchains, d_grad != nullptr);
@@ -713,11 +677,10 @@ static void mark_pending(tamcmc_ctx *c, int n, size_t nw)
     for (size_t m = 0; m < nw; m++) o[m] = TM_PENDING_BITS;
     for (int m = 0; m < n; m++) c->h_status[m] = -1;
 }
-// o / st: first logL (then gradient) slot and first status slot of the (sub-)batch; ev / recorded / stream: its completion
-// event, recorded lazily; ticket / nticket: its arrival counters (re-armed when a launch retired without finalizing).
-static int wait_slots(tamcmc_ctx *c, volatile const uint64_t *o, volatile const int32_t *st, int n, size_t nw,
-                      hipEvent_t *ev, bool *recorded, hipStream_t stream, int32_t *ticket, int nticket)
+static int wait_data(tamcmc_ctx *c, int n, size_t nw)
 {
+    volatile const uint64_t *o = reinterpret_cast<volatile const uint64_t *>(c->h_out);
+    volatile const int32_t *st = c->h_status;
     unsigned spins = 0;
     for (size_t m = 0; m < nw;) {
         if (o[m] != TM_PENDING_BITS && (m >= (size_t)n || st[m] != -1)) { m++; continue; }
@@ -726,12 +689,12 @@ static int wait_slots(tamcmc_ctx *c, volatile const uint64_t *o, volatile const 
             // The completion event is recorded only now, behind the kernels already in the stream (it completes once they
             // have): a call that gets its results within the first ~2000 polls -- every healthy call -- never pays for an
             // event on the launch path (~1.5 us of host time per call in a sampler loop).
-            if (!*recorded) {
-                if (!*ev && hipEventCreateWithFlags(ev, hipEventDisableTiming) != hipSuccess) return TAMCMC_E_HIP;
-                if (hipEventRecord(*ev, stream) != hipSuccess) return TAMCMC_E_HIP;
-                *recorded = true;
+            if (!c->ev_recorded) {
+                if (!c->ev_done && hipEventCreateWithFlags(&c->ev_done, hipEventDisableTiming) != hipSuccess) return TAMCMC_E_HIP;
+                if (hipEventRecord(c->ev_done, c->stream) != hipSuccess) return TAMCMC_E_HIP;
+                c->ev_recorded = true;
             }
-            const hipError_t e = hipEventQuery(*ev);
+            const hipError_t e = hipEventQuery(c->ev_done);
             if (e == hipSuccess) {
                 // The launch has retired: whatever the slots hold is final.  A logL / status slot that still holds its
                 // marker was never written -- a chain whose finalize did not run (e.g. an arrival counter left non-zero
@@ -740,24 +703,19 @@ static int wait_slots(tamcmc_ctx *c, volatile const uint64_t *o, volatile const 
                 for (size_t k = 0; k < (size_t)n; k++)
                     if (o[k] == TM_PENDING_BITS || st[k] == -1) {
                         snprintf(g_hip_err, sizeof(g_hip_err), "chain %zu was not finalized by a retired launch", k);
-                        (void)hipMemsetAsync(ticket, 0, (size_t)nticket * sizeof(int32_t), stream);
+                        (void)hipMemsetAsync(c->d_ticket, 0, (size_t)c->cap * sizeof(int32_t), c->stream);
                         return TAMCMC_E_HIP;
                     }
                 return TAMCMC_OK;
             }
             if (e != hipErrorNotReady) {
                 snprintf(g_hip_err, sizeof(g_hip_err), "hipEventQuery -> %s", hipGetErrorString(e));
-                (void)hipMemsetAsync(ticket, 0, (size_t)nticket * sizeof(int32_t), stream);
+                (void)hipMemsetAsync(c->d_ticket, 0, (size_t)c->cap * sizeof(int32_t), c->stream);
                 return TAMCMC_E_HIP;
             }
         }
     }
     return TAMCMC_OK;
-}
-static int wait_data(tamcmc_ctx *c, int n, size_t nw)
-{
-    return wait_slots(c, reinterpret_cast<volatile const uint64_t *>(c->h_out), c->h_status, n, nw, &c->ev_done, &c->ev_recorded,
-                      c->stream, c->d_ticket, c->cap);
 }
 
 // pinned, device-mapped staging of the host-pointer entry points
@@ -782,7 +740,7 @@ static int ensure_staging(tamcmc_ctx *c, int Nchains)
 
 extern "C" int tamcmc_eval_batch_begin(tamcmc_ctx *c, int32_t Nchains, int32_t Nparams, const double *params, const double *Tcoefs)
 {
-    if (!c || Nchains < 1 || !params || !Tcoefs || Nparams != c->L.Nparams || c->in_flight || c->armed || c->parts_busy()) return TAMCMC_E_INVALID;
+    if (!c || Nchains < 1 || !params || !Tcoefs || Nparams != c->L.Nparams || c->in_flight || c->armed) return TAMCMC_E_INVALID;
     TM_HIP(hipSetDevice(c->device));
     int rc = ensure_capacity(c, Nchains, false);
     if (rc != TAMCMC_OK) return rc;
@@ -840,7 +798,7 @@ static bool gate_claim(tamcmc_ctx *c)
 // hidden under that evaluation) and fires it with one store once the parameters are known.
 extern "C" int tamcmc_eval_batch_arm(tamcmc_ctx *c, int32_t Nchains)
 {
-    if (!c || Nchains < 1 || c->armed || c->parts_busy()) return TAMCMC_E_INVALID;
+    if (!c || Nchains < 1 || c->armed) return TAMCMC_E_INVALID;
     if (c->in_flight && c->in_flight != Nchains) return TAMCMC_E_INVALID;
     // never (re)allocate under a batch in flight: tamcmc_ctx_reserve (or an earlier batch of this size) sized the buffers
     if (Nchains > c->cap || Nchains > c->h_cap || c->h_nvars != c->Nvars) {
@@ -915,54 +873,11 @@ extern "C" int tamcmc_eval_batch_disarm(tamcmc_ctx *c)
 
 extern "C" int tamcmc_ctx_reserve(tamcmc_ctx *c, int32_t Nchains)
 {
-    if (!c || Nchains < 1 || c->in_flight || c->armed || c->parts_busy()) return TAMCMC_E_INVALID;
+    if (!c || Nchains < 1 || c->in_flight || c->armed) return TAMCMC_E_INVALID;
     TM_HIP(hipSetDevice(c->device));
     int rc = ensure_capacity(c, Nchains, false);
     if (rc != TAMCMC_OK) return rc;
     return ensure_staging(c, Nchains);
-}
-
-extern "C" int tamcmc_eval_batch_begin_part(tamcmc_ctx *c, int32_t part, int32_t first, int32_t Nchains, int32_t Nparams,
-                                            const double *params, const double *Tcoefs)
-{
-    if (!c || part < 0 || part >= TAMCMC_MAX_PARTS || first < 0 || Nchains < 1 || !params || !Tcoefs || Nparams != c->L.Nparams) return TAMCMC_E_INVALID;
-    if (c->in_flight || c->part_n[part]) return TAMCMC_E_INVALID;
-    for (int o = 0; o < TAMCMC_MAX_PARTS; o++)      // ranges of parts in flight must not overlap
-        if (o != part && c->part_n[o] && first < c->part_first[o] + c->part_n[o] && c->part_first[o] < first + Nchains) return TAMCMC_E_INVALID;
-    // buffers are never (re)allocated under a part in flight: tamcmc_ctx_reserve sizes them beforehand
-    if (first + Nchains > c->cap || first + Nchains > c->h_cap || c->h_nvars != c->Nvars) {
-        if (c->parts_busy()) return TAMCMC_E_INVALID;
-        const int rc = tamcmc_ctx_reserve(c, first + Nchains);
-        if (rc != TAMCMC_OK) return rc;
-    }
-    TM_HIP(hipSetDevice(c->device));
-    if (part > 0 && !c->part_streams[part]) TM_HIP(hipStreamCreateWithFlags(&c->part_streams[part], hipStreamNonBlocking));
-    hipStream_t stream = (part == 0) ? c->stream : c->part_streams[part];
-    const size_t f = (size_t)first, n = (size_t)Nchains, np = (size_t)Nparams, hc = (size_t)c->h_cap;
-    std::memcpy(c->h_in + f * np, params, n * np * sizeof(double));
-    std::memcpy(c->h_in + hc * np + f, Tcoefs, n * sizeof(double));
-    uint64_t *o = reinterpret_cast<uint64_t *>(c->h_out) + f;
-    for (size_t m = 0; m < n; m++) { o[m] = TM_PENDING_BITS; c->h_status[f + m] = -1; }
-    const int rc = enqueue(c, Nchains, c->dv_in + f * np, c->dv_in + hc * np + f, c->dv_out + f, nullptr, c->dv_status + f, nullptr, nullptr,
-                           first, stream);
-    if (rc != TAMCMC_OK) return rc;
-    c->part_ev_recorded[part] = false;
-    c->part_first[part] = first; c->part_n[part] = Nchains;
-    return TAMCMC_OK;
-}
-
-extern "C" int tamcmc_eval_batch_end_part(tamcmc_ctx *c, int32_t part, double *logL, int32_t *status)
-{
-    if (!c || part < 0 || part >= TAMCMC_MAX_PARTS || !logL || !c->part_n[part]) return TAMCMC_E_INVALID;
-    const int n = c->part_n[part], first = c->part_first[part];
-    c->part_n[part] = 0;
-    hipStream_t stream = (part == 0) ? c->stream : c->part_streams[part];
-    const int rc = wait_slots(c, reinterpret_cast<volatile const uint64_t *>(c->h_out) + first, c->h_status + first, n, (size_t)n,
-                              &c->part_ev[part], &c->part_ev_recorded[part], stream, c->d_ticket + first, n);
-    if (rc != TAMCMC_OK) return rc;
-    std::memcpy(logL, c->h_out + first, (size_t)n * sizeof(double));
-    if (status) std::memcpy(status, c->h_status + first, (size_t)n * sizeof(int32_t));
-    return TAMCMC_OK;
 }
 
 extern "C" int tamcmc_eval_batch(tamcmc_ctx *c, int32_t Nchains, int32_t Nparams,
@@ -977,7 +892,7 @@ extern "C" int tamcmc_eval_batch(tamcmc_ctx *c, int32_t Nchains, int32_t Nparams
     for (int r = 0; r < n_rows; r++)
         if (model_rows[r] < 0 || model_rows[r] >= Nchains) return TAMCMC_E_INVALID;
     if (grad) { int rc = grad_supported(c); if (rc != TAMCMC_OK) return rc; }
-    if (c->in_flight || c->parts_busy()) return TAMCMC_E_INVALID;   // (buffers may move below)
+    if (c->in_flight || c->armed) return TAMCMC_E_INVALID;   // (buffers may move below)
     TM_HIP(hipSetDevice(c->device));
     int rc = ensure_capacity(c, Nchains, grad != nullptr);
     if (rc != TAMCMC_OK) return rc;

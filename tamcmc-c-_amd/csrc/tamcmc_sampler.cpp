@@ -603,27 +603,6 @@ struct tamcmc_sampler {
     std::vector<double> step;                    // [nloc][Nvars]
     std::vector<uint64_t> step_zgen, step_cgen, chol_gen;   // per chain: generations the step was made from; factor generation
     uint64_t z_gen = 1;                          // bumped whenever z_all is rewritten
-    // Pipelined loop (tamcmc_sampler_run / _run_sharded with the HIP evaluator): the local chains in two halves, each its
-    // own sub-batch on its own stream (tamcmc_eval_batch_begin_part).  One half's accept step, next proposals and next
-    // launch happen on the host while the GPU evaluates the other half -- chains are independent inside an iteration
-    // (MALA.cpp:632-655) and no draw depends on an outcome, so every chain sees exactly the numbers of the plain loop.
-    // ... and the random numbers of the iteration after the next come from a thread of their own (DrawAhead below): with
-    // the GPU hidden behind the host, the draws (a serial stream, ~30 us per iteration at 64 x 44) would otherwise be the
-    // longest item on the host's critical path.  The thread is asked for exactly the packets the plain loop would draw,
-    // one iteration early, and never beyond the last iteration of a call: the stream position on return is the plain
-    // loop's.
-    struct Packet { std::vector<double> u_mh, z_all; double pt_u = 0.0; int32_t pt_A = 0; bool has_pt = false; };
-    Packet packet;                               // what the thread fills: PT draws of iteration j, MH draws of j + 1
-    std::unique_ptr<ChainPool> draw_pool;        // the thread's helpers for the Box-Muller transforms
-    std::thread draw_thread;
-    std::atomic<uint64_t> draw_req{0}, draw_done{0};
-    std::atomic<bool> draw_stop{false};
-    bool draw_req_pt = false;                    // (written before draw_req is bumped) the requested packet has PT draws
-    bool draw_pending = false;                   // a request is outstanding (main thread's view)
-    int split = 0;                               // > 0: pipelining on (chains per part, rounded up)
-    int nparts = 0;                              // sub-batches in flight (2 .. TAMCMC_MAX_PARTS)
-    bool inflight = false;                       // both halves of iteration `iter` are launched (only inside a run call)
-    bool reserved = false;                       // the context's buffers are sized for nloc chains
     std::atomic<int64_t> bad_chol_ahead{0};
     int32_t pt_A = 0;
     double pt_u = 0.0;
@@ -696,29 +675,12 @@ static int sampler_alloc(tamcmc_sampler **out, const tamcmc_sampler_cfg *cfg, ta
         if (nt > n) nt = n;
         if (nt < 1) nt = 1;
         s->pool.reset(new ChainPool(nt));
+    }
     { const char *e = getenv("TAMCMC_SAMPLER_TIMING"); s->timing = e && e[0] == '1'; }
     { const char *e = getenv("TAMCMC_SAMPLER_ARM"); s->arm_enabled = !(e && e[0] == '0'); s->arm_sharded = e && e[0] == '2'; }
     { const char *e = getenv("TAMCMC_SAMPLER_ARRIVE"); s->arrive_enabled = !(e && e[0] == '0'); }
     s->arrived.assign((size_t)n, 0);
-    {   // Two halves in flight (pipelined_iteration) with the draws on a thread of their own: OFF unless
-        // TAMCMC_SAMPLER_PIPELINE=1.  Measured at 64 chains x 1e5 bins, PT every iteration (profiles/README.md, round 3):
-        // without the draw thread the loop is host-bound and SLOWER (84 us per iteration against 65 us with one batch: four
-        // launches instead of two, two pool forks, and the priors and draws with no GPU evaluation left to hide under);
-        // with it 60-62 us (Acquire, +6 %) and 85-90 us (Learning, +-0): the main thread now waits ~26 us per iteration
-        // for the GPU, because a half batch is not half the GPU time -- launch + setup kernel + eval floor are ~33 us from
-        // launch to result against 42 us for the whole batch -- while the host has only ~18 us of work on the other half.
-        // More parts make it worse (3: 74 us, 4: 85 us per Acquire iteration): every part costs two launches (8-9 us of
-        // host time) and a pool fork (~10 us whatever the number of chains on this host).
-        // Same draws, same decisions either way (tests/test_sampler_gpu.py).
-        const char *e = getenv("TAMCMC_SAMPLER_PIPELINE");      // 1: two parts; 2 .. TAMCMC_MAX_PARTS: that many
-        int parts = e ? atoi(e) : 0;
-        if (parts == 1) parts = 2;
-        if (parts > TAMCMC_MAX_PARTS) parts = TAMCMC_MAX_PARTS;
-        if (n < 4 * parts) parts = 0;
-        s->nparts = parts;
-        s->split = parts > 0 ? (n + parts - 1) / parts : 0;
-    }
-    }
+    // (one batch in flight: the local chains split into sub-batches on streams of their own measured slower)
     s->rng.g.seed(cfg->seed);
     *out = s;
     return TAMCMC_OK;
@@ -747,11 +709,6 @@ extern "C" int tamcmc_sampler_destroy(tamcmc_sampler *s)
         const double k = 1e6 / (double)s->t_iters;
         fprintf(stderr, "[tamcmc sampler] %lld iterations; us per iteration: proposals %.1f, launch %.1f, arm + priors %.1f, draw-ahead %.1f, wait %.1f, accept %.1f\n",
                 (long long)s->t_iters, s->t_phase[0] * k, s->t_phase[1] * k, s->t_phase[2] * k, s->t_phase[3] * k, s->t_phase[4] * k, s->t_phase[5] * k);
-    }
-    if (s && s->draw_thread.joinable()) {
-        s->draw_stop.store(true, std::memory_order_relaxed);
-        s->draw_req.fetch_add(1, std::memory_order_release);
-        s->draw_thread.join();
     }
     delete s;
     return TAMCMC_OK;
@@ -870,16 +827,15 @@ static void skip_foreign(tamcmc_sampler *s, int count)
     s->rng.draw(nv, s->plans[(size_t)n]);
 }
 
-static void draw_mh(tamcmc_sampler *s, double *u_out = nullptr)
+static void draw_mh(tamcmc_sampler *s)
 {
     const int n = s->nloc, nv = s->Nvars, off = s->cfg.chain_offset, N = s->cfg.Nchains;
-    if (!u_out) u_out = s->u_mh.data();
     const bool tm = s->timing && n < N;
     double t0 = tm ? wall_now() : 0.0;
     skip_foreign(s, off);
     if (tm) { const double t1 = wall_now(); s->t_phase[6] += t1 - t0; }
     for (int m = 0; m < n; m++) {
-        u_out[m] = s->rng.uniform();
+        s->u_mh[m] = s->rng.uniform();
         s->rng.draw(nv, s->plans[(size_t)m]);
     }
     if (tm) t0 = wall_now();
@@ -922,7 +878,7 @@ static inline void step_chain(tamcmc_sampler *s, int m)
 // Proposal of local chain m from its current vars and the normals in z_all: v' = v + chol((Sigma + eps2 I) sigma) z
 // (MALA.cpp:335-353), the factor recomputed only when the proposal parameters changed.  Returns false when the matrix
 // was not positive definite.
-static bool propose_chain(tamcmc_sampler *s, int m, bool with_prior = false)
+static bool propose_chain(tamcmc_sampler *s, int m)
 {
     const int nv = s->Nvars, np = s->Nparams;
     bool ok = true;
@@ -950,11 +906,6 @@ static bool propose_chain(tamcmc_sampler *s, int m, bool with_prior = false)
     }
     std::memcpy(&s->p_prop[(size_t)m * np], &s->params[(size_t)m * np], sizeof(double) * np);
     for (int k = 0; k < nv; k++) s->p_prop[(size_t)m * np + s->index_to_relax[k]] = s->v_prop[(size_t)m * nv + k];
-    if (with_prior) {       // pipelined loop: the proposal's prior in the same pass (no GPU evaluation left to hide it under)
-        int perr = 0;
-        s->lpr_prop[m] = (double)log_prior(s->prior, &s->p_prop[(size_t)m * np], &perr);
-        s->perr_prop[m] = perr;
-    }
     return ok;
 }
 
@@ -984,209 +935,8 @@ static inline void accept_chain(tamcmc_sampler *s, int m, int64_t i, double gamm
     }
     s->Pmove[m] = r;
     if (learn && (i % period) == 0) update_proposal(s, m, gamma, r);
-    if (ahead && !propose_chain(s, m, s->split > 0)) s->bad_chol_ahead.fetch_add(1, std::memory_order_relaxed);
+    if (ahead && !propose_chain(s, m)) s->bad_chol_ahead.fetch_add(1, std::memory_order_relaxed);
 }
-
-// ---- the draw thread of the pipelined loop ------------------------------------------------------------------------
-static void draw_packet(tamcmc_sampler *s, bool with_pt, ChainPool *pool)
-{
-    const int n = s->nloc, nv = s->Nvars;
-    tamcmc_sampler::Packet &P = s->packet;
-    P.has_pt = with_pt;
-    if (with_pt) {
-        P.pt_u = s->rng.uniform();                                    // MALA.cpp:384
-        P.pt_A = (int32_t)(s->rng.g.next() % (s->cfg.Nchains - 1));   // :390
-    }
-    draw_mh(s, P.u_mh.data());
-    pool->run(n, [&](int m) { s->plans[m].fill(&P.z_all[(size_t)m * nv]); });
-}
-
-static void draw_thread_main(tamcmc_sampler *s)
-{
-    uint64_t seen = 0;
-    for (;;) {
-        uint64_t r = s->draw_req.load(std::memory_order_acquire);
-        for (int spin = 0; r == seen && !s->draw_stop.load(std::memory_order_relaxed); spin++) {
-            if (spin < 20000) __builtin_ia32_pause(); else std::this_thread::sleep_for(std::chrono::microseconds(50));
-            r = s->draw_req.load(std::memory_order_acquire);
-        }
-        if (s->draw_stop.load(std::memory_order_relaxed)) return;
-        seen = r;
-        draw_packet(s, s->draw_req_pt, s->draw_pool.get());
-        s->draw_done.store(r, std::memory_order_release);
-    }
-}
-
-static void draw_request(tamcmc_sampler *s, bool with_pt)
-{
-    if (!s->draw_thread.joinable()) {
-        s->packet.u_mh.resize((size_t)s->nloc); s->packet.z_all.resize((size_t)s->nloc * s->Nvars);
-        s->draw_pool.reset(new ChainPool(4));
-        s->draw_thread = std::thread(draw_thread_main, s);
-    }
-    s->draw_req_pt = with_pt;
-    s->draw_req.fetch_add(1, std::memory_order_release);
-    s->draw_pending = true;
-}
-
-// the requested packet becomes the sampler's current draws (u_mh / z_all of the coming iteration, PT draws of this one)
-static void draw_collect(tamcmc_sampler *s)
-{
-    const uint64_t want = s->draw_req.load(std::memory_order_relaxed);
-    while (s->draw_done.load(std::memory_order_acquire) != want) __builtin_ia32_pause();
-    s->draw_pending = false;
-    std::swap(s->u_mh, s->packet.u_mh);
-    std::swap(s->z_all, s->packet.z_all); s->z_gen++;
-    if (s->packet.has_pt) { s->pt_u = s->packet.pt_u; s->pt_A = s->packet.pt_A; s->pt_cached = true; }
-}
-
-static void drain_parts(tamcmc_sampler *s)
-{
-    if (!s->inflight) return;
-    std::vector<double> l((size_t)s->nloc);
-    for (int q = 0; q < s->nparts; q++) (void)tamcmc_eval_batch_end_part(s->hip_ctx, q, l.data(), nullptr);   // (parts not in flight: refused, harmless)
-    s->inflight = false;
-}
-
-// One iteration of the pipelined loop.  pt_step() is the caller's parallel-tempering step (draw, local swap or boundary
-// exchange, bookkeeping); it is called exactly once, when the accept step of every local chain of the drawn pair is done
-// and before those chains are launched again.  moved_row (may be NULL) receives the acceptance flags as they are BEFORE
-// the swap (what the plain loop records).  launch_next: leave iteration iter + 1 in flight on return.
-template <class PT>
-static int pipelined_iteration(tamcmc_sampler *s, bool launch_next, uint8_t *moved_row, PT &&pt_step)
-{
-    const int n = s->nloc, nv = s->Nvars, np = s->Nparams, off = s->cfg.chain_offset, P = s->nparts;
-    const int64_t i = s->iter;
-    const double gamma = s->cfg.c0 / (1. + (double)i);             // MALA.cpp:630
-    auto now = [&]() { return s->timing ? wall_now() : 0.0; };
-    double t0 = now(), t1;
-    int m0[TAMCMC_MAX_PARTS + 1];
-    for (int q = 0; q <= P; q++) m0[q] = (int)(((long long)q * n) / P);     // part q = chains [m0[q], m0[q + 1])
-    auto part_of = [&](int m) { int q = 0; while (q + 1 < P && m >= m0[q + 1]) q++; return q; };
-    auto launch = [&](int q) {
-        return tamcmc_eval_batch_begin_part(s->hip_ctx, q, m0[q], m0[q + 1] - m0[q], np, &s->p_prop[(size_t)m0[q] * np], &s->T[off + m0[q]]);
-    };
-    bool flying[TAMCMC_MAX_PARTS] = {};
-    auto fail = [&](int code) {      // leave nothing in flight behind an error
-        if (s->draw_pending) draw_collect(s);
-        std::vector<double> l((size_t)n);
-        for (int q = 0; q < P; q++) if (flying[q]) (void)tamcmc_eval_batch_end_part(s->hip_ctx, q, l.data(), nullptr);
-        s->inflight = false; s->proposed_ahead = false;
-        return code;
-    };
-    int rc = TAMCMC_OK;
-    std::atomic<int64_t> bad{0};
-    if (!s->inflight) {
-        // pipeline start: this iteration's draws and proposals (unless made ahead), every part launched
-        if (!s->reserved) { rc = tamcmc_ctx_reserve(s->hip_ctx, n); if (rc != TAMCMC_OK) return rc; s->reserved = true; }
-        if (!s->drawn_ahead) {
-            draw_mh(s);
-            s->z_gen++; s->pool->run(n, [&](int m) { s->plans[m].fill(&s->z_all[(size_t)m * nv]); });
-        }
-        s->drawn_ahead = false;
-        if (!s->proposed_ahead)
-            s->pool->run(n, [&](int m) { if (!propose_chain(s, m, true)) bad.fetch_add(1, std::memory_order_relaxed); });
-        else      // proposals made by the plain loop (mh_step) carry no prior yet
-            s->pool->run(n, [&](int m) {
-                int perr = 0;
-                s->lpr_prop[m] = (double)log_prior(s->prior, &s->p_prop[(size_t)m * np], &perr);
-                s->perr_prop[m] = perr;
-            });
-        s->proposed_ahead = false;
-        t1 = now(); s->t_phase[0] += t1 - t0; t0 = t1;
-        for (int q = 0; q < P; q++) { rc = launch(q); if (rc != TAMCMC_OK) return fail(rc); flying[q] = true; }
-        t1 = now(); s->t_phase[1] += t1 - t0; t0 = t1;
-    } else {
-        for (int q = 0; q < P; q++) flying[q] = true;
-    }
-    s->inflight = true;
-    bad.fetch_add(s->bad_chol_ahead.exchange(0), std::memory_order_relaxed);
-    s->bad_chol += bad.load();
-    // The stream one iteration ahead: the parallel-tempering draws of THIS iteration (they come first, MALA.cpp:384,390),
-    // then the MH draws of the next.  From the draw thread if it was asked for them during the previous iteration, else
-    // made here (first iteration of a call); the packet after that is requested at once, unless this call ends first.
-    s->u_now = s->u_mh;
-    const bool due = tamcmc_sampler_pt_due(s) != 0;
-    if (s->draw_pending) {
-        draw_collect(s);
-    } else {
-        if (due && !s->pt_cached) { draw_pt(s); s->pt_cached = true; }
-        draw_mh(s);
-        s->z_gen++; s->pool->run(n, [&](int m) { s->plans[m].fill(&s->z_all[(size_t)m * nv]); });
-    }
-    s->drawn_ahead = true;
-    if (launch_next) {
-        const int64_t inext = i + 1;
-        const bool due_next = s->cfg.dN_mixing > 0 && s->cfg.Nchains >= 2 && (inext % s->cfg.dN_mixing == 0) && inext != 0;
-        draw_request(s, due_next);
-    }
-    t1 = now(); s->t_phase[3] += t1 - t0; t0 = t1;
-
-    // Order of the parts: the one(s) holding the local chain(s) of the drawn pair first -- their accept step, the swap,
-    // their relaunch -- then the others in turn.  A pair with a chain in each of two parts needs both before the swap.
-    int pa = -1, pb = -1;                                 // parts of the pair's local chains (pb: second part, or -1)
-    if (due) {
-        const int a = s->pt_A - off, b = a + 1;
-        const bool inA = a >= 0 && a < n, inB = b >= 0 && b < n;
-        if (inA) pa = part_of(a);
-        if (inB) { const int q = part_of(b); if (pa < 0) pa = q; else if (q != pa) pb = q; }
-    }
-    int64_t period = 1;
-    const bool learn = learning_now(s, i, &period);
-    std::atomic<int> perr_any{0};
-    auto finish = [&](int q) {
-        int r = tamcmc_eval_batch_end_part(s->hip_ctx, q, &s->L_prop[(size_t)m0[q]], &s->status[(size_t)m0[q]]);
-        flying[q] = false;
-        t1 = now(); s->t_phase[4] += t1 - t0; t0 = t1;
-        if (r != TAMCMC_OK) return r;
-        s->pool->run(m0[q + 1] - m0[q], [&](int k) { accept_chain(s, m0[q] + k, i, gamma, learn, period, true, perr_any); });
-        if (moved_row) std::memcpy(moved_row + m0[q], &s->moved[(size_t)m0[q]], (size_t)(m0[q + 1] - m0[q]));
-        t1 = now(); s->t_phase[5] += t1 - t0; t0 = t1;
-        return (int)TAMCMC_OK;
-    };
-    auto relaunch = [&](int q) {
-        const int r = launch(q);
-        if (r == TAMCMC_OK) flying[q] = true;
-        t1 = now(); s->t_phase[1] += t1 - t0; t0 = t1;
-        return r;
-    };
-    bool pt_done = false;
-    if (!launch_next) {
-        // last iteration of a call: nothing is launched ahead
-        for (int q = 0; q < P; q++) { rc = finish(q); if (rc != TAMCMC_OK) return fail(rc); }
-        s->inflight = false;
-        s->proposed_ahead = true;
-        rc = pt_step();
-        if (rc != TAMCMC_OK) return fail(rc);
-    } else {
-        if (pa >= 0) {
-            rc = finish(pa);
-            if (rc != TAMCMC_OK) return fail(rc);
-            if (pb >= 0) { rc = finish(pb); if (rc != TAMCMC_OK) return fail(rc); }
-            s->proposed_ahead = true;                   // (for the pair's chains: a swap re-proposes them, pt_apply)
-            rc = pt_step();
-            pt_done = true;
-            if (rc != TAMCMC_OK) return fail(rc);
-            rc = relaunch(pa);
-            if (rc != TAMCMC_OK) return fail(rc);
-            if (pb >= 0) { rc = relaunch(pb); if (rc != TAMCMC_OK) return fail(rc); }
-        }
-        for (int q = 0; q < P; q++) {
-            if (q == pa || q == pb) continue;
-            rc = finish(q);
-            if (rc != TAMCMC_OK) return fail(rc);
-            rc = relaunch(q);
-            if (rc != TAMCMC_OK) return fail(rc);
-        }
-        if (!pt_done) { rc = pt_step(); if (rc != TAMCMC_OK) return fail(rc); }   // no local chain in the pair (or no attempt): bookkeeping only
-        s->inflight = true; s->proposed_ahead = false;
-    }
-    s->t_iters++;
-    if (perr_any.load()) { if (s->draw_pending) draw_collect(s); if (s->inflight) drain_parts(s); s->proposed_ahead = false; return TAMCMC_E_INVALID; }
-    return TAMCMC_OK;
-}
-
-static bool pipeline_on(const tamcmc_sampler *s) { return s->hip_ctx != nullptr && s->split > 0; }
 
 extern "C" int tamcmc_sampler_mh_step(tamcmc_sampler *s)
 {
@@ -1366,8 +1116,8 @@ static void pt_apply(tamcmc_sampler *s, int A, double u, const double *recA, con
     }
     if (sw && s->proposed_ahead) {      // the proposals computed ahead started from the rows just replaced
         const int a = A - off, b = B - off;
-        if (a >= 0 && a < s->nloc && !propose_chain(s, a, s->split > 0)) s->bad_chol_ahead.fetch_add(1, std::memory_order_relaxed);
-        if (b >= 0 && b < s->nloc && !propose_chain(s, b, s->split > 0)) s->bad_chol_ahead.fetch_add(1, std::memory_order_relaxed);
+        if (a >= 0 && a < s->nloc && !propose_chain(s, a)) s->bad_chol_ahead.fetch_add(1, std::memory_order_relaxed);
+        if (b >= 0 && b < s->nloc && !propose_chain(s, b)) s->bad_chol_ahead.fetch_add(1, std::memory_order_relaxed);
     }
     if (swapped) *swapped = sw ? 1 : 0;
     if (r_out) *r_out = r_T;
@@ -1409,38 +1159,6 @@ struct ArmGuard {
         s->ctx_armed = false;
     }
 };
-
-extern "C" int tamcmc_sampler_run(tamcmc_sampler *s, int64_t n_iter, uint8_t *moved_hist, int32_t *swap_hist)
-{
-    if (!s || s->nloc != s->cfg.Nchains) return TAMCMC_E_INVALID;   // single process only
-    ArmGuard guard{s};
-    for (int64_t k = 0; k < n_iter; k++) {
-        int32_t sh = -1;
-        auto pt_step = [&]() {
-            if (!tamcmc_sampler_pt_due(s)) return (int)TAMCMC_OK;
-            int32_t A, swapped; double u, r;
-            tamcmc_sampler_pt_draw(s, &A, &u);
-            const int rc2 = tamcmc_sampler_pt_local(s, A, u, &swapped, &r);
-            if (rc2 == TAMCMC_OK) sh = 2 * A + swapped;
-            return rc2;
-        };
-        int rc;
-        if (pipeline_on(s)) {
-            rc = pipelined_iteration(s, k + 1 < n_iter, moved_hist ? moved_hist + (size_t)k * s->nloc : nullptr, pt_step);
-            if (rc != TAMCMC_OK) return rc;
-        } else {
-            s->arm_next = (k + 1 < n_iter);
-            rc = tamcmc_sampler_mh_step(s);
-            if (rc != TAMCMC_OK) return rc;
-            if (moved_hist) std::memcpy(moved_hist + (size_t)k * s->nloc, s->moved.data(), s->nloc);
-            rc = pt_step();
-            if (rc != TAMCMC_OK) return rc;
-        }
-        if (swap_hist) swap_hist[k] = sh;
-        s->iter++;
-    }
-    return TAMCMC_OK;
-}
 
 // ------------------------------------------------------------------------------------------------
 // Sharded runs: the iteration loop of MALA::execute (MALA.cpp:608-737) for the block of chains this process owns.
@@ -1556,29 +1274,30 @@ extern "C" int tamcmc_sampler_run_sharded(tamcmc_sampler *s, int64_t n_iter, tam
             }
             return (int)TAMCMC_OK;
         };
-        int rc;
-        if (pipeline_on(s)) {
-            const bool more = (k + 1 < n_iter) && !(block && block->n + 1 >= block->cap);
-            rc = pipelined_iteration(s, more, moved_hist ? moved_hist + (size_t)k * nloc : nullptr, pt_step);
-            if (rc != TAMCMC_OK) return rc;
-        } else {
-            // (chains spread over several processes: between this step and the next lies the boundary exchange, which
-            // runs the caller's communication library on the same GPU while the armed launches would wait behind their
-            // gate.  Nothing in that is known to synchronise the device, but it cannot be tried on the one-GPU boxes this
-            // was developed on, and a device-wide wait under an armed batch costs the gate's whole patience: armed only
-            // when this process owns the whole ladder, or on request -- TAMCMC_SAMPLER_ARM=2.)
-            s->arm_next = (k + 1 < n_iter) && !(block && block->n + 1 >= block->cap) && (nloc == s->cfg.Nchains || s->arm_sharded);
-            rc = tamcmc_sampler_mh_step(s);
-            if (rc != TAMCMC_OK) return rc;
-            if (moved_hist) std::memcpy(moved_hist + (size_t)k * nloc, s->moved.data(), (size_t)nloc);
-            rc = pt_step();
-            if (rc != TAMCMC_OK) return rc;
-        }
+        // (chains spread over several processes: between this step and the next lies the boundary exchange, which
+        // runs the caller's communication library on the same GPU while the armed launches would wait behind their
+        // gate.  Nothing in that is known to synchronise the device, but it cannot be tried on the one-GPU boxes this
+        // was developed on, and a device-wide wait under an armed batch costs the gate's whole patience: armed only
+        // when this process owns the whole ladder, or on request -- TAMCMC_SAMPLER_ARM=2.)
+        s->arm_next = (k + 1 < n_iter) && !(block && block->n + 1 >= block->cap) && (nloc == s->cfg.Nchains || s->arm_sharded);
+        int rc = tamcmc_sampler_mh_step(s);
+        if (rc != TAMCMC_OK) return rc;
+        if (moved_hist) std::memcpy(moved_hist + (size_t)k * nloc, s->moved.data(), (size_t)nloc);
+        rc = pt_step();
+        if (rc != TAMCMC_OK) return rc;
         if (swap_hist) swap_hist[k] = sh;
         if (block) shard_block_record(block, s, att, Ad, r, swd);
         s->iter++;
     }
     return TAMCMC_OK;
+}
+
+// Single process: the sharded loop with no exchange and no block -- this process owns every pair, so each attempt is a
+// local swap and swap_hist holds -1 or 2*A + swapped.
+extern "C" int tamcmc_sampler_run(tamcmc_sampler *s, int64_t n_iter, uint8_t *moved_hist, int32_t *swap_hist)
+{
+    if (!s || s->nloc != s->cfg.Nchains) return TAMCMC_E_INVALID;   // single process only
+    return tamcmc_sampler_run_sharded(s, n_iter > 0 ? n_iter : 0, nullptr, nullptr, nullptr, moved_hist, swap_hist, nullptr);
 }
 
 extern "C" int tamcmc_sampler_set_timing(tamcmc_sampler *s, int32_t enable)

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Developer tool: iterations/s of the library's sampler loop at C2 (64 chains x 1e5 bins, PT every iteration) for the
-environment it is started in (TAMCMC_SAMPLER_PIPELINE, TAMCMC_SAMPLER_THREADS, TAMCMC_SAMPLER_TIMING=1 ...)."""
+environment it is started in (TAMCMC_SAMPLER_THREADS, TAMCMC_SAMPLER_ARM, TAMCMC_SAMPLER_TIMING=1 ...)."""
 import os, sys, time
 import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
