@@ -379,13 +379,21 @@ static int orc_model_global(int flavour, const double *params, const int *plengt
         if (lmax >= 3) Vl3 = fabs(params[Nmax + 2]);
     }
     if (flavour == 12) {
-        /* models.cpp:1010-1030 -- m-heights given directly, symmetric in m */
-        ratios_l1[0] = fabs(params[z + Nnoise + 1]); ratios_l1[1] = fabs(params[z + Nnoise]); ratios_l1[2] = fabs(params[z + Nnoise + 1]);
-        ratios_l2[0] = fabs(params[z + Nnoise + 4]); ratios_l2[1] = fabs(params[z + Nnoise + 3]); ratios_l2[2] = fabs(params[z + Nnoise + 2]);
-        ratios_l2[3] = fabs(params[z + Nnoise + 3]); ratios_l2[4] = fabs(params[z + Nnoise + 4]);
-        ratios_l3[0] = fabs(params[z + Nnoise + 8]); ratios_l3[1] = fabs(params[z + Nnoise + 7]); ratios_l3[2] = fabs(params[z + Nnoise + 6]);
-        ratios_l3[3] = fabs(params[z + Nnoise + 5]); ratios_l3[4] = fabs(params[z + Nnoise + 6]); ratios_l3[5] = fabs(params[z + Nnoise + 7]);
-        ratios_l3[6] = fabs(params[z + Nnoise + 8]);
+        /* models.cpp:1010-1030 -- m-heights given directly, symmetric in m.  The reference reads all nine entries
+         * (its reader always makes Ninc = 9, io_ms_global.cpp:916-928); a row may end after the degrees it has
+         * (Ninc = 2 + 3 [lmax >= 2] + 4 [lmax >= 3]), so only those are read here -- the others are never used. */
+        if (lmax >= 1) {
+            ratios_l1[0] = fabs(params[z + Nnoise + 1]); ratios_l1[1] = fabs(params[z + Nnoise]); ratios_l1[2] = fabs(params[z + Nnoise + 1]);
+        }
+        if (lmax >= 2) {
+            ratios_l2[0] = fabs(params[z + Nnoise + 4]); ratios_l2[1] = fabs(params[z + Nnoise + 3]); ratios_l2[2] = fabs(params[z + Nnoise + 2]);
+            ratios_l2[3] = fabs(params[z + Nnoise + 3]); ratios_l2[4] = fabs(params[z + Nnoise + 4]);
+        }
+        if (lmax >= 3) {
+            ratios_l3[0] = fabs(params[z + Nnoise + 8]); ratios_l3[1] = fabs(params[z + Nnoise + 7]); ratios_l3[2] = fabs(params[z + Nnoise + 6]);
+            ratios_l3[3] = fabs(params[z + Nnoise + 5]); ratios_l3[4] = fabs(params[z + Nnoise + 6]); ratios_l3[5] = fabs(params[z + Nnoise + 7]);
+            ratios_l3[6] = fabs(params[z + Nnoise + 8]);
+        }
     } else if (flavour != 13) {
         if (lmax >= 1) orc_amplitude_ratio(1, inclination, ratios_l1);
         if (lmax >= 2) orc_amplitude_ratio(2, inclination, ratios_l2);
@@ -1011,7 +1019,7 @@ static int orc_grad_global(int flavour, const double *params, const int *plength
         for (int l = 1; l <= lmax; l++) Vl[l] = fabs(params[Nmax + l - 1]);
     if (flavour == 12) {
         const int base[4] = {0, q + 0, q + 2, q + 5};
-        for (int l = 1; l <= 3; l++)
+        for (int l = 1; l <= lmax; l++)      /* the degrees the row has (see orc_model_global) */
             for (int m = -l; m <= l; m++) ratios[l][m + l] = fabs(params[base[l] + (m < 0 ? -m : m)]);
     } else if (flavour != 13) {
         const double PI = 3.141592653589793238462643;

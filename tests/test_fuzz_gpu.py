@@ -1,6 +1,8 @@
 """Randomized HIP-vs-oracle parity sweep: model id, grid length (2 ... 60000 bins: fused one-tile launches, short-grid
 tiles, full-size tiles), truncation constant, asymmetry, amplitude mode, likelihood, chain count and parameter scatter
-are drawn at random.  60 cases by default; TAMCMC_FUZZ_CASES / TAMCMC_FUZZ_SEED widen the sweep."""
+are drawn at random; so are, through tests/workloads.py's layout generator, lmax (0-3) of the global ids and their Harvey
+background (0-3 active profiles, now and then p = 0 or a non-integer p, negative entries).  60 cases by default;
+TAMCMC_FUZZ_CASES / TAMCMC_FUZZ_SEED widen the sweep."""
 import os
 
 import numpy as np
@@ -11,6 +13,17 @@ import workloads as W
 from tamcmc_amd import synth
 
 pytestmark = pytest.mark.gpu
+
+
+def _random_noise(rng):
+    """0..3 Harvey profiles (H, tau, p) around the synthetic star's, p = 0 or non-integer now and then, signs at random."""
+    out = []
+    for _ in range(int(rng.integers(0, 4))):
+        H, tau = float(rng.uniform(0.3, 12.0)), float(rng.uniform(1.0, 60.0))
+        pw = float(rng.choice([0.0, 1.0, 2.0, 4.0, rng.uniform(0.5, 4.5)]))
+        sg = rng.choice([-1.0, 1.0], size=3, p=[0.15, 0.85])
+        out.append((sg[0] * H, sg[1] * tau, sg[2] * pw))
+    return tuple(out)
 
 
 @pytest.mark.parametrize("balanced", [0, 1], ids=["equal-length-tiles", "equal-cost-tiles"])
@@ -29,7 +42,11 @@ def test_random_configurations_match_the_oracle(accel_mod, orc, monkeypatch, bal
         if mid not in (0, 1):
             kw.update(trunc_c=float(rng.choice([3.0, 7.0, 20.0, 50.0, 10000.0])), asym=float(rng.choice([0.0, 0.0, 25.0, -40.0, 5.0])),
                       do_amp=bool(rng.integers(0, 2)))
-        w = W.any_model(mid, **kw)
+        if mid in W.LAYOUT_IDS and rng.integers(0, 2):
+            # another layout: lmax 0..3, 2..6 radial orders, 0..3 Harvey profiles
+            w = W.layout(mid, int(rng.integers(0, 4)), noise=_random_noise(rng), Nmax=int(rng.integers(2, 7)), **kw)
+        else:
+            w = W.any_model(mid, **kw)
         m, st0 = orc.model(mid, w["params_true"], w["plength"], w["x"])
         if st0 != 0 or not np.all(np.isfinite(m)) or np.any(m <= 0):
             continue                                  # not a usable truth spectrum (e.g. 2 bins and an empty window)

@@ -160,6 +160,104 @@ def test_model_id2_against_numpy_restatement(orc, kw):
     assert np.max(np.abs(m - ref) / ref) < 1e-13
 
 
+def numpy_global_any_lmax(w, x):
+    """Model ids 2, 3, 6, 7, 8 and 12 at any lmax, straight from SURVEY.md App. A and models.cpp / build_lorentzian.cpp
+    (formulas, not the oracle's code): the a1l family (6/7/8) splits l = 1 by a1(l=1) with c_lm = 0, l = 2 by a1(l=2),
+    l = 3 by the MEAN (a1(l=1) + a1(l=2)) / 2 with c_lm = 0, and cuts every window with that mean; id 12 takes the
+    m-heights of l = 1, 2, 3 from its inclination block (m = 0 first, then |m| = 1 ...)."""
+    mid = w["model_case"]
+    p, pl = w["params_true"], w["plength"]
+    Nmax, lmax = int(pl[0]), int(pl[1])
+    s = Nmax + lmax + int(pl[2:6].sum())
+    wq = s + int(pl[6])
+    z = wq + int(pl[7])
+    q = z + int(pl[8])
+    trunc_c, do_amp = p[q + int(pl[9])], p[q + int(pl[9]) + 1] != 0
+    eta, a3, asym = p[s + 1], p[s + 2], p[s + 5]
+    if mid == 2:
+        a1 = p[s + 3] ** 2 + p[s + 4] ** 2
+        inc = math.degrees(math.atan(p[s + 4] / p[s + 3]))
+    else:
+        a1 = abs(p[s])
+        inc = p[q]
+    fl0 = p[Nmax + lmax:Nmax + lmax + Nmax]
+    Wl0 = p[wq:wq + Nmax]
+    M = np.zeros_like(x)
+    step = x[1] - x[0]
+    for n in range(Nmax):
+        fs = {1: a1, 2: a1, 3: a1}
+        if mid == 6:
+            fs = {1: abs(p[s]), 2: abs(p[s + 6])}
+        elif mid == 7:
+            fs = {1: abs(p[s + 6 + n]), 2: abs(p[s + 6 + n])}
+        elif mid == 8:
+            fs = {1: abs(p[s + 6 + n]), 2: abs(p[s + 6 + Nmax + n])}
+        if mid in (6, 7, 8):
+            fs[3] = 0.5 * (fs[1] + fs[2])
+        f_win = fs[3] if mid in (6, 7, 8) else a1
+        for l in range(lmax + 1):
+            f = p[Nmax + lmax + l * Nmax + n]
+            if l == 0:
+                G = abs(Wl0[n])
+            elif fl0[0] <= f <= fl0[-1]:
+                G = abs(np.interp(f, fl0, Wl0))
+            else:
+                i = 0 if f < fl0[0] else Nmax - 2
+                G = abs(Wl0[i] + (Wl0[i + 1] - Wl0[i]) / (fl0[i + 1] - fl0[i]) * (f - fl0[i]))
+            V = 1.0 if l == 0 else abs(p[Nmax + l - 1])
+            H = abs(p[n] / (math.pi * G)) * V if do_amp else abs(p[n] * V)
+            if l == 0:
+                ratios = np.ones(1)
+            elif mid == 12:
+                base = {1: q, 2: q + 2, 3: q + 5}[l]
+                ratios = np.array([abs(p[base + abs(m)]) for m in range(-l, l + 1)])
+            else:
+                ratios = closed_form_ratios(l, inc)
+            if G >= 1 and f_win >= 1:
+                hw = trunc_c * (l * f_win + G) if l else trunc_c * G * 2.2
+            elif G <= 1 and f_win >= 1:
+                hw = trunc_c * (l * f_win + 1) if l else trunc_c * 2.2
+            elif G >= 1:
+                hw = trunc_c * (l + G) if l else trunc_c * 2.2 * G
+            else:
+                hw = trunc_c * (l + 1) if l else trunc_c * 2.2
+            imin = max(0, math.floor((f - hw - x[0]) / step))
+            imax = min(x.size, math.ceil((f + hw - x[0]) / step))
+            xs = x[imin:imax]
+            A = 1.0 if asym == 0 else (1 + asym * (xs / f - 1)) ** 2 + (0.5 * G * asym / f) ** 2
+            for m in range(-l, l + 1):
+                if l == 0:
+                    nu = f
+                else:
+                    Q = (l * (l + 1) - 3 * m * m) / ((2 * l - 1) * (2 * l + 3))
+                    if l == 2:
+                        clm = (5 * m ** 3 - 17 * m) / 3.0
+                    elif l == 1 and mid not in (6, 7, 8):
+                        clm = m
+                    else:
+                        clm = 0.0
+                    nu = f * (1 + eta * Q) + m * fs[l] + clm * a3
+                M[imin:imax] += H * ratios[m + l] * A / (1 + 4 * (xs - nu) ** 2 / G ** 2)
+    noise = np.abs(p[z:z + 10])
+    for k in range(3):
+        if noise[3 * k + 1] != 0:
+            M += noise[3 * k] / (1 + (1e-3 * noise[3 * k + 1] * x) ** noise[3 * k + 2])
+    return M + noise[9]
+
+
+@pytest.mark.parametrize("mid", [2, 3, 6, 7, 8, 12])
+@pytest.mark.parametrize("lmax", [0, 1, 2, 3])
+@pytest.mark.parametrize("kw", [dict(), dict(asym=-12.0, do_amp=True, trunc_c=5.0)], ids=["plain", "asym-amp-c5"])
+def test_model_any_lmax_against_numpy_restatement(orc, mid, lmax, kw):
+    """The oracle's model itself at every lmax -- l = 3 of the a1l family and id 12's l = 3 ratios included -- since
+    the finite-difference pins of tests/test_oracle_grad.py only check the gradient against this same model."""
+    w = W.layout(mid, lmax, Nx=6000, noise=((11.049588, 49.669854, 4.0), (0.9, 1.35, 0.0), (0.4, 8.0, 2.45)), **kw)
+    m, st = orc.model(mid, w["params_true"], w["plength"], w["x"])
+    assert st == 0
+    ref = numpy_global_any_lmax(w, w["x"])
+    assert np.max(np.abs(m - ref) / ref) < 1e-13
+
+
 def test_ids_2_and_3_agree_on_equivalent_parameters(orc):
     # id 3 takes a1 and the inclination directly; id 2 derives them from sqrt(a1) cos i / sin i
     w2 = W.make(2, Nx=5000)

@@ -139,3 +139,64 @@ def test_gradient_scales_with_temperature_and_p(orc):
     gp, *_ = orc.grad_analytic(2, w["plength"], w["x"], y, P, [1.0], idx, likelihood_p=2.9)
     assert np.allclose(g4 * 4.0, g1, rtol=1e-15, atol=0)
     assert np.allclose(gp, 2.0 * g1, rtol=1e-15, atol=0)
+
+
+# ---------------------------------------------------------------- layouts beyond the C2 star (tests/workloads.py: layout)
+LAYOUT_IDS = [2, 3, 6, 7, 8, 9, 10, 12, 13]
+
+
+def _layout_check(orc, w, seed, idx=None, nchains=2):
+    mid = w["model_case"]
+    m, st = orc.model(mid, w["params_true"], w["plength"], w["x"])
+    assert st == 0
+    y = synth.make_spectrum(m, seed=seed)
+    P = W.perturbed(w, nchains, scale=0.002, seed=5)
+    return entrywise_error(orc, mid, w, y, P, np.array([1.0, 3.7])[:nchains], w["index_to_relax"] if idx is None else idx)
+
+
+@pytest.mark.parametrize("mid", LAYOUT_IDS)
+@pytest.mark.parametrize("lmax", [0, 1, 2, 3])
+@pytest.mark.parametrize("kw", [dict(), dict(asym=25.0, do_amp=True)], ids=["plain", "asym-amp"])
+def test_analytic_gradient_every_global_id_at_lmax(orc, mid, lmax, kw):
+    """Global ids at lmax = 3 (the l = 3 splitting of the a1l family, id 12's l = 3 ratios, id 13's l = 3 heights) and
+    at lmax = 0 / 1 (layouts without interpolated widths or with one visibility), no window, all variables."""
+    w = W.layout(mid, lmax, Nmax=4, Nx=3000, trunc_c=10000.0, **kw)
+    _layout_check(orc, w, seed=43 + mid + lmax)
+
+
+@pytest.mark.parametrize("mid", [11, 14])
+def test_analytic_gradient_local_ids_with_l3_modes(orc, mid):
+    w = W.layout(mid, Nx=3000, trunc_c=10000.0, asym=25.0, do_amp=True)
+    assert w["plength"][5] > 0
+    _layout_check(orc, w, seed=47 + mid)
+
+
+@pytest.mark.parametrize("mid", [2, 13])
+@pytest.mark.parametrize("noise", [((11.049588, 49.669854, 4.0), (0.93569041, 1.3516447, 0.0), (0.4, 8.0, 2.45)),
+                                   ((-11.049588, 49.669854, 3.3), (0.93569041, -1.3516447, 2.0), (0.4, 8.0, -1.7)),
+                                   ()],
+                         ids=["three-p0-nonint", "negative", "none"])
+def test_analytic_gradient_harvey_backgrounds(orc, mid, noise):
+    """Three active profiles (one with p = 0: the constant H/2, one with a non-integer p), negative H / tau / p (the
+    model takes their absolute values), and no active profile."""
+    w = W.layout(mid, 3, noise=noise, Nmax=4, Nx=3000, trunc_c=10000.0)
+    _layout_check(orc, w, seed=53 + mid)
+
+
+@pytest.mark.parametrize("mid", [6, 12])
+def test_analytic_gradient_window_on_at_lmax3(orc, mid):
+    """lmax = 3 with the truncation window on: the variables that move no window edge (see
+    test_analytic_gradient_with_the_window_on)."""
+    w = W.layout(mid, 3, Nmax=4, Nx=3000, trunc_c=7.0, asym=10.0)
+    pl = w["plength"]
+    Nmax, nvis = int(pl[0]), int(pl[1])
+    s = int(pl[0] + pl[1] + pl[2:6].sum())
+    z = s + int(pl[6]) + int(pl[7])
+    q = z + int(pl[8])
+    keep = np.zeros(w["params_true"].size, dtype=bool)
+    keep[:Nmax + nvis] = True
+    keep[[s + 1, s + 2, s + 5]] = True
+    keep[z:q + int(pl[9])] = True
+    idx = np.array([i for i in w["index_to_relax"] if keep[i]], dtype=np.int32)
+    assert idx.size >= 10
+    _layout_check(orc, w, seed=59 + mid, idx=idx)

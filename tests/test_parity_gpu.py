@@ -3,8 +3,8 @@ seeded inputs.  Tolerances (written here once):
     log-likelihood  : |dL| <= 1e-10 * |L|          (north-star: "log-L within 1e-10 relative")
     model spectrum  : max |dM|/M <= 1e-12 per bin
     status codes    : identical
-    gradient        : vs Richardson finite differences of the ORACLE logL, 2e-5 relative to the
-                      largest gradient entry of the chain (FD noise floor; the reference has no gradient)
+    gradient        : every entry against the oracle's analytic gradient, with the per-entry bar of
+                      tests/gradcheck.py (the reference has no gradient)
 """
 import numpy as np
 import pytest
