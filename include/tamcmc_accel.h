@@ -105,6 +105,38 @@ int tamcmc_ctx_set_vars(tamcmc_ctx *ctx, int32_t Nvars, const int32_t *index_to_
 int tamcmc_ctx_set_spectra(tamcmc_ctx *ctx, int32_t Nspectra, const double *y, const double *sigma_y);
 int tamcmc_ctx_set_chain_spectrum(tamcmc_ctx *ctx, int32_t Nchains, const int32_t *spectrum_of_chain);
 
+/* Extension: fit GROUPS -- the likelihood batches of several contexts (different grids, model ids, likelihoods, parameter
+ * layouts: the slices of a local fit, an ensemble of stars) evaluated together, one launch per kernel kind (at most a
+ * setup launch, a fused one-tile launch and two eval launches -- the generic body of chi_square and ids 0 / 1 apart --
+ * instead of one to two launches per context).
+ *   create      members: n_members distinct contexts on one device, 1 <= n_members <= TAMCMC_GROUP_MAX_MEMBERS.  A
+ *               context counts the groups it belongs to; while that count is non-zero tamcmc_ctx_destroy returns
+ *               TAMCMC_E_INVALID and leaves it intact: destroy the group first.
+ *   eval        host pointers, synchronous.  Nchains[k] >= 0 chains of member k (0: the member sits this call out; the
+ *               sum must be >= 1), Nparams[k] must equal member k's.  params / Tcoefs / logL / status are the members'
+ *               blocks concatenated in member order (member k: Nchains[k] rows of Nparams[k]); status may be NULL.
+ *               One pinned staging area, one copy in, one copy out.
+ *   eval_device the same with device pointers, enqueued on the group's stream without synchronising; d_status may be NULL.
+ * Results: every chain's logL and status are bit for bit what its member returns alone through tamcmc_eval_batch --
+ * multi-spectrum members included (their chain map applies, and must cover the member's batch as set_spectra requires).
+ * Refused with TAMCMC_E_INVALID: NULL arguments, an Nparams mismatch, a negative count or an all-zero call, a member
+ * that is armed or has a batch in flight, and a call whose 1-D launch would exceed 2^32 work-items.
+ * Ordering: the group has a stream of its own (set_stream replaces it).  Work enqueued earlier on a member's stream runs
+ * before a group call that includes the member, and work enqueued later on it runs after: solo calls and group calls
+ * on the same contexts may alternate without any synchronisation by the caller.  Calls on one group, and on its
+ * members, must be serialised by the caller as for a context.
+ * Out of scope: gradients and model rows -- use a member alone for those. */
+#define TAMCMC_GROUP_MAX_MEMBERS 1024
+typedef struct tamcmc_group tamcmc_group;
+int tamcmc_group_create(tamcmc_group **out, int32_t n_members, tamcmc_ctx *const *members);
+int tamcmc_group_eval(tamcmc_group *g, const int32_t *Nchains, const int32_t *Nparams, const double *params,
+                      const double *Tcoefs, double *logL, int32_t *status);
+int tamcmc_group_eval_device(tamcmc_group *g, const int32_t *Nchains, const int32_t *Nparams, const double *d_params,
+                             const double *d_Tcoefs, double *d_logL, int32_t *d_status);
+int tamcmc_group_set_stream(tamcmc_group *g, void *hip_stream);
+int tamcmc_group_synchronize(tamcmc_group *g);
+int tamcmc_group_destroy(tamcmc_group *g);
+
 /* Replaces: the `for chain` loop of generate_model() calls (MALA.cpp:632-639, model_def.cpp:139-143).
  * Host pointers, row-major.  Synchronous: results are valid on return.
  *   params      Nchains x Nparams
@@ -190,6 +222,7 @@ int tamcmc_ctx_clock_probe_end(tamcmc_ctx *ctx, double *core_GHz, double *second
 int tamcmc_ctx_geometry(tamcmc_ctx *ctx, int32_t *bins_per_tile, int32_t *tiles, int32_t *threads_per_block,
                         int32_t *n_multiplets);
 
+/* TAMCMC_E_INVALID (and nothing happens) while the context is a member of a fit group. */
 int tamcmc_ctx_destroy(tamcmc_ctx *ctx);
 
 int tamcmc_device_count(void);

@@ -25,6 +25,8 @@ EXPORTS = [
     "tamcmc_model_explicit", "tamcmc_ctx_set_stream", "tamcmc_ctx_synchronize", "tamcmc_ctx_profile",
     "tamcmc_ctx_kernel_time", "tamcmc_ctx_clock_probe_begin", "tamcmc_ctx_clock_probe_end", "tamcmc_ctx_geometry", "tamcmc_ctx_destroy", "tamcmc_device_count",
     "tamcmc_strerror", "tamcmc_last_hip_error", "tamcmc_version",
+    "tamcmc_group_create", "tamcmc_group_eval", "tamcmc_group_eval_device", "tamcmc_group_set_stream",
+    "tamcmc_group_synchronize", "tamcmc_group_destroy",
 ]
 
 
@@ -70,6 +72,12 @@ def load_library():
     lib.tamcmc_strerror.restype = C.c_char_p
     lib.tamcmc_last_hip_error.restype = C.c_char_p
     lib.tamcmc_version.restype = C.c_char_p
+    lib.tamcmc_group_create.argtypes = [C.POINTER(vp), C.c_int32, C.POINTER(vp)]
+    lib.tamcmc_group_eval.argtypes = [vp, ip, ip, dp, dp, dp, ip]
+    lib.tamcmc_group_eval_device.argtypes = [vp, ip, ip, vp, vp, vp, vp]
+    lib.tamcmc_group_set_stream.argtypes = [vp, vp]
+    lib.tamcmc_group_synchronize.argtypes = [vp]
+    lib.tamcmc_group_destroy.argtypes = [vp]
     for name in EXPORTS:
         fn = getattr(lib, name)
         if fn.restype is not C.c_char_p:
@@ -124,7 +132,8 @@ class Accel:
 
     def close(self):
         if getattr(self, "_ctx", None) is not None and self._ctx.value:
-            self._lib.tamcmc_ctx_destroy(self._ctx)
+            # refused (and the context kept) while a fit group holds it: close the Group first
+            self._check(self._lib.tamcmc_ctx_destroy(self._ctx), "tamcmc_ctx_destroy")
             self._ctx = C.c_void_p()
 
     def __del__(self):
@@ -269,6 +278,77 @@ class Accel:
         v = [C.c_int32(0) for _ in range(4)]
         self._check(self._lib.tamcmc_ctx_geometry(self._ctx, *[C.byref(e) for e in v]), "tamcmc_ctx_geometry")
         return dict(bins_per_tile=v[0].value, tiles=v[1].value, threads_per_block=v[2].value, n_multiplets=v[3].value)
+
+
+class Group:
+    """A fit group (tamcmc_accel.h, tamcmc_group_*): the likelihood batches of several Accel contexts -- different grids,
+    model ids, layouts -- in one call.  Every chain's result equals its member's own eval_batch bit for bit.  The group
+    keeps references to its members; a member cannot be closed while the group is open."""
+
+    def __init__(self, accels):
+        self._lib = load_library()
+        self.members = list(accels)
+        self._g = C.c_void_p()
+        arr = (C.c_void_p * max(len(self.members), 1))(*[a._ctx.value for a in self.members])
+        self._check(self._lib.tamcmc_group_create(C.byref(self._g), len(self.members), arr), "tamcmc_group_create")
+        self.Nparams = np.array([a.Nparams for a in self.members], dtype=np.int32)
+
+    _check = Accel._check
+
+    def _counts(self, P_list, T_list):
+        if len(P_list) != len(self.members) or len(T_list) != len(self.members):
+            raise ValueError(f"expected {len(self.members)} params / Tcoefs blocks")
+        P = [_c64(p).reshape(-1, a.Nparams) for p, a in zip(P_list, self.members)]
+        T = [_c64(t).reshape(-1) for t in T_list]
+        n = np.array([p.shape[0] for p in P], dtype=np.int32)
+        if any(t.size != k for t, k in zip(T, n)):
+            raise ValueError("Tcoefs block sizes must match the params blocks")
+        return P, T, n
+
+    def eval(self, P_list, T_list):
+        """P_list[k]: (n_k, Nparams_k) rows of member k (n_k may be 0).  Returns (list of logL, list of status)."""
+        P, T, n = self._counts(P_list, T_list)
+        Pc = np.ascontiguousarray(np.concatenate([p.ravel() for p in P])) if P else np.empty(0)
+        Tc = np.ascontiguousarray(np.concatenate(T))
+        logL = np.empty(int(n.sum()))
+        st = np.empty(int(n.sum()), dtype=np.int32)
+        self._check(self._lib.tamcmc_group_eval(self._g, _iptr(n), _iptr(self.Nparams), _dptr(Pc), _dptr(Tc), _dptr(logL),
+                                                _iptr(st)), "tamcmc_group_eval")
+        cut = np.cumsum(n)[:-1]
+        return np.split(logL, cut), np.split(st, cut)
+
+    def eval_device(self, nchains, d_params, d_T, d_logL, d_status=0):
+        """Device pointers (ints, e.g. torch.Tensor.data_ptr()) of the concatenated blocks; enqueued, no sync."""
+        n = np.ascontiguousarray(nchains, dtype=np.int32).ravel()
+        if n.size != len(self.members):
+            raise ValueError(f"expected {len(self.members)} chain counts, got {n.size}")
+        rc = self._lib.tamcmc_group_eval_device(self._g, _iptr(n), _iptr(self.Nparams), C.c_void_p(d_params), C.c_void_p(d_T),
+                                                C.c_void_p(d_logL), C.c_void_p(d_status) if d_status else None)
+        self._check(rc, "tamcmc_group_eval_device")
+
+    def set_stream(self, hip_stream):
+        self._check(self._lib.tamcmc_group_set_stream(self._g, C.c_void_p(hip_stream) if hip_stream else None),
+                    "tamcmc_group_set_stream")
+
+    def synchronize(self):
+        self._check(self._lib.tamcmc_group_synchronize(self._g), "tamcmc_group_synchronize")
+
+    def close(self):
+        if getattr(self, "_g", None) is not None and self._g.value:
+            self._lib.tamcmc_group_destroy(self._g)
+            self._g = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
 
 
 def device_count():

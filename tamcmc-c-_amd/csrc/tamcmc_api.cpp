@@ -10,6 +10,7 @@
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
+#include <algorithm>
 #include <cstring>
 #include <new>
 #include <type_traits>
@@ -17,6 +18,7 @@
 
 #include "tamcmc_accel.h"
 #include "tamcmc_dev.h"
+#include "tamcmc_group.h"
 
 static thread_local char g_hip_err[256] = "";
 
@@ -93,6 +95,7 @@ struct tamcmc_ctx {
     long long profile_count = 0;
     std::vector<hipEvent_t> ev;   // pairs (start, stop)
     size_t ev_used = 0;
+    int groups = 0;               // fit groups this context is a member of (tamcmc_group_create); destroy is refused meanwhile
 };
 
 static int pick_tiles(const tamcmc_ctx *c, int Nchains, bool grad);
@@ -358,6 +361,7 @@ extern "C" int tamcmc_ctx_create(tamcmc_ctx **out, int device_id, int model_case
 extern "C" int tamcmc_ctx_destroy(tamcmc_ctx *c)
 {
     if (!c) return TAMCMC_OK;
+    if (c->groups > 0) return TAMCMC_E_INVALID;     // a fit group still refers to it: destroy the group first
     (void)hipSetDevice(c->device);
     if (c->armed && c->h_gate) { __atomic_store_n(c->h_gate, c->gate_seq, __ATOMIC_RELEASE); c->armed = 0; }   // let the gate go
     if (c->stream) (void)hipStreamSynchronize(c->stream);
@@ -551,6 +555,29 @@ static int pick_tiles(const tamcmc_ctx *c, int /*Nchains*/, bool grad)
     return grad ? c->tiles_g : c->tiles_l;
 }
 
+// Arguments of the eval launch of a batch on the context (solo launches and fit groups alike).
+static TmEvalArgs eval_args(const tamcmc_ctx *c, int tiles, bool grad, double *d_logL, int32_t *d_status, const int32_t *d_rows,
+                            double *d_model)
+{
+    TmEvalArgs a{};
+    a.x2 = c->d_x2; a.y = c->d_y; a.lx = c->d_lx; a.isig2 = c->d_isig2;
+    a.spec = (c->nspec > 1) ? c->d_spec : nullptr;
+    a.mult = c->d_mult; a.noise = c->d_noise; a.cell = c->d_cell; a.thdr = c->d_thdr; a.tidx = c->d_tidx; a.wt = c->d_wt;
+    a.part = c->d_part; a.gmult = grad ? c->d_gmult : nullptr; a.gnoise = grad ? c->d_gnoise : nullptr;
+    a.row_of_chain = d_rows; a.model_out = d_model;
+    a.ticket = grad ? nullptr : c->d_ticket; a.logL = d_logL; a.status = d_status;
+    a.Nx = c->L.Nx; a.n_mult = c->L.n_mult; a.tiles = tiles; a.cells = c->cells; a.likelihood_case = c->L.likelihood_case;
+    a.like_p = c->L.like_p;
+    a.order = c->d_order; a.order_mode = (tiles <= 65535) ? c->order_mode : 0; a.prio = c->prio;
+    a.generic = (c->L.likelihood_case != 0 || c->L.family == TM_FAM_GAUSS || d_rows != nullptr) ? 1 : 0;
+    if (tiles == 1 && a.order_mode == 2) a.order_mode = 1;     // nothing to rank
+    a.tile_magic = ((1ULL << 40) + (unsigned long long)tiles - 1) / (unsigned long long)tiles;
+    return a;
+}
+
+// one tile per chain (short grids): prologue and evaluation share a launch (TAMCMC_TILES=1 on a 9..16-unit grid: two launches)
+static bool takes_fused(const tamcmc_ctx *c, int tiles) { return tiles == 1 && c->fuse != 0 && c->units <= TM_TILE_MAXU; }
+
 // Enqueue setup -> eval (-> backward) for device-resident inputs on the context stream.
 static int enqueue(tamcmc_ctx *c, int Nchains, const double *d_params, const double *d_T, double *d_logL,
                    double *d_grad, int32_t *d_status, const int32_t *d_rows, double *d_model)
@@ -563,26 +590,11 @@ static int enqueue(tamcmc_ctx *c, int Nchains, const double *d_params, const dou
     const int units = c->units, cells = c->cells;
     const int tiles = pick_tiles(c, Nchains, grad);
     if (!grad) c->last_tiles = tiles;
-    double *const p_gmult = grad ? c->d_gmult : nullptr;
-    double *const p_gnoise = grad ? c->d_gnoise : nullptr;
     double *const p_hser = grad ? c->d_hser : nullptr;
     void *const p_chain_rec = grad ? c->d_chain_rec : nullptr;
     void *const p_aux = grad ? c->d_aux : nullptr;
-    TmEvalArgs a{};
-    a.x2 = c->d_x2; a.y = c->d_y; a.lx = c->d_lx; a.isig2 = c->d_isig2;
-    a.spec = (c->nspec > 1) ? c->d_spec : nullptr;
-    a.mult = c->d_mult; a.noise = c->d_noise; a.cell = c->d_cell; a.thdr = c->d_thdr; a.tidx = c->d_tidx; a.wt = c->d_wt;
-    a.part = c->d_part; a.gmult = p_gmult; a.gnoise = p_gnoise;
-    a.row_of_chain = d_rows; a.model_out = d_model;
-    a.ticket = grad ? nullptr : c->d_ticket; a.logL = d_logL; a.status = d_status;
-    a.Nx = c->L.Nx; a.n_mult = c->L.n_mult; a.tiles = tiles; a.cells = cells; a.likelihood_case = c->L.likelihood_case;
-    a.like_p = c->L.like_p;
-    a.order = c->d_order; a.order_mode = (tiles <= 65535) ? c->order_mode : 0; a.prio = c->prio;
-    a.generic = (c->L.likelihood_case != 0 || c->L.family == TM_FAM_GAUSS || d_rows != nullptr) ? 1 : 0;
-    if (tiles == 1 && a.order_mode == 2) a.order_mode = 1;     // nothing to rank
-    a.tile_magic = ((1ULL << 40) + (unsigned long long)tiles - 1) / (unsigned long long)tiles;
-    // one tile per chain (short grids): prologue and evaluation share a launch
-    const bool fused = (tiles == 1) && c->fuse != 0 && units <= TM_TILE_MAXU;   // (TAMCMC_TILES=1 on a 9..16-unit grid: two launches)
+    const TmEvalArgs a = eval_args(c, tiles, grad, d_logL, d_status, d_rows, d_model);
+    const bool fused = takes_fused(c, tiles);
     int rc = 0;
     if (!fused) {
         rc = tm_launch_setup(c->L, Nchains, d_params, d_T, c->d_wt, c->d_lx, units, cells, tiles, c->equal_cost, grad ? c->cost_g : c->cost_l,
@@ -621,7 +633,7 @@ static int enqueue(tamcmc_ctx *c, int Nchains, const double *d_params, const dou
         // finalize happens inside the eval launch (last-arriving workgroup per chain)
     } else {
         rc = tm_launch_backward(c->L, Nchains, units, cells, tiles, tm_setup_balances(units, tiles, c->equal_cost, (grad ? c->cost_g : c->cost_l).pad), c->cost_g, d_params, c->d_wt, p_chain_rec, p_aux, c->d_noise, c->d_part,
-                                p_gmult, p_gnoise, c->d_cell, c->d_thdr, p_hser, c->Nvars, c->d_relax, d_grad, d_logL, d_status,
+                                a.gmult, a.gnoise, c->d_cell, c->d_thdr, p_hser, c->Nvars, c->d_relax, d_grad, d_logL, d_status,
                                 stream);
         if (rc != 0) { snprintf(g_hip_err, sizeof(g_hip_err), "backward launch -> %s", hipGetErrorString((hipError_t)rc)); return TAMCMC_E_HIP; }
     }
@@ -961,6 +973,318 @@ extern "C" int tamcmc_model_explicit(tamcmc_ctx *c, int32_t Nparams, const doubl
     int rc = tamcmc_eval_batch(c, 1, Nparams, params, &T, &logL, nullptr, 1, &row, model_out, &st);
     if (status) *status = st;
     return rc;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// Fit groups (tamcmc_accel.h, tamcmc_group.h): the likelihood batches of several contexts in one launch per kernel kind.
+struct tamcmc_group {
+    int device = 0;
+    std::vector<tamcmc_ctx *> m;
+    hipStream_t own_stream = nullptr, stream = nullptr;
+    std::vector<hipEvent_t> ev_before;   // per member: recorded on its stream, waited for by the group stream
+    hipEvent_t ev_after = nullptr;       // recorded on the group stream after a call's launches, waited for by the members
+    hipEvent_t ev_done = nullptr;        // completion of a host-pointer call (polled)
+    // descriptor table: one device copy (rewritten in stream order) from two pinned host images, so that the image a
+    // pending upload reads is never the one being filled
+    char *d_tab = nullptr;
+    size_t d_tab_cap = 0;
+    char *h_tab[2] = {nullptr, nullptr};
+    size_t h_tab_cap[2] = {0, 0};
+    hipEvent_t ev_tab[2] = {nullptr, nullptr};
+    bool tab_pending[2] = {false, false};
+    int tab_slot = 0;
+    std::vector<char> last;              // the table as last uploaded
+    // host-pointer calls: one pinned staging area [params | Tcoefs | logL | status] and its device copy
+    char *h_stage = nullptr, *d_stage = nullptr;
+    size_t stage_cap = 0;
+    bool counted = false;                // the members' group counts include this group (set once creation succeeded)
+};
+
+static bool generic_body(const tamcmc_ctx *c) { return eval_args(c, 1, false, nullptr, nullptr, nullptr, nullptr).generic != 0; }
+
+// Everything a group call refuses, checked before anything is allocated or enqueued.
+static int group_check(const tamcmc_group *g, const int32_t *Nchains, const int32_t *Nparams)
+{
+    if (!g || !Nchains || !Nparams) return TAMCMC_E_INVALID;
+    long long total = 0, wg_setup = 0, wg_fused = 0, wg_eval[2] = {0, 0};
+    for (size_t k = 0; k < g->m.size(); k++) {
+        const tamcmc_ctx *c = g->m[k];
+        const int nc = Nchains[k];
+        if (nc < 0 || Nparams[k] != c->L.Nparams || c->armed || c->in_flight) return TAMCMC_E_INVALID;
+        if (nc == 0) continue;
+        if (c->nspec > 1 && (c->d_spec == nullptr || nc > c->spec_n)) return TAMCMC_E_INVALID;   // the map must cover the batch
+        total += nc;
+        const int tiles = pick_tiles(c, nc, false);
+        if (takes_fused(c, tiles)) wg_fused += nc;
+        else { wg_setup += nc; wg_eval[generic_body(c) ? 1 : 0] += (long long)nc * tiles; }
+    }
+    if (total < 1) return TAMCMC_E_INVALID;
+    // 1-D launches: workgroups x threads must stay within 32 bits
+    const long long lim = 0xFFFFFFFFLL;
+    if (wg_setup > lim / TM_SETUP_THREADS || wg_fused > lim / TM_THREADS || wg_eval[0] > lim / TM_THREADS ||
+        wg_eval[1] > lim / TM_THREADS)
+        return TAMCMC_E_INVALID;
+    return TAMCMC_OK;
+}
+
+// Uploads the table when it differs from the one the device holds (stream-ordered: launches already enqueued keep
+// reading the previous contents).
+static int group_upload(tamcmc_group *g, const std::vector<char> &tab)
+{
+    if (tab == g->last) return TAMCMC_OK;
+    if (tab.size() > g->d_tab_cap) {
+        TM_HIP(hipStreamSynchronize(g->stream));
+        (void)hipFree(g->d_tab); g->d_tab = nullptr; g->d_tab_cap = 0;
+        TM_HIP(hipMalloc(&g->d_tab, tab.size()));
+        g->d_tab_cap = tab.size();
+    }
+    const int s = g->tab_slot ^= 1;
+    if (g->tab_pending[s]) { TM_HIP(hipEventSynchronize(g->ev_tab[s])); g->tab_pending[s] = false; }
+    if (tab.size() > g->h_tab_cap[s]) {
+        (void)hipHostFree(g->h_tab[s]); g->h_tab[s] = nullptr; g->h_tab_cap[s] = 0;
+        TM_HIP(hipHostMalloc(reinterpret_cast<void **>(&g->h_tab[s]), tab.size(), hipHostMallocDefault));
+        g->h_tab_cap[s] = tab.size();
+    }
+    std::memcpy(g->h_tab[s], tab.data(), tab.size());
+    g->last.clear();                     // (a failed copy leaves no claim about the device contents)
+    TM_HIP(hipMemcpyAsync(g->d_tab, g->h_tab[s], tab.size(), hipMemcpyHostToDevice, g->stream));
+    TM_HIP(hipEventRecord(g->ev_tab[s], g->stream));
+    g->tab_pending[s] = true;
+    g->last = tab;
+    return TAMCMC_OK;
+}
+
+// Enqueue one group call on the group stream: member k's chains read Nchains[k] rows of Nparams[k] from d_params (blocks
+// in member order) and write their logL / status at their offset in the concatenated outputs.  group_check has passed.
+static int group_enqueue(tamcmc_group *g, const int32_t *Nchains, const double *d_params, const double *d_T, double *d_logL,
+                         int32_t *d_status)
+{
+    const int n = (int)g->m.size();
+    bool grow = false;
+    for (int k = 0; k < n; k++) grow = grow || Nchains[k] > g->m[k]->cap;
+    if (grow) TM_HIP(hipStreamSynchronize(g->stream));   // an earlier group launch may still use the buffers about to move
+    for (int k = 0; k < n; k++)
+        if (Nchains[k] > 0) { const int rc = ensure_capacity(g->m[k], Nchains[k], false); if (rc != TAMCMC_OK) return rc; }
+
+    std::vector<TmGroupSetup> su;
+    std::vector<TmGroupFused> fu;
+    std::vector<TmEvalArgs> ev[2];
+    std::vector<int32_t> su_pre{0}, fu_pre{0}, ev_pre[2] = {{0}, {0}}, ev_nch[2];
+    size_t lds_su = 8, lds_fu = 8;
+    size_t po = 0, co = 0;
+    for (int k = 0; k < n; k++) {
+        tamcmc_ctx *c = g->m[k];
+        const int nc = Nchains[k];
+        if (nc > 0) {
+            const int tiles = pick_tiles(c, nc, false);
+            const double *P = d_params + po, *T = d_T + co;
+            const TmEvalArgs a = eval_args(c, tiles, false, d_logL + co, d_status ? d_status + co : nullptr, nullptr, nullptr);
+            const int p_doubles = (c->L.Nparams + 1) & ~1;
+            if (takes_fused(c, tiles)) {
+                TmGroupFused d{};
+                d.L = c->L; d.a = a;
+                d.f.params = P; d.f.Tcoefs = T; d.f.p_doubles = p_doubles;
+                fu.push_back(d);
+                fu_pre.push_back(fu_pre.back() + nc);
+                lds_fu = std::max(lds_fu, ((size_t)p_doubles + 1) * sizeof(double));     // as tm_launch_fused
+            } else {
+                TmGroupSetup d{};
+                d.L = c->L; d.params = P; d.Tcoefs = T; d.wt = c->d_wt; d.lx = c->d_lx;
+                d.mult = c->d_mult; d.noise = c->d_noise; d.cell = c->d_cell; d.thdr = c->d_thdr; d.tidx = c->d_tidx;
+                d.order = (a.order_mode == 2) ? c->d_order : nullptr;
+                d.cm = c->cost_l; d.units = c->units; d.cells = c->cells; d.tiles = tiles;
+                d.eq = tm_setup_balances(c->units, tiles, c->equal_cost, c->cost_l.pad);
+                d.p_doubles = p_doubles;
+                su.push_back(d);
+                su_pre.push_back(su_pre.back() + nc);
+                lds_su = std::max(lds_su, (size_t)p_doubles * sizeof(double) + (d.eq ? (size_t)c->units * sizeof(int) : 0));   // as tm_launch_setup
+                const int gen = a.generic ? 1 : 0;
+                ev[gen].push_back(a);
+                ev_pre[gen].push_back(ev_pre[gen].back() + nc * tiles);
+                ev_nch[gen].push_back(nc);
+            }
+        }
+        po += (size_t)nc * (size_t)c->L.Nparams;
+        co += (size_t)nc;
+    }
+    // the table, one section per array at 256-byte boundaries (tamcmc_group.h)
+    std::vector<char> tab;
+    auto put = [&](const void *src, size_t bytes) {
+        const size_t off = (tab.size() + 255) & ~(size_t)255;
+        tab.resize(off + (bytes > 0 ? bytes : 1));
+        if (bytes) std::memcpy(tab.data() + off, src, bytes);
+        return off;
+    };
+    const size_t o_su_pre = put(su_pre.data(), su_pre.size() * sizeof(int32_t)), o_su = put(su.data(), su.size() * sizeof(TmGroupSetup));
+    const size_t o_fu_pre = put(fu_pre.data(), fu_pre.size() * sizeof(int32_t)), o_fu = put(fu.data(), fu.size() * sizeof(TmGroupFused));
+    size_t o_ev_pre[2], o_ev_nch[2], o_ev[2];
+    for (int gen = 0; gen < 2; gen++) {
+        o_ev_pre[gen] = put(ev_pre[gen].data(), ev_pre[gen].size() * sizeof(int32_t));
+        o_ev_nch[gen] = put(ev_nch[gen].data(), ev_nch[gen].size() * sizeof(int32_t));
+        o_ev[gen] = put(ev[gen].data(), ev[gen].size() * sizeof(TmEvalArgs));
+    }
+
+    // work enqueued earlier on a member's stream comes first
+    for (int k = 0; k < n; k++) {
+        tamcmc_ctx *c = g->m[k];
+        if (Nchains[k] > 0 && c->stream != g->stream) {
+            TM_HIP(hipEventRecord(g->ev_before[k], c->stream));
+            TM_HIP(hipStreamWaitEvent(g->stream, g->ev_before[k], 0));
+        }
+    }
+    int rc = group_upload(g, tab);
+    if (rc != TAMCMC_OK) return rc;
+    const char *D = g->d_tab;
+    const char *what = "";
+    int hr = 0;
+    if (!su.empty()) {
+        what = "group setup launch";
+        hr = tm_launch_group_setup(reinterpret_cast<const TmGroupSetup *>(D + o_su), reinterpret_cast<const int32_t *>(D + o_su_pre),
+                                   (int)su.size(), su_pre.back(), lds_su, g->stream);
+    }
+    if (hr == 0 && !fu.empty()) {
+        what = "group fused launch";
+        hr = tm_launch_group_fused(reinterpret_cast<const TmGroupFused *>(D + o_fu), reinterpret_cast<const int32_t *>(D + o_fu_pre),
+                                   (int)fu.size(), fu_pre.back(), lds_fu, g->stream);
+    }
+    for (int gen = 0; gen < 2 && hr == 0; gen++) {
+        if (ev[gen].empty()) continue;
+        what = "group eval launch";
+        hr = tm_launch_group_eval(reinterpret_cast<const TmEvalArgs *>(D + o_ev[gen]), reinterpret_cast<const int32_t *>(D + o_ev_pre[gen]),
+                                  reinterpret_cast<const int32_t *>(D + o_ev_nch[gen]), (int)ev[gen].size(), ev_pre[gen].back(),
+                                  gen == 1, g->stream);
+    }
+    if (hr != 0) {
+        snprintf(g_hip_err, sizeof(g_hip_err), "%s -> %s", what, hipGetErrorString((hipError_t)hr));
+        for (int k = 0; k < n; k++)        // arrival counters back to zero
+            if (Nchains[k] > 0) (void)hipMemsetAsync(g->m[k]->d_ticket, 0, (size_t)Nchains[k] * sizeof(int32_t), g->stream);
+        rc = TAMCMC_E_HIP;
+    }
+    // and later work on a member's stream comes after
+    if (hipEventRecord(g->ev_after, g->stream) != hipSuccess) return TAMCMC_E_HIP;
+    for (int k = 0; k < n; k++) {
+        tamcmc_ctx *c = g->m[k];
+        if (Nchains[k] > 0 && c->stream != g->stream && hipStreamWaitEvent(c->stream, g->ev_after, 0) != hipSuccess) return TAMCMC_E_HIP;
+    }
+    return rc;
+}
+
+extern "C" int tamcmc_group_create(tamcmc_group **out, int32_t n_members, tamcmc_ctx *const *members)
+{
+    if (!out) return TAMCMC_E_INVALID;
+    *out = nullptr;
+    if (n_members < 1 || n_members > TM_GROUP_MAX_MEMBERS || !members) return TAMCMC_E_INVALID;
+    for (int k = 0; k < n_members; k++) {
+        if (!members[k] || members[k]->device != members[0]->device) return TAMCMC_E_INVALID;
+        for (int j = 0; j < k; j++) if (members[j] == members[k]) return TAMCMC_E_INVALID;
+    }
+    tamcmc_group *g = new (std::nothrow) tamcmc_group();
+    if (!g) return TAMCMC_E_NOMEM;
+    g->device = members[0]->device;
+    g->m.assign(members, members + n_members);
+    g->ev_before.assign((size_t)n_members, nullptr);
+    auto fail = [&](int code) { tamcmc_group_destroy(g); return code; };
+    if (hipSetDevice(g->device) != hipSuccess) return fail(TAMCMC_E_NODEVICE);
+    if (hipStreamCreateWithFlags(&g->own_stream, hipStreamNonBlocking) != hipSuccess) return fail(TAMCMC_E_HIP);
+    g->stream = g->own_stream;
+    for (auto &e : g->ev_before) if (hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess) return fail(TAMCMC_E_HIP);
+    if (hipEventCreateWithFlags(&g->ev_after, hipEventDisableTiming) != hipSuccess ||
+        hipEventCreateWithFlags(&g->ev_done, hipEventDisableTiming) != hipSuccess ||
+        hipEventCreateWithFlags(&g->ev_tab[0], hipEventDisableTiming) != hipSuccess ||
+        hipEventCreateWithFlags(&g->ev_tab[1], hipEventDisableTiming) != hipSuccess)
+        return fail(TAMCMC_E_HIP);
+    for (tamcmc_ctx *c : g->m) c->groups++;
+    g->counted = true;
+    *out = g;
+    return TAMCMC_OK;
+}
+
+extern "C" int tamcmc_group_destroy(tamcmc_group *g)
+{
+    if (!g) return TAMCMC_OK;
+    (void)hipSetDevice(g->device);
+    if (g->stream) (void)hipStreamSynchronize(g->stream);
+    if (g->counted) for (tamcmc_ctx *c : g->m) c->groups--;
+    (void)hipFree(g->d_tab); (void)hipFree(g->d_stage);
+    (void)hipHostFree(g->h_tab[0]); (void)hipHostFree(g->h_tab[1]); (void)hipHostFree(g->h_stage);
+    for (hipEvent_t e : g->ev_before) if (e) (void)hipEventDestroy(e);
+    for (hipEvent_t e : {g->ev_after, g->ev_done, g->ev_tab[0], g->ev_tab[1]}) if (e) (void)hipEventDestroy(e);
+    if (g->own_stream) (void)hipStreamDestroy(g->own_stream);
+    delete g;
+    return TAMCMC_OK;
+}
+
+extern "C" int tamcmc_group_set_stream(tamcmc_group *g, void *hip_stream)
+{
+    if (!g) return TAMCMC_E_INVALID;
+    TM_HIP(hipSetDevice(g->device));
+    TM_HIP(hipStreamSynchronize(g->stream));
+    g->stream = hip_stream ? (hipStream_t)hip_stream : g->own_stream;
+    return TAMCMC_OK;
+}
+
+extern "C" int tamcmc_group_synchronize(tamcmc_group *g)
+{
+    if (!g) return TAMCMC_E_INVALID;
+    TM_HIP(hipSetDevice(g->device));
+    TM_HIP(hipStreamSynchronize(g->stream));
+    return TAMCMC_OK;
+}
+
+extern "C" int tamcmc_group_eval_device(tamcmc_group *g, const int32_t *Nchains, const int32_t *Nparams, const double *d_params,
+                                        const double *d_Tcoefs, double *d_logL, int32_t *d_status)
+{
+    int rc = group_check(g, Nchains, Nparams);
+    if (rc != TAMCMC_OK) return rc;
+    if (!d_params || !d_Tcoefs || !d_logL) return TAMCMC_E_INVALID;
+    TM_HIP(hipSetDevice(g->device));
+    return group_enqueue(g, Nchains, d_params, d_Tcoefs, d_logL, d_status);
+}
+
+extern "C" int tamcmc_group_eval(tamcmc_group *g, const int32_t *Nchains, const int32_t *Nparams, const double *params,
+                                 const double *Tcoefs, double *logL, int32_t *status)
+{
+    int rc = group_check(g, Nchains, Nparams);
+    if (rc != TAMCMC_OK) return rc;
+    if (!params || !Tcoefs || !logL) return TAMCMC_E_INVALID;
+    TM_HIP(hipSetDevice(g->device));
+    size_t np = 0, nc = 0;
+    for (size_t k = 0; k < g->m.size(); k++) { np += (size_t)Nchains[k] * (size_t)Nparams[k]; nc += (size_t)Nchains[k]; }
+    // staging [params | Tcoefs | logL | status]: one copy in, one copy out
+    const size_t o_out = (np + nc) * sizeof(double), bytes_out = nc * (sizeof(double) + sizeof(int32_t)), bytes = o_out + bytes_out;
+    if (bytes > g->stage_cap) {
+        TM_HIP(hipStreamSynchronize(g->stream));
+        (void)hipHostFree(g->h_stage); (void)hipFree(g->d_stage);
+        g->h_stage = g->d_stage = nullptr; g->stage_cap = 0;
+        TM_HIP(hipHostMalloc(reinterpret_cast<void **>(&g->h_stage), bytes, hipHostMallocDefault));
+        TM_HIP(hipMalloc(&g->d_stage, bytes));
+        g->stage_cap = bytes;
+    }
+    std::memcpy(g->h_stage, params, np * sizeof(double));
+    std::memcpy(g->h_stage + np * sizeof(double), Tcoefs, nc * sizeof(double));
+    // from here on, a failure waits for the stream before it returns: a copy from or into h_stage may still be pending,
+    // and the next call refills it
+    auto fail = [&](int code) { (void)hipStreamSynchronize(g->stream); return code; };
+    hipError_t e = hipMemcpyAsync(g->d_stage, g->h_stage, o_out, hipMemcpyHostToDevice, g->stream);
+    if (e != hipSuccess) { snprintf(g_hip_err, sizeof(g_hip_err), "group input copy -> %s", hipGetErrorString(e)); return fail(TAMCMC_E_HIP); }
+    double *d_in = reinterpret_cast<double *>(g->d_stage);
+    double *d_logL = reinterpret_cast<double *>(g->d_stage + o_out);
+    int32_t *d_status = reinterpret_cast<int32_t *>(g->d_stage + o_out + nc * sizeof(double));
+    rc = group_enqueue(g, Nchains, d_in, d_in + np, d_logL, d_status);
+    if (rc != TAMCMC_OK) return fail(rc);
+    e = hipMemcpyAsync(g->h_stage + o_out, g->d_stage + o_out, bytes_out, hipMemcpyDeviceToHost, g->stream);
+    if (e == hipSuccess) e = hipEventRecord(g->ev_done, g->stream);
+    if (e != hipSuccess) { snprintf(g_hip_err, sizeof(g_hip_err), "group output copy -> %s", hipGetErrorString(e)); return fail(TAMCMC_E_HIP); }
+    // wait by polling an event (see wait_done)
+    for (;;) {
+        e = hipEventQuery(g->ev_done);
+        if (e == hipSuccess) break;
+        if (e != hipErrorNotReady) { snprintf(g_hip_err, sizeof(g_hip_err), "hipEventQuery -> %s", hipGetErrorString(e)); return fail(TAMCMC_E_HIP); }
+        __builtin_ia32_pause();
+    }
+    std::memcpy(logL, g->h_stage + o_out, nc * sizeof(double));
+    if (status) std::memcpy(status, g->h_stage + o_out + nc * sizeof(double), nc * sizeof(int32_t));
+    return TAMCMC_OK;
 }
 
 extern "C" const char *tamcmc_strerror(int code)
