@@ -136,6 +136,28 @@ int tamcmc_group_eval_device(tamcmc_group *g, const int32_t *Nchains, const int3
 int tamcmc_group_set_stream(tamcmc_group *g, void *hip_stream);
 int tamcmc_group_synchronize(tamcmc_group *g);
 int tamcmc_group_destroy(tamcmc_group *g);
+/* tamcmc_group_eval in two halves, for callers that have host work to overlap with the GPU (a sampler per member, see
+ * tamcmc_lockstep in tamcmc_sampler.h): _begin takes the same concatenated blocks and refuses what tamcmc_group_eval
+ * refuses, copies params / Tcoefs into pinned, device-mapped, coherent memory owned by the group and enqueues the
+ * launches, which read them and write logL / status there directly -- no copy-engine transfer; _end waits until every
+ * result has arrived (a few microseconds before the launch retires, as for tamcmc_eval_batch_end) and delivers them
+ * (status may be NULL); same bits as tamcmc_group_eval.  The inputs are double-buffered by call parity: filling the
+ * buffers of one call never touches what a kernel of the previous call may still read.
+ *   One batch in flight per group: while it is, a second _begin and every other entry point of the group return
+ *   TAMCMC_E_INVALID, except _poll and _destroy (which waits for the batch and hands nothing out); _end without _begin
+ *   returns TAMCMC_E_INVALID.  A failed launch ends _end with TAMCMC_E_HIP, and the members stay usable.
+ *   _poll   chain `chain` of member `member` of the batch in flight: TAMCMC_OK with its logL and status once they have
+ *           arrived, TAMCMC_PENDING before.  Read-only: any number of threads may poll while no other entry point of the
+ *           group is called; _end is still due, and is the call that reports a failed launch.
+ * Ordering is as stated above; on this path the group orders its stream after a member's own stream only when something
+ * was enqueued there since it last did, and a member's stream is made to wait for the group's launches when it is next
+ * used, not by the group call.
+ * _members: the number of members, their Nparams[n_members] and the device (each pointer may be NULL). */
+int tamcmc_group_eval_begin(tamcmc_group *g, const int32_t *Nchains, const int32_t *Nparams, const double *params,
+                            const double *Tcoefs);
+int tamcmc_group_eval_end(tamcmc_group *g, double *logL, int32_t *status);
+int tamcmc_group_eval_poll(const tamcmc_group *g, int32_t member, int32_t chain, double *logL, int32_t *status);
+int tamcmc_group_members(const tamcmc_group *g, int32_t *n_members, int32_t *Nparams, int32_t *device);
 
 /* Replaces: the `for chain` loop of generate_model() calls (MALA.cpp:632-639, model_def.cpp:139-143).
  * Host pointers, row-major.  Synchronous: results are valid on return.

@@ -81,6 +81,52 @@ int tamcmc_sampler_create_hip(tamcmc_sampler **out, const tamcmc_sampler_cfg *cf
                               const int32_t *priors_names_switch, const double *priors_params, int32_t n_prior_rows,
                               const double extra_priors[4], const double *err);
 
+/* Lockstep evaluator: K samplers, each running its unchanged loop on a host thread of its own, share ONE evaluation call
+ * per iteration -- with a fit group as the backend, one launch per kernel kind for all of them (the slices of a local
+ * fit: 8 x 10 chains in one launch of 80 workgroups instead of eight launches of 10).
+ *   create        any backend of tamcmc_group_eval's shape: eval(user, n_members, Nchains, Nparams, params, Tcoefs, logL,
+ *                 status) evaluates the members' concatenated blocks (Nchains[k] = 0: member k sits the call out).
+ *   create_group  the backend is the group's _eval_begin / _end / _poll; member k of the object is member k of the group.
+ *                 The group must outlive the object and be used through it only.
+ *   join / leave  a round fires when every JOINED member has deposited its batch; the thread that completes the round
+ *                 makes the one call.  A member that has left, or has not joined yet, sits rounds out: results do not
+ *                 depend on who shares a round (group results are the solo bits), only the number of launches does.  A
+ *                 caller that wants full rounds joins every member before the first thread starts.  A joined member
+ *                 that is busy elsewhere (writing a block of samples) holds the others up for that long.  leave is
+ *                 refused (TAMCMC_E_INVALID) between a member's deposit and its collect, destroy while a member is joined.
+ *   create_lockstep  a sampler whose evaluations (tamcmc_sampler_init's included) are member `member`'s share of the
+ *                 rounds: deposit takes the place of tamcmc_eval_batch_begin in tamcmc_sampler_mh_step, the priors and the
+ *                 draws of the next iteration follow, collect takes the place of _end.  Armed batches and accept on
+ *                 arrival are not used on this path; neither changes a draw or a decision, so the chains are bit for bit
+ *                 those of the same sampler on tamcmc_sampler_create_hip.  Single process only (Nchains_local == Nchains).
+ *   deposit / collect  what the sampler calls: deposit hands in pointers (they must stay valid and unchanged until the
+ *                 member's collect returns), collect waits for the round and fills logL / status.
+ * Threads: one per member; every entry point may be called from any of them.  All backend calls are serialised by the
+ * object (and made with the group's device current).  Nobody waits holding the lock, and no thread is created: a member
+ * waits for its round by watching host memory (pauses, then yields, then 50 us sleeps).
+ * Errors: when the backend fails, every member of that round gets the error from its collect (the sampler's step returns
+ * it) and can leave; the object keeps the text of the failed round, HIP's included -- tamcmc_last_hip_error is per thread
+ * and only the thread that made the call has it -- and hands it out through tamcmc_lockstep_error.  A sampler whose step
+ * fails for a reason of its own leaves, and the others go on. */
+typedef struct tamcmc_lockstep tamcmc_lockstep;
+typedef int (*tamcmc_group_eval_fn)(void *user, int32_t n_members, const int32_t *Nchains, const int32_t *Nparams,
+                                    const double *params, const double *Tcoefs, double *logL, int32_t *status);
+int tamcmc_lockstep_create(tamcmc_lockstep **out, int32_t n_members, const int32_t *Nparams, tamcmc_group_eval_fn eval, void *user);
+int tamcmc_lockstep_create_group(tamcmc_lockstep **out, tamcmc_group *g);
+int tamcmc_lockstep_join(tamcmc_lockstep *ls, int32_t member);
+int tamcmc_lockstep_leave(tamcmc_lockstep *ls, int32_t member);
+int tamcmc_lockstep_destroy(tamcmc_lockstep *ls);
+int tamcmc_lockstep_deposit(tamcmc_lockstep *ls, int32_t member, int32_t Nchains, int32_t Nparams, const double *params,
+                            const double *Tcoefs, double *logL, int32_t *status);
+int tamcmc_lockstep_collect(tamcmc_lockstep *ls, int32_t member);
+const char *tamcmc_lockstep_error(const tamcmc_lockstep *ls);      /* text of the last failed round ("" if none) */
+int64_t tamcmc_lockstep_calls(const tamcmc_lockstep *ls);           /* backend calls made so far (rounds fired) */
+int32_t tamcmc_lockstep_nparams(const tamcmc_lockstep *ls, int32_t member);   /* -1: no such member */
+int tamcmc_sampler_create_lockstep(tamcmc_sampler **out, const tamcmc_sampler_cfg *cfg, tamcmc_lockstep *ls, int32_t member,
+                                   int32_t Nparams, const int32_t plength[11], const double *inputs, const int32_t *relax,
+                                   const int32_t *priors_names_switch, const double *priors_params, int32_t n_prior_rows,
+                                   const double extra_priors[4], const double *err);
+
 /* Model_def constructor's initial generate_model() of every chain (model_def.cpp:139-143). */
 int tamcmc_sampler_init(tamcmc_sampler *s);
 

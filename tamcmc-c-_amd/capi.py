@@ -27,6 +27,7 @@ EXPORTS = [
     "tamcmc_strerror", "tamcmc_last_hip_error", "tamcmc_version",
     "tamcmc_group_create", "tamcmc_group_eval", "tamcmc_group_eval_device", "tamcmc_group_set_stream",
     "tamcmc_group_synchronize", "tamcmc_group_destroy",
+    "tamcmc_group_eval_begin", "tamcmc_group_eval_end", "tamcmc_group_eval_poll", "tamcmc_group_members",
 ]
 
 
@@ -78,6 +79,10 @@ def load_library():
     lib.tamcmc_group_set_stream.argtypes = [vp, vp]
     lib.tamcmc_group_synchronize.argtypes = [vp]
     lib.tamcmc_group_destroy.argtypes = [vp]
+    lib.tamcmc_group_eval_begin.argtypes = [vp, ip, ip, dp, dp]
+    lib.tamcmc_group_eval_end.argtypes = [vp, dp, ip]
+    lib.tamcmc_group_eval_poll.argtypes = [vp, C.c_int32, C.c_int32, dp, ip]
+    lib.tamcmc_group_members.argtypes = [vp, ip, ip, ip]
     for name in EXPORTS:
         fn = getattr(lib, name)
         if fn.restype is not C.c_char_p:
@@ -316,6 +321,36 @@ class Group:
                                                 _iptr(st)), "tamcmc_group_eval")
         cut = np.cumsum(n)[:-1]
         return np.split(logL, cut), np.split(st, cut)
+
+    def begin(self, P_list, T_list):
+        """eval() in two halves: the batch is launched and not waited for (end() collects it, poll() looks at one chain)."""
+        P, T, n = self._counts(P_list, T_list)
+        Pc = np.ascontiguousarray(np.concatenate([p.ravel() for p in P])) if P else np.empty(0)
+        Tc = np.ascontiguousarray(np.concatenate(T))
+        self._check(self._lib.tamcmc_group_eval_begin(self._g, _iptr(n), _iptr(self.Nparams), _dptr(Pc), _dptr(Tc)),
+                    "tamcmc_group_eval_begin")
+        self._n_flight = n
+
+    def end(self):
+        n = getattr(self, "_n_flight", None)
+        if n is None:
+            n = np.zeros(len(self.members), dtype=np.int32)     # (the library refuses an _end without _begin)
+        logL = np.empty(max(int(n.sum()), 1))
+        st = np.empty(max(int(n.sum()), 1), dtype=np.int32)
+        rc = self._lib.tamcmc_group_eval_end(self._g, _dptr(logL), _iptr(st))
+        self._n_flight = None
+        self._check(rc, "tamcmc_group_eval_end")
+        cut = np.cumsum(n)[:-1]
+        return np.split(logL[:int(n.sum())], cut), np.split(st[:int(n.sum())], cut)
+
+    def poll(self, member, chain):
+        """(logL, status) of one chain of one member of the batch in flight, or None while it has not arrived."""
+        L, st = C.c_double(), C.c_int32()
+        rc = self._lib.tamcmc_group_eval_poll(self._g, int(member), int(chain), C.byref(L), C.byref(st))
+        if rc == -1:
+            return None
+        self._check(rc, "tamcmc_group_eval_poll")
+        return L.value, st.value
 
     def eval_device(self, nchains, d_params, d_T, d_logL, d_status=0):
         """Device pointers (ints, e.g. torch.Tensor.data_ptr()) of the concatenated blocks; enqueued, no sync."""

@@ -96,7 +96,29 @@ struct tamcmc_ctx {
     std::vector<hipEvent_t> ev;   // pairs (start, stop)
     size_t ev_used = 0;
     int groups = 0;               // fit groups this context is a member of (tamcmc_group_create); destroy is refused meanwhile
+    // ordering against fit groups (tamcmc_group_eval_begin): enq_seq counts what this library put on the stream, so that a
+    // group can tell whether anything came since it last ordered itself against it; after_ev is a group's "launches done"
+    // event this stream has still to wait for -- the wait is enqueued by the next use of the stream (ctx_settle), not by
+    // the group call
+    uint64_t enq_seq = 0;
+    hipEvent_t after_ev = nullptr;
+    const void *after_owner = nullptr;
 };
+
+// A group call left an event for this stream to wait for: enqueue the wait now (before anything else goes on the stream).
+static inline hipError_t ctx_settle(tamcmc_ctx *c)
+{
+    if (!c->after_ev) return hipSuccess;
+    const hipEvent_t e = c->after_ev;
+    c->after_ev = nullptr; c->after_owner = nullptr;
+    return hipStreamWaitEvent(c->stream, e, 0);
+}
+static inline hipError_t ctx_stream_sync(tamcmc_ctx *c)
+{
+    const hipError_t e = ctx_settle(c);
+    if (e != hipSuccess) return e;
+    return hipStreamSynchronize(c->stream);
+}
 
 static int pick_tiles(const tamcmc_ctx *c, int Nchains, bool grad);
 
@@ -198,7 +220,7 @@ static int ensure_capacity(tamcmc_ctx *c, int Nchains, bool grad)
     if (Nchains <= c->cap && (!grad || c->cap_grad)) return TAMCMC_OK;
     const int cap = Nchains > c->cap ? Nchains : c->cap;
     const bool g = grad || c->cap_grad;
-    TM_HIP(hipStreamSynchronize(c->stream));
+    TM_HIP(ctx_stream_sync(c));
     free_batch(c);
     const size_t n = (size_t)cap;
     const size_t nm = (size_t)(c->L.n_mult > 0 ? c->L.n_mult : 1);
@@ -364,7 +386,7 @@ extern "C" int tamcmc_ctx_destroy(tamcmc_ctx *c)
     if (c->groups > 0) return TAMCMC_E_INVALID;     // a fit group still refers to it: destroy the group first
     (void)hipSetDevice(c->device);
     if (c->armed && c->h_gate) { __atomic_store_n(c->h_gate, c->gate_seq, __ATOMIC_RELEASE); c->armed = 0; }   // let the gate go
-    if (c->stream) (void)hipStreamSynchronize(c->stream);
+    if (c->stream) (void)ctx_stream_sync(c);
     free_batch(c);
     (void)hipHostFree(c->h_gate);
     (void)hipFree(c->d_x2); (void)hipFree(c->d_y); (void)hipFree(c->d_lx); (void)hipFree(c->d_isig2); (void)hipFree(c->d_spec);
@@ -386,7 +408,7 @@ extern "C" int tamcmc_ctx_set_vars(tamcmc_ctx *c, int32_t Nvars, const int32_t *
     for (int i = 0; i < Nvars; i++)
         if (index_to_relax[i] < 0 || index_to_relax[i] >= c->L.Nparams) return TAMCMC_E_INVALID;
     TM_HIP(hipSetDevice(c->device));
-    TM_HIP(hipStreamSynchronize(c->stream));
+    TM_HIP(ctx_stream_sync(c));
     (void)hipFree(c->d_relax); c->d_relax = nullptr;
     c->Nvars = Nvars;
     // the asymmetry as a variable: its derivative does not vanish at asym == 0 although the factor is 1 there
@@ -406,7 +428,7 @@ extern "C" int tamcmc_ctx_set_spectra(tamcmc_ctx *c, int32_t Nspectra, const dou
     if (c && c->armed) return TAMCMC_E_INVALID;     // launches wait behind a gate: only _fire / _end / _disarm / destroy (tamcmc_accel.h)
     if (!c || Nspectra < 1 || !y || (c->L.likelihood_case == 1 && !sigma_y)) return TAMCMC_E_INVALID;
     TM_HIP(hipSetDevice(c->device));
-    TM_HIP(hipStreamSynchronize(c->stream));
+    TM_HIP(ctx_stream_sync(c));
     const size_t nx = (size_t)c->L.Nx, bytes = nx * (size_t)Nspectra * sizeof(double);
     // the new blocks first, the swap last: a failure leaves the context as it was
     double *ny = nullptr, *nis = nullptr;
@@ -432,7 +454,7 @@ extern "C" int tamcmc_ctx_set_chain_spectrum(tamcmc_ctx *c, int32_t Nchains, con
     for (int m = 0; m < Nchains; m++)
         if (spectrum_of_chain[m] < 0 || spectrum_of_chain[m] >= c->nspec) return TAMCMC_E_INVALID;
     TM_HIP(hipSetDevice(c->device));
-    TM_HIP(hipStreamSynchronize(c->stream));
+    TM_HIP(ctx_stream_sync(c));
     (void)hipFree(c->d_spec); c->d_spec = nullptr; c->spec_n = 0;
     if (Nchains > 0) {
         TM_HIP(hipMalloc(&c->d_spec, (size_t)Nchains * sizeof(int32_t)));
@@ -447,8 +469,9 @@ extern "C" int tamcmc_ctx_set_stream(tamcmc_ctx *c, void *hip_stream)
     if (c && c->armed) return TAMCMC_E_INVALID;     // launches wait behind a gate: only _fire / _end / _disarm / destroy (tamcmc_accel.h)
     if (!c) return TAMCMC_E_INVALID;
     TM_HIP(hipSetDevice(c->device));
-    TM_HIP(hipStreamSynchronize(c->stream));
+    TM_HIP(ctx_stream_sync(c));
     c->stream = hip_stream ? (hipStream_t)hip_stream : c->own_stream;
+    c->enq_seq++;
     return TAMCMC_OK;
 }
 
@@ -457,7 +480,7 @@ extern "C" int tamcmc_ctx_synchronize(tamcmc_ctx *c)
     if (c && c->armed) return TAMCMC_E_INVALID;     // launches wait behind a gate: only _fire / _end / _disarm / destroy (tamcmc_accel.h)
     if (!c) return TAMCMC_E_INVALID;
     TM_HIP(hipSetDevice(c->device));
-    TM_HIP(hipStreamSynchronize(c->stream));
+    TM_HIP(ctx_stream_sync(c));
     return TAMCMC_OK;
 }
 
@@ -465,7 +488,7 @@ extern "C" int tamcmc_ctx_profile(tamcmc_ctx *c, int enable)
 {
     if (!c) return TAMCMC_E_INVALID;
     TM_HIP(hipSetDevice(c->device));
-    TM_HIP(hipStreamSynchronize(c->stream));
+    TM_HIP(ctx_stream_sync(c));
     c->profile = enable != 0;
     c->profile_stride = enable > 1 ? enable : 1;
     c->profile_count = 0;
@@ -484,7 +507,7 @@ extern "C" int tamcmc_ctx_kernel_time(tamcmc_ctx *c, double *total_ms, int64_t *
     if (c && c->armed) return TAMCMC_E_INVALID;     // launches wait behind a gate: only _fire / _end / _disarm / destroy (tamcmc_accel.h)
     if (!c || !total_ms || !launches) return TAMCMC_E_INVALID;
     TM_HIP(hipSetDevice(c->device));
-    TM_HIP(hipStreamSynchronize(c->stream));
+    TM_HIP(ctx_stream_sync(c));
     double t = 0.0;
     for (size_t i = 0; i + 1 < c->ev_used; i += 2) {
         float ms = 0.f;
@@ -584,6 +607,8 @@ static int enqueue(tamcmc_ctx *c, int Nchains, const double *d_params, const dou
 {
     const bool grad = d_grad != nullptr;
     const hipStream_t stream = c->stream;
+    TM_HIP(ctx_settle(c));
+    c->enq_seq++;
     // several spectra resident: every chain of the batch must have been told which one it is fitted to (a batch longer
     // than the map used to fall back to spectrum 0 for all chains -- silently the wrong data)
     if (c->nspec > 1 && (c->d_spec == nullptr || Nchains > c->spec_n)) return TAMCMC_E_INVALID;
@@ -682,17 +707,28 @@ static int wait_done(tamcmc_ctx *c)
 // a failed launch ends the wait with an error instead of a hang, and should a result ever equal the marker (a kernel
 // NaN does not have this payload) the wait ends when the launch retires.
 static const uint64_t TM_PENDING_BITS = 0x7FF8DEADBEEF5A5AULL;
-// nw = doubles to watch in h_out: n (logL) or n * (1 + Nvars) (logL, then the gradient rows)
-static void mark_pending(tamcmc_ctx *c, int n, size_t nw)
+// The marker / wait code, shared by a context's host path and a fit group's (tamcmc_group_eval_begin): out = the watched
+// doubles (the first n of them are the logL slots), st = the n status slots, ev / recorded = the completion event of the
+// call, recorded lazily on `stream`.
+struct TmWatch {
+    uint64_t *out;
+    int32_t *st;
+    hipEvent_t *ev;
+    bool *recorded;
+    hipStream_t stream;
+};
+// nw = doubles to watch: n (logL) or n * (1 + Nvars) (logL, then the gradient rows)
+static void mark_slots(const TmWatch &w, int n, size_t nw)
 {
-    uint64_t *o = reinterpret_cast<uint64_t *>(c->h_out);
-    for (size_t m = 0; m < nw; m++) o[m] = TM_PENDING_BITS;
-    for (int m = 0; m < n; m++) c->h_status[m] = -1;
+    for (size_t m = 0; m < nw; m++) w.out[m] = TM_PENDING_BITS;
+    for (int m = 0; m < n; m++) w.st[m] = -1;
 }
-static int wait_data(tamcmc_ctx *c, int n, size_t nw)
+// rearm(): puts the arrival counters behind the watched launch back to zero (called on every error path)
+template <class Rearm>
+static int wait_slots(const TmWatch &w, int n, size_t nw, Rearm rearm)
 {
-    volatile const uint64_t *o = reinterpret_cast<volatile const uint64_t *>(c->h_out);
-    volatile const int32_t *st = c->h_status;
+    volatile const uint64_t *o = w.out;
+    volatile const int32_t *st = w.st;
     unsigned spins = 0;
     for (size_t m = 0; m < nw;) {
         if (o[m] != TM_PENDING_BITS && (m >= (size_t)n || st[m] != -1)) { m++; continue; }
@@ -701,12 +737,12 @@ static int wait_data(tamcmc_ctx *c, int n, size_t nw)
             // The completion event is recorded only now, behind the kernels already in the stream (it completes once they
             // have): a call that gets its results within the first ~2000 polls -- every healthy call -- never pays for an
             // event on the launch path (~1.5 us of host time per call in a sampler loop).
-            if (!c->ev_recorded) {
-                if (!c->ev_done && hipEventCreateWithFlags(&c->ev_done, hipEventDisableTiming) != hipSuccess) return TAMCMC_E_HIP;
-                if (hipEventRecord(c->ev_done, c->stream) != hipSuccess) return TAMCMC_E_HIP;
-                c->ev_recorded = true;
+            if (!*w.recorded) {
+                if (!*w.ev && hipEventCreateWithFlags(w.ev, hipEventDisableTiming) != hipSuccess) return TAMCMC_E_HIP;
+                if (hipEventRecord(*w.ev, w.stream) != hipSuccess) return TAMCMC_E_HIP;
+                *w.recorded = true;
             }
-            const hipError_t e = hipEventQuery(c->ev_done);
+            const hipError_t e = hipEventQuery(*w.ev);
             if (e == hipSuccess) {
                 // The launch has retired: whatever the slots hold is final.  A logL / status slot that still holds its
                 // marker was never written -- a chain whose finalize did not run (e.g. an arrival counter left non-zero
@@ -715,19 +751,39 @@ static int wait_data(tamcmc_ctx *c, int n, size_t nw)
                 for (size_t k = 0; k < (size_t)n; k++)
                     if (o[k] == TM_PENDING_BITS || st[k] == -1) {
                         snprintf(g_hip_err, sizeof(g_hip_err), "chain %zu was not finalized by a retired launch", k);
-                        (void)hipMemsetAsync(c->d_ticket, 0, (size_t)c->cap * sizeof(int32_t), c->stream);
+                        rearm();
                         return TAMCMC_E_HIP;
                     }
                 return TAMCMC_OK;
             }
             if (e != hipErrorNotReady) {
                 snprintf(g_hip_err, sizeof(g_hip_err), "hipEventQuery -> %s", hipGetErrorString(e));
-                (void)hipMemsetAsync(c->d_ticket, 0, (size_t)c->cap * sizeof(int32_t), c->stream);
+                rearm();
                 return TAMCMC_E_HIP;
             }
         }
     }
     return TAMCMC_OK;
+}
+// one slot: TAMCMC_PENDING, or its final value
+static inline int poll_slot(const uint64_t *out, const int32_t *status, size_t slot, double *logL, int32_t *st_out)
+{
+    const uint64_t v = reinterpret_cast<volatile const uint64_t *>(out)[slot];
+    const int32_t st = reinterpret_cast<volatile const int32_t *>(status)[slot];
+    if (v == TM_PENDING_BITS || st == -1) return TAMCMC_PENDING;
+    std::memcpy(logL, &v, sizeof(double));
+    *st_out = st;
+    return TAMCMC_OK;
+}
+
+static inline TmWatch ctx_watch(tamcmc_ctx *c)
+{
+    return TmWatch{reinterpret_cast<uint64_t *>(c->h_out), c->h_status, &c->ev_done, &c->ev_recorded, c->stream};
+}
+static void mark_pending(tamcmc_ctx *c, int n, size_t nw) { mark_slots(ctx_watch(c), n, nw); }
+static int wait_data(tamcmc_ctx *c, int n, size_t nw)
+{
+    return wait_slots(ctx_watch(c), n, nw, [c]() { (void)hipMemsetAsync(c->d_ticket, 0, (size_t)c->cap * sizeof(int32_t), c->stream); });
 }
 
 // pinned, device-mapped staging of the host-pointer entry points
@@ -735,7 +791,7 @@ static int ensure_staging(tamcmc_ctx *c, int Nchains)
 {
     const int Nparams = c->L.Nparams;
     if (Nchains <= c->h_cap && c->h_nvars == c->Nvars) return TAMCMC_OK;
-    TM_HIP(hipStreamSynchronize(c->stream));
+    TM_HIP(ctx_stream_sync(c));
     (void)hipHostFree(c->h_in); (void)hipHostFree(c->h_out); (void)hipHostFree(c->h_status);
     c->h_in = c->h_out = nullptr; c->h_status = nullptr; c->h_cap = 0;
     const unsigned flags = hipHostMallocMapped | hipHostMallocCoherent;
@@ -785,12 +841,7 @@ extern "C" int tamcmc_eval_batch_end(tamcmc_ctx *c, int32_t Nchains, double *log
 extern "C" int tamcmc_eval_batch_poll(const tamcmc_ctx *c, int32_t chain, double *logL, int32_t *status)
 {
     if (!c || !logL || !status || chain < 0 || chain >= c->in_flight) return TAMCMC_E_INVALID;
-    const uint64_t v = reinterpret_cast<volatile const uint64_t *>(c->h_out)[chain];
-    const int32_t st = reinterpret_cast<volatile const int32_t *>(c->h_status)[chain];
-    if (v == TM_PENDING_BITS || st == -1) return TAMCMC_PENDING;
-    std::memcpy(logL, &v, sizeof(double));
-    *status = st;
-    return TAMCMC_OK;
+    return poll_slot(reinterpret_cast<const uint64_t *>(c->h_out), c->h_status, (size_t)chain, logL, status);
 }
 
 int tm_launch_gate(uint32_t *dv_gate, uint32_t target, int patience, void *stream);      // tamcmc_setup.hip
@@ -827,6 +878,8 @@ extern "C" int tamcmc_eval_batch_arm(tamcmc_ctx *c, int32_t Nchains)
         *c->h_gate = c->gate_seq;
     }
     const uint32_t target = c->gate_seq + 1;
+    TM_HIP(ctx_settle(c));
+    c->enq_seq++;
     int rc = tm_launch_gate(c->dv_gate, target, c->gate_patience, c->stream);
     if (rc != 0) { snprintf(g_hip_err, sizeof(g_hip_err), "gate launch -> %s", hipGetErrorString((hipError_t)rc)); return TAMCMC_E_HIP; }
     const size_t n = (size_t)Nchains;
@@ -848,7 +901,7 @@ extern "C" int tamcmc_eval_batch_fire(tamcmc_ctx *c, int32_t Nchains, int32_t Np
         // drain and evaluate this batch the plain way.
         __atomic_store_n(c->h_gate, c->gate_seq, __ATOMIC_RELEASE);
         c->armed = 0;
-        TM_HIP(hipStreamSynchronize(c->stream));
+        TM_HIP(ctx_stream_sync(c));
         return tamcmc_eval_batch_begin(c, Nchains, Nparams, params, Tcoefs);
     }
     const size_t n = (size_t)Nchains;
@@ -873,7 +926,7 @@ extern "C" int tamcmc_eval_batch_disarm(tamcmc_ctx *c)
     if (gate_claim(c)) {              // it has run (or is running) already: just let it retire
         __atomic_store_n(c->h_gate, c->gate_seq, __ATOMIC_RELEASE);
         c->armed = 0;
-        TM_HIP(hipStreamSynchronize(c->stream));
+        TM_HIP(ctx_stream_sync(c));
         return TAMCMC_OK;
     }
     mark_pending(c, n, (size_t)n);
@@ -923,13 +976,13 @@ extern "C" int tamcmc_eval_batch(tamcmc_ctx *c, int32_t Nchains, int32_t Nparams
         for (int r = 0; r < n_rows; r++) rows[(size_t)model_rows[r]] = r;   // a chain listed twice keeps the last row
         const size_t need = (size_t)n_rows * (size_t)c->L.Nx;
         if (need > c->model_cap) {
-            TM_HIP(hipStreamSynchronize(c->stream));
+            TM_HIP(ctx_stream_sync(c));
             (void)hipFree(c->d_model); c->d_model = nullptr; c->model_cap = 0;
             TM_HIP(hipMalloc(&c->d_model, need * sizeof(double)));
             c->model_cap = need;
         }
         TM_HIP(hipMemcpyAsync(c->d_rows, rows.data(), n * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
-        TM_HIP(hipStreamSynchronize(c->stream));   // rows is a local
+        TM_HIP(ctx_stream_sync(c));   // rows is a local
         d_rows = c->d_rows;
     }
     // logL / status (a few hundred bytes) are written straight into the mapped host buffer by the last kernel; the
@@ -986,18 +1039,31 @@ struct tamcmc_group {
     hipEvent_t ev_done = nullptr;        // completion of a host-pointer call (polled)
     // descriptor table: one device copy (rewritten in stream order) from two pinned host images, so that the image a
     // pending upload reads is never the one being filled
-    char *d_tab = nullptr;
-    size_t d_tab_cap = 0;
+    // (one device copy per caller: 0 tamcmc_group_eval / _eval_device, 1 and 2 the two input buffers of _eval_begin --
+    // a caller whose chain counts do not change finds its table in place and uploads nothing)
+    struct Tab { char *d = nullptr; size_t cap = 0; std::vector<char> last; } tab[3];   // (last: the table as uploaded)
     char *h_tab[2] = {nullptr, nullptr};
     size_t h_tab_cap[2] = {0, 0};
     hipEvent_t ev_tab[2] = {nullptr, nullptr};
     bool tab_pending[2] = {false, false};
     int tab_slot = 0;
-    std::vector<char> last;              // the table as last uploaded
     // host-pointer calls: one pinned staging area [params | Tcoefs | logL | status] and its device copy
     char *h_stage = nullptr, *d_stage = nullptr;
     size_t stage_cap = 0;
     bool counted = false;                // the members' group counts include this group (set once creation succeeded)
+    // _eval_begin / _end / _poll: mapped, coherent pinned staging [params | Tcoefs | logL | status] the grouped kernels
+    // read and write directly, one per call parity (filling the inputs of call n+1 never touches what a kernel of call n
+    // may still read)
+    char *h_map[2] = {nullptr, nullptr}, *dv_map[2] = {nullptr, nullptr};
+    size_t map_cap[2] = {0, 0};
+    int parity = 0;
+    int flight = 0;                      // chains of the batch in flight (0: none)
+    std::vector<int32_t> fl_off;         // [members + 1] first slot of each member's block in the batch in flight
+    uint64_t *fl_out = nullptr;          // its result slots (host view): logL, status
+    int32_t *fl_st = nullptr;
+    bool ev_recorded = false;            // wait_slots: ev_done has been recorded for the batch in flight
+    std::vector<uint64_t> seen_seq;      // per member: its enq_seq when the group stream last ordered itself after its stream
+    std::vector<hipStream_t> seen_stream;
 };
 
 static bool generic_body(const tamcmc_ctx *c) { return eval_args(c, 1, false, nullptr, nullptr, nullptr, nullptr).generic != 0; }
@@ -1029,14 +1095,15 @@ static int group_check(const tamcmc_group *g, const int32_t *Nchains, const int3
 
 // Uploads the table when it differs from the one the device holds (stream-ordered: launches already enqueued keep
 // reading the previous contents).
-static int group_upload(tamcmc_group *g, const std::vector<char> &tab)
+static int group_upload(tamcmc_group *g, const std::vector<char> &tab, int tslot)
 {
-    if (tab == g->last) return TAMCMC_OK;
-    if (tab.size() > g->d_tab_cap) {
+    tamcmc_group::Tab &t = g->tab[tslot];
+    if (tab == t.last) return TAMCMC_OK;
+    if (tab.size() > t.cap) {
         TM_HIP(hipStreamSynchronize(g->stream));
-        (void)hipFree(g->d_tab); g->d_tab = nullptr; g->d_tab_cap = 0;
-        TM_HIP(hipMalloc(&g->d_tab, tab.size()));
-        g->d_tab_cap = tab.size();
+        (void)hipFree(t.d); t.d = nullptr; t.cap = 0;
+        TM_HIP(hipMalloc(&t.d, tab.size()));
+        t.cap = tab.size();
     }
     const int s = g->tab_slot ^= 1;
     if (g->tab_pending[s]) { TM_HIP(hipEventSynchronize(g->ev_tab[s])); g->tab_pending[s] = false; }
@@ -1046,18 +1113,21 @@ static int group_upload(tamcmc_group *g, const std::vector<char> &tab)
         g->h_tab_cap[s] = tab.size();
     }
     std::memcpy(g->h_tab[s], tab.data(), tab.size());
-    g->last.clear();                     // (a failed copy leaves no claim about the device contents)
-    TM_HIP(hipMemcpyAsync(g->d_tab, g->h_tab[s], tab.size(), hipMemcpyHostToDevice, g->stream));
+    t.last.clear();                      // (a failed copy leaves no claim about the device contents)
+    TM_HIP(hipMemcpyAsync(t.d, g->h_tab[s], tab.size(), hipMemcpyHostToDevice, g->stream));
     TM_HIP(hipEventRecord(g->ev_tab[s], g->stream));
     g->tab_pending[s] = true;
-    g->last = tab;
+    t.last = tab;
     return TAMCMC_OK;
 }
 
 // Enqueue one group call on the group stream: member k's chains read Nchains[k] rows of Nparams[k] from d_params (blocks
 // in member order) and write their logL / status at their offset in the concatenated outputs.  group_check has passed.
+// tslot: the device table to use (tamcmc_group::tab).  lazy: the members' streams are not made to wait here; each gets
+// the group's event to wait for before its next use (ctx_settle), and a member on whose own stream nothing was enqueued
+// since the group last ordered itself after it is not waited for either.
 static int group_enqueue(tamcmc_group *g, const int32_t *Nchains, const double *d_params, const double *d_T, double *d_logL,
-                         int32_t *d_status)
+                         int32_t *d_status, int tslot = 0, bool lazy = false)
 {
     const int n = (int)g->m.size();
     bool grow = false;
@@ -1128,13 +1198,19 @@ static int group_enqueue(tamcmc_group *g, const int32_t *Nchains, const double *
     for (int k = 0; k < n; k++) {
         tamcmc_ctx *c = g->m[k];
         if (Nchains[k] > 0 && c->stream != g->stream) {
+            // an event another group left for this stream goes onto it first (and counts as work enqueued there); this
+            // group's own is on the group stream already
+            if (c->after_ev && c->after_owner != g) { TM_HIP(ctx_settle(c)); c->enq_seq++; }
+            // (a stream handed in by the caller may carry work this library has not counted)
+            if (c->stream == c->own_stream && g->seen_stream[k] == c->stream && g->seen_seq[k] == c->enq_seq) continue;
             TM_HIP(hipEventRecord(g->ev_before[k], c->stream));
             TM_HIP(hipStreamWaitEvent(g->stream, g->ev_before[k], 0));
+            g->seen_stream[k] = c->stream; g->seen_seq[k] = c->enq_seq;
         }
     }
-    int rc = group_upload(g, tab);
+    int rc = group_upload(g, tab, tslot);
     if (rc != TAMCMC_OK) return rc;
-    const char *D = g->d_tab;
+    const char *D = g->tab[tslot].d;
     const char *what = "";
     int hr = 0;
     if (!su.empty()) {
@@ -1164,8 +1240,28 @@ static int group_enqueue(tamcmc_group *g, const int32_t *Nchains, const double *
     if (hipEventRecord(g->ev_after, g->stream) != hipSuccess) return TAMCMC_E_HIP;
     for (int k = 0; k < n; k++) {
         tamcmc_ctx *c = g->m[k];
-        if (Nchains[k] > 0 && c->stream != g->stream && hipStreamWaitEvent(c->stream, g->ev_after, 0) != hipSuccess) return TAMCMC_E_HIP;
+        if (Nchains[k] == 0 || c->stream == g->stream) continue;
+        if (lazy) { c->after_ev = g->ev_after; c->after_owner = g; continue; }
+        if (c->after_owner == g) { c->after_ev = nullptr; c->after_owner = nullptr; }     // (the wait below covers it)
+        if (hipStreamWaitEvent(c->stream, g->ev_after, 0) != hipSuccess) return TAMCMC_E_HIP;
+        c->enq_seq++;
     }
+    return rc;
+}
+
+// The batch in flight of tamcmc_group_eval_begin: wait until every result slot holds its final value (wait_slots: a
+// failed launch ends the wait with an error and the members' arrival counters are put back to zero).
+static int group_drain(tamcmc_group *g)
+{
+    const int n = g->flight;
+    const TmWatch w{g->fl_out, g->fl_st, &g->ev_done, &g->ev_recorded, g->stream};
+    const int rc = wait_slots(w, n, (size_t)n, [g]() {
+        for (size_t k = 0; k < g->m.size(); k++) {
+            const int nc = g->fl_off[k + 1] - g->fl_off[k];
+            if (nc > 0) (void)hipMemsetAsync(g->m[k]->d_ticket, 0, (size_t)nc * sizeof(int32_t), g->stream);
+        }
+    });
+    g->flight = 0;                   // (only now: _poll is answered until the batch is closed)
     return rc;
 }
 
@@ -1183,6 +1279,8 @@ extern "C" int tamcmc_group_create(tamcmc_group **out, int32_t n_members, tamcmc
     g->device = members[0]->device;
     g->m.assign(members, members + n_members);
     g->ev_before.assign((size_t)n_members, nullptr);
+    g->seen_seq.assign((size_t)n_members, ~(uint64_t)0);
+    g->seen_stream.assign((size_t)n_members, nullptr);
     auto fail = [&](int code) { tamcmc_group_destroy(g); return code; };
     if (hipSetDevice(g->device) != hipSuccess) return fail(TAMCMC_E_NODEVICE);
     if (hipStreamCreateWithFlags(&g->own_stream, hipStreamNonBlocking) != hipSuccess) return fail(TAMCMC_E_HIP);
@@ -1203,9 +1301,14 @@ extern "C" int tamcmc_group_destroy(tamcmc_group *g)
 {
     if (!g) return TAMCMC_OK;
     (void)hipSetDevice(g->device);
+    if (g->flight) (void)group_drain(g);           // a batch in flight: wait for it, hand nothing out
     if (g->stream) (void)hipStreamSynchronize(g->stream);
+    for (tamcmc_ctx *c : g->m)                     // (everything of this group has retired: nothing left to wait for)
+        if (c->after_owner == g) { c->after_ev = nullptr; c->after_owner = nullptr; }
     if (g->counted) for (tamcmc_ctx *c : g->m) c->groups--;
-    (void)hipFree(g->d_tab); (void)hipFree(g->d_stage);
+    for (auto &t : g->tab) (void)hipFree(t.d);
+    (void)hipFree(g->d_stage);
+    (void)hipHostFree(g->h_map[0]); (void)hipHostFree(g->h_map[1]);
     (void)hipHostFree(g->h_tab[0]); (void)hipHostFree(g->h_tab[1]); (void)hipHostFree(g->h_stage);
     for (hipEvent_t e : g->ev_before) if (e) (void)hipEventDestroy(e);
     for (hipEvent_t e : {g->ev_after, g->ev_done, g->ev_tab[0], g->ev_tab[1]}) if (e) (void)hipEventDestroy(e);
@@ -1216,7 +1319,7 @@ extern "C" int tamcmc_group_destroy(tamcmc_group *g)
 
 extern "C" int tamcmc_group_set_stream(tamcmc_group *g, void *hip_stream)
 {
-    if (!g) return TAMCMC_E_INVALID;
+    if (!g || g->flight) return TAMCMC_E_INVALID;
     TM_HIP(hipSetDevice(g->device));
     TM_HIP(hipStreamSynchronize(g->stream));
     g->stream = hip_stream ? (hipStream_t)hip_stream : g->own_stream;
@@ -1225,7 +1328,7 @@ extern "C" int tamcmc_group_set_stream(tamcmc_group *g, void *hip_stream)
 
 extern "C" int tamcmc_group_synchronize(tamcmc_group *g)
 {
-    if (!g) return TAMCMC_E_INVALID;
+    if (!g || g->flight) return TAMCMC_E_INVALID;
     TM_HIP(hipSetDevice(g->device));
     TM_HIP(hipStreamSynchronize(g->stream));
     return TAMCMC_OK;
@@ -1234,6 +1337,7 @@ extern "C" int tamcmc_group_synchronize(tamcmc_group *g)
 extern "C" int tamcmc_group_eval_device(tamcmc_group *g, const int32_t *Nchains, const int32_t *Nparams, const double *d_params,
                                         const double *d_Tcoefs, double *d_logL, int32_t *d_status)
 {
+    if (g && g->flight) return TAMCMC_E_INVALID;      // a batch of _eval_begin is in flight: _eval_end first
     int rc = group_check(g, Nchains, Nparams);
     if (rc != TAMCMC_OK) return rc;
     if (!d_params || !d_Tcoefs || !d_logL) return TAMCMC_E_INVALID;
@@ -1244,6 +1348,7 @@ extern "C" int tamcmc_group_eval_device(tamcmc_group *g, const int32_t *Nchains,
 extern "C" int tamcmc_group_eval(tamcmc_group *g, const int32_t *Nchains, const int32_t *Nparams, const double *params,
                                  const double *Tcoefs, double *logL, int32_t *status)
 {
+    if (g && g->flight) return TAMCMC_E_INVALID;      // a batch of _eval_begin is in flight: _eval_end first
     int rc = group_check(g, Nchains, Nparams);
     if (rc != TAMCMC_OK) return rc;
     if (!params || !Tcoefs || !logL) return TAMCMC_E_INVALID;
@@ -1284,6 +1389,82 @@ extern "C" int tamcmc_group_eval(tamcmc_group *g, const int32_t *Nchains, const 
     }
     std::memcpy(logL, g->h_stage + o_out, nc * sizeof(double));
     if (status) std::memcpy(status, g->h_stage + o_out + nc * sizeof(double), nc * sizeof(int32_t));
+    return TAMCMC_OK;
+}
+
+// The host-pointer call in two halves, on mapped memory: no copy-engine transfer and no event on the way of a healthy call.
+extern "C" int tamcmc_group_eval_begin(tamcmc_group *g, const int32_t *Nchains, const int32_t *Nparams, const double *params,
+                                       const double *Tcoefs)
+{
+    if (g && g->flight) return TAMCMC_E_INVALID;      // one batch in flight per group
+    int rc = group_check(g, Nchains, Nparams);
+    if (rc != TAMCMC_OK) return rc;
+    if (!params || !Tcoefs) return TAMCMC_E_INVALID;
+    TM_HIP(hipSetDevice(g->device));
+    const size_t nm = g->m.size();
+    size_t np = 0, nc = 0;
+    g->fl_off.assign(nm + 1, 0);
+    for (size_t k = 0; k < nm; k++) {
+        np += (size_t)Nchains[k] * (size_t)Nparams[k]; nc += (size_t)Nchains[k];
+        g->fl_off[k + 1] = (int32_t)nc;
+    }
+    if (nc > 0x7FFFFFFFu) return TAMCMC_E_INVALID;
+    const int p = g->parity ^= 1;
+    const size_t o_out = (np + nc) * sizeof(double), bytes = o_out + nc * (sizeof(double) + sizeof(int32_t));
+    if (bytes > g->map_cap[p]) {
+        TM_HIP(hipStreamSynchronize(g->stream));       // (a launch of two calls ago may not have retired yet)
+        (void)hipHostFree(g->h_map[p]); g->h_map[p] = g->dv_map[p] = nullptr; g->map_cap[p] = 0;
+        const size_t cap = bytes + bytes / 2;
+        TM_HIP(hipHostMalloc(reinterpret_cast<void **>(&g->h_map[p]), cap, hipHostMallocMapped | hipHostMallocCoherent));
+        TM_HIP(hipHostGetDevicePointer(reinterpret_cast<void **>(&g->dv_map[p]), g->h_map[p], 0));
+        g->map_cap[p] = cap;
+    }
+    char *h = g->h_map[p], *dv = g->dv_map[p];
+    std::memcpy(h, params, np * sizeof(double));
+    std::memcpy(h + np * sizeof(double), Tcoefs, nc * sizeof(double));
+    g->fl_out = reinterpret_cast<uint64_t *>(h + o_out);
+    g->fl_st = reinterpret_cast<int32_t *>(h + o_out + nc * sizeof(double));
+    const TmWatch w{g->fl_out, g->fl_st, &g->ev_done, &g->ev_recorded, g->stream};
+    mark_slots(w, (int)nc, nc);
+    double *d_in = reinterpret_cast<double *>(dv);
+    rc = group_enqueue(g, Nchains, d_in, d_in + np, reinterpret_cast<double *>(dv + o_out),
+                       reinterpret_cast<int32_t *>(dv + o_out + nc * sizeof(double)), 1 + p, true);
+    if (rc != TAMCMC_OK) {
+        // whatever did get launched may still write into this buffer: let it retire before the buffer is reused
+        (void)hipStreamSynchronize(g->stream);
+        return rc;
+    }
+    g->ev_recorded = false;          // wait_slots records the completion event only if the results are slow to arrive
+    g->flight = (int)nc;
+    return TAMCMC_OK;
+}
+
+extern "C" int tamcmc_group_eval_end(tamcmc_group *g, double *logL, int32_t *status)
+{
+    if (!g || !logL || !g->flight) return TAMCMC_E_INVALID;
+    const size_t nc = (size_t)g->flight;
+    TM_HIP(hipSetDevice(g->device));
+    const int rc = group_drain(g);
+    if (rc != TAMCMC_OK) return rc;
+    std::memcpy(logL, g->fl_out, nc * sizeof(double));
+    if (status) std::memcpy(status, g->fl_st, nc * sizeof(int32_t));
+    return TAMCMC_OK;
+}
+
+extern "C" int tamcmc_group_eval_poll(const tamcmc_group *g, int32_t member, int32_t chain, double *logL, int32_t *status)
+{
+    if (!g || !logL || !status || !g->flight || member < 0 || (size_t)member >= g->m.size() || chain < 0) return TAMCMC_E_INVALID;
+    const int32_t o = g->fl_off[(size_t)member];
+    if (chain >= g->fl_off[(size_t)member + 1] - o) return TAMCMC_E_INVALID;
+    return poll_slot(g->fl_out, g->fl_st, (size_t)(o + chain), logL, status);
+}
+
+extern "C" int tamcmc_group_members(const tamcmc_group *g, int32_t *n_members, int32_t *Nparams, int32_t *device)
+{
+    if (!g) return TAMCMC_E_INVALID;
+    if (n_members) *n_members = (int32_t)g->m.size();
+    if (Nparams) for (size_t k = 0; k < g->m.size(); k++) Nparams[k] = g->m[k]->L.Nparams;
+    if (device) *device = g->device;
     return TAMCMC_OK;
 }
 

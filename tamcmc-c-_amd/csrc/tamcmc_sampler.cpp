@@ -607,6 +607,9 @@ struct tamcmc_sampler {
     int32_t pt_A = 0;
     double pt_u = 0.0;
     tamcmc_ctx *hip_ctx = nullptr;               // set by create_hip: the evaluation can be split in begin / end
+    // set by create_lockstep: the evaluation is this member's share of a round (deposit / collect take the place of
+    // begin / end; no armed batch, no accept on arrival)
+    struct { tamcmc_lockstep *ls = nullptr; int32_t member = 0; } lsb;
     std::unique_ptr<ChainPool> pool;
     Rng rng;
     int64_t iter = 0;
@@ -700,6 +703,26 @@ extern "C" int tamcmc_sampler_create_hip(tamcmc_sampler **out, const tamcmc_samp
     if (!ctx) return TAMCMC_E_INVALID;
     const int rc = sampler_alloc(out, cfg, hip_eval_trampoline, ctx, Nparams, plength, inputs, relax, sw, pp, nrows, extra, err);
     if (rc == TAMCMC_OK) (*out)->hip_ctx = ctx;
+    return rc;
+}
+
+static int lockstep_eval_trampoline(void *user, int32_t n, int32_t np, const double *params, const double *T, double *logL,
+                                    int32_t *status)
+{
+    tamcmc_sampler *s = static_cast<tamcmc_sampler *>(user);
+    const int rc = tamcmc_lockstep_deposit(s->lsb.ls, s->lsb.member, n, np, params, T, logL, status);
+    return rc != TAMCMC_OK ? rc : tamcmc_lockstep_collect(s->lsb.ls, s->lsb.member);
+}
+
+extern "C" int tamcmc_sampler_create_lockstep(tamcmc_sampler **out, const tamcmc_sampler_cfg *cfg, tamcmc_lockstep *ls, int32_t member,
+                                              int32_t Nparams, const int32_t plength[11], const double *inputs, const int32_t *relax,
+                                              const int32_t *sw, const double *pp, int32_t nrows, const double extra[4], const double *err)
+{
+    if (out) *out = nullptr;
+    if (!ls || !cfg || cfg->Nchains_local != cfg->Nchains) return TAMCMC_E_INVALID;   // (sharded runs do not go through a lockstep object)
+    if (tamcmc_lockstep_nparams(ls, member) != Nparams) return TAMCMC_E_INVALID;        // (member out of range, or not this fit)
+    const int rc = sampler_alloc(out, cfg, lockstep_eval_trampoline, nullptr, Nparams, plength, inputs, relax, sw, pp, nrows, extra, err);
+    if (rc == TAMCMC_OK) { (*out)->eval_user = *out; (*out)->lsb.ls = ls; (*out)->lsb.member = member; }
     return rc;
 }
 
@@ -966,8 +989,10 @@ extern "C" int tamcmc_sampler_mh_step(tamcmc_sampler *s)
     int rc;
     int perr_arrive = 0;
     bool arrive_used = false;
-    if (s->hip_ctx) {
-        if (s->ctx_armed) {
+    if (s->hip_ctx || s->lsb.ls) {
+        if (s->lsb.ls) {
+            rc = tamcmc_lockstep_deposit(s->lsb.ls, s->lsb.member, n, np, s->p_prop.data(), &s->T[off], s->L_prop.data(), s->status.data());
+        } else if (s->ctx_armed) {
             s->ctx_armed = false;
             rc = tamcmc_eval_batch_fire(s->hip_ctx, n, np, s->p_prop.data(), &s->T[off]);
         } else {
@@ -975,7 +1000,7 @@ extern "C" int tamcmc_sampler_mh_step(tamcmc_sampler *s)
         }
         if (rc != TAMCMC_OK) return rc;
         t1 = now(); s->t_phase[1] += t1 - t0; t0 = t1;
-        if (s->arm_next && s->arm_enabled) {       // the next iteration's launches, under this one's evaluation
+        if (s->arm_next && s->arm_enabled && s->hip_ctx) {       // the next iteration's launches, under this one's evaluation
             s->ctx_armed = tamcmc_eval_batch_arm(s->hip_ctx, n) == TAMCMC_OK;      // (refused: the next step launches as usual)
         }
         s->u_now = s->u_mh;
@@ -1002,7 +1027,7 @@ extern "C" int tamcmc_sampler_mh_step(tamcmc_sampler *s)
         // Only where the accept step is long -- the iterations that adapt the proposal (covariance update and a
         // factorisation per chain): with a frozen proposal the pass is a few microseconds, and sixteen threads watching
         // the result lines cost the evaluation's last stores more than the earlier start gains (measured).
-        arrive_used = s->arrive_enabled && learn_a && (i % period_a) == 0;
+        arrive_used = s->hip_ctx && s->arrive_enabled && learn_a && (i % period_a) == 0;
         if (arrive_used) {
             // accept on arrival (the pass below then only picks up chains whose result was slow to come, if any)
             std::atomic<int> perr_a{0};
@@ -1023,7 +1048,8 @@ extern "C" int tamcmc_sampler_mh_step(tamcmc_sampler *s)
             });
             if (perr_a.load()) perr_arrive = 1;
         }
-        rc = tamcmc_eval_batch_end(s->hip_ctx, n, s->L_prop.data(), s->status.data());
+        rc = s->lsb.ls ? tamcmc_lockstep_collect(s->lsb.ls, s->lsb.member)
+                       : tamcmc_eval_batch_end(s->hip_ctx, n, s->L_prop.data(), s->status.data());
         t1 = now(); s->t_phase[4] += t1 - t0; t0 = t1;
     } else {
         s->u_now = s->u_mh;

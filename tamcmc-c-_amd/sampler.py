@@ -2,7 +2,8 @@
 parallel-tempering sampler (N2) that calls the hot path once per iteration (MALA.cpp:608-692).
 
 The evaluator is either a HIP context (Accel) or, for tests, any Python callable
-f(params[n, Nparams], Tcoefs[n]) -> (logL[n], status[n])."""
+f(params[n, Nparams], Tcoefs[n]) -> (logL[n], status[n]); or the sampler is a member of a Lockstep object, which
+evaluates the batches of several samplers (one thread each) in one call per iteration."""
 import ctypes as C
 
 import numpy as np
@@ -12,6 +13,8 @@ from . import capi
 MAX_LEARN = 8
 EVAL_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_double),
                       C.POINTER(C.c_double), C.POINTER(C.c_int32))
+GROUP_EVAL_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_double),
+                            C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int32))
 EXCHANGE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_int32)
 
 
@@ -34,6 +37,19 @@ def _lib():
         common = [C.c_int32, ip, dp, ip, ip, dp, C.c_int32, dp, dp]
         lib.tamcmc_sampler_create.argtypes = [C.POINTER(vp), C.POINTER(SamplerCfg), EVAL_FN, vp] + common
         lib.tamcmc_sampler_create_hip.argtypes = [C.POINTER(vp), C.POINTER(SamplerCfg), vp] + common
+        lib.tamcmc_sampler_create_lockstep.argtypes = [C.POINTER(vp), C.POINTER(SamplerCfg), vp, C.c_int32] + common
+        lib.tamcmc_lockstep_create.argtypes = [C.POINTER(vp), C.c_int32, ip, GROUP_EVAL_FN, vp]
+        lib.tamcmc_lockstep_create_group.argtypes = [C.POINTER(vp), vp]
+        lib.tamcmc_lockstep_join.argtypes = [vp, C.c_int32]
+        lib.tamcmc_lockstep_leave.argtypes = [vp, C.c_int32]
+        lib.tamcmc_lockstep_destroy.argtypes = [vp]
+        lib.tamcmc_lockstep_deposit.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, dp, dp, dp, ip]
+        lib.tamcmc_lockstep_collect.argtypes = [vp, C.c_int32]
+        lib.tamcmc_lockstep_error.argtypes = [vp]
+        lib.tamcmc_lockstep_error.restype = C.c_char_p
+        lib.tamcmc_lockstep_calls.argtypes = [vp]
+        lib.tamcmc_lockstep_calls.restype = C.c_int64
+        lib.tamcmc_lockstep_nparams.argtypes = [vp, C.c_int32]
         for name in ("init", "mh_step", "end_iteration", "destroy"):
             getattr(lib, "tamcmc_sampler_" + name).argtypes = [vp]
         lib.tamcmc_sampler_pt_due.argtypes = [vp]
@@ -136,9 +152,82 @@ def default_cfg(Nchains, chain_offset=0, Nchains_local=None, Tmax=150.0, seed=1,
     return cfg
 
 
+class Lockstep:
+    """tamcmc_lockstep (include/tamcmc_sampler.h): K samplers on K threads share one evaluation call per iteration.
+    backend: a capi.Group (its begin / end / poll), or for tests a Python callable
+    f(P_list, T_list) -> (list of logL, list of status) with one block per member (empty for a member that sits out);
+    Nparams (one entry per member) is needed with a callable only."""
+
+    def __init__(self, backend, Nparams=None):
+        self._lib = _lib()
+        self._h = C.c_void_p()
+        self._cb = None
+        self.errors = []                   # exceptions raised by a Python backend (the round returns E_INVALID)
+        if isinstance(backend, capi.Group):
+            self._keep = backend
+            self.n = len(backend.members)
+            rc = self._lib.tamcmc_lockstep_create_group(C.byref(self._h), backend._g)
+        else:
+            npar = np.ascontiguousarray(Nparams, dtype=np.int32)
+            self.n = int(npar.size)
+
+            def cb(user, n, p_nch, p_npar, p_params, p_T, p_logL, p_status):
+                try:
+                    nch = np.ctypeslib.as_array(p_nch, shape=(n,))
+                    npr = np.ctypeslib.as_array(p_npar, shape=(n,))
+                    tot, totp = int(nch.sum()), int((nch * npr).sum())
+                    Pc = np.ctypeslib.as_array(p_params, shape=(totp,))
+                    Tc = np.ctypeslib.as_array(p_T, shape=(tot,))
+                    P, T, po, co = [], [], 0, 0
+                    for k in range(n):
+                        P.append(Pc[po:po + nch[k] * npr[k]].reshape(nch[k], npr[k]))
+                        T.append(Tc[co:co + nch[k]])
+                        po += int(nch[k] * npr[k])
+                        co += int(nch[k])
+                    L, st = backend(P, T)
+                    np.ctypeslib.as_array(p_logL, shape=(tot,))[:] = np.concatenate([np.asarray(v, dtype=np.float64).ravel() for v in L])
+                    np.ctypeslib.as_array(p_status, shape=(tot,))[:] = np.concatenate([np.asarray(v, dtype=np.int32).ravel() for v in st])
+                    return 0
+                except Exception as e:      # noqa: BLE001 -- must not propagate through the C frame
+                    self.errors.append(e)
+                    return capi.E_INVALID
+            self._cb = GROUP_EVAL_FN(cb)
+            rc = self._lib.tamcmc_lockstep_create(C.byref(self._h), self.n, _ip(npar), self._cb, None)
+        if rc != 0:
+            raise capi.AccelError(rc, "tamcmc_lockstep_create", self._lib.tamcmc_strerror(rc).decode())
+
+    def _check(self, rc, where):
+        if rc != 0:
+            raise capi.AccelError(rc, where, self._lib.tamcmc_strerror(rc).decode() + " | " + self.error())
+
+    def join(self, member):
+        self._check(self._lib.tamcmc_lockstep_join(self._h, int(member)), "tamcmc_lockstep_join")
+
+    def leave(self, member):
+        self._check(self._lib.tamcmc_lockstep_leave(self._h, int(member)), "tamcmc_lockstep_leave")
+
+    def error(self):
+        return self._lib.tamcmc_lockstep_error(self._h).decode()
+
+    def calls(self):
+        return int(self._lib.tamcmc_lockstep_calls(self._h))
+
+    def close(self):
+        """Refused (AccelError) while a member is joined."""
+        if self._h and self._h.value:
+            self._check(self._lib.tamcmc_lockstep_destroy(self._h), "tamcmc_lockstep_destroy")
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class Sampler:
     def __init__(self, cfg, evaluator, plength, inputs, relax, err, priors_names_switch=None, priors_params=None,
-                 extra_priors=(0.0, 1.0, 1e30, 0.0)):
+                 extra_priors=(0.0, 1.0, 1e30, 0.0), lockstep=None):
         self._lib = _lib()
         self.cfg = cfg
         self.plength = np.ascontiguousarray(plength, dtype=np.int32)
@@ -155,7 +244,11 @@ class Sampler:
         self._cb = None
         common = (self.Nparams, _ip(self.plength), _dp(self.inputs), _ip(self.relax), _ip(self.sw), _dp(self.pp),
                   self.pp.shape[0], _dp(self.extra), _dp(self.err))
-        if isinstance(evaluator, capi.Accel):
+        if lockstep is not None:
+            # (ls, member): the evaluations are this member's share of the rounds of a Lockstep object; evaluator is unused
+            self._keep = lockstep[0]
+            rc = self._lib.tamcmc_sampler_create_lockstep(C.byref(self._h), C.byref(cfg), lockstep[0]._h, int(lockstep[1]), *common)
+        elif isinstance(evaluator, capi.Accel):
             self._keep = evaluator
             rc = self._lib.tamcmc_sampler_create_hip(C.byref(self._h), C.byref(cfg), evaluator._ctx, *common)
         else:
