@@ -61,7 +61,9 @@ typedef struct tamcmc_ctx tamcmc_ctx;
 #define TAMCMC_E_UNKNOWN_MODEL     5  /* id not in models_ctrl.list / likelihoods_ctrl.list                   */
 #define TAMCMC_E_NOMEM             6
 #define TAMCMC_E_NOVARS            7  /* gradient requested before tamcmc_ctx_set_vars                        */
-#define TAMCMC_E_NOGRAD            8  /* gradient not available for this model/likelihood id                  */
+#define TAMCMC_E_NOGRAD            8  /* gradient not available for this model/likelihood id, or (tamcmc_ctx_set_vars)
+                                         for this many multiplets and variables: the backward kernel's tables would
+                                         not fit its LDS; the context keeps its earlier variables              */
 #define TAMCMC_PENDING            -1  /* tamcmc_eval_batch_poll only: not an error, the chain's result has not arrived yet */
 
 /* per-chain status written by the eval calls */
@@ -91,7 +93,11 @@ int tamcmc_ctx_create(tamcmc_ctx **out, int device_id, int model_case, int likel
                       const double *x, const double *y, const double *sigma_y);
 
 /* Replaces: Model_def::index_to_relax (model_def.cpp:81-88).  Declares which params columns are
- * the free variables; needed only for gradients.  grad column k = d(logL/T)/d params[index_to_relax[k]]. */
+ * the free variables; needed only for gradients.  grad column k = d(logL/T)/d params[index_to_relax[k]].
+ * TAMCMC_E_NOGRAD (nothing changed) when the gradient tables of the layout with these variables exceed the backward
+ * kernel's LDS (504 bytes per multiplet + 72 per variable + 12 per parameter > 150 KB: with every entry a variable
+ * from some 210 (id 13) to 235 (id 2) multiplets on; 256 multiplets take up to 262 variables); likelihood batches are
+ * not affected. */
 int tamcmc_ctx_set_vars(tamcmc_ctx *ctx, int32_t Nvars, const int32_t *index_to_relax);
 
 /* Extension (no counterpart in the reference, which fits one spectrum per process): several spectra ON THE SAME GRID

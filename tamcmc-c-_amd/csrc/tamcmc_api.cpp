@@ -407,6 +407,9 @@ extern "C" int tamcmc_ctx_set_vars(tamcmc_ctx *c, int32_t Nvars, const int32_t *
     if (!c || Nvars < 0 || (Nvars > 0 && !index_to_relax)) return TAMCMC_E_INVALID;
     for (int i = 0; i < Nvars; i++)
         if (index_to_relax[i] < 0 || index_to_relax[i] >= c->L.Nparams) return TAMCMC_E_INVALID;
+    // a layout whose gradient tables outgrow the backward kernel's LDS (every entry a variable: from some 210 to 235 multiplets on)
+    // is refused here, the context left as it was -- not at the first gradient batch, after two of its three launches
+    if (Nvars > 0 && !tm_backward_fits(c->L, c->tiles_g, Nvars)) return TAMCMC_E_NOGRAD;
     TM_HIP(hipSetDevice(c->device));
     TM_HIP(ctx_stream_sync(c));
     (void)hipFree(c->d_relax); c->d_relax = nullptr;
@@ -1479,7 +1482,7 @@ extern "C" const char *tamcmc_strerror(int code)
     case TAMCMC_E_UNKNOWN_MODEL: return "unknown model or likelihood id";
     case TAMCMC_E_NOMEM: return "out of memory";
     case TAMCMC_E_NOVARS: return "gradient requested before tamcmc_ctx_set_vars";
-    case TAMCMC_E_NOGRAD: return "gradient not available for this model";
+    case TAMCMC_E_NOGRAD: return "gradient not available for this model (or for so many multiplets and variables)";
     default: return "unknown error code";
     }
 }

@@ -41,6 +41,7 @@ __shared__ unsigned long long g_bfine[8];
 #define TM_NPAIR 12   // pairs a multiplet can emit
 #define TM_NSHARED 20 // chain-level adjoint slots per multiplet
 #define TM_NCPAIR 64  // base number of chain-level pairs (plus numax pairs for id 9)
+#define TM_BW_LDS_MAX ((size_t)150 * 1024)   // dynamic LDS of a workgroup at most (160 KB per CU, ~10 KB of static tables)
 
 // chain-level slots
 #define SL_A1 0
@@ -688,6 +689,25 @@ __global__ __launch_bounds__(TM_BW_THREADS) void tamcmc_backward_kernel(TmLayout
 #endif
 }
 
+// Dynamic LDS of the backward kernel without the staged records (the carve-up at the top of the kernel), and those records.
+static size_t tm_backward_lds_base(const TmLayout &L, int tiles, int Nvars)
+{
+    const int nm = L.n_mult;
+    const int ncp = TM_NCPAIR + (L.model_case == 9 ? (L.Nmax * (L.lmax + 2) + L.lmax) : 0);
+    const int npairs_max = nm * TM_NPAIR + ncp;
+    return ((size_t)L.Nparams + (size_t)Nvars) * sizeof(double) + (size_t)npairs_max * sizeof(double) +
+           (size_t)nm * (TM_NSHARED + TM_GSLOTS + 1) * sizeof(double) + 16 + (size_t)((npairs_max + 7) & ~7) * sizeof(int) +
+           (size_t)((tiles + 2) & ~1) * sizeof(int) + (size_t)((L.Nparams + 1) & ~1) * sizeof(int) +
+           (size_t)(TM_BW_THREADS / 64) * Nvars * sizeof(double);
+}
+
+// Whether the backward kernel's tables for this layout, tile count and variable count fit the workgroup's LDS
+// (tamcmc_ctx_set_vars refuses the variables otherwise, so that no gradient batch is launched that cannot be finished).
+int tm_backward_fits(const TmLayout &L, int tiles, int Nvars)
+{
+    return tm_backward_lds_base(L, tiles, Nvars) <= TM_BW_LDS_MAX ? 1 : 0;
+}
+
 int tm_launch_backward(const TmLayout &L, int Nchains, int units, int cells, int tiles, int equal_cost, TmCostModel geom, const double *d_params,
                        const double *d_Tcoefs, const void *d_chain_rec, const void *d_aux, const TmNoise *d_noise,
                        const double *d_part, const double *d_gmult, const double *d_gnoise, const TmCellRec *d_cell,
@@ -695,17 +715,12 @@ int tm_launch_backward(const TmLayout &L, int Nchains, int units, int cells, int
                        double *d_logL, int32_t *d_status, void *stream)
 {
     const int nm = L.n_mult;
-    const int ncp = TM_NCPAIR + (L.model_case == 9 ? (L.Nmax * (L.lmax + 2) + L.lmax) : 0);
-    const int npairs_max = nm * TM_NPAIR + ncp;
     if (units < 1 || cells < 1 || tiles < 1) return (int)hipErrorInvalidValue;
-    size_t lds = ((size_t)L.Nparams + (size_t)Nvars) * sizeof(double) + (size_t)npairs_max * sizeof(double) +
-                 (size_t)nm * (TM_NSHARED + TM_GSLOTS + 1) * sizeof(double) + 16 + (size_t)((npairs_max + 7) & ~7) * sizeof(int) +
-                 (size_t)((tiles + 2) & ~1) * sizeof(int) + (size_t)((L.Nparams + 1) & ~1) * sizeof(int) +
-                 (size_t)(TM_BW_THREADS / 64) * Nvars * sizeof(double);
+    size_t lds = tm_backward_lds_base(L, tiles, Nvars);
     const size_t aux_bytes = (size_t)nm * sizeof(TmMultFull);
     const int aux_in_lds = (lds + aux_bytes <= 100 * 1024) ? 1 : 0;
     if (aux_in_lds) lds += aux_bytes;
-    if (lds > 150 * 1024) return (int)hipErrorInvalidValue;
+    if (lds > TM_BW_LDS_MAX) return (int)hipErrorInvalidValue;
     if (lds > 48 * 1024) {
         hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(tamcmc_backward_kernel),
                                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);

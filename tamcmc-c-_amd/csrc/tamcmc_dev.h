@@ -257,5 +257,7 @@ int tm_launch_backward(const TmLayout &L, int Nchains, int units, int cells, int
                        const double *d_part, const double *d_gmult, const double *d_gnoise, const TmCellRec *d_cell,
                        const TmTileHdr *d_thdr, const double *d_hser, int Nvars, const int32_t *d_index_to_relax, double *d_grad,
                        double *d_logL, int32_t *d_status, void *stream);
+// 1 when the backward kernel's LDS tables fit for this layout, gradient tile count and number of variables
+int tm_backward_fits(const TmLayout &L, int tiles, int Nvars);
 }
 #endif
