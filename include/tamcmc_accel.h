@@ -86,6 +86,8 @@ typedef struct tamcmc_ctx tamcmc_ctx;
  *   plength          the 11 block lengths of the params row.
  *   x, y, sigma_y    Nx doubles each on the host; sigma_y may be NULL unless likelihood_case == 1.
  *                    x must be the regular grid the reference assumes (build_lorentzian.cpp:423).
+ *                    x[0] == 0 is supported (likelihood and gradient) with every active Harvey exponent |p| >= 1e-297;
+ *                    a Harvey exponent of 0 on such a grid, and negative frequencies, are not.
  *   Nx               2 <= Nx <= 2^28 (TAMCMC_E_INVALID outside): the kernels address the grid with 32-bit byte
  *                    offsets; the reference itself reads at most 1e6 rows (config.cpp:531). */
 int tamcmc_ctx_create(tamcmc_ctx **out, int device_id, int model_case, int likelihood_case,

@@ -959,7 +959,10 @@ static void orc_noise_adjoint(const double *params, int z, int Nnoise, int Nharv
                 const long double sx = s * x[i], t = powl(sx, p), u = 1.0L / (1.0L + t);
                 adj_term(&gH, wgt[i] * u);
                 adj_term(&gT, wgt[i] * (-(long double)H * p * t * u * u / tau));
-                adj_term(&gP, wgt[i] * (-(long double)H * t * logl(sx) * u * u));
+                /* t ln(sx) -> 0 as sx -> 0 (p > 0): a grid that starts at x = 0 has t = 0, ln = -inf there.  The weight stays
+                 * a factor (a NaN or inf weight reaches this entry as it reaches the other two).  p == 0 with x == 0 is
+                 * t = 1, ln = -inf: the term is -inf, the profile jumps there; the library does not support that input. */
+                adj_term(&gP, wgt[i] * (t == 0 ? 0.0L : -(long double)H * t * logl(sx) * u * u));
             }
             adj_axpy(&G[z + 3 * k], orc_sgn(params[z + 3 * k]), gH);
             adj_axpy(&G[z + 3 * k + 1], orc_sgn(params[z + 3 * k + 1]), gT);

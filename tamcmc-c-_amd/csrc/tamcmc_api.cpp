@@ -367,7 +367,14 @@ extern "C" int tamcmc_ctx_create(tamcmc_ctx **out, int device_id, int model_case
     std::vector<double> tmp((size_t)Nx);
     for (int64_t i = 0; i < Nx; i++) tmp[(size_t)i] = 2.0 * x[i];        // exact; the Lorentzians are written in d = 2x - 2nu
     if (hipMemcpy(c->d_x2, tmp.data(), bytes, hipMemcpyHostToDevice) != hipSuccess) return fail(TAMCMC_E_HIP);
-    for (int64_t i = 0; i < Nx; i++) tmp[(size_t)i] = std::log(x[i]);   // log x table for the Harvey powers
+    // log x table for the Harvey powers.  x == 0 (the first bin of a spectrum made by an FFT) is stored as -1e300, not -inf:
+    // t = exp(p (lt - 1e300)) is exactly 0 while p * 1e300 exceeds about 745, i.e. for every Harvey exponent p >= 1e-297,
+    // so u = 1 and the model are as with -inf, while the gradient's t u^2 (lt + log x) is 0 * finite = 0, the limit of
+    // t ln(sx), and not 0 * inf = NaN.  The cell's span |p (log x - lxc)| is about p * 1e300 there, far above the 0.04 a
+    // polynomial cell needs, so the cell that holds x == 0 takes the exp path.  An exponent below 1e-297 (p == 0 among
+    // them) together with x == 0 is not supported: t is no longer 0, the cell may pass for a polynomial one and the weight
+    // moments then overflow (include/tamcmc_accel.h).
+    for (int64_t i = 0; i < Nx; i++) tmp[(size_t)i] = x[i] == 0.0 ? -1e300 : std::log(x[i]);
     if (hipMemcpy(c->d_y, y, bytes, hipMemcpyHostToDevice) != hipSuccess ||
         hipMemcpy(c->d_lx, tmp.data(), bytes, hipMemcpyHostToDevice) != hipSuccess)
         return fail(TAMCMC_E_HIP);
