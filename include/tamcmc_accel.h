@@ -167,6 +167,59 @@ int tamcmc_group_eval_end(tamcmc_group *g, double *logL, int32_t *status);
 int tamcmc_group_eval_poll(const tamcmc_group *g, int32_t member, int32_t chain, double *logL, int32_t *status);
 int tamcmc_group_members(const tamcmc_group *g, int32_t *n_members, int32_t *Nparams, int32_t *device);
 
+/* Extension: posterior SUMMARIES of a stored chain -- what a user does with the samples of an Acquire phase: the
+ * posterior-mean model with its envelope, and WAIC to compare two fits of the same spectrum -- without handing S x Nx
+ * model values through host memory.  (The reference's diagnostics.cpp needs gnuplot, Boost and the whole temperature
+ * ladder; this is its data-parallel core: a per-bin reduction over samples of what the eval kernels already produce.)
+ * A summary object is bound to one context, is fed parameter rows in any number of pushes and keeps per-bin running
+ * statistics on the device.  Samples are evaluated at temperature 1.  For every sample s with status TAMCMC_CHAIN_OK and
+ * every bin i: the model value M_is and the POINTWISE log-likelihood l_is,
+ *     chi(2,2p)    l_is = -p (y_i / M_is + log M_is)        p = likelihood_p truncated as everywhere in this library
+ *     chi_square   l_is = -(y_i - M_is)^2 / sigma_i^2       the REFERENCE'S convention (likelihoods.cpp:31-39): no factor
+ *                                                            1/2, so lppd / p_waic / waic are on that scale too
+ * Per bin, with n = samples accepted so far:
+ *     mean_M, var_M   mean and variance (divisor n - 1) of M_is           min_M, max_M   the envelope
+ *     mean_l, var_l   the same for l_is; var_l is the bin's WAIC penalty   lppd           log((1/n) sum_s exp l_is)
+ * and the totals n_used, n_rejected, lppd_total = sum_i lppd_i, p_waic = sum_i var_l_i, waic = -2 (lppd_total - p_waic),
+ * summed on the host in bin order in long double.  With n < 2 the two variances are NaN; with n = 0 everything is NaN.
+ * A sample whose status is not OK is left out of every bin and counted in n_rejected.
+ *   create       block_chains: samples evaluated per block (the object owns block_chains x Nx doubles for their model
+ *                rows); 0 picks 64, lowered so that this buffer stays within 64 MiB.  A context counts its summary
+ *                objects like its groups: while one exists tamcmc_ctx_destroy and tamcmc_ctx_set_spectra return
+ *                TAMCMC_E_INVALID.
+ *   push         host pointers, synchronous.  params: Nsamples x Nparams; logL / status (each may be NULL): per sample,
+ *                the bits tamcmc_eval_batch returns for that row at T = 1 with that chain listed in model_rows.  More
+ *                samples than one block are cut into blocks internally.
+ *   push_device  the same with device pointers, enqueued on the context's stream without synchronising.
+ *   result       synchronises the stream; may be called between pushes and does not disturb the running state.  Seven
+ *                arrays of Nx doubles on the host, any of them (and totals) may be NULL.
+ *   reset        forgets every sample.       destroy   TAMCMC_E_INVALID while a batch is armed on the context.
+ * Every bin is folded one sample at a time in push order by one thread (Welford's recurrence for the two mean / variance
+ * pairs, a running-maximum log-sum-exp for lppd; tamcmc_summary.hip), so every result is BIT FOR BIT independent of
+ * block_chains and of how the samples are split over pushes.
+ * Refused with TAMCMC_E_INVALID: NULL arguments, Nsamples < 1, an Nparams mismatch, block_chains < 0, a context with a
+ * batch in flight or armed, and a context holding more than one spectrum (tamcmc_ctx_set_spectra; out of scope, as are
+ * fit groups and quantile bands).
+ *   profile / kernel_time   as tamcmc_ctx_profile / tamcmc_ctx_kernel_time, for the fold kernel alone (one event pair per
+ *                block while enabled). */
+typedef struct tamcmc_summary tamcmc_summary;
+typedef struct {
+    int64_t n_used, n_rejected;
+    double lppd_total, p_waic, waic;
+} tamcmc_summary_totals;
+int tamcmc_summary_create(tamcmc_summary **out, tamcmc_ctx *ctx, int32_t block_chains);
+int tamcmc_summary_push(tamcmc_summary *s, int32_t Nsamples, int32_t Nparams, const double *params,
+                        double *logL, int32_t *status);
+int tamcmc_summary_push_device(tamcmc_summary *s, int32_t Nsamples, int32_t Nparams, const double *d_params,
+                               double *d_logL, int32_t *d_status);
+int tamcmc_summary_result(tamcmc_summary *s, tamcmc_summary_totals *totals,
+                          double *mean_M, double *var_M, double *min_M, double *max_M,
+                          double *mean_l, double *var_l, double *lppd);
+int tamcmc_summary_reset(tamcmc_summary *s);
+int tamcmc_summary_destroy(tamcmc_summary *s);
+int tamcmc_summary_profile(tamcmc_summary *s, int enable);
+int tamcmc_summary_kernel_time(tamcmc_summary *s, double *total_ms, int64_t *launches);
+
 /* Replaces: the `for chain` loop of generate_model() calls (MALA.cpp:632-639, model_def.cpp:139-143).
  * Host pointers, row-major.  Synchronous: results are valid on return.
  *   params      Nchains x Nparams
@@ -252,7 +305,7 @@ int tamcmc_ctx_clock_probe_end(tamcmc_ctx *ctx, double *core_GHz, double *second
 int tamcmc_ctx_geometry(tamcmc_ctx *ctx, int32_t *bins_per_tile, int32_t *tiles, int32_t *threads_per_block,
                         int32_t *n_multiplets);
 
-/* TAMCMC_E_INVALID (and nothing happens) while the context is a member of a fit group. */
+/* TAMCMC_E_INVALID (and nothing happens) while the context is a member of a fit group or has a summary object. */
 int tamcmc_ctx_destroy(tamcmc_ctx *ctx);
 
 int tamcmc_device_count(void);

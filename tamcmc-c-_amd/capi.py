@@ -28,7 +28,15 @@ EXPORTS = [
     "tamcmc_group_create", "tamcmc_group_eval", "tamcmc_group_eval_device", "tamcmc_group_set_stream",
     "tamcmc_group_synchronize", "tamcmc_group_destroy",
     "tamcmc_group_eval_begin", "tamcmc_group_eval_end", "tamcmc_group_eval_poll", "tamcmc_group_members",
+    "tamcmc_summary_create", "tamcmc_summary_push", "tamcmc_summary_push_device", "tamcmc_summary_result",
+    "tamcmc_summary_reset", "tamcmc_summary_destroy", "tamcmc_summary_profile", "tamcmc_summary_kernel_time",
 ]
+
+
+class SummaryTotals(C.Structure):
+    """tamcmc_summary_totals"""
+    _fields_ = [("n_used", C.c_int64), ("n_rejected", C.c_int64), ("lppd_total", C.c_double), ("p_waic", C.c_double),
+                ("waic", C.c_double)]
 
 
 class AccelError(RuntimeError):
@@ -83,6 +91,14 @@ def load_library():
     lib.tamcmc_group_eval_end.argtypes = [vp, dp, ip]
     lib.tamcmc_group_eval_poll.argtypes = [vp, C.c_int32, C.c_int32, dp, ip]
     lib.tamcmc_group_members.argtypes = [vp, ip, ip, ip]
+    lib.tamcmc_summary_create.argtypes = [C.POINTER(vp), vp, C.c_int32]
+    lib.tamcmc_summary_push.argtypes = [vp, C.c_int32, C.c_int32, dp, dp, ip]
+    lib.tamcmc_summary_push_device.argtypes = [vp, C.c_int32, C.c_int32, vp, vp, vp]
+    lib.tamcmc_summary_result.argtypes = [vp, C.POINTER(SummaryTotals), dp, dp, dp, dp, dp, dp, dp]
+    lib.tamcmc_summary_reset.argtypes = [vp]
+    lib.tamcmc_summary_destroy.argtypes = [vp]
+    lib.tamcmc_summary_profile.argtypes = [vp, C.c_int]
+    lib.tamcmc_summary_kernel_time.argtypes = [vp, dp, C.POINTER(C.c_int64)]
     for name in EXPORTS:
         fn = getattr(lib, name)
         if fn.restype is not C.c_char_p:
@@ -372,6 +388,81 @@ class Group:
         if getattr(self, "_g", None) is not None and self._g.value:
             self._lib.tamcmc_group_destroy(self._g)
             self._g = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
+class Summary:
+    """Posterior summaries of a stored chain (tamcmc_accel.h, tamcmc_summary_*): per-bin running statistics of the model
+    and of the pointwise log-likelihood over the parameter rows pushed so far, kept on the device.  Results do not depend,
+    bit for bit, on block_chains or on how the rows are split over pushes.  The Accel cannot be closed while the summary
+    is open."""
+
+    ARRAYS = ("mean_M", "var_M", "min_M", "max_M", "mean_l", "var_l", "lppd")
+
+    def __init__(self, accel, block_chains=0):
+        self._lib = load_library()
+        self.accel = accel
+        self._s = C.c_void_p()
+        self._check(self._lib.tamcmc_summary_create(C.byref(self._s), accel._ctx, int(block_chains)), "tamcmc_summary_create")
+
+    _check = Accel._check
+
+    def push(self, params):
+        """params: (n, Nparams) rows.  Returns (logL, status) of these rows at T = 1."""
+        params = _c64(params)
+        if params.ndim != 2 or params.shape[1] != self.accel.Nparams:
+            raise ValueError(f"params must be (Nsamples, {self.accel.Nparams})")
+        n = params.shape[0]
+        logL = np.empty(n)
+        status = np.empty(n, dtype=np.int32)
+        self._check(self._lib.tamcmc_summary_push(self._s, n, self.accel.Nparams, _dptr(params), _dptr(logL), _iptr(status)),
+                    "tamcmc_summary_push")
+        return logL, status
+
+    def push_device(self, nsamples, d_params, d_logL=0, d_status=0):
+        """Device pointers (ints, e.g. torch.Tensor.data_ptr()); enqueued on the context's stream, no sync."""
+        rc = self._lib.tamcmc_summary_push_device(self._s, int(nsamples), self.accel.Nparams, C.c_void_p(d_params),
+                                                  C.c_void_p(d_logL) if d_logL else None,
+                                                  C.c_void_p(d_status) if d_status else None)
+        self._check(rc, "tamcmc_summary_push_device")
+
+    def result(self):
+        """dict of the seven per-bin arrays and the totals n_used, n_rejected, lppd_total, p_waic, waic."""
+        out = {k: np.empty(self.accel.Nx) for k in self.ARRAYS}
+        t = SummaryTotals()
+        self._check(self._lib.tamcmc_summary_result(self._s, C.byref(t), *[_dptr(out[k]) for k in self.ARRAYS]),
+                    "tamcmc_summary_result")
+        out.update(n_used=int(t.n_used), n_rejected=int(t.n_rejected), lppd_total=t.lppd_total, p_waic=t.p_waic, waic=t.waic)
+        return out
+
+    def reset(self):
+        self._check(self._lib.tamcmc_summary_reset(self._s), "tamcmc_summary_reset")
+
+    def profile(self, enable=True):
+        self._check(self._lib.tamcmc_summary_profile(self._s, int(enable)), "tamcmc_summary_profile")
+
+    def kernel_time(self):
+        """(summed milliseconds, launches) of the fold kernel since profile(True)."""
+        ms = C.c_double(0.0)
+        n = C.c_int64(0)
+        self._check(self._lib.tamcmc_summary_kernel_time(self._s, C.byref(ms), C.byref(n)), "tamcmc_summary_kernel_time")
+        return ms.value, n.value
+
+    def close(self):
+        if getattr(self, "_s", None) is not None and self._s.value:
+            self._check(self._lib.tamcmc_summary_destroy(self._s), "tamcmc_summary_destroy")
+            self._s = C.c_void_p()
 
     def __del__(self):
         try:

@@ -19,6 +19,7 @@
 #include "tamcmc_accel.h"
 #include "tamcmc_dev.h"
 #include "tamcmc_group.h"
+#include "tamcmc_summary.h"
 
 static thread_local char g_hip_err[256] = "";
 
@@ -96,6 +97,7 @@ struct tamcmc_ctx {
     std::vector<hipEvent_t> ev;   // pairs (start, stop)
     size_t ev_used = 0;
     int groups = 0;               // fit groups this context is a member of (tamcmc_group_create); destroy is refused meanwhile
+    int summaries = 0;            // summary objects bound to this context (tamcmc_summary_create); destroy is refused meanwhile
     // ordering against fit groups (tamcmc_group_eval_begin): enq_seq counts what this library put on the stream, so that a
     // group can tell whether anything came since it last ordered itself against it; after_ev is a group's "launches done"
     // event this stream has still to wait for -- the wait is enqueued by the next use of the stream (ctx_settle), not by
@@ -391,6 +393,7 @@ extern "C" int tamcmc_ctx_destroy(tamcmc_ctx *c)
 {
     if (!c) return TAMCMC_OK;
     if (c->groups > 0) return TAMCMC_E_INVALID;     // a fit group still refers to it: destroy the group first
+    if (c->summaries > 0) return TAMCMC_E_INVALID;  // and so does a summary object
     (void)hipSetDevice(c->device);
     if (c->armed && c->h_gate) { __atomic_store_n(c->h_gate, c->gate_seq, __ATOMIC_RELEASE); c->armed = 0; }   // let the gate go
     if (c->stream) (void)ctx_stream_sync(c);
@@ -437,6 +440,7 @@ extern "C" int tamcmc_ctx_set_spectra(tamcmc_ctx *c, int32_t Nspectra, const dou
 {
     if (c && c->armed) return TAMCMC_E_INVALID;     // launches wait behind a gate: only _fire / _end / _disarm / destroy (tamcmc_accel.h)
     if (!c || Nspectra < 1 || !y || (c->L.likelihood_case == 1 && !sigma_y)) return TAMCMC_E_INVALID;
+    if (c->summaries > 0) return TAMCMC_E_INVALID;  // a summary's running state belongs to the resident spectrum
     TM_HIP(hipSetDevice(c->device));
     TM_HIP(ctx_stream_sync(c));
     const size_t nx = (size_t)c->L.Nx, bytes = nx * (size_t)Nspectra * sizeof(double);
@@ -1475,6 +1479,293 @@ extern "C" int tamcmc_group_members(const tamcmc_group *g, int32_t *n_members, i
     if (n_members) *n_members = (int32_t)g->m.size();
     if (Nparams) for (size_t k = 0; k < g->m.size(); k++) Nparams[k] = g->m[k]->L.Nparams;
     if (device) *device = g->device;
+    return TAMCMC_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// Posterior summaries of a stored chain (tamcmc_accel.h, tamcmc_summary.h): per-bin running statistics of the model and
+// of the pointwise log-likelihood over the samples pushed so far.  A block of samples = the context's own launches with
+// a row map covering every chain (stage 1) + tamcmc_summary_fold_kernel (stage 2), both on the context's stream.
+struct tamcmc_summary {
+    tamcmc_ctx *c = nullptr;
+    int B = 0;                           // samples per block
+    bool counted = false;                // the context's count includes this object
+    double *d_model = nullptr;           // [B][Nx] model rows of the block in flight (the context's d_model is not touched)
+    double *d_state = nullptr;           // [TM_SUM_NSTATE][Nx]
+    long long *d_cnt = nullptr;          // [2][2] {accepted, rejected}: launch k reads pair k & 1 and writes the other
+    int parity = 0;
+    int32_t *d_rows = nullptr;           // [B] the identity row map
+    double *d_T = nullptr;               // [B] ones: samples are evaluated at temperature 1
+    double *d_logL = nullptr;            // [B] / [B]: where a block's logL / status go when the caller wants none
+    int32_t *d_status = nullptr;
+    // host-pointer pushes: [params | logL | status] of a block, pinned and on the device, two of each (block k fills
+    // slot k & 1 while block k - 1 may still be read by its copies)
+    char *h_stage[2] = {nullptr, nullptr}, *d_stage[2] = {nullptr, nullptr};
+    hipEvent_t ev_stage[2] = {nullptr, nullptr};
+    // timing of the fold kernel alone (tamcmc_summary_profile)
+    bool profile = false;
+    std::vector<hipEvent_t> ev;
+    size_t ev_used = 0;
+};
+
+static size_t summary_stage_out(const tamcmc_summary *s) { return (size_t)s->B * (size_t)s->c->L.Nparams * sizeof(double); }
+static size_t summary_stage_bytes(const tamcmc_summary *s) { return summary_stage_out(s) + (size_t)s->B * (sizeof(double) + sizeof(int32_t)); }
+
+// what every push refuses (the context's state may have changed since the object was created)
+static int summary_check(const tamcmc_summary *s, int32_t Nsamples, int32_t Nparams, const double *params)
+{
+    if (!s || !params || Nsamples < 1) return TAMCMC_E_INVALID;
+    const tamcmc_ctx *c = s->c;
+    if (Nparams != c->L.Nparams || c->in_flight || c->armed || c->nspec > 1) return TAMCMC_E_INVALID;
+    return TAMCMC_OK;
+}
+
+// One block of n <= B samples, device pointers, enqueued on the context's stream.
+static int summary_block(tamcmc_summary *s, int n, const double *d_params, double *d_logL, int32_t *d_status)
+{
+    tamcmc_ctx *c = s->c;
+    int rc = ensure_capacity(c, n, false);
+    if (rc != TAMCMC_OK) return rc;
+    if (!d_logL) d_logL = s->d_logL;
+    if (!d_status) d_status = s->d_status;
+    rc = enqueue(c, n, d_params, s->d_T, d_logL, nullptr, d_status, s->d_rows, s->d_model);
+    if (rc != TAMCMC_OK) return rc;
+    TmSummaryArgs a{};
+    a.rows = s->d_model; a.status = d_status; a.y = c->d_y; a.isig2 = c->d_isig2; a.state = s->d_state;
+    a.cnt_in = s->d_cnt + 2 * s->parity; a.cnt_out = s->d_cnt + 2 * (s->parity ^ 1);
+    a.Nx = c->L.Nx; a.B = n; a.likelihood_case = c->L.likelihood_case; a.like_p = c->L.like_p;
+    if (s->profile) {
+        while (s->ev.size() < s->ev_used + 2) {
+            hipEvent_t e;
+            TM_HIP(hipEventCreate(&e));
+            s->ev.push_back(e);
+        }
+        TM_HIP(hipEventRecord(s->ev[s->ev_used], c->stream));
+    }
+    const int hr = tm_launch_summary_fold(a, c->stream);
+    if (hr != 0) { snprintf(g_hip_err, sizeof(g_hip_err), "summary fold launch -> %s", hipGetErrorString((hipError_t)hr)); return TAMCMC_E_HIP; }
+    s->parity ^= 1;
+    if (s->profile) {
+        TM_HIP(hipEventRecord(s->ev[s->ev_used + 1], c->stream));
+        s->ev_used += 2;
+    }
+    return TAMCMC_OK;
+}
+
+static int summary_clear(tamcmc_summary *s)
+{
+    const tamcmc_ctx *c = s->c;
+    TM_HIP(hipMemsetAsync(s->d_state, 0, (size_t)TM_SUM_NSTATE * (size_t)c->L.Nx * sizeof(double), c->stream));
+    TM_HIP(hipMemsetAsync(s->d_cnt, 0, 4 * sizeof(long long), c->stream));
+    s->parity = 0;
+    return TAMCMC_OK;
+}
+
+extern "C" int tamcmc_summary_create(tamcmc_summary **out, tamcmc_ctx *c, int32_t block_chains)
+{
+    if (!out) return TAMCMC_E_INVALID;
+    *out = nullptr;
+    if (!c || block_chains < 0 || c->in_flight || c->armed) return TAMCMC_E_INVALID;
+    if (c->nspec > 1) return TAMCMC_E_INVALID;      // several spectra in one context: out of scope
+    tamcmc_summary *s = new (std::nothrow) tamcmc_summary();
+    if (!s) return TAMCMC_E_NOMEM;
+    s->c = c;
+    const size_t nx = (size_t)c->L.Nx;
+    int B = block_chains;
+    if (B == 0) {                                   // 64, lowered so that a block's rows take at most 64 MiB
+        const size_t fit = ((size_t)64 << 20) / (nx * sizeof(double));
+        B = fit >= 64 ? 64 : (fit >= 1 ? (int)fit : 1);
+    }
+    s->B = B;
+    auto fail = [&](int code) { tamcmc_summary_destroy(s); return code; };
+    if (hipSetDevice(c->device) != hipSuccess) return fail(TAMCMC_E_NODEVICE);
+    const size_t b = (size_t)B;
+    if (hipMalloc(&s->d_model, b * nx * sizeof(double)) != hipSuccess || hipMalloc(&s->d_state, TM_SUM_NSTATE * nx * sizeof(double)) != hipSuccess ||
+        hipMalloc(&s->d_cnt, 4 * sizeof(long long)) != hipSuccess || hipMalloc(&s->d_rows, b * sizeof(int32_t)) != hipSuccess ||
+        hipMalloc(&s->d_T, b * sizeof(double)) != hipSuccess || hipMalloc(&s->d_logL, b * sizeof(double)) != hipSuccess ||
+        hipMalloc(&s->d_status, b * sizeof(int32_t)) != hipSuccess)
+        return fail(TAMCMC_E_NOMEM);
+    {
+        std::vector<int32_t> rows(b);
+        std::vector<double> ones(b, 1.0);
+        for (size_t k = 0; k < b; k++) rows[k] = (int32_t)k;
+        if (hipMemcpy(s->d_rows, rows.data(), b * sizeof(int32_t), hipMemcpyHostToDevice) != hipSuccess ||
+            hipMemcpy(s->d_T, ones.data(), b * sizeof(double), hipMemcpyHostToDevice) != hipSuccess)
+            return fail(TAMCMC_E_HIP);
+    }
+    if (ctx_settle(c) != hipSuccess || summary_clear(s) != TAMCMC_OK) return fail(TAMCMC_E_HIP);
+    c->enq_seq++;
+    c->summaries++;
+    s->counted = true;
+    *out = s;
+    return TAMCMC_OK;
+}
+
+extern "C" int tamcmc_summary_destroy(tamcmc_summary *s)
+{
+    if (!s) return TAMCMC_OK;
+    tamcmc_ctx *c = s->c;
+    if (c->armed) return TAMCMC_E_INVALID;          // the stream cannot be waited for behind a closed gate: _fire or _disarm first
+    (void)hipSetDevice(c->device);
+    if (c->stream) (void)ctx_stream_sync(c);
+    if (s->counted) c->summaries--;
+    (void)hipFree(s->d_model); (void)hipFree(s->d_state); (void)hipFree(s->d_cnt); (void)hipFree(s->d_rows);
+    (void)hipFree(s->d_T); (void)hipFree(s->d_logL); (void)hipFree(s->d_status);
+    for (int p = 0; p < 2; p++) {
+        (void)hipHostFree(s->h_stage[p]); (void)hipFree(s->d_stage[p]);
+        if (s->ev_stage[p]) (void)hipEventDestroy(s->ev_stage[p]);
+    }
+    for (hipEvent_t e : s->ev) (void)hipEventDestroy(e);
+    delete s;
+    return TAMCMC_OK;
+}
+
+extern "C" int tamcmc_summary_reset(tamcmc_summary *s)
+{
+    if (!s || s->c->in_flight || s->c->armed) return TAMCMC_E_INVALID;
+    tamcmc_ctx *c = s->c;
+    TM_HIP(hipSetDevice(c->device));
+    TM_HIP(ctx_settle(c));
+    c->enq_seq++;
+    return summary_clear(s);
+}
+
+extern "C" int tamcmc_summary_push_device(tamcmc_summary *s, int32_t Nsamples, int32_t Nparams, const double *d_params,
+                                          double *d_logL, int32_t *d_status)
+{
+    int rc = summary_check(s, Nsamples, Nparams, d_params);
+    if (rc != TAMCMC_OK) return rc;
+    TM_HIP(hipSetDevice(s->c->device));
+    for (int32_t k = 0; k < Nsamples; k += s->B) {
+        const int n = Nsamples - k < s->B ? Nsamples - k : s->B;
+        rc = summary_block(s, n, d_params + (size_t)k * (size_t)Nparams, d_logL ? d_logL + k : nullptr, d_status ? d_status + k : nullptr);
+        if (rc != TAMCMC_OK) return rc;
+    }
+    return TAMCMC_OK;
+}
+
+extern "C" int tamcmc_summary_push(tamcmc_summary *s, int32_t Nsamples, int32_t Nparams, const double *params,
+                                   double *logL, int32_t *status)
+{
+    int rc = summary_check(s, Nsamples, Nparams, params);
+    if (rc != TAMCMC_OK) return rc;
+    tamcmc_ctx *c = s->c;
+    TM_HIP(hipSetDevice(c->device));
+    const size_t o_out = summary_stage_out(s), bytes = summary_stage_bytes(s), np = (size_t)Nparams;
+    for (int p = 0; p < 2; p++) {
+        if (s->h_stage[p]) continue;
+        TM_HIP(hipHostMalloc(reinterpret_cast<void **>(&s->h_stage[p]), bytes, hipHostMallocDefault));
+        TM_HIP(hipMalloc(&s->d_stage[p], bytes));
+        TM_HIP(hipEventCreateWithFlags(&s->ev_stage[p], hipEventDisableTiming));
+    }
+    // slot p's copies have landed: hand its block's logL / status out (polled, see wait_done)
+    int pend_k[2] = {-1, -1}, pend_n[2] = {0, 0};
+    auto collect = [&](int p) -> int {
+        if (pend_k[p] < 0) return TAMCMC_OK;
+        for (;;) {
+            const hipError_t e = hipEventQuery(s->ev_stage[p]);
+            if (e == hipSuccess) break;
+            if (e != hipErrorNotReady) { snprintf(g_hip_err, sizeof(g_hip_err), "hipEventQuery -> %s", hipGetErrorString(e)); return TAMCMC_E_HIP; }
+            __builtin_ia32_pause();
+        }
+        const size_t n = (size_t)pend_n[p];
+        if (logL) std::memcpy(logL + pend_k[p], s->h_stage[p] + o_out, n * sizeof(double));
+        if (status) std::memcpy(status + pend_k[p], s->h_stage[p] + o_out + (size_t)s->B * sizeof(double), n * sizeof(int32_t));
+        pend_k[p] = -1;
+        return TAMCMC_OK;
+    };
+    // a failure waits for the stream before it returns: a copy from or into the pinned slots may still be pending
+    auto fail = [&](int code) { (void)hipStreamSynchronize(c->stream); return code; };
+    int slot = 0;
+    for (int32_t k = 0; k < Nsamples; k += s->B, slot ^= 1) {
+        const int n = Nsamples - k < s->B ? Nsamples - k : s->B;
+        rc = collect(slot);
+        if (rc != TAMCMC_OK) return fail(rc);
+        std::memcpy(s->h_stage[slot], params + (size_t)k * np, (size_t)n * np * sizeof(double));
+        char *d = s->d_stage[slot];
+        if (ctx_settle(c) != hipSuccess ||
+            hipMemcpyAsync(d, s->h_stage[slot], (size_t)n * np * sizeof(double), hipMemcpyHostToDevice, c->stream) != hipSuccess)
+            return fail(TAMCMC_E_HIP);
+        rc = summary_block(s, n, reinterpret_cast<const double *>(d), reinterpret_cast<double *>(d + o_out),
+                           reinterpret_cast<int32_t *>(d + o_out + (size_t)s->B * sizeof(double)));
+        if (rc != TAMCMC_OK) return fail(rc);
+        if (hipMemcpyAsync(s->h_stage[slot] + o_out, d + o_out, bytes - o_out, hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
+            hipEventRecord(s->ev_stage[slot], c->stream) != hipSuccess)
+            return fail(TAMCMC_E_HIP);
+        pend_k[slot] = k; pend_n[slot] = n;
+    }
+    // the older of the two pending blocks first: the stream runs them in order
+    rc = collect(slot);
+    if (rc == TAMCMC_OK) rc = collect(slot ^ 1);
+    if (rc != TAMCMC_OK) return fail(rc);
+    TM_HIP(hipGetLastError());
+    return TAMCMC_OK;
+}
+
+extern "C" int tamcmc_summary_result(tamcmc_summary *s, tamcmc_summary_totals *totals,
+                                     double *mean_M, double *var_M, double *min_M, double *max_M,
+                                     double *mean_l, double *var_l, double *lppd)
+{
+    if (!s || s->c->in_flight || s->c->armed) return TAMCMC_E_INVALID;
+    tamcmc_ctx *c = s->c;
+    TM_HIP(hipSetDevice(c->device));
+    TM_HIP(ctx_stream_sync(c));
+    const size_t nx = (size_t)c->L.Nx;
+    long long cnt[2] = {0, 0};
+    std::vector<double> st;
+    try { st.resize(TM_SUM_NSTATE * nx); } catch (const std::bad_alloc &) { return TAMCMC_E_NOMEM; }
+    TM_HIP(hipMemcpy(cnt, s->d_cnt + 2 * s->parity, sizeof(cnt), hipMemcpyDeviceToHost));
+    TM_HIP(hipMemcpy(st.data(), s->d_state, st.size() * sizeof(double), hipMemcpyDeviceToHost));
+    const long long n = cnt[0];
+    const double nan = std::nan(""), dn = (double)n;
+    long double lppd_total = 0.0L, p_waic = 0.0L;
+    for (size_t i = 0; i < nx; i++) {
+        const double vM = n >= 2 ? st[TM_SUM_M2_M * nx + i] / (dn - 1.0) : nan;
+        const double vl = n >= 2 ? st[TM_SUM_M2_L * nx + i] / (dn - 1.0) : nan;
+        const double lp = n >= 1 ? st[TM_SUM_LSE_A * nx + i] + std::log(st[TM_SUM_LSE_R * nx + i] / dn) : nan;
+        if (mean_M) mean_M[i] = n >= 1 ? st[TM_SUM_MEAN_M * nx + i] : nan;
+        if (var_M) var_M[i] = vM;
+        if (min_M) min_M[i] = n >= 1 ? st[TM_SUM_MIN_M * nx + i] : nan;
+        if (max_M) max_M[i] = n >= 1 ? st[TM_SUM_MAX_M * nx + i] : nan;
+        if (mean_l) mean_l[i] = n >= 1 ? st[TM_SUM_MEAN_L * nx + i] : nan;
+        if (var_l) var_l[i] = vl;
+        if (lppd) lppd[i] = lp;
+        lppd_total += (long double)lp;          // in bin order
+        p_waic += (long double)vl;
+    }
+    if (totals) {
+        totals->n_used = n;
+        totals->n_rejected = cnt[1];
+        totals->lppd_total = (double)lppd_total;
+        totals->p_waic = (double)p_waic;
+        totals->waic = (double)(-2.0L * (lppd_total - p_waic));
+    }
+    return TAMCMC_OK;
+}
+
+extern "C" int tamcmc_summary_profile(tamcmc_summary *s, int enable)
+{
+    if (!s || s->c->armed) return TAMCMC_E_INVALID;
+    TM_HIP(hipSetDevice(s->c->device));
+    TM_HIP(ctx_stream_sync(s->c));
+    s->profile = enable != 0;
+    s->ev_used = 0;
+    return TAMCMC_OK;
+}
+
+extern "C" int tamcmc_summary_kernel_time(tamcmc_summary *s, double *total_ms, int64_t *launches)
+{
+    if (!s || !total_ms || !launches || s->c->armed) return TAMCMC_E_INVALID;
+    TM_HIP(hipSetDevice(s->c->device));
+    TM_HIP(ctx_stream_sync(s->c));
+    double t = 0.0;
+    for (size_t i = 0; i + 1 < s->ev_used; i += 2) {
+        float ms = 0.f;
+        TM_HIP(hipEventElapsedTime(&ms, s->ev[i], s->ev[i + 1]));
+        t += (double)ms;
+    }
+    *total_ms = t;
+    *launches = (int64_t)(s->ev_used / 2);
     return TAMCMC_OK;
 }
 

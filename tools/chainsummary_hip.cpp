@@ -1,0 +1,160 @@
+// chainsummary_hip -- posterior summaries of a stored chain on the GPU path (tamcmc_summary_* in tamcmc_accel.h): the
+// posterior-mean model with its envelope and the WAIC terms, per bin, from the samples a run has written.
+//
+//   chainsummary_hip <config dir> <model file> <data file> <params root> <output file>
+//                    [--chain m] [--slice s] [--first i] [--last j] [--thin k] [--block B]
+//
+// <config dir> is the reference's Config/default; model id, likelihood, p, plength, the inputs row and the relax mask
+// come from the setup it describes (tamcmc_setup_create / tamcmc_setup_load, slice s counted from 0).  The samples are
+// read from <params root>_chain-<m>.bin with Nvars from <params root>.hdr (written by tamcmc_outputs.cpp); every row of
+// variables is scattered into the inputs row (Model_def::update_params_with_vars, model_def.cpp:370-378) -- the
+// constants come from the .model file, not from the header's 6-digit constant_values.  Samples first, first + thin, ...
+// up to last (both counted from 0, inclusive) are pushed in blocks of B (0: the library's default).
+// Output: `#` header lines with the totals and the sample range, then the columns
+//   x  y  mean_M  sd_M  min_M  max_M  lppd  var_l            (12 significant digits, like getmodel_hip)
+#include <cmath>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <fstream>
+#include <string>
+#include <vector>
+
+#include "tamcmc_accel.h"
+#include "tamcmc_io.h"
+
+static int usage()
+{
+    fprintf(stderr, " Usage: chainsummary_hip <config dir> <model file> <data file> <params root> <output file>\n"
+                    "                         [--chain m] [--slice s] [--first i] [--last j] [--thin k] [--block B]\n"
+                    "     [1] The directory of config_default.cfg, errors_default.cfg and the *_ctrl.list files (Config/default)\n"
+                    "     [2] The .model file and [3] the .data file of the fit\n"
+                    "     [4] The root of the parameter files: <root>_chain-<m>.bin and <root>.hdr\n"
+                    "     [5] The output file (ASCII): x y mean_M sd_M min_M max_M lppd var_l\n"
+                    "     --chain m   chain to read (default 0, the coldest)     --slice s   slice of the .model file, from 0 (default 0)\n"
+                    "     --first i / --last j / --thin k   samples i, i + k, ... <= j, counted from 0 (default: all)\n"
+                    "     --block B   samples per block on the GPU (default 0: chosen by the library)\n"
+                    " chainsummary_hip version   prints the library version\n");
+    return EXIT_FAILURE;
+}
+
+static int fail(const std::string &msg)
+{
+    fprintf(stderr, "chainsummary_hip: %s\n", msg.c_str());
+    return EXIT_FAILURE;
+}
+
+// `! Nvars= 12` of a .hdr file; -1 when the key is missing
+static long header_value(const std::string &hdr, const std::string &key)
+{
+    std::ifstream f(hdr.c_str());
+    std::string line;
+    while (std::getline(f, line)) {
+        if (line.empty() || line[0] != '!') continue;
+        const size_t eq = line.find('=');
+        if (eq == std::string::npos) continue;
+        std::string k = line.substr(1, eq - 1);
+        const size_t b = k.find_first_not_of(" \t");
+        if (b == std::string::npos) continue;
+        k = k.substr(b, k.find_last_not_of(" \t") - b + 1);
+        if (k == key) return strtol(line.c_str() + eq + 1, nullptr, 10);
+    }
+    return -1;
+}
+
+int main(int argc, char *argv[])
+{
+    if (argc == 2 && std::string(argv[1]) == "version") { printf("chainsummary_hip (%s)\n", tamcmc_version()); return 0; }
+    if (argc < 6) return usage();
+    const std::string cfg_dir = argv[1], model_file = argv[2], data_file = argv[3], root = argv[4], out_file = argv[5];
+    long chain = 0, slice = 0, first = 0, last = -1, thin = 1, block = 0;
+    for (int i = 6; i < argc; i++) {
+        const std::string a = argv[i];
+        long *dst = a == "--chain" ? &chain : a == "--slice" ? &slice : a == "--first" ? &first : a == "--last" ? &last :
+                    a == "--thin" ? &thin : a == "--block" ? &block : nullptr;
+        char *end = nullptr;
+        if (!dst || i + 1 >= argc) return usage();
+        *dst = strtol(argv[++i], &end, 10);
+        if (end == argv[i] || *end != '\0') return usage();
+    }
+    if (chain < 0 || slice < 0 || first < 0 || thin < 1 || block < 0 || block > 0x7FFFFFFF) return usage();
+
+    tamcmc_setup *S = nullptr;
+    if (tamcmc_setup_create(&S, cfg_dir.c_str()) != TAMCMC_IO_OK) return fail("cannot read the default configuration in " + cfg_dir);
+    if (tamcmc_setup_load(S, model_file.c_str(), data_file.c_str(), (int32_t)slice) != TAMCMC_IO_OK)
+        return fail("reading " + model_file + " / " + data_file + ": " + tamcmc_setup_error(S));
+    int32_t Nparams = 0, Nvars = 0, plength[11], model_case = 0, like_case = 0, prior_case = 0;
+    int64_t Nx = 0;
+    double like_p = 1.0;
+    tamcmc_setup_sizes(S, &Nparams, &Nvars, &Nx, plength, &model_case, &like_case, &prior_case, &like_p);
+    std::vector<double> x(Nx), y(Nx), sig(Nx), inputs(Nparams);
+    std::vector<int32_t> relax(Nparams), idx;
+    tamcmc_setup_data(S, x.data(), y.data(), sig.data());
+    tamcmc_setup_inputs(S, inputs.data(), relax.data(), nullptr, nullptr, nullptr, nullptr);
+    tamcmc_setup_destroy(S);
+    for (int32_t i = 0; i < Nparams; i++) if (relax[i] == 1) idx.push_back(i);      // Model_def::index_to_relax, model_def.cpp:81-88
+    if ((int32_t)idx.size() != Nvars) return fail("the setup's relax mask does not match its Nvars");
+
+    const long hv = header_value(root + ".hdr", "Nvars");
+    if (hv < 0) return fail("cannot read Nvars from " + root + ".hdr");
+    if (hv != Nvars) return fail("Nvars = " + std::to_string(hv) + " in " + root + ".hdr, but the setup has " + std::to_string(Nvars) + " variables");
+    const std::string bin = root + "_chain-" + std::to_string(chain) + ".bin";
+    std::ifstream f(bin.c_str(), std::ios::binary);
+    if (!f.is_open()) return fail("unable to open " + bin);
+    f.seekg(0, std::ios::end);
+    const long long fbytes = (long long)f.tellg();
+    f.seekg(0, std::ios::beg);
+    const long long rowb = (long long)Nvars * (long long)sizeof(double);
+    if (Nvars < 1 || fbytes < rowb || fbytes % rowb != 0) return fail(bin + " does not hold whole rows of " + std::to_string(Nvars) + " doubles");
+    const long long Nrows = fbytes / rowb;
+    if (last < 0 || last >= Nrows) last = (long)(Nrows - 1);
+    if (first > last) return fail("no sample in the requested range (the file has " + std::to_string(Nrows) + ")");
+    const long long Nsel = (last - first) / thin + 1;
+
+    tamcmc_ctx *ctx = nullptr;
+    int rc = tamcmc_ctx_create(&ctx, 0, model_case, like_case, like_p, plength, Nx, x.data(), y.data(), sig.data());
+    if (rc != TAMCMC_OK) return fail(std::string("tamcmc_ctx_create: ") + tamcmc_strerror(rc) + " " + tamcmc_last_hip_error());
+    tamcmc_summary *sum = nullptr;
+    rc = tamcmc_summary_create(&sum, ctx, (int32_t)block);
+    if (rc != TAMCMC_OK) return fail(std::string("tamcmc_summary_create: ") + tamcmc_strerror(rc) + " " + tamcmc_last_hip_error());
+    // a few thousand rows per push: the library cuts them into its blocks
+    const long long chunk = 4096;
+    std::vector<double> vars((size_t)Nvars), P;
+    long long last_used = first;
+    for (long long k0 = 0; k0 < Nsel; k0 += chunk) {
+        const long long n = Nsel - k0 < chunk ? Nsel - k0 : chunk;
+        P.assign((size_t)n * (size_t)Nparams, 0.0);
+        for (long long k = 0; k < n; k++) {
+            last_used = first + (k0 + k) * thin;
+            f.seekg(last_used * rowb, std::ios::beg);
+            f.read(reinterpret_cast<char *>(vars.data()), (std::streamsize)rowb);
+            if (!f) return fail("short read in " + bin);
+            double *row = P.data() + (size_t)k * (size_t)Nparams;
+            std::memcpy(row, inputs.data(), (size_t)Nparams * sizeof(double));
+            for (int32_t v = 0; v < Nvars; v++) row[idx[(size_t)v]] = vars[(size_t)v];
+        }
+        rc = tamcmc_summary_push(sum, (int32_t)n, Nparams, P.data(), nullptr, nullptr);
+        if (rc != TAMCMC_OK) return fail(std::string("tamcmc_summary_push: ") + tamcmc_strerror(rc) + " " + tamcmc_last_hip_error());
+    }
+    tamcmc_summary_totals t;
+    std::vector<double> mean_M(Nx), var_M(Nx), min_M(Nx), max_M(Nx), var_l(Nx), lppd(Nx);
+    rc = tamcmc_summary_result(sum, &t, mean_M.data(), var_M.data(), min_M.data(), max_M.data(), nullptr, var_l.data(), lppd.data());
+    if (rc != TAMCMC_OK) return fail(std::string("tamcmc_summary_result: ") + tamcmc_strerror(rc) + " " + tamcmc_last_hip_error());
+    tamcmc_summary_destroy(sum);
+    tamcmc_ctx_destroy(ctx);
+
+    FILE *o = fopen(out_file.c_str(), "w");
+    if (!o) return fail("unable to open the output file " + out_file);
+    fprintf(o, "# chainsummary_hip (%s)\n", tamcmc_version());
+    fprintf(o, "# params= %s  chain= %ld  slice= %ld  model_case= %d  likelihood_case= %d\n", bin.c_str(), chain, slice, model_case, like_case);
+    fprintf(o, "# samples_in_file= %lld  first= %ld  last= %lld  thin= %ld\n", Nrows, first, last_used, thin);
+    fprintf(o, "# n_used= %lld  n_rejected= %lld\n", (long long)t.n_used, (long long)t.n_rejected);
+    fprintf(o, "# lppd_total= %.12g  p_waic= %.12g  waic= %.12g\n", t.lppd_total, t.p_waic, t.waic);
+    fprintf(o, "# x y mean_M sd_M min_M max_M lppd var_l\n");
+    for (int64_t i = 0; i < Nx; i++)
+        fprintf(o, "%.12g %.12g %.12g %.12g %.12g %.12g %.12g %.12g\n", x[i], y[i], mean_M[i], std::sqrt(var_M[i]), min_M[i], max_M[i],
+                lppd[i], var_l[i]);
+    fclose(o);
+    printf("Summary of %lld samples (%lld rejected) written to %s\n", (long long)t.n_used, (long long)t.n_rejected, out_file.c_str());
+    return 0;
+}

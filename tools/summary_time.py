@@ -1,0 +1,118 @@
+#!/usr/bin/env python
+"""Times the posterior summary (tamcmc_amd.Summary) on C2's grid: Nx = 1e5 bins, model id 2, S rows of synth.chain_params.
+
+Prints one JSON line:
+  a_summary_s_per_1000      seconds per 1000 samples through Summary.push (host pointers, blocks of --block)
+  b_host_route_s_per_1000   the same work without the summary object: eval_batch with every chain in model_rows in blocks
+                            of 64, S x Nx doubles through host memory, and the same recurrences in numpy, sample by sample
+                            (timed on --samples-b rows: it is slow)
+  c_fold_*                  the fold kernel alone, from HIP events around every launch: time per block, bytes per second
+                            (the block's rows read once + the running state read and written) and that rate over the
+                            6.29 TB/s measured copy ceiling of the MI355X
+Every timed shape is warmed up first (--warmup pushes); host clocks stop after calls that end in a device synchronise.
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+import tamcmc_amd  # noqa: E402
+from tamcmc_amd import synth  # noqa: E402
+
+COPY_CEILING = 6.29e12
+
+
+def host_fold(acc, P, y, like_p=1.0, block=64):
+    """The route without the summary object: model rows to the host, Welford + running-maximum log-sum-exp in numpy."""
+    nx = y.size
+    n = 0
+    mean, M2, ml, M2l = np.zeros(nx), np.zeros(nx), np.zeros(nx), np.zeros(nx)
+    mn = mx = a = r = None
+    for k in range(0, len(P), block):
+        Pb = P[k:k + block]
+        _, st, rows = acc.eval_batch(Pb, np.ones(len(Pb)), model_rows=np.arange(len(Pb)))
+        for s in range(len(Pb)):
+            if st[s] != 0:
+                continue
+            n += 1
+            v = rows[s]
+            l = -like_p * (y / v + np.log(v))
+            d = v - mean; mean += d / n; M2 += d * (v - mean)
+            d = l - ml; ml += d / n; M2l += d * (l - ml)
+            if n == 1:
+                mn, mx, a, r = v.copy(), v.copy(), l.copy(), np.ones(nx)
+            else:
+                np.minimum(mn, v, out=mn); np.maximum(mx, v, out=mx)
+                up = l > a
+                r = np.where(up, r * np.exp(np.minimum(a - l, 0.0)) + 1.0, r + np.exp(np.minimum(l - a, 0.0)))
+                a = np.where(up, l, a)
+    return dict(mean_M=mean, var_M=M2 / (n - 1), lppd=a + np.log(r / n), var_l=M2l / (n - 1), n_used=n)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--samples", type=int, default=4096)
+    ap.add_argument("--samples-b", type=int, default=256)
+    ap.add_argument("--block", type=int, default=0)
+    ap.add_argument("--steps", type=int, default=5)
+    ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--nx", type=int, default=100000)
+    a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0 or a.samples < 1 or a.samples_b < 2:
+        ap.error("--steps >= 1, --warmup >= 0, --samples >= 1, --samples-b >= 2")
+    w = synth.workload_c2(Nx=a.nx)
+    P = synth.chain_params(w, a.samples)
+    with tamcmc_amd.Accel(2, w["plength"], w["x"], np.ones(a.nx)) as acc:
+        m_true, st = acc.model_explicit(w["params_true"])
+    assert st == 0
+    y = synth.make_spectrum(m_true)
+    out = dict(tool="summary_time", Nx=a.nx, samples=a.samples, steps=a.steps, warmup=a.warmup, version=tamcmc_amd.capi.version())
+    with tamcmc_amd.Accel(2, w["plength"], w["x"], y) as acc:
+        with tamcmc_amd.Summary(acc, a.block) as s:
+            for _ in range(a.warmup):
+                s.push(P)
+            times = []
+            for _ in range(a.steps):
+                s.reset()
+                acc.synchronize()
+                t0 = time.perf_counter()
+                s.push(P)                                   # synchronous: results are on the host on return
+                times.append(time.perf_counter() - t0)
+            res = s.result()
+            out["a_summary_s_per_1000"] = float(np.median(times)) * 1000.0 / a.samples
+            out["a_spread"] = [float(min(times)) * 1000.0 / a.samples, float(max(times)) * 1000.0 / a.samples]
+            out["n_used"], out["n_rejected"] = res["n_used"], res["n_rejected"]
+            # (c) the fold kernel alone
+            s.reset()
+            s.profile(True)
+            s.push(P)
+            ms, launches = s.kernel_time()
+            s.profile(False)
+            B = -(-a.samples // launches)                   # samples per block (the last block may be shorter)
+            bytes_moved = (a.samples * a.nx + launches * 2 * 8 * a.nx) * 8.0
+            out.update(c_fold_launches=launches, c_block_chains=B, c_fold_us_per_block=ms * 1e3 / launches,
+                       c_fold_s_per_1000=ms * 1e-3 * 1000.0 / a.samples, c_fold_bytes_per_s=bytes_moved / (ms * 1e-3),
+                       c_fold_share_of_copy_ceiling=bytes_moved / (ms * 1e-3) / COPY_CEILING)
+        # (b) the host route, on fewer rows
+        Pb = P[:a.samples_b]
+        host_fold(acc, Pb[:64], y)
+        t0 = time.perf_counter()
+        ref = host_fold(acc, Pb, y)
+        out["b_host_route_s_per_1000"] = (time.perf_counter() - t0) * 1000.0 / len(Pb)
+        out["b_samples"] = len(Pb)
+        # same numbers from both routes (the recurrences are the same; numpy's log / exp differ from the device's in the last bits)
+        with tamcmc_amd.Summary(acc, a.block) as s:
+            s.push(Pb)
+            r2 = s.result()
+        out["ab_max_rel_diff"] = {k: float(np.max(np.abs(r2[k] - ref[k]) / np.maximum(np.abs(ref[k]), 1e-300)))
+                                  for k in ("mean_M", "var_M", "lppd", "var_l")}
+    print(json.dumps(out))
+
+
+if __name__ == "__main__":
+    main()
