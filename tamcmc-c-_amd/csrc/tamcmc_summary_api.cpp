@@ -1,0 +1,268 @@
+// tamcmc_summary_api.cpp -- posterior summaries of a stored chain (tamcmc_accel.h, tamcmc_summary.h): per-bin running
+// statistics of the model and of the pointwise log-likelihood over the samples pushed so far.  A block of samples = the
+// context's own launches (tamcmc_host.h: tm_enqueue) with a row map covering every chain (stage 1) +
+// tamcmc_summary_fold_kernel (stage 2), both on the context's stream.
+#include <cmath>
+#include <new>
+
+#include "tamcmc_host.h"
+#include "tamcmc_summary.h"
+
+struct tamcmc_summary {
+    tamcmc_ctx *c = nullptr;
+    int B = 0;                           // samples per block
+    bool counted = false;                // the context's count includes this object
+    double *d_model = nullptr;           // [B][Nx] model rows of the block in flight (the context's d_model is not touched)
+    double *d_state = nullptr;           // [TM_SUM_NSTATE][Nx]
+    long long *d_cnt = nullptr;          // [2][2] {accepted, rejected}: launch k reads pair k & 1 and writes the other
+    int parity = 0;
+    int32_t *d_rows = nullptr;           // [B] the identity row map
+    double *d_T = nullptr;               // [B] ones: samples are evaluated at temperature 1
+    double *d_logL = nullptr;            // [B] / [B]: where a block's logL / status go when the caller wants none
+    int32_t *d_status = nullptr;
+    // host-pointer pushes: [params | logL | status] of a block, pinned and on the device, two of each (block k fills
+    // slot k & 1 while block k - 1 may still be read by its copies)
+    TmPinned stage[2];
+    hipEvent_t ev_stage[2] = {nullptr, nullptr};
+    // timing of the fold kernel alone (tamcmc_summary_profile)
+    bool profile = false;
+    TmTimer timer;
+};
+
+static size_t summary_stage_out(const tamcmc_summary *s) { return (size_t)s->B * (size_t)s->c->L.Nparams * sizeof(double); }
+static size_t summary_stage_bytes(const tamcmc_summary *s) { return summary_stage_out(s) + (size_t)s->B * (sizeof(double) + sizeof(int32_t)); }
+
+// what every push refuses (the context's state may have changed since the object was created)
+static int summary_check(const tamcmc_summary *s, int32_t Nsamples, int32_t Nparams, const double *params)
+{
+    if (!s || !params || Nsamples < 1) return TAMCMC_E_INVALID;
+    const tamcmc_ctx *c = s->c;
+    if (Nparams != c->L.Nparams || c->in_flight || c->armed || c->nspec > 1) return TAMCMC_E_INVALID;
+    return TAMCMC_OK;
+}
+
+// One block of n <= B samples, device pointers, enqueued on the context's stream.
+static int summary_block(tamcmc_summary *s, int n, const double *d_params, double *d_logL, int32_t *d_status)
+{
+    tamcmc_ctx *c = s->c;
+    int rc = tm_ensure_capacity(c, n, false);
+    if (rc != TAMCMC_OK) return rc;
+    if (!d_logL) d_logL = s->d_logL;
+    if (!d_status) d_status = s->d_status;
+    rc = tm_enqueue(c, n, d_params, s->d_T, d_logL, nullptr, d_status, s->d_rows, s->d_model);
+    if (rc != TAMCMC_OK) return rc;
+    TmSummaryArgs a{};
+    a.rows = s->d_model; a.status = d_status; a.y = c->d_y; a.isig2 = c->d_isig2; a.state = s->d_state;
+    a.cnt_in = s->d_cnt + 2 * s->parity; a.cnt_out = s->d_cnt + 2 * (s->parity ^ 1);
+    a.Nx = c->L.Nx; a.B = n; a.likelihood_case = c->L.likelihood_case; a.like_p = c->L.like_p;
+    if (s->profile) { rc = s->timer.begin(c->stream); if (rc != TAMCMC_OK) return rc; }
+    const int hr = tm_launch_summary_fold(a, c->stream);
+    if (hr != 0) return tm_launch_failed("summary fold", hr);
+    s->parity ^= 1;
+    return s->profile ? s->timer.end(c->stream) : TAMCMC_OK;
+}
+
+static int summary_clear(tamcmc_summary *s)
+{
+    const tamcmc_ctx *c = s->c;
+    TM_HIP(hipMemsetAsync(s->d_state, 0, (size_t)TM_SUM_NSTATE * (size_t)c->L.Nx * sizeof(double), c->stream));
+    TM_HIP(hipMemsetAsync(s->d_cnt, 0, 4 * sizeof(long long), c->stream));
+    s->parity = 0;
+    return TAMCMC_OK;
+}
+
+extern "C" int tamcmc_summary_create(tamcmc_summary **out, tamcmc_ctx *c, int32_t block_chains)
+{
+    if (!out) return TAMCMC_E_INVALID;
+    *out = nullptr;
+    if (!c || block_chains < 0 || c->in_flight || c->armed) return TAMCMC_E_INVALID;
+    if (c->nspec > 1) return TAMCMC_E_INVALID;      // several spectra in one context: out of scope
+    tamcmc_summary *s = new (std::nothrow) tamcmc_summary();
+    if (!s) return TAMCMC_E_NOMEM;
+    s->c = c;
+    const size_t nx = (size_t)c->L.Nx;
+    int B = block_chains;
+    if (B == 0) {                                   // 64, lowered so that a block's rows take at most 64 MiB
+        const size_t fit = ((size_t)64 << 20) / (nx * sizeof(double));
+        B = fit >= 64 ? 64 : (fit >= 1 ? (int)fit : 1);
+    }
+    s->B = B;
+    auto fail = [&](int code) { tamcmc_summary_destroy(s); return code; };
+    if (hipSetDevice(c->device) != hipSuccess) return fail(TAMCMC_E_NODEVICE);
+    const size_t b = (size_t)B;
+    if (hipMalloc(&s->d_model, b * nx * sizeof(double)) != hipSuccess || hipMalloc(&s->d_state, TM_SUM_NSTATE * nx * sizeof(double)) != hipSuccess ||
+        hipMalloc(&s->d_cnt, 4 * sizeof(long long)) != hipSuccess || hipMalloc(&s->d_rows, b * sizeof(int32_t)) != hipSuccess ||
+        hipMalloc(&s->d_T, b * sizeof(double)) != hipSuccess || hipMalloc(&s->d_logL, b * sizeof(double)) != hipSuccess ||
+        hipMalloc(&s->d_status, b * sizeof(int32_t)) != hipSuccess)
+        return fail(TAMCMC_E_NOMEM);
+    {
+        std::vector<int32_t> rows(b);
+        std::vector<double> ones(b, 1.0);
+        for (size_t k = 0; k < b; k++) rows[k] = (int32_t)k;
+        if (hipMemcpy(s->d_rows, rows.data(), b * sizeof(int32_t), hipMemcpyHostToDevice) != hipSuccess ||
+            hipMemcpy(s->d_T, ones.data(), b * sizeof(double), hipMemcpyHostToDevice) != hipSuccess)
+            return fail(TAMCMC_E_HIP);
+    }
+    if (tm_ctx_settle(c) != hipSuccess || summary_clear(s) != TAMCMC_OK) return fail(TAMCMC_E_HIP);
+    c->enq_seq++;
+    c->summaries++;
+    s->counted = true;
+    *out = s;
+    return TAMCMC_OK;
+}
+
+extern "C" int tamcmc_summary_destroy(tamcmc_summary *s)
+{
+    if (!s) return TAMCMC_OK;
+    tamcmc_ctx *c = s->c;
+    if (c->armed) return TAMCMC_E_INVALID;          // the stream cannot be waited for behind a closed gate: _fire or _disarm first
+    (void)hipSetDevice(c->device);
+    if (c->stream) (void)tm_ctx_stream_sync(c);
+    if (s->counted) c->summaries--;
+    (void)hipFree(s->d_model); (void)hipFree(s->d_state); (void)hipFree(s->d_cnt); (void)hipFree(s->d_rows);
+    (void)hipFree(s->d_T); (void)hipFree(s->d_logL); (void)hipFree(s->d_status);
+    for (int p = 0; p < 2; p++) {
+        s->stage[p].release();
+        if (s->ev_stage[p]) (void)hipEventDestroy(s->ev_stage[p]);
+    }
+    s->timer.destroy();
+    delete s;
+    return TAMCMC_OK;
+}
+
+extern "C" int tamcmc_summary_reset(tamcmc_summary *s)
+{
+    if (!s || s->c->in_flight || s->c->armed) return TAMCMC_E_INVALID;
+    tamcmc_ctx *c = s->c;
+    TM_HIP(hipSetDevice(c->device));
+    TM_HIP(tm_ctx_settle(c));
+    c->enq_seq++;
+    return summary_clear(s);
+}
+
+extern "C" int tamcmc_summary_push_device(tamcmc_summary *s, int32_t Nsamples, int32_t Nparams, const double *d_params,
+                                          double *d_logL, int32_t *d_status)
+{
+    int rc = summary_check(s, Nsamples, Nparams, d_params);
+    if (rc != TAMCMC_OK) return rc;
+    TM_HIP(hipSetDevice(s->c->device));
+    for (int32_t k = 0; k < Nsamples; k += s->B) {
+        const int n = Nsamples - k < s->B ? Nsamples - k : s->B;
+        rc = summary_block(s, n, d_params + (size_t)k * (size_t)Nparams, d_logL ? d_logL + k : nullptr, d_status ? d_status + k : nullptr);
+        if (rc != TAMCMC_OK) return rc;
+    }
+    return TAMCMC_OK;
+}
+
+extern "C" int tamcmc_summary_push(tamcmc_summary *s, int32_t Nsamples, int32_t Nparams, const double *params,
+                                   double *logL, int32_t *status)
+{
+    int rc = summary_check(s, Nsamples, Nparams, params);
+    if (rc != TAMCMC_OK) return rc;
+    tamcmc_ctx *c = s->c;
+    TM_HIP(hipSetDevice(c->device));
+    const size_t o_out = summary_stage_out(s), bytes = summary_stage_bytes(s), np = (size_t)Nparams;
+    for (int p = 0; p < 2; p++) {
+        if (s->stage[p].fits(bytes)) continue;
+        rc = s->stage[p].reserve(bytes, TM_PIN_TWIN);
+        if (rc != TAMCMC_OK) return rc;
+        TM_HIP(hipEventCreateWithFlags(&s->ev_stage[p], hipEventDisableTiming));
+    }
+    // slot p's copies have landed: hand its block's logL / status out (polled: tm_poll_event)
+    int pend_k[2] = {-1, -1}, pend_n[2] = {0, 0};
+    auto collect = [&](int p) -> int {
+        if (pend_k[p] < 0) return TAMCMC_OK;
+        const int prc = tm_poll_event(s->ev_stage[p]);
+        if (prc != TAMCMC_OK) return prc;
+        const size_t n = (size_t)pend_n[p];
+        if (logL) std::memcpy(logL + pend_k[p], s->stage[p].h + o_out, n * sizeof(double));
+        if (status) std::memcpy(status + pend_k[p], s->stage[p].h + o_out + (size_t)s->B * sizeof(double), n * sizeof(int32_t));
+        pend_k[p] = -1;
+        return TAMCMC_OK;
+    };
+    // a failure waits for the stream before it returns: a copy from or into the pinned slots may still be pending
+    auto fail = [&](int code) { (void)hipStreamSynchronize(c->stream); return code; };
+    int slot = 0;
+    for (int32_t k = 0; k < Nsamples; k += s->B, slot ^= 1) {
+        const int n = Nsamples - k < s->B ? Nsamples - k : s->B;
+        rc = collect(slot);
+        if (rc != TAMCMC_OK) return fail(rc);
+        char *const h = s->stage[slot].h, *const d = s->stage[slot].d;
+        std::memcpy(h, params + (size_t)k * np, (size_t)n * np * sizeof(double));
+        if (tm_ctx_settle(c) != hipSuccess ||
+            hipMemcpyAsync(d, h, (size_t)n * np * sizeof(double), hipMemcpyHostToDevice, c->stream) != hipSuccess)
+            return fail(TAMCMC_E_HIP);
+        rc = summary_block(s, n, reinterpret_cast<const double *>(d), reinterpret_cast<double *>(d + o_out),
+                           reinterpret_cast<int32_t *>(d + o_out + (size_t)s->B * sizeof(double)));
+        if (rc != TAMCMC_OK) return fail(rc);
+        if (hipMemcpyAsync(h + o_out, d + o_out, bytes - o_out, hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
+            hipEventRecord(s->ev_stage[slot], c->stream) != hipSuccess)
+            return fail(TAMCMC_E_HIP);
+        pend_k[slot] = k; pend_n[slot] = n;
+    }
+    // the older of the two pending blocks first: the stream runs them in order
+    rc = collect(slot);
+    if (rc == TAMCMC_OK) rc = collect(slot ^ 1);
+    if (rc != TAMCMC_OK) return fail(rc);
+    TM_HIP(hipGetLastError());
+    return TAMCMC_OK;
+}
+
+extern "C" int tamcmc_summary_result(tamcmc_summary *s, tamcmc_summary_totals *totals,
+                                     double *mean_M, double *var_M, double *min_M, double *max_M,
+                                     double *mean_l, double *var_l, double *lppd)
+{
+    if (!s || s->c->in_flight || s->c->armed) return TAMCMC_E_INVALID;
+    tamcmc_ctx *c = s->c;
+    TM_HIP(hipSetDevice(c->device));
+    TM_HIP(tm_ctx_stream_sync(c));
+    const size_t nx = (size_t)c->L.Nx;
+    long long cnt[2] = {0, 0};
+    std::vector<double> st;
+    try { st.resize(TM_SUM_NSTATE * nx); } catch (const std::bad_alloc &) { return TAMCMC_E_NOMEM; }
+    TM_HIP(hipMemcpy(cnt, s->d_cnt + 2 * s->parity, sizeof(cnt), hipMemcpyDeviceToHost));
+    TM_HIP(hipMemcpy(st.data(), s->d_state, st.size() * sizeof(double), hipMemcpyDeviceToHost));
+    const long long n = cnt[0];
+    const double nan = std::nan(""), dn = (double)n;
+    long double lppd_total = 0.0L, p_waic = 0.0L;
+    for (size_t i = 0; i < nx; i++) {
+        const double vM = n >= 2 ? st[TM_SUM_M2_M * nx + i] / (dn - 1.0) : nan;
+        const double vl = n >= 2 ? st[TM_SUM_M2_L * nx + i] / (dn - 1.0) : nan;
+        const double lp = n >= 1 ? st[TM_SUM_LSE_A * nx + i] + std::log(st[TM_SUM_LSE_R * nx + i] / dn) : nan;
+        if (mean_M) mean_M[i] = n >= 1 ? st[TM_SUM_MEAN_M * nx + i] : nan;
+        if (var_M) var_M[i] = vM;
+        if (min_M) min_M[i] = n >= 1 ? st[TM_SUM_MIN_M * nx + i] : nan;
+        if (max_M) max_M[i] = n >= 1 ? st[TM_SUM_MAX_M * nx + i] : nan;
+        if (mean_l) mean_l[i] = n >= 1 ? st[TM_SUM_MEAN_L * nx + i] : nan;
+        if (var_l) var_l[i] = vl;
+        if (lppd) lppd[i] = lp;
+        lppd_total += (long double)lp;          // in bin order
+        p_waic += (long double)vl;
+    }
+    if (totals) {
+        totals->n_used = n;
+        totals->n_rejected = cnt[1];
+        totals->lppd_total = (double)lppd_total;
+        totals->p_waic = (double)p_waic;
+        totals->waic = (double)(-2.0L * (lppd_total - p_waic));
+    }
+    return TAMCMC_OK;
+}
+
+extern "C" int tamcmc_summary_profile(tamcmc_summary *s, int enable)
+{
+    if (!s || s->c->armed) return TAMCMC_E_INVALID;
+    TM_HIP(hipSetDevice(s->c->device));
+    TM_HIP(tm_ctx_stream_sync(s->c));
+    s->profile = enable != 0;
+    s->timer.used = 0;
+    return TAMCMC_OK;
+}
+
+extern "C" int tamcmc_summary_kernel_time(tamcmc_summary *s, double *total_ms, int64_t *launches)
+{
+    if (!s || !total_ms || !launches || s->c->armed) return TAMCMC_E_INVALID;
+    TM_HIP(hipSetDevice(s->c->device));
+    TM_HIP(tm_ctx_stream_sync(s->c));
+    return s->timer.total(total_ms, launches);
+}

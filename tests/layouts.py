@@ -6,7 +6,7 @@ Device rules restated here (precondition bookkeeping, not a model of the device)
   * a multiplet of degree l is a (2l+1)-component shape; it takes the asymmetric variant when the chain's asymmetry is
     not 0 or, in the gradient launch, when the asymmetry is one of the variables (tamcmc_setup_body.h: asym_bit);
   * a grid of at most 4 units of 512 bins is one tile, and one tile is evaluated by the fused launch (tamcmc_dev.h:
-    tm_tiles, tamcmc_api.cpp: `fused`); longer grids are tiled."""
+    tm_tiles, tamcmc_host.h: `tm_takes_fused`); longer grids are tiled."""
 import workloads as W
 
 GLOBAL_IDS = (2, 3, 6, 7, 8, 9, 10, 12, 13)

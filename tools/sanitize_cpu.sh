@@ -14,7 +14,7 @@ for f in tamcmc_sampler tamcmc_lockstep tamcmc_io tamcmc_outputs; do
 done
 g++ $SAN -shared -fPIC -o "$OUT/libtamcmc_accel.so" "$OUT"/tamcmc_sampler.o "$OUT"/tamcmc_lockstep.o "$OUT"/tamcmc_io.o "$OUT"/tamcmc_outputs.o \
     "$SRC"/tamcmc_api.o "$SRC"/tamcmc_setup.o "$SRC"/tamcmc_eval.o "$SRC"/tamcmc_fused.o "$SRC"/tamcmc_backward.o \
-    "$SRC"/tamcmc_group_setup.o "$SRC"/tamcmc_group_eval.o "$SRC"/tamcmc_group_fused.o "$SRC"/tamcmc_summary.o \
+    "$SRC"/tamcmc_group_setup.o "$SRC"/tamcmc_group_eval.o "$SRC"/tamcmc_group_fused.o "$SRC"/tamcmc_summary.o "$SRC"/tamcmc_group.o "$SRC"/tamcmc_summary_api.o \
     -L/opt/rocm/lib -lamdhip64 -Wl,-rpath,/opt/rocm/lib -pthread
 cd "$ROOT"
 # python itself is not instrumented: preload the runtime, and leave leak checking off (the interpreter never frees all)
