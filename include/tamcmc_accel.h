@@ -199,9 +199,42 @@ int tamcmc_group_members(const tamcmc_group *g, int32_t *n_members, int32_t *Npa
  * block_chains and of how the samples are split over pushes.
  * Refused with TAMCMC_E_INVALID: NULL arguments, Nsamples < 1, an Nparams mismatch, block_chains < 0, a context with a
  * batch in flight or armed, and a context holding more than one spectrum (tamcmc_ctx_set_spectra; out of scope, as are
- * fit groups and quantile bands).
+ * fit groups).
  *   profile / kernel_time   as tamcmc_ctx_profile / tamcmc_ctx_kernel_time, for the fold kernel alone (one event pair per
- *                block while enabled). */
+ *                block while enabled); in quantile mode, for the histogram kernel that takes its place.
+ *
+ * QUANTILES (credible bands): the exact per-bin order statistics of M_is over the accepted samples -- the median model
+ * with its 16 / 84 % band, say -- by a radix selection that takes a few passes over the chain: the caller pushes the SAME
+ * samples again once per pass, and every pass resolves bits_per_pass more bits of every requested quantile of every bin
+ * (tamcmc_quantile.h).  Nothing is approximated: a resolved value is one of the pushed model values, bit for bit, and is
+ * independent of block_chains and of how the samples are split over pushes (which may differ from pass to pass).
+ *   Rank rule, the same for every bin: k = (int64_t)ceil(q n) - 1 clamped to [0, n - 1], n = n_used -- the smallest sample
+ *   whose empirical CDF reaches q (numpy's method "inverted_cdf").  q = 0 is min_M, q = 1 is max_M, q = 0.5 with odd n is
+ *   the middle sample.  Values are ordered as doubles with -0 = +0.  An accepted sample cannot hold a NaN model value: its
+ *   logL would be NaN and its status TAMCMC_CHAIN_NAN.
+ *   quantiles_begin   freezes the fold state (n_used, the envelope min_M / max_M), computes the ranks and allocates the
+ *                selection's memory on the device: Nq x 2^bits x Nx x 4 bytes of histogram plus (16 Nq + 20) Nx bytes of
+ *                state; TAMCMC_E_NOMEM when that fails, and the object stays as it was.  bits_per_pass: 1 ... 6, or 0 for
+ *                the library's default (6).  Refused with TAMCMC_E_INVALID: n_used < 1 or >= 2^32, Nq outside
+ *                1 ... TAMCMC_SUMMARY_MAX_QUANTILES, a q that is NaN or outside [0, 1], bits_per_pass outside 0 ... 6,
+ *                quantile mode already on, a context with a batch in flight or armed.
+ *   While the mode is on, push and push_device evaluate the rows as before and hand out the same logL and status bits, but
+ *   feed the histogram kernel instead of the fold kernel; tamcmc_summary_result keeps returning the frozen fold results.
+ *   quantiles_step    after the caller has pushed the same samples again.  If the pass saw n_used accepted samples, the
+ *                fold pass's rejected count and no model value outside the envelope, every bracket is narrowed and
+ *                *bits_left (may be NULL) gets the largest number of unresolved bits over all bins and quantiles; 0 =
+ *                every result is exact.  Otherwise TAMCMC_E_INVALID: the pass is discarded, the state of the previous
+ *                step stays and the pass can be repeated.  (A pass of other samples that happen to pass these three
+ *                checks cannot be told apart and gives brackets without meaning.)  A bin's key range has u0 <= 64
+ *                unresolved bits at first -- 48 or 49 for a typical posterior -- and exactness takes ceil(u0 / bits)
+ *                steps.  A step with nothing left to resolve is a no-op that returns 0 bits left.
+ *   quantiles_result  may be called after any step, and before the first (the bracket is the envelope then).  ranks[Nq],
+ *                lo[Nq x Nx], hi[Nq x Nx] on the host, any of them may be NULL: the doubles of the lowest and highest key
+ *                of the bracket that holds the order statistic, hi clipped to max_M.  Where a bin is resolved,
+ *                lo == hi == the order statistic, bit for bit.
+ *   quantiles_end     frees the selection's memory and goes back to fold mode: the running statistics are untouched and
+ *                further pushes fold as before.  tamcmc_summary_reset also leaves the mode; tamcmc_summary_destroy works
+ *                in either.  _step, _result and _end outside the mode return TAMCMC_E_INVALID. */
 typedef struct tamcmc_summary tamcmc_summary;
 typedef struct {
     int64_t n_used, n_rejected;
@@ -219,6 +252,11 @@ int tamcmc_summary_reset(tamcmc_summary *s);
 int tamcmc_summary_destroy(tamcmc_summary *s);
 int tamcmc_summary_profile(tamcmc_summary *s, int enable);
 int tamcmc_summary_kernel_time(tamcmc_summary *s, double *total_ms, int64_t *launches);
+#define TAMCMC_SUMMARY_MAX_QUANTILES 8
+int tamcmc_summary_quantiles_begin(tamcmc_summary *s, int32_t Nq, const double *q, int32_t bits_per_pass);
+int tamcmc_summary_quantiles_step(tamcmc_summary *s, int32_t *bits_left);
+int tamcmc_summary_quantiles_result(tamcmc_summary *s, int64_t *ranks, double *lo, double *hi);
+int tamcmc_summary_quantiles_end(tamcmc_summary *s);
 
 /* Replaces: the `for chain` loop of generate_model() calls (MALA.cpp:632-639, model_def.cpp:139-143).
  * Host pointers, row-major.  Synchronous: results are valid on return.

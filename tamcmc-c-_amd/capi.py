@@ -30,6 +30,8 @@ EXPORTS = [
     "tamcmc_group_eval_begin", "tamcmc_group_eval_end", "tamcmc_group_eval_poll", "tamcmc_group_members",
     "tamcmc_summary_create", "tamcmc_summary_push", "tamcmc_summary_push_device", "tamcmc_summary_result",
     "tamcmc_summary_reset", "tamcmc_summary_destroy", "tamcmc_summary_profile", "tamcmc_summary_kernel_time",
+    "tamcmc_summary_quantiles_begin", "tamcmc_summary_quantiles_step", "tamcmc_summary_quantiles_result",
+    "tamcmc_summary_quantiles_end",
 ]
 
 
@@ -99,6 +101,10 @@ def load_library():
     lib.tamcmc_summary_destroy.argtypes = [vp]
     lib.tamcmc_summary_profile.argtypes = [vp, C.c_int]
     lib.tamcmc_summary_kernel_time.argtypes = [vp, dp, C.POINTER(C.c_int64)]
+    lib.tamcmc_summary_quantiles_begin.argtypes = [vp, C.c_int32, dp, C.c_int32]
+    lib.tamcmc_summary_quantiles_step.argtypes = [vp, C.POINTER(C.c_int32)]
+    lib.tamcmc_summary_quantiles_result.argtypes = [vp, C.POINTER(C.c_int64), dp, dp]
+    lib.tamcmc_summary_quantiles_end.argtypes = [vp]
     for name in EXPORTS:
         fn = getattr(lib, name)
         if fn.restype is not C.c_char_p:
@@ -405,8 +411,9 @@ class Group:
 class Summary:
     """Posterior summaries of a stored chain (tamcmc_accel.h, tamcmc_summary_*): per-bin running statistics of the model
     and of the pointwise log-likelihood over the parameter rows pushed so far, kept on the device.  Results do not depend,
-    bit for bit, on block_chains or on how the rows are split over pushes.  The Accel cannot be closed while the summary
-    is open."""
+    bit for bit, on block_chains or on how the rows are split over pushes.  quantiles() gives the exact per-bin quantiles
+    of the model (credible bands) by pushing the same rows again a few times.  The Accel cannot be closed while the
+    summary is open."""
 
     ARRAYS = ("mean_M", "var_M", "min_M", "max_M", "mean_l", "var_l", "lppd")
 
@@ -448,6 +455,7 @@ class Summary:
 
     def reset(self):
         self._check(self._lib.tamcmc_summary_reset(self._s), "tamcmc_summary_reset")
+        self._nq = 0                                            # reset leaves quantile mode
 
     def profile(self, enable=True):
         self._check(self._lib.tamcmc_summary_profile(self._s, int(enable)), "tamcmc_summary_profile")
@@ -458,6 +466,62 @@ class Summary:
         n = C.c_int64(0)
         self._check(self._lib.tamcmc_summary_kernel_time(self._s, C.byref(ms), C.byref(n)), "tamcmc_summary_kernel_time")
         return ms.value, n.value
+
+    # ---- quantiles: exact per-bin order statistics of the model over the accepted samples, a few bits per pass ----
+    MAX_QUANTILES = 8
+
+    def quantiles_begin(self, q, bits_per_pass=0):
+        """Enters quantile mode for the quantiles q (1 ... 8 values in [0, 1]); bits_per_pass 1 ... 6, 0 = the library's
+        default.  From here on push / push_device feed the selection: push the same rows again, then quantiles_step()."""
+        q = _c64(np.atleast_1d(q))
+        if q.ndim != 1:
+            raise ValueError("q must be a sequence of quantiles")
+        self._check(self._lib.tamcmc_summary_quantiles_begin(self._s, q.size, _dptr(q), int(bits_per_pass)),
+                    "tamcmc_summary_quantiles_begin")
+        self._nq = int(q.size)
+
+    def quantiles_step(self):
+        """Narrows every bracket by the pass just pushed; returns the largest number of unresolved bits (0: exact)."""
+        left = C.c_int32(-1)
+        self._check(self._lib.tamcmc_summary_quantiles_step(self._s, C.byref(left)), "tamcmc_summary_quantiles_step")
+        return int(left.value)
+
+    def quantiles_result(self):
+        """dict: ranks (Nq), lo and hi (Nq, Nx) -- the bracket of every quantile of every bin; lo == hi where resolved."""
+        nq = getattr(self, "_nq", 0) or self.MAX_QUANTILES
+        ranks = np.zeros(nq, dtype=np.int64)
+        lo, hi = np.empty((nq, self.accel.Nx)), np.empty((nq, self.accel.Nx))
+        self._check(self._lib.tamcmc_summary_quantiles_result(self._s, ranks.ctypes.data_as(C.POINTER(C.c_int64)), _dptr(lo), _dptr(hi)),
+                    "tamcmc_summary_quantiles_result")
+        return dict(ranks=ranks, lo=lo, hi=hi)
+
+    def quantiles_end(self):
+        self._check(self._lib.tamcmc_summary_quantiles_end(self._s), "tamcmc_summary_quantiles_end")
+        self._nq = 0
+
+    def quantiles(self, params, q, bits_per_pass=0, max_passes=None):
+        """The quantiles q of the model over the rows already pushed, `params` being those rows: pushes them once per pass
+        until every value is exact or max_passes passes are done, and always leaves quantile mode.  Returns a dict: q,
+        ranks, lo, hi (Nq x Nx; equal where resolved), passes, bits_left."""
+        q = _c64(np.atleast_1d(q))
+        self.quantiles_begin(q, bits_per_pass)
+        try:
+            r = self.quantiles_result()
+            passes = 0
+            bits_left = 0 if np.array_equal(r["lo"].view(np.uint64), r["hi"].view(np.uint64)) else -1
+            while bits_left != 0 and (max_passes is None or passes < max_passes):
+                self.push(params)
+                bits_left = self.quantiles_step()
+                passes += 1
+            if passes:
+                r = self.quantiles_result()
+            if bits_left < 0:                                   # max_passes = 0: not known without a step
+                bits_left = None
+            r.update(q=q.copy(), passes=passes, bits_left=bits_left)
+            return r
+        finally:
+            if getattr(self, "_nq", 0):
+                self.quantiles_end()
 
     def close(self):
         if getattr(self, "_s", None) is not None and self._s.value:

@@ -1,12 +1,30 @@
 // tamcmc_summary_api.cpp -- posterior summaries of a stored chain (tamcmc_accel.h, tamcmc_summary.h): per-bin running
 // statistics of the model and of the pointwise log-likelihood over the samples pushed so far.  A block of samples = the
 // context's own launches (tamcmc_host.h: tm_enqueue) with a row map covering every chain (stage 1) +
-// tamcmc_summary_fold_kernel (stage 2), both on the context's stream.
+// tamcmc_summary_fold_kernel (stage 2), both on the context's stream.  While the object selects quantiles
+// (tamcmc_summary_quantiles_*, tamcmc_quantile.h) stage 2 is the histogram kernel instead and the fold state is frozen.
 #include <cmath>
 #include <new>
 
 #include "tamcmc_host.h"
+#include "tamcmc_quantile.h"
 #include "tamcmc_summary.h"
+
+// Quantile mode: the selection's state on the device and what the host remembers of it.
+struct TmQuantMode {
+    bool on = false;
+    int Nq = 0, bits = 0, passes = 0;
+    int u0max = 0;                       // the largest number of unresolved bits over the bins, before the first step
+    long long n_used = 0, n_rejected = 0;   // of the fold pass, frozen by _begin
+    int64_t ranks[TM_Q_MAXQ] = {};
+    char *d_state = nullptr;             // one allocation: kmin | R | prefix | below | ranks | cnt[2][2] | u | flag
+    uint32_t *d_hist = nullptr;          // [Nq][2^bits][Nx]
+    size_t hist_bytes = 0;
+    uint64_t *kmin = nullptr, *R = nullptr, *prefix = nullptr, *below = nullptr, *d_ranks = nullptr;
+    long long *cnt = nullptr;            // as tamcmc_summary::d_cnt, for the samples of the pass under way
+    uint32_t *u = nullptr, *flag = nullptr;
+    int parity = 0;
+};
 
 struct tamcmc_summary {
     tamcmc_ctx *c = nullptr;
@@ -27,6 +45,7 @@ struct tamcmc_summary {
     // timing of the fold kernel alone (tamcmc_summary_profile)
     bool profile = false;
     TmTimer timer;
+    TmQuantMode q;
 };
 
 static size_t summary_stage_out(const tamcmc_summary *s) { return (size_t)s->B * (size_t)s->c->L.Nparams * sizeof(double); }
@@ -41,6 +60,49 @@ static int summary_check(const tamcmc_summary *s, int32_t Nsamples, int32_t Npar
     return TAMCMC_OK;
 }
 
+static TmQuantArgs quantile_args(const tamcmc_summary *s)
+{
+    const TmQuantMode &q = s->q;
+    TmQuantArgs a{};
+    a.rows = s->d_model; a.fold_state = s->d_state;
+    a.kmin = q.kmin; a.R = q.R; a.u = q.u; a.prefix = q.prefix; a.below = q.below; a.ranks = q.d_ranks; a.hist = q.d_hist;
+    a.cnt_in = q.cnt + 2 * q.parity; a.cnt_out = q.cnt + 2 * (q.parity ^ 1); a.flag = q.flag;
+    a.Nx = s->c->L.Nx; a.Nq = q.Nq; a.bits = q.bits;
+    return a;
+}
+
+// stage 2 of a block in quantile mode: the histogram kernel in the fold kernel's place
+static int quantile_block(tamcmc_summary *s, int n, const int32_t *d_status)
+{
+    tamcmc_ctx *c = s->c;
+    TmQuantArgs a = quantile_args(s);
+    a.status = d_status; a.B = n;
+    int rc = TAMCMC_OK;
+    if (s->profile) { rc = s->timer.begin(c->stream); if (rc != TAMCMC_OK) return rc; }
+    const int hr = tm_launch_quantile_hist(a, c->stream);
+    if (hr != 0) return tm_launch_failed("summary quantile histogram", hr);
+    s->q.parity ^= 1;
+    return s->profile ? s->timer.end(c->stream) : TAMCMC_OK;
+}
+
+// a pass starts from empty counts and a clear flag (the cells are cleared by whoever read them last)
+static int quantile_pass_clear(tamcmc_summary *s, bool cells)
+{
+    TmQuantMode &q = s->q;
+    TM_HIP(hipMemsetAsync(q.cnt, 0, 4 * sizeof(long long), s->c->stream));
+    TM_HIP(hipMemsetAsync(q.flag, 0, sizeof(uint32_t), s->c->stream));
+    if (cells) TM_HIP(hipMemsetAsync(q.d_hist, 0, q.hist_bytes, s->c->stream));
+    q.parity = 0;
+    return TAMCMC_OK;
+}
+
+// the stream must be idle
+static void quantile_free(tamcmc_summary *s)
+{
+    (void)hipFree(s->q.d_state); (void)hipFree(s->q.d_hist);
+    s->q = TmQuantMode();
+}
+
 // One block of n <= B samples, device pointers, enqueued on the context's stream.
 static int summary_block(tamcmc_summary *s, int n, const double *d_params, double *d_logL, int32_t *d_status)
 {
@@ -51,6 +113,7 @@ static int summary_block(tamcmc_summary *s, int n, const double *d_params, doubl
     if (!d_status) d_status = s->d_status;
     rc = tm_enqueue(c, n, d_params, s->d_T, d_logL, nullptr, d_status, s->d_rows, s->d_model);
     if (rc != TAMCMC_OK) return rc;
+    if (s->q.on) return quantile_block(s, n, d_status);
     TmSummaryArgs a{};
     a.rows = s->d_model; a.status = d_status; a.y = c->d_y; a.isig2 = c->d_isig2; a.state = s->d_state;
     a.cnt_in = s->d_cnt + 2 * s->parity; a.cnt_out = s->d_cnt + 2 * (s->parity ^ 1);
@@ -119,6 +182,7 @@ extern "C" int tamcmc_summary_destroy(tamcmc_summary *s)
     (void)hipSetDevice(c->device);
     if (c->stream) (void)tm_ctx_stream_sync(c);
     if (s->counted) c->summaries--;
+    quantile_free(s);
     (void)hipFree(s->d_model); (void)hipFree(s->d_state); (void)hipFree(s->d_cnt); (void)hipFree(s->d_rows);
     (void)hipFree(s->d_T); (void)hipFree(s->d_logL); (void)hipFree(s->d_status);
     for (int p = 0; p < 2; p++) {
@@ -135,6 +199,10 @@ extern "C" int tamcmc_summary_reset(tamcmc_summary *s)
     if (!s || s->c->in_flight || s->c->armed) return TAMCMC_E_INVALID;
     tamcmc_ctx *c = s->c;
     TM_HIP(hipSetDevice(c->device));
+    if (s->q.on) {                                  // reset leaves quantile mode
+        TM_HIP(tm_ctx_stream_sync(c));
+        quantile_free(s);
+    }
     TM_HIP(tm_ctx_settle(c));
     c->enq_seq++;
     return summary_clear(s);
@@ -265,4 +333,131 @@ extern "C" int tamcmc_summary_kernel_time(tamcmc_summary *s, double *total_ms, i
     TM_HIP(hipSetDevice(s->c->device));
     TM_HIP(tm_ctx_stream_sync(s->c));
     return s->timer.total(total_ms, launches);
+}
+
+// ---- quantiles (tamcmc_quantile.h) ----
+
+extern "C" int tamcmc_summary_quantiles_begin(tamcmc_summary *s, int32_t Nq, const double *q, int32_t bits_per_pass)
+{
+    if (!s || !q || Nq < 1 || Nq > TAMCMC_SUMMARY_MAX_QUANTILES || bits_per_pass < 0 || bits_per_pass > TM_Q_MAXBITS) return TAMCMC_E_INVALID;
+    tamcmc_ctx *c = s->c;
+    if (s->q.on || c->in_flight || c->armed) return TAMCMC_E_INVALID;
+    for (int j = 0; j < Nq; j++)
+        if (!(q[j] >= 0.0 && q[j] <= 1.0)) return TAMCMC_E_INVALID;        // (a NaN fails both comparisons)
+    TM_HIP(hipSetDevice(c->device));
+    TM_HIP(tm_ctx_stream_sync(c));
+    long long cnt[2] = {0, 0};
+    TM_HIP(hipMemcpy(cnt, s->d_cnt + 2 * s->parity, sizeof(cnt), hipMemcpyDeviceToHost));
+    if (cnt[0] < 1 || cnt[0] >= ((long long)1 << 32)) return TAMCMC_E_INVALID;
+    TmQuantMode m;
+    m.Nq = Nq;
+    m.bits = bits_per_pass ? bits_per_pass : TM_Q_DEFAULT_BITS;
+    m.n_used = cnt[0]; m.n_rejected = cnt[1];
+    uint64_t ranks[TM_Q_MAXQ] = {};
+    for (int j = 0; j < Nq; j++) {
+        m.ranks[j] = tmq_rank(q[j], (int64_t)cnt[0]);
+        ranks[j] = (uint64_t)m.ranks[j];
+    }
+    const size_t nx = (size_t)c->L.Nx, nq = (size_t)Nq;
+    const size_t state_bytes = (2 * nx + 2 * nq * nx + TM_Q_MAXQ) * sizeof(uint64_t) + 4 * sizeof(long long) + (nx + 1) * sizeof(uint32_t);
+    m.hist_bytes = (nq << m.bits) * nx * sizeof(uint32_t);
+    if (hipMalloc(&m.d_state, state_bytes) != hipSuccess) { (void)hipGetLastError(); return TAMCMC_E_NOMEM; }
+    if (hipMalloc(&m.d_hist, m.hist_bytes) != hipSuccess) { (void)hipGetLastError(); (void)hipFree(m.d_state); return TAMCMC_E_NOMEM; }
+    m.kmin = reinterpret_cast<uint64_t *>(m.d_state);
+    m.R = m.kmin + nx;
+    m.prefix = m.R + nx;
+    m.below = m.prefix + nq * nx;
+    m.d_ranks = m.below + nq * nx;
+    m.cnt = reinterpret_cast<long long *>(m.d_ranks + TM_Q_MAXQ);
+    m.u = reinterpret_cast<uint32_t *>(m.cnt + 4);
+    m.flag = m.u + nx;
+    m.on = true;
+    s->q = m;
+    auto fail = [&](int code) { (void)hipStreamSynchronize(c->stream); quantile_free(s); return code; };
+    c->enq_seq++;
+    if (hipMemcpyAsync(m.d_ranks, ranks, sizeof(ranks), hipMemcpyHostToDevice, c->stream) != hipSuccess) return fail(TAMCMC_E_HIP);
+    if (quantile_pass_clear(s, true) != TAMCMC_OK) return fail(TAMCMC_E_HIP);
+    const int hr = tm_launch_quantile_init(quantile_args(s), c->stream);
+    if (hr != 0) { (void)tm_launch_failed("summary quantile init", hr); return fail(TAMCMC_E_HIP); }
+    std::vector<uint32_t> u;
+    try { u.resize(nx); } catch (const std::bad_alloc &) { return fail(TAMCMC_E_NOMEM); }
+    if (hipMemcpyAsync(u.data(), m.u, nx * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
+        hipStreamSynchronize(c->stream) != hipSuccess)                    // (also: `ranks` is read before it goes out of scope)
+        return fail(TAMCMC_E_HIP);
+    for (size_t i = 0; i < nx; i++) s->q.u0max = (int)u[i] > s->q.u0max ? (int)u[i] : s->q.u0max;
+    return TAMCMC_OK;
+}
+
+static int quantile_bits_left(const TmQuantMode &q)
+{
+    const int left = q.u0max - q.passes * q.bits;
+    return left > 0 ? left : 0;
+}
+
+extern "C" int tamcmc_summary_quantiles_step(tamcmc_summary *s, int32_t *bits_left)
+{
+    if (!s || !s->q.on || s->c->in_flight || s->c->armed) return TAMCMC_E_INVALID;
+    tamcmc_ctx *c = s->c;
+    TmQuantMode &q = s->q;
+    TM_HIP(hipSetDevice(c->device));
+    TM_HIP(tm_ctx_stream_sync(c));
+    c->enq_seq++;
+    if (quantile_bits_left(q) == 0) {                  // nothing to resolve: whatever was pushed is dropped
+        const int rc = quantile_pass_clear(s, false);
+        if (bits_left) *bits_left = 0;
+        return rc;
+    }
+    long long cnt[2] = {0, 0};
+    uint32_t flag = 0;
+    TM_HIP(hipMemcpy(cnt, q.cnt + 2 * q.parity, sizeof(cnt), hipMemcpyDeviceToHost));
+    TM_HIP(hipMemcpy(&flag, q.flag, sizeof(flag), hipMemcpyDeviceToHost));
+    if (cnt[0] != q.n_used || cnt[1] != q.n_rejected || flag != 0) {      // not the fold pass's samples: the pass is discarded
+        const int rc = quantile_pass_clear(s, true);
+        return rc != TAMCMC_OK ? rc : TAMCMC_E_INVALID;
+    }
+    const int hr = tm_launch_quantile_narrow(quantile_args(s), c->stream);
+    if (hr != 0) return tm_launch_failed("summary quantile narrow", hr);
+    q.passes++;
+    const int rc = quantile_pass_clear(s, false);      // the narrow kernel cleared the cells it read; the others were never written
+    if (bits_left) *bits_left = quantile_bits_left(q);
+    return rc;
+}
+
+extern "C" int tamcmc_summary_quantiles_result(tamcmc_summary *s, int64_t *ranks, double *lo, double *hi)
+{
+    if (!s || !s->q.on || s->c->in_flight || s->c->armed) return TAMCMC_E_INVALID;
+    tamcmc_ctx *c = s->c;
+    const TmQuantMode &q = s->q;
+    TM_HIP(hipSetDevice(c->device));
+    TM_HIP(tm_ctx_stream_sync(c));
+    if (ranks) for (int j = 0; j < q.Nq; j++) ranks[j] = q.ranks[j];
+    if (!lo && !hi) return TAMCMC_OK;
+    const size_t nx = (size_t)c->L.Nx, nq = (size_t)q.Nq;
+    std::vector<uint64_t> kr, pre;
+    std::vector<uint32_t> u;
+    std::vector<double> env;
+    try { kr.resize(2 * nx); pre.resize(nq * nx); u.resize(nx); env.resize(2 * nx); } catch (const std::bad_alloc &) { return TAMCMC_E_NOMEM; }
+    TM_HIP(hipMemcpy(kr.data(), q.kmin, 2 * nx * sizeof(uint64_t), hipMemcpyDeviceToHost));          // kmin | R
+    TM_HIP(hipMemcpy(pre.data(), q.prefix, nq * nx * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    TM_HIP(hipMemcpy(u.data(), q.u, nx * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    TM_HIP(hipMemcpy(env.data(), s->d_state + (size_t)TM_SUM_MIN_M * nx, 2 * nx * sizeof(double), hipMemcpyDeviceToHost));   // min_M | max_M
+    // the double of an offset: the envelope's own bits at its two ends
+    auto value = [&](size_t i, uint64_t D) { return D == 0 ? env[i] : (D == kr[nx + i] ? env[nx + i] : tmq_unkey(kr[i] + D)); };
+    for (size_t j = 0; j < nq; j++)
+        for (size_t i = 0; i < nx; i++) {
+            uint64_t dlo, dhi;
+            tmq_bracket(pre[j * nx + i], (int)u[i], kr[nx + i], &dlo, &dhi);
+            if (lo) lo[j * nx + i] = value(i, dlo);
+            if (hi) hi[j * nx + i] = value(i, dhi);
+        }
+    return TAMCMC_OK;
+}
+
+extern "C" int tamcmc_summary_quantiles_end(tamcmc_summary *s)
+{
+    if (!s || !s->q.on || s->c->in_flight || s->c->armed) return TAMCMC_E_INVALID;
+    TM_HIP(hipSetDevice(s->c->device));
+    TM_HIP(tm_ctx_stream_sync(s->c));
+    quantile_free(s);
+    return TAMCMC_OK;
 }

@@ -3,6 +3,7 @@
 //
 //   chainsummary_hip <config dir> <model file> <data file> <params root> <output file>
 //                    [--chain m] [--slice s] [--first i] [--last j] [--thin k] [--block B]
+//                    [--quantiles q1,q2,...] [--qbits b]
 //
 // <config dir> is the reference's Config/default; model id, likelihood, p, plength, the inputs row and the relax mask
 // come from the setup it describes (tamcmc_setup_create / tamcmc_setup_load, slice s counted from 0).  The samples are
@@ -12,6 +13,10 @@
 // up to last (both counted from 0, inclusive) are pushed in blocks of B (0: the library's default).
 // Output: `#` header lines with the totals and the sample range, then the columns
 //   x  y  mean_M  sd_M  min_M  max_M  lppd  var_l            (12 significant digits, like getmodel_hip)
+// With --quantiles (up to 8 values in [0, 1]) the selected samples are read again once per pass of the exact quantile
+// selection (tamcmc_summary_quantiles_*; b bits per pass, 0: the library's default), the header gains a line
+// `# quantiles= q1,q2,...  passes= N`, and one column per quantile follows var_l: the order statistic of the model in that
+// bin, numpy's "inverted_cdf".
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -27,13 +32,16 @@ static int usage()
 {
     fprintf(stderr, " Usage: chainsummary_hip <config dir> <model file> <data file> <params root> <output file>\n"
                     "                         [--chain m] [--slice s] [--first i] [--last j] [--thin k] [--block B]\n"
+                    "                         [--quantiles q1,q2,...] [--qbits b]\n"
                     "     [1] The directory of config_default.cfg, errors_default.cfg and the *_ctrl.list files (Config/default)\n"
                     "     [2] The .model file and [3] the .data file of the fit\n"
                     "     [4] The root of the parameter files: <root>_chain-<m>.bin and <root>.hdr\n"
-                    "     [5] The output file (ASCII): x y mean_M sd_M min_M max_M lppd var_l\n"
+                    "     [5] The output file (ASCII): x y mean_M sd_M min_M max_M lppd var_l [one column per quantile]\n"
                     "     --chain m   chain to read (default 0, the coldest)     --slice s   slice of the .model file, from 0 (default 0)\n"
                     "     --first i / --last j / --thin k   samples i, i + k, ... <= j, counted from 0 (default: all)\n"
                     "     --block B   samples per block on the GPU (default 0: chosen by the library)\n"
+                    "     --quantiles q1,q2,...   up to 8 values in [0, 1]: one more column each, the exact quantile of the model per bin\n"
+                    "                             (the samples are read again once per pass)     --qbits b   bits per pass, 1 ... 6 (default 0: the library's)\n"
                     " chainsummary_hip version   prints the library version\n");
     return EXIT_FAILURE;
 }
@@ -67,17 +75,33 @@ int main(int argc, char *argv[])
     if (argc == 2 && std::string(argv[1]) == "version") { printf("chainsummary_hip (%s)\n", tamcmc_version()); return 0; }
     if (argc < 6) return usage();
     const std::string cfg_dir = argv[1], model_file = argv[2], data_file = argv[3], root = argv[4], out_file = argv[5];
-    long chain = 0, slice = 0, first = 0, last = -1, thin = 1, block = 0;
+    long chain = 0, slice = 0, first = 0, last = -1, thin = 1, block = 0, qbits = 0;
+    std::vector<double> quant;
+    std::string quant_text;
     for (int i = 6; i < argc; i++) {
         const std::string a = argv[i];
-        long *dst = a == "--chain" ? &chain : a == "--slice" ? &slice : a == "--first" ? &first : a == "--last" ? &last :
+        if (a == "--quantiles") {                   // a comma-separated list of numbers in [0, 1]
+            if (i + 1 >= argc || !quant.empty()) return usage();
+            quant_text = argv[++i];
+            for (const char *p = quant_text.c_str();;) {
+                char *end = nullptr;
+                const double q = strtod(p, &end);
+                if (end == p || !(q >= 0.0 && q <= 1.0) || quant.size() >= TAMCMC_SUMMARY_MAX_QUANTILES) return usage();
+                quant.push_back(q);
+                if (*end == '\0') break;
+                if (*end != ',') return usage();
+                p = end + 1;
+            }
+            continue;
+        }
+        long *dst = a == "--qbits" ? &qbits : a == "--chain" ? &chain : a == "--slice" ? &slice : a == "--first" ? &first : a == "--last" ? &last :
                     a == "--thin" ? &thin : a == "--block" ? &block : nullptr;
         char *end = nullptr;
         if (!dst || i + 1 >= argc) return usage();
         *dst = strtol(argv[++i], &end, 10);
         if (end == argv[i] || *end != '\0') return usage();
     }
-    if (chain < 0 || slice < 0 || first < 0 || thin < 1 || block < 0 || block > 0x7FFFFFFF) return usage();
+    if (chain < 0 || slice < 0 || first < 0 || thin < 1 || block < 0 || block > 0x7FFFFFFF || qbits < 0 || qbits > 6) return usage();
 
     tamcmc_setup *S = nullptr;
     if (tamcmc_setup_create(&S, cfg_dir.c_str()) != TAMCMC_IO_OK) return fail("cannot read the default configuration in " + cfg_dir);
@@ -117,29 +141,50 @@ int main(int argc, char *argv[])
     tamcmc_summary *sum = nullptr;
     rc = tamcmc_summary_create(&sum, ctx, (int32_t)block);
     if (rc != TAMCMC_OK) return fail(std::string("tamcmc_summary_create: ") + tamcmc_strerror(rc) + " " + tamcmc_last_hip_error());
-    // a few thousand rows per push: the library cuts them into its blocks
+    // One pass over the selected samples, a few thousand rows per push: the library cuts them into its blocks.
     const long long chunk = 4096;
     std::vector<double> vars((size_t)Nvars), P;
     long long last_used = first;
-    for (long long k0 = 0; k0 < Nsel; k0 += chunk) {
-        const long long n = Nsel - k0 < chunk ? Nsel - k0 : chunk;
-        P.assign((size_t)n * (size_t)Nparams, 0.0);
-        for (long long k = 0; k < n; k++) {
-            last_used = first + (k0 + k) * thin;
-            f.seekg(last_used * rowb, std::ios::beg);
-            f.read(reinterpret_cast<char *>(vars.data()), (std::streamsize)rowb);
-            if (!f) return fail("short read in " + bin);
-            double *row = P.data() + (size_t)k * (size_t)Nparams;
-            std::memcpy(row, inputs.data(), (size_t)Nparams * sizeof(double));
-            for (int32_t v = 0; v < Nvars; v++) row[idx[(size_t)v]] = vars[(size_t)v];
+    auto push_selected = [&]() -> int {
+        for (long long k0 = 0; k0 < Nsel; k0 += chunk) {
+            const long long n = Nsel - k0 < chunk ? Nsel - k0 : chunk;
+            P.assign((size_t)n * (size_t)Nparams, 0.0);
+            for (long long k = 0; k < n; k++) {
+                last_used = first + (k0 + k) * thin;
+                f.seekg(last_used * rowb, std::ios::beg);
+                f.read(reinterpret_cast<char *>(vars.data()), (std::streamsize)rowb);
+                if (!f) return fail("short read in " + bin);
+                double *row = P.data() + (size_t)k * (size_t)Nparams;
+                std::memcpy(row, inputs.data(), (size_t)Nparams * sizeof(double));
+                for (int32_t v = 0; v < Nvars; v++) row[idx[(size_t)v]] = vars[(size_t)v];
+            }
+            rc = tamcmc_summary_push(sum, (int32_t)n, Nparams, P.data(), nullptr, nullptr);
+            if (rc != TAMCMC_OK) return fail(std::string("tamcmc_summary_push: ") + tamcmc_strerror(rc) + " " + tamcmc_last_hip_error());
         }
-        rc = tamcmc_summary_push(sum, (int32_t)n, Nparams, P.data(), nullptr, nullptr);
-        if (rc != TAMCMC_OK) return fail(std::string("tamcmc_summary_push: ") + tamcmc_strerror(rc) + " " + tamcmc_last_hip_error());
-    }
+        return 0;
+    };
+    if (push_selected() != 0) return EXIT_FAILURE;
     tamcmc_summary_totals t;
     std::vector<double> mean_M(Nx), var_M(Nx), min_M(Nx), max_M(Nx), var_l(Nx), lppd(Nx);
     rc = tamcmc_summary_result(sum, &t, mean_M.data(), var_M.data(), min_M.data(), max_M.data(), nullptr, var_l.data(), lppd.data());
     if (rc != TAMCMC_OK) return fail(std::string("tamcmc_summary_result: ") + tamcmc_strerror(rc) + " " + tamcmc_last_hip_error());
+    // quantiles: the same samples again, once per pass, until every value is exact
+    const size_t Nq = quant.size();
+    std::vector<double> qlo(Nq * (size_t)Nx);
+    int passes = 0;
+    if (Nq) {
+        auto qfail = [&](const char *what) { return fail(std::string(what) + ": " + tamcmc_strerror(rc) + " " + tamcmc_last_hip_error()); };
+        rc = tamcmc_summary_quantiles_begin(sum, (int32_t)Nq, quant.data(), (int32_t)qbits);
+        if (rc != TAMCMC_OK) return qfail("tamcmc_summary_quantiles_begin");
+        for (int32_t left = 1; left > 0; passes++) {              // (a chain whose samples are all equal takes one idle pass)
+            if (push_selected() != 0) return EXIT_FAILURE;
+            rc = tamcmc_summary_quantiles_step(sum, &left);
+            if (rc != TAMCMC_OK) return qfail("tamcmc_summary_quantiles_step");
+        }
+        rc = tamcmc_summary_quantiles_result(sum, nullptr, qlo.data(), nullptr);
+        if (rc != TAMCMC_OK) return qfail("tamcmc_summary_quantiles_result");
+        tamcmc_summary_quantiles_end(sum);
+    }
     tamcmc_summary_destroy(sum);
     tamcmc_ctx_destroy(ctx);
 
@@ -150,10 +195,16 @@ int main(int argc, char *argv[])
     fprintf(o, "# samples_in_file= %lld  first= %ld  last= %lld  thin= %ld\n", Nrows, first, last_used, thin);
     fprintf(o, "# n_used= %lld  n_rejected= %lld\n", (long long)t.n_used, (long long)t.n_rejected);
     fprintf(o, "# lppd_total= %.12g  p_waic= %.12g  waic= %.12g\n", t.lppd_total, t.p_waic, t.waic);
-    fprintf(o, "# x y mean_M sd_M min_M max_M lppd var_l\n");
-    for (int64_t i = 0; i < Nx; i++)
-        fprintf(o, "%.12g %.12g %.12g %.12g %.12g %.12g %.12g %.12g\n", x[i], y[i], mean_M[i], std::sqrt(var_M[i]), min_M[i], max_M[i],
+    if (Nq) fprintf(o, "# quantiles= %s  passes= %d\n", quant_text.c_str(), passes);
+    fprintf(o, "# x y mean_M sd_M min_M max_M lppd var_l");
+    for (size_t j = 0; j < Nq; j++) fprintf(o, " q%.6g", quant[j]);
+    fprintf(o, "\n");
+    for (int64_t i = 0; i < Nx; i++) {
+        fprintf(o, "%.12g %.12g %.12g %.12g %.12g %.12g %.12g %.12g", x[i], y[i], mean_M[i], std::sqrt(var_M[i]), min_M[i], max_M[i],
                 lppd[i], var_l[i]);
+        for (size_t j = 0; j < Nq; j++) fprintf(o, " %.12g", qlo[j * (size_t)Nx + (size_t)i]);
+        fprintf(o, "\n");
+    }
     fclose(o);
     printf("Summary of %lld samples (%lld rejected) written to %s\n", (long long)t.n_used, (long long)t.n_rejected, out_file.c_str());
     return 0;

@@ -9,6 +9,9 @@ Prints one JSON line:
   c_fold_*                  the fold kernel alone, from HIP events around every launch: time per block, bytes per second
                             (the block's rows read once + the running state read and written) and that rate over the
                             6.29 TB/s measured copy ceiling of the MI355X
+  d_quantile_*              quantile mode (Summary.quantiles_*) at --quantiles quantiles and --qbits bits per pass, after leg
+                            (a)'s fold pass: seconds per pass per 1000 samples through Summary.push (the step included), the
+                            histogram kernel alone from the same HIP-event hooks, and the number of passes to exactness
 Every timed shape is warmed up first (--warmup pushes); host clocks stop after calls that end in a device synchronise.
 """
 import argparse
@@ -62,6 +65,8 @@ def main():
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--nx", type=int, default=100000)
+    ap.add_argument("--quantiles", type=int, default=3)
+    ap.add_argument("--qbits", type=int, default=0)
     a = ap.parse_args()
     if a.steps < 1 or a.warmup < 0 or a.samples < 1 or a.samples_b < 2:
         ap.error("--steps >= 1, --warmup >= 0, --samples >= 1, --samples-b >= 2")
@@ -98,6 +103,31 @@ def main():
             out.update(c_fold_launches=launches, c_block_chains=B, c_fold_us_per_block=ms * 1e3 / launches,
                        c_fold_s_per_1000=ms * 1e-3 * 1000.0 / a.samples, c_fold_bytes_per_s=bytes_moved / (ms * 1e-3),
                        c_fold_share_of_copy_ceiling=bytes_moved / (ms * 1e-3) / COPY_CEILING)
+            # (d) quantile mode: the same rows again, once per pass, until every value is exact
+            s.reset()
+            s.push(P)
+            q = [0.16, 0.5, 0.84, 0.025, 0.975, 0.0, 1.0, 0.25][:a.quantiles]
+            s.quantiles_begin(q, a.qbits)
+            pass_times, left = [], None
+            while left != 0:
+                acc.synchronize()
+                t0 = time.perf_counter()
+                s.push(P)
+                left = s.quantiles_step()                   # synchronises the stream
+                pass_times.append(time.perf_counter() - t0)
+            s.quantiles_end()
+            s.quantiles_begin(q, a.qbits)                   # the histogram kernel alone, over the first pass
+            s.profile(True)
+            s.push(P)
+            ms, launches = s.kernel_time()
+            s.profile(False)
+            s.quantiles_end()
+            out.update(d_quantile_Nq=len(q), d_quantile_bits=a.qbits or 6, d_quantile_passes=len(pass_times),
+                       d_quantile_s_per_pass_per_1000=float(np.median(pass_times)) * 1000.0 / a.samples,
+                       d_quantile_spread=[float(min(pass_times)) * 1000.0 / a.samples, float(max(pass_times)) * 1000.0 / a.samples],
+                       d_quantile_total_s_per_1000=float(np.sum(pass_times)) * 1000.0 / a.samples,
+                       d_quantile_hist_us_per_block=ms * 1e3 / launches, d_quantile_hist_s_per_1000=ms * 1e-3 * 1000.0 / a.samples,
+                       d_quantile_hist_bytes=len(q) * (1 << (a.qbits or 6)) * a.nx * 4)
         # (b) the host route, on fewer rows
         Pb = P[:a.samples_b]
         host_fold(acc, Pb[:64], y)
