@@ -266,7 +266,17 @@ int tamcmc_summary_quantiles_end(tamcmc_summary *s);
  *   grad        NULL, or Nchains x Nvars
  *   model_rows  n_rows chain indices whose model spectrum is wanted (Model_def::model rows), or NULL
  *   model_out   n_rows x Nx, or NULL
- *   status      NULL or Nchains TAMCMC_CHAIN_* codes */
+ *   status      NULL or Nchains TAMCMC_CHAIN_* codes
+ * Largest batch of one call -- here and in every other entry point that evaluates chains on one context (_device, _begin,
+ * _arm, _reserve, and the blocks of tamcmc_summary_push): no launch may exceed 2^32 - 1 work-items, the rule of
+ * tamcmc_group_eval, so with T tiles per chain (tamcmc_ctx_geometry)
+ *     Nchains * T <= 16 777 215          (workgroups of 256 threads), and
+ *     Nchains     <=  8 388 607          (per-chain workgroups of 512 threads) unless the grid is one tile and no gradient
+ *                                        is asked for (one launch of 256 threads per chain).
+ * A larger Nchains is refused with TAMCMC_E_INVALID before anything is allocated or enqueued; split the batch -- a chain's
+ * result depends neither on the batch nor on its position in it.  Device memory is the limit met first on most grids:
+ * a batch needs a few KB per chain and tile (more with a gradient).  Tested at 70 001 chains on every launch path and at
+ * 131 073 on the one-tile path (tests/test_chain_counts_gpu.py, tests/test_summary_large_gpu.py). */
 int tamcmc_eval_batch(tamcmc_ctx *ctx, int32_t Nchains, int32_t Nparams,
                       const double *params, const double *Tcoefs,
                       double *logL, double *grad,

@@ -116,6 +116,7 @@ static void free_batch(tamcmc_ctx *c)
 
 int tm_ensure_capacity(tamcmc_ctx *c, int Nchains, bool grad)
 {
+    if (!tm_batch_fits(c, Nchains, grad)) return TAMCMC_E_INVALID;   // before anything is sized for a batch no launch can take
     if (Nchains <= c->cap && (!grad || c->cap_grad)) return TAMCMC_OK;
     const int cap = Nchains > c->cap ? Nchains : c->cap;
     const bool g = grad || c->cap_grad;
@@ -488,6 +489,7 @@ int tm_enqueue(tamcmc_ctx *c, int Nchains, const double *d_params, const double 
 {
     const bool grad = d_grad != nullptr;
     const hipStream_t stream = c->stream;
+    if (!tm_batch_fits(c, Nchains, grad)) return TAMCMC_E_INVALID;   // a grid the runtime would reject (tamcmc_host.h)
     TM_HIP(tm_ctx_settle(c));
     c->enq_seq++;
     // several spectra resident: every chain of the batch must have been told which one it is fitted to (a batch longer

@@ -195,6 +195,18 @@ static inline hipError_t tm_ctx_stream_sync(tamcmc_ctx *c)
 static inline int tm_ctx_tiles(const tamcmc_ctx *c, bool grad) { return grad ? c->tiles_g : c->tiles_l; }
 // one tile per chain (short grids): prologue and evaluation share a launch (TAMCMC_TILES=1 on a 9..16-unit grid: two launches)
 static inline bool tm_takes_fused(const tamcmc_ctx *c, int tiles) { return tiles == 1 && c->fuse != 0 && c->units <= TM_TILE_MAXU; }
+// The largest batch of one call (tamcmc_eval_batch in tamcmc_accel.h states it): no launch of the batch may exceed 2^32 - 1
+// work-items, the rule tamcmc_group_eval applies to its 1-D launches.  Per chain the launches are one workgroup of the
+// setup kernel (and, with a gradient, of the backward kernel: 512 threads each, TM_SETUP_THREADS / TM_BW_THREADS) and
+// `tiles` workgroups of TM_THREADS of the eval kernel; the fused launch is one workgroup of TM_THREADS per chain.
+#define TM_CHAIN_WG_MAX 512
+static inline bool tm_batch_fits(const tamcmc_ctx *c, int Nchains, bool grad)
+{
+    const long long lim = 0xFFFFFFFFLL, n = Nchains;
+    const int tiles = tm_ctx_tiles(c, grad);
+    if (n * tiles > lim / TM_THREADS) return false;
+    return (tm_takes_fused(c, tiles) && !grad) || n <= lim / TM_CHAIN_WG_MAX;
+}
 // The arrival counters of the first n chains back to zero (after a launch that failed, or did not finalize them).
 static inline void tm_zero_tickets(const tamcmc_ctx *c, int n, hipStream_t stream) { (void)hipMemsetAsync(c->d_ticket, 0, (size_t)n * sizeof(int32_t), stream); }
 

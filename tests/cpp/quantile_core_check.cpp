@@ -100,9 +100,63 @@ static long check_column(const char *name, const std::vector<double> &col)
     return selections;
 }
 
+// tmq_narrow<uint32_t> on cells that hold 65 535, 65 536 and 4 294 967 295 counts -- past the 16-bit LDS counters of the
+// histogram kernel and at the end of the global uint32 cells -- with the wanted rank first and last in such a cell.  The
+// cumulative counts are uint64: three full cells sum to 3 (2^32 - 1), which a 32-bit running sum would wrap.
+static long check_big_cells()
+{
+    long cases = 0;
+    const uint64_t bigs[] = {65535u, 65536u, 4294967295u};
+    for (const uint64_t big : bigs)
+        for (int d = 1; d <= TM_Q_MAXBITS; d++) {
+            const unsigned ncell = 1u << d;
+            // the big cell at c0, a few small ones around it, and (where there is room) big cells under it too
+            for (const unsigned c0 : {0u, ncell / 2, ncell - 1})
+                for (int full_below = 0; full_below < 2; full_below++) {
+                    std::vector<uint32_t> cells(ncell);
+                    for (unsigned c = 0; c < ncell; c++) cells[c] = (c % 3 == 0) ? 0u : (c % 3 == 1 ? 1u : 7u);
+                    if (full_below)
+                        for (unsigned c = 0; c < c0 && c < 3; c++) cells[c] = (uint32_t)big;
+                    cells[c0] = (uint32_t)big;
+                    uint64_t under = 0;
+                    for (unsigned c = 0; c < c0; c++) under += cells[c];
+                    if (full_below && c0 >= 2) CHECK(big < 4294967295u || under > 0xFFFFFFFFull, "the cells under the big one must pass 2^32");
+                    const uint64_t below0 = 12345678901ull, prefix0 = 5;
+                    for (const uint64_t within : {(uint64_t)0, big - 1}) {            // first and last rank of the big cell
+                        std::vector<uint32_t> h = cells;
+                        uint64_t prefix = prefix0, below = below0;
+                        tmq_narrow<uint32_t>(&prefix, &below, below0 + under + within, h.data(), 1, d);
+                        CHECK(prefix == ((prefix0 << d) | c0), "big %llu d %d cell %u rank +%llu: digit %llu", (unsigned long long)big, d, c0,
+                              (unsigned long long)within, (unsigned long long)(prefix & (ncell - 1)));
+                        CHECK(below == below0 + under, "big %llu d %d cell %u rank +%llu: below off by %lld", (unsigned long long)big, d, c0,
+                              (unsigned long long)within, (long long)(below - below0 - under));
+                        for (unsigned c = 0; c < ncell; c++) CHECK(h[c] == 0, "narrow left a cell uncleared");
+                        cases++;
+                    }
+                    // the rank just past the big cell belongs to the next cell that holds anything (or, none left, the top cell)
+                    {
+                        std::vector<uint32_t> h = cells;
+                        uint64_t prefix = prefix0, below = below0;
+                        tmq_narrow<uint32_t>(&prefix, &below, below0 + under + big, h.data(), 1, d);
+                        unsigned next = c0 + 1;
+                        uint64_t u2 = under + big;
+                        while (next < ncell && cells[next] == 0) next++;
+                        if (next < ncell) {
+                            CHECK(prefix == ((prefix0 << d) | next) && below == below0 + u2, "big %llu d %d cell %u: the rank past it", (unsigned long long)big, d, c0);
+                        } else {
+                            CHECK(prefix == ((prefix0 << d) | (ncell - 1)) && below == below0, "big %llu d %d cell %u: a rank no cell holds", (unsigned long long)big, d, c0);
+                        }
+                        cases++;
+                    }
+                }
+        }
+    return cases;
+}
+
 int main()
 {
     const long nkeys = check_keys();
+    const long nbig = check_big_cells();
     const double inf = std::numeric_limits<double>::infinity(), den = std::numeric_limits<double>::denorm_min();
     uint64_t rng = 0x9E3779B97F4A7C15ull;
     auto uniform = [&]() {                                    // xorshift64*: [0, 1)
@@ -126,6 +180,6 @@ int main()
     sel += check_column("straddle-2", {1.9999999999999998, 2.0000000000000004});
     sel += check_column("full-range", {-inf, inf});                        // R needs all 64 bits
     if (failures) { fprintf(stderr, "%d check(s) failed\n", failures); return 1; }
-    printf("ok quantile_core_check: %ld key values, %ld selections\n", nkeys, sel);
+    printf("ok quantile_core_check: %ld key values, %ld selections, %ld narrowings of cells of 65535 ... 2^32 - 1 counts\n", nkeys, sel, nbig);
     return 0;
 }

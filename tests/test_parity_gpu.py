@@ -222,7 +222,7 @@ def test_model_def_mirror(accel_mod, orc):
 
 
 def test_large_grid_and_many_chains(accel_mod, orc):
-    """Nx = 1e6 (the reference's own row limit, config.cpp:531): 489 tiles per chain, more than one pass of the
+    """Nx = 1e6 (the reference's own row limit, config.cpp:531): 245 tiles per chain, more than one pass of the
     setup kernel's tile loops; and 256 chains (config C3's total) in one batch."""
     w = synth.workload_c2(Nx=1000000)
     w["x"] = synth.grid(1000000, 2300.0, 840.0 / 1000000)
