@@ -234,7 +234,46 @@ int tamcmc_group_members(const tamcmc_group *g, int32_t *n_members, int32_t *Npa
  *                lo == hi == the order statistic, bit for bit.
  *   quantiles_end     frees the selection's memory and goes back to fold mode: the running statistics are untouched and
  *                further pushes fold as before.  tamcmc_summary_reset also leaves the mode; tamcmc_summary_destroy works
- *                in either.  _step, _result and _end outside the mode return TAMCMC_E_INVALID. */
+ *                in either.  _step, _result and _end outside the mode return TAMCMC_E_INVALID.
+ *
+ * PSIS-LOO: leave-one-out cross-validation by Pareto-smoothed importance sampling (Vehtari, Gelman & Gabry 2017; Vehtari
+ * et al. 2024) -- elpd_loo on the scale of lppd, and per bin the Pareto shape k-hat that says whether the bin's value can
+ * be trusted (k-hat > 0.7: it cannot; WAIC is biased in the same bins and gives no sign of it).  A third mode beside fold
+ * and quantile mode: after the fold pass the caller pushes the SAME samples once more.  For chi_square l keeps the
+ * reference's convention without the factor 1/2, as lppd and WAIC do here, so elpd_loo / p_loo / looic are on that scale.
+ *   Definition, per bin i, with x_s = -l_is over the n = n_used accepted samples:
+ *     1. M = (int64)ceil(fmin(n / 5.0, 3.0 * sqrt((double)n))), xmax = max_s x_s, z_s = x_s - xmax.
+ *     2. If n > M: c = max(the (M+1)-th largest z, log(DBL_MIN)); the tail T = {s : z_s > c} (strictly: ties with the
+ *        cutoff are body), L = |T|.  If n <= M (only n = 1) there is no tail.
+ *     3. If L >= 5: t_j = exp(z_(j)) - exp(c) ascending, j = 1 ... L, and the generalised Pareto fit of Zhang & Stephens:
+ *        m = 30 + floor(sqrt(L)); theta_j = (1 - sqrt(m / (j - 0.5))) / (3 t_(q)) + 1 / t_(L), q = floor(L/4 + 0.5),
+ *        j = 1 ... m; k_j = mean_i log1p(-theta_j t_i); l_j = L (log(-theta_j / k_j) - k_j - 1); w_j = 1 / sum_i exp(l_i -
+ *        l_j), every w_j < 10 * 2^-52 dropped and the rest renormalised; theta = sum w_j theta_j; k = mean_i log1p(-theta
+ *        t_i); sigma = -k / theta; k-hat = (L k + 5) / (L + 10).  If k-hat is finite the smoothed tail is zt_(j) =
+ *        min(log(sigma / k-hat * expm1(-k-hat log1p(-p_j)) + exp(c)), 0), p_j = (j - 0.5) / L (for k-hat == 0 the inner
+ *        term is -sigma log1p(-p_j)); otherwise zt = z.  If L <= 4: k-hat = +inf and zt = z (every n <= 20).
+ *     4. elpd_loo_i = log(n_body + sum_T exp(zt_(j) - z_(j))) - xmax - log(sum_body exp(z_s) + sum_T exp(zt_(j))), the
+ *        body sum accumulated as such.  With n = 0 everything is NaN.
+ *     5. Totals, summed on the host in bin order in long double: elpd_loo; p_loo = lppd_total - elpd_loo; looic =
+ *        -2 elpd_loo; k_max (may be +inf; a NaN k-hat is skipped); n_k_high = bins with k-hat > 0.7, +inf counted;
+ *        n_k_inf = bins with k-hat = +inf.
+ *   loo_begin    freezes the fold state as quantiles_begin does, computes M and allocates (M + 1) x Nx doubles for the
+ *                per-bin sets of the M + 1 largest x plus 52 Nx bytes of state; TAMCMC_E_NOMEM when that fails, and the
+ *                object stays as it was.  Refused with TAMCMC_E_INVALID: n_used < 1, M > TAMCMC_SUMMARY_LOO_MAX_TAIL
+ *                (n_used > 466 033: thin the chain), quantile mode or LOO mode already on, a context with a batch in
+ *                flight or armed.  tamcmc_summary_quantiles_begin is refused while LOO mode is on.
+ *   While the mode is on, push and push_device evaluate the rows as before and hand out the same logL and status bits, but
+ *   feed the tail kernel (tamcmc_loo.hip) instead of the fold kernel; tamcmc_summary_result keeps returning the frozen fold
+ *   results.  Every result is bit for bit independent of block_chains and of how the pass is split over pushes.
+ *   loo_result   totals, elpd_loo[Nx], pareto_k[Nx], cutoff[Nx], tail_len[Nx] on the host, any of them may be NULL.
+ *                cutoff is the un-shifted (M+1)-th largest x, before the log(DBL_MIN) floor and before xmax is subtracted
+ *                (NaN where there is no tail rule); tail_len is L.  If the pass did not see exactly the fold pass's
+ *                accepted and rejected counts: TAMCMC_E_INVALID, the pass is discarded and may be repeated.  May be called
+ *                again without another pass.
+ *   loo_end      frees the mode's memory and goes back to fold mode: the running statistics are untouched and further
+ *                pushes fold as before.  tamcmc_summary_reset also leaves the mode; tamcmc_summary_destroy works in any.
+ *                _result and _end outside the mode return TAMCMC_E_INVALID.
+ *   profile / kernel_time in LOO mode: the tail kernel of every block, and the finalize kernel of every loo_result. */
 typedef struct tamcmc_summary tamcmc_summary;
 typedef struct {
     int64_t n_used, n_rejected;
@@ -257,6 +296,16 @@ int tamcmc_summary_quantiles_begin(tamcmc_summary *s, int32_t Nq, const double *
 int tamcmc_summary_quantiles_step(tamcmc_summary *s, int32_t *bits_left);
 int tamcmc_summary_quantiles_result(tamcmc_summary *s, int64_t *ranks, double *lo, double *hi);
 int tamcmc_summary_quantiles_end(tamcmc_summary *s);
+#define TAMCMC_SUMMARY_LOO_MAX_TAIL 2048
+typedef struct {
+    int64_t n_used, n_rejected;
+    double elpd_loo, p_loo, looic, k_max;
+    int64_t n_k_high, n_k_inf;
+} tamcmc_summary_loo_totals;
+int tamcmc_summary_loo_begin(tamcmc_summary *s);
+int tamcmc_summary_loo_result(tamcmc_summary *s, tamcmc_summary_loo_totals *totals,
+                              double *elpd_loo, double *pareto_k, double *cutoff, int32_t *tail_len);
+int tamcmc_summary_loo_end(tamcmc_summary *s);
 
 /* Replaces: the `for chain` loop of generate_model() calls (MALA.cpp:632-639, model_def.cpp:139-143).
  * Host pointers, row-major.  Synchronous: results are valid on return.

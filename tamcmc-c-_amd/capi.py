@@ -32,6 +32,7 @@ EXPORTS = [
     "tamcmc_summary_reset", "tamcmc_summary_destroy", "tamcmc_summary_profile", "tamcmc_summary_kernel_time",
     "tamcmc_summary_quantiles_begin", "tamcmc_summary_quantiles_step", "tamcmc_summary_quantiles_result",
     "tamcmc_summary_quantiles_end",
+    "tamcmc_summary_loo_begin", "tamcmc_summary_loo_result", "tamcmc_summary_loo_end",
 ]
 
 
@@ -39,6 +40,12 @@ class SummaryTotals(C.Structure):
     """tamcmc_summary_totals"""
     _fields_ = [("n_used", C.c_int64), ("n_rejected", C.c_int64), ("lppd_total", C.c_double), ("p_waic", C.c_double),
                 ("waic", C.c_double)]
+
+
+class SummaryLooTotals(C.Structure):
+    """tamcmc_summary_loo_totals"""
+    _fields_ = [("n_used", C.c_int64), ("n_rejected", C.c_int64), ("elpd_loo", C.c_double), ("p_loo", C.c_double),
+                ("looic", C.c_double), ("k_max", C.c_double), ("n_k_high", C.c_int64), ("n_k_inf", C.c_int64)]
 
 
 class AccelError(RuntimeError):
@@ -105,6 +112,9 @@ def load_library():
     lib.tamcmc_summary_quantiles_step.argtypes = [vp, C.POINTER(C.c_int32)]
     lib.tamcmc_summary_quantiles_result.argtypes = [vp, C.POINTER(C.c_int64), dp, dp]
     lib.tamcmc_summary_quantiles_end.argtypes = [vp]
+    lib.tamcmc_summary_loo_begin.argtypes = [vp]
+    lib.tamcmc_summary_loo_result.argtypes = [vp, C.POINTER(SummaryLooTotals), dp, dp, dp, ip]
+    lib.tamcmc_summary_loo_end.argtypes = [vp]
     for name in EXPORTS:
         fn = getattr(lib, name)
         if fn.restype is not C.c_char_p:
@@ -412,8 +422,8 @@ class Summary:
     """Posterior summaries of a stored chain (tamcmc_accel.h, tamcmc_summary_*): per-bin running statistics of the model
     and of the pointwise log-likelihood over the parameter rows pushed so far, kept on the device.  Results do not depend,
     bit for bit, on block_chains or on how the rows are split over pushes.  quantiles() gives the exact per-bin quantiles
-    of the model (credible bands) by pushing the same rows again a few times.  The Accel cannot be closed while the
-    summary is open."""
+    of the model (credible bands) by pushing the same rows again a few times; loo() gives PSIS-LOO (elpd_loo and the
+    Pareto k-hat per bin) by pushing them once more.  The Accel cannot be closed while the summary is open."""
 
     ARRAYS = ("mean_M", "var_M", "min_M", "max_M", "mean_l", "var_l", "lppd")
 
@@ -456,6 +466,7 @@ class Summary:
     def reset(self):
         self._check(self._lib.tamcmc_summary_reset(self._s), "tamcmc_summary_reset")
         self._nq = 0                                            # reset leaves quantile mode
+        self._loo = False                                       # and LOO mode
 
     def profile(self, enable=True):
         self._check(self._lib.tamcmc_summary_profile(self._s, int(enable)), "tamcmc_summary_profile")
@@ -522,6 +533,44 @@ class Summary:
         finally:
             if getattr(self, "_nq", 0):
                 self.quantiles_end()
+
+    # ---- PSIS-LOO: leave-one-out elpd and the Pareto k-hat per bin, one more pass over the same rows ----
+    LOO_MAX_TAIL = 2048
+    LOO_ARRAYS = ("elpd_loo", "pareto_k", "cutoff")
+    LOO_TOTALS = ("n_used", "n_rejected", "elpd_loo_total", "p_loo", "looic", "k_max", "n_k_high", "n_k_inf")
+
+    def loo_begin(self):
+        """Enters LOO mode.  From here on push / push_device feed the tail kernel: push the same rows again, then
+        loo_result()."""
+        self._check(self._lib.tamcmc_summary_loo_begin(self._s), "tamcmc_summary_loo_begin")
+        self._loo = True
+
+    def loo_result(self):
+        """dict: elpd_loo, pareto_k, cutoff (Nx doubles), tail_len (Nx int32) and the totals n_used, n_rejected,
+        elpd_loo_total, p_loo, looic, k_max, n_k_high, n_k_inf."""
+        out = {k: np.empty(self.accel.Nx) for k in self.LOO_ARRAYS}
+        out["tail_len"] = np.empty(self.accel.Nx, dtype=np.int32)
+        t = SummaryLooTotals()
+        self._check(self._lib.tamcmc_summary_loo_result(self._s, C.byref(t), *[_dptr(out[k]) for k in self.LOO_ARRAYS],
+                                                        _iptr(out["tail_len"])), "tamcmc_summary_loo_result")
+        out.update(n_used=int(t.n_used), n_rejected=int(t.n_rejected), elpd_loo_total=t.elpd_loo, p_loo=t.p_loo, looic=t.looic,
+                   k_max=t.k_max, n_k_high=int(t.n_k_high), n_k_inf=int(t.n_k_inf))
+        return out
+
+    def loo_end(self):
+        self._check(self._lib.tamcmc_summary_loo_end(self._s), "tamcmc_summary_loo_end")
+        self._loo = False
+
+    def loo(self, params):
+        """PSIS-LOO over the rows already pushed, `params` being those rows: begin, one push, result, end.  Returns the
+        dict of loo_result() and always leaves the mode."""
+        self.loo_begin()
+        try:
+            self.push(params)
+            return self.loo_result()
+        finally:
+            if getattr(self, "_loo", False):
+                self.loo_end()
 
     def close(self):
         if getattr(self, "_s", None) is not None and self._s.value:

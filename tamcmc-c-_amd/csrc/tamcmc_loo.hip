@@ -1,0 +1,125 @@
+// tamcmc_loo.hip -- stage 2 of a block of samples while a summary object is in LOO mode (tamcmc_loo.h), and the kernel that
+// turns the pass into per-bin PSIS-LOO results.
+//
+// Tail kernel.  One thread owns one bin, as in the fold kernel (tamcmc_summary.hip): rows are read coalesced with 64-bit
+// row offsets, TM_LOO_UNROLL loads requested before the first is used; the status words come from device memory and a
+// sample that is not OK is skipped and counted.  Per bin the thread keeps the exact multiset of the M + 1 largest
+// x = -l seen so far in a binary min-heap laid out [slot][Nx] (a wave's accesses to one slot are consecutive), with the
+// root in a register: the common sample (x <= root) goes into the body's running-maximum log-sum-exp (a Kahan sum whose
+// maximum follows lazily: tamcmc_loo.h) and touches no memory.
+// While the heap fills, every thread writes the same slots (the number of accepted samples is the same for every bin); a
+// replacement walks down a path of its own.  No LDS, no atomics, no cross-thread reduction: a bin's state after a pass is
+// bit for bit independent of the block size and of how the pass was split over pushes.
+// l is the fold kernel's, restated (tests/test_summary_loo_gpu.py pins that the two agree bit for bit), without FMA
+// contraction:
+//     chi(2,2p)    l = -p (y / M + log M)
+//     chi_square   l = -(y - M)^2 / sigma^2
+//
+// Finalize kernel.  One wave per bin.  The bin's heap goes into LDS (the M <= 2048 values above the root, padded with
+// +inf to a power of two), is sorted ascending by a bitonic network, and tml_finalize (tamcmc_loo.h) does the rest with
+// fixed-order wave reductions: 64 partial sums over the tail in stride-64 order, then a butterfly of 6 exchanges that
+// leaves the same bits in every lane.  LDS: the sorted values, the tail's t_j, and the profile's theta / l: 2 x 16 KiB +
+// 1.2 KiB.  The kernel reads the pass's state and writes only the four result arrays, so it can run again.
+#include <hip/hip_runtime.h>
+#include <cmath>
+
+// no FMA contraction anywhere in this file: the two formulas for l must round as the fold kernel's do, and the shared
+// arithmetic of tamcmc_loo.h (heap, body sum, tml_finalize) is compiled under the same rule
+#pragma clang fp contract(off)
+
+#include "tamcmc_loo.h"
+
+__global__ __launch_bounds__(TM_LOO_THREADS) void tamcmc_loo_tail_kernel(const TmLooArgs a)
+{
+    const int bin = (int)(blockIdx.x * TM_LOO_THREADS + threadIdx.x);
+    if (bin >= a.Nx) return;
+    const size_t nx = (size_t)a.Nx;
+    long long n = a.cnt_in[0], rej = a.cnt_in[1];
+    double *const heap = a.heap + bin;
+    double root = n > 0 ? heap[0] : 0.0;
+    double ba = a.body[bin], br = a.body[nx + bin], bc = a.body[2 * nx + bin];
+    const double y = a.y[bin];
+    const bool chi2 = a.likelihood_case != 0;
+    const double is2 = chi2 ? a.isig2[bin] : 0.0;
+    const double p = a.like_p;
+    const double *__restrict__ rows = a.rows + bin;
+
+    for (int s0 = 0; s0 < a.B; s0 += TM_LOO_UNROLL) {
+        double v[TM_LOO_UNROLL];
+#pragma unroll
+        for (int k = 0; k < TM_LOO_UNROLL; k++)
+            v[k] = (s0 + k < a.B) ? rows[(size_t)(s0 + k) * nx] : 1.0;       // (a rejected sample's row is loaded and dropped)
+#pragma unroll
+        for (int k = 0; k < TM_LOO_UNROLL; k++) {
+            if (s0 + k >= a.B) break;
+            if (a.status[s0 + k] != 0) { rej++; continue; }
+            double l;
+            if (chi2) { const double dd = y - v[k]; l = -((dd * dd) * is2); }
+            else l = -p * (y / v[k] + log(v[k]));
+            tml_top_push(heap, nx, a.cap, n, -l, &root, &ba, &br, &bc);
+            n++;
+        }
+    }
+
+    a.body[bin] = ba; a.body[nx + bin] = br; a.body[2 * nx + bin] = bc;
+    if (bin == 0) { a.cnt_out[0] = n; a.cnt_out[1] = rej; }
+}
+
+struct TmlWave {
+    __device__ int lane() const { return (int)threadIdx.x; }
+    __device__ int lanes() const { return TM_LOO_THREADS; }
+    __device__ double sum(double v) const
+    {
+#pragma unroll
+        for (int o = TM_LOO_THREADS / 2; o > 0; o >>= 1) v += __shfl_xor(v, o, TM_LOO_THREADS);
+        return v;
+    }
+    __device__ void sync() const { __syncthreads(); }
+};
+
+__global__ __launch_bounds__(TM_LOO_THREADS) void tamcmc_loo_finalize_kernel(const TmLooArgs a)
+{
+    __shared__ double s[TM_LOO_MAX_TAIL], t[TM_LOO_MAX_TAIL];
+    __shared__ double theta[TM_LOO_MAX_THETA], ell[TM_LOO_MAX_THETA];
+    const int bin = (int)blockIdx.x, lane = (int)threadIdx.x;
+    const size_t nx = (size_t)a.Nx;
+    const int cnt = a.n < (long long)a.cap ? (int)a.n : a.cap;               // >= 1: the host does not launch for n = 0
+    const int ncand = cnt - 1;                                               // <= M <= TM_LOO_MAX_TAIL
+    int P = 1;
+    while (P < ncand) P <<= 1;
+    const double *heap = a.heap + bin;
+    for (int j = lane; j < P; j += TM_LOO_THREADS) s[j] = j < ncand ? heap[(size_t)(j + 1) * nx] : (double)INFINITY;
+    const double root = heap[0];
+    __syncthreads();
+    for (int k = 2; k <= P; k <<= 1)
+        for (int j = k >> 1; j > 0; j >>= 1) {
+            for (int i = lane; i < P; i += TM_LOO_THREADS) {
+                const int o = i ^ j;
+                if (o > i) {
+                    const double u = s[i], v = s[o];
+                    if ((u > v) == ((i & k) == 0)) { s[i] = v; s[o] = u; }
+                }
+            }
+            __syncthreads();
+        }
+    TmlWave w;
+    const TmlBin r = tml_finalize(w, s, ncand, root, a.n >= (long long)a.cap, a.n, a.body[bin], a.body[nx + bin] - a.body[2 * nx + bin], t, theta, ell);
+    if (lane == 0) {
+        a.elpd[bin] = r.elpd_loo; a.khat[bin] = r.pareto_k; a.cutoff[bin] = r.cutoff; a.tail_len[bin] = r.tail_len;
+    }
+}
+
+int tm_launch_loo_tail(const TmLooArgs &a, void *stream)
+{
+    if (a.cap < 2 || a.cap > TM_LOO_MAX_TAIL + 1) return (int)hipErrorInvalidValue;
+    const unsigned blocks = (unsigned)(((long long)a.Nx + TM_LOO_THREADS - 1) / TM_LOO_THREADS);
+    hipLaunchKernelGGL(tamcmc_loo_tail_kernel, dim3(blocks), dim3(TM_LOO_THREADS), 0, (hipStream_t)stream, a);
+    return (int)hipGetLastError();
+}
+
+int tm_launch_loo_finalize(const TmLooArgs &a, void *stream)
+{
+    if (a.cap < 2 || a.cap > TM_LOO_MAX_TAIL + 1 || a.n < 1) return (int)hipErrorInvalidValue;
+    hipLaunchKernelGGL(tamcmc_loo_finalize_kernel, dim3((unsigned)a.Nx), dim3(TM_LOO_THREADS), 0, (hipStream_t)stream, a);
+    return (int)hipGetLastError();
+}

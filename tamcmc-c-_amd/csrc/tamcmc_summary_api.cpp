@@ -2,11 +2,13 @@
 // statistics of the model and of the pointwise log-likelihood over the samples pushed so far.  A block of samples = the
 // context's own launches (tamcmc_host.h: tm_enqueue) with a row map covering every chain (stage 1) +
 // tamcmc_summary_fold_kernel (stage 2), both on the context's stream.  While the object selects quantiles
-// (tamcmc_summary_quantiles_*, tamcmc_quantile.h) stage 2 is the histogram kernel instead and the fold state is frozen.
+// (tamcmc_summary_quantiles_*, tamcmc_quantile.h) stage 2 is the histogram kernel instead and the fold state is frozen;
+// in LOO mode (tamcmc_summary_loo_*, tamcmc_loo.h) it is the tail kernel.
 #include <cmath>
 #include <new>
 
 #include "tamcmc_host.h"
+#include "tamcmc_loo.h"
 #include "tamcmc_quantile.h"
 #include "tamcmc_summary.h"
 
@@ -23,6 +25,19 @@ struct TmQuantMode {
     uint64_t *kmin = nullptr, *R = nullptr, *prefix = nullptr, *below = nullptr, *d_ranks = nullptr;
     long long *cnt = nullptr;            // as tamcmc_summary::d_cnt, for the samples of the pass under way
     uint32_t *u = nullptr, *flag = nullptr;
+    int parity = 0;
+};
+
+// LOO mode: the top sets and the body sums of the pass on the device, and what the host remembers of the fold pass.
+struct TmLooMode {
+    bool on = false;
+    int cap = 0;                         // M + 1 heap slots per bin
+    long long n_used = 0, n_rejected = 0;   // of the fold pass, frozen by _begin
+    double *d_heap = nullptr;            // [cap][Nx]
+    char *d_state = nullptr;             // one allocation: body[3][Nx] | elpd | khat | cutoff | cnt[2][2] | tail_len
+    double *body = nullptr, *elpd = nullptr, *khat = nullptr, *cutoff = nullptr;
+    long long *cnt = nullptr;            // as tamcmc_summary::d_cnt, for the samples of the pass under way
+    int32_t *tail_len = nullptr;
     int parity = 0;
 };
 
@@ -46,6 +61,7 @@ struct tamcmc_summary {
     bool profile = false;
     TmTimer timer;
     TmQuantMode q;
+    TmLooMode loo;
 };
 
 static size_t summary_stage_out(const tamcmc_summary *s) { return (size_t)s->B * (size_t)s->c->L.Nparams * sizeof(double); }
@@ -103,6 +119,49 @@ static void quantile_free(tamcmc_summary *s)
     s->q = TmQuantMode();
 }
 
+static TmLooArgs loo_args(const tamcmc_summary *s)
+{
+    const TmLooMode &m = s->loo;
+    const tamcmc_ctx *c = s->c;
+    TmLooArgs a{};
+    a.rows = s->d_model; a.y = c->d_y; a.isig2 = c->d_isig2; a.heap = m.d_heap; a.body = m.body;
+    a.cnt_in = m.cnt + 2 * m.parity; a.cnt_out = m.cnt + 2 * (m.parity ^ 1);
+    a.elpd = m.elpd; a.khat = m.khat; a.cutoff = m.cutoff; a.tail_len = m.tail_len;
+    a.Nx = c->L.Nx; a.likelihood_case = c->L.likelihood_case; a.cap = m.cap; a.like_p = c->L.like_p;
+    return a;
+}
+
+// stage 2 of a block in LOO mode: the tail kernel in the fold kernel's place
+static int loo_block(tamcmc_summary *s, int n, const int32_t *d_status)
+{
+    tamcmc_ctx *c = s->c;
+    TmLooArgs a = loo_args(s);
+    a.status = d_status; a.B = n;
+    int rc = TAMCMC_OK;
+    if (s->profile) { rc = s->timer.begin(c->stream); if (rc != TAMCMC_OK) return rc; }
+    const int hr = tm_launch_loo_tail(a, c->stream);
+    if (hr != 0) return tm_launch_failed("summary loo tail", hr);
+    s->loo.parity ^= 1;
+    return s->profile ? s->timer.end(c->stream) : TAMCMC_OK;
+}
+
+// a pass starts from empty counts and empty body sums (with no sample counted the heap holds nothing)
+static int loo_pass_clear(tamcmc_summary *s)
+{
+    TmLooMode &m = s->loo;
+    TM_HIP(hipMemsetAsync(m.cnt, 0, 4 * sizeof(long long), s->c->stream));
+    TM_HIP(hipMemsetAsync(m.body, 0, 3 * (size_t)s->c->L.Nx * sizeof(double), s->c->stream));
+    m.parity = 0;
+    return TAMCMC_OK;
+}
+
+// the stream must be idle
+static void loo_free(tamcmc_summary *s)
+{
+    (void)hipFree(s->loo.d_state); (void)hipFree(s->loo.d_heap);
+    s->loo = TmLooMode();
+}
+
 // One block of n <= B samples, device pointers, enqueued on the context's stream.
 static int summary_block(tamcmc_summary *s, int n, const double *d_params, double *d_logL, int32_t *d_status)
 {
@@ -114,6 +173,7 @@ static int summary_block(tamcmc_summary *s, int n, const double *d_params, doubl
     rc = tm_enqueue(c, n, d_params, s->d_T, d_logL, nullptr, d_status, s->d_rows, s->d_model);
     if (rc != TAMCMC_OK) return rc;
     if (s->q.on) return quantile_block(s, n, d_status);
+    if (s->loo.on) return loo_block(s, n, d_status);
     TmSummaryArgs a{};
     a.rows = s->d_model; a.status = d_status; a.y = c->d_y; a.isig2 = c->d_isig2; a.state = s->d_state;
     a.cnt_in = s->d_cnt + 2 * s->parity; a.cnt_out = s->d_cnt + 2 * (s->parity ^ 1);
@@ -183,6 +243,7 @@ extern "C" int tamcmc_summary_destroy(tamcmc_summary *s)
     if (c->stream) (void)tm_ctx_stream_sync(c);
     if (s->counted) c->summaries--;
     quantile_free(s);
+    loo_free(s);
     (void)hipFree(s->d_model); (void)hipFree(s->d_state); (void)hipFree(s->d_cnt); (void)hipFree(s->d_rows);
     (void)hipFree(s->d_T); (void)hipFree(s->d_logL); (void)hipFree(s->d_status);
     for (int p = 0; p < 2; p++) {
@@ -199,9 +260,10 @@ extern "C" int tamcmc_summary_reset(tamcmc_summary *s)
     if (!s || s->c->in_flight || s->c->armed) return TAMCMC_E_INVALID;
     tamcmc_ctx *c = s->c;
     TM_HIP(hipSetDevice(c->device));
-    if (s->q.on) {                                  // reset leaves quantile mode
+    if (s->q.on || s->loo.on) {                     // reset leaves quantile mode and LOO mode
         TM_HIP(tm_ctx_stream_sync(c));
         quantile_free(s);
+        loo_free(s);
     }
     TM_HIP(tm_ctx_settle(c));
     c->enq_seq++;
@@ -341,7 +403,7 @@ extern "C" int tamcmc_summary_quantiles_begin(tamcmc_summary *s, int32_t Nq, con
 {
     if (!s || !q || Nq < 1 || Nq > TAMCMC_SUMMARY_MAX_QUANTILES || bits_per_pass < 0 || bits_per_pass > TM_Q_MAXBITS) return TAMCMC_E_INVALID;
     tamcmc_ctx *c = s->c;
-    if (s->q.on || c->in_flight || c->armed) return TAMCMC_E_INVALID;
+    if (s->q.on || s->loo.on || c->in_flight || c->armed) return TAMCMC_E_INVALID;
     for (int j = 0; j < Nq; j++)
         if (!(q[j] >= 0.0 && q[j] <= 1.0)) return TAMCMC_E_INVALID;        // (a NaN fails both comparisons)
     TM_HIP(hipSetDevice(c->device));
@@ -459,5 +521,107 @@ extern "C" int tamcmc_summary_quantiles_end(tamcmc_summary *s)
     TM_HIP(hipSetDevice(s->c->device));
     TM_HIP(tm_ctx_stream_sync(s->c));
     quantile_free(s);
+    return TAMCMC_OK;
+}
+
+// ---- PSIS-LOO (tamcmc_loo.h) ----
+
+extern "C" int tamcmc_summary_loo_begin(tamcmc_summary *s)
+{
+    if (!s) return TAMCMC_E_INVALID;
+    tamcmc_ctx *c = s->c;
+    if (s->q.on || s->loo.on || c->in_flight || c->armed) return TAMCMC_E_INVALID;
+    TM_HIP(hipSetDevice(c->device));
+    TM_HIP(tm_ctx_stream_sync(c));
+    long long cnt[2] = {0, 0};
+    TM_HIP(hipMemcpy(cnt, s->d_cnt + 2 * s->parity, sizeof(cnt), hipMemcpyDeviceToHost));
+    if (cnt[0] < 1) return TAMCMC_E_INVALID;
+    const int64_t M = tml_tail_M((int64_t)cnt[0]);
+    if (M > TAMCMC_SUMMARY_LOO_MAX_TAIL) return TAMCMC_E_INVALID;       // thin the chain
+    TmLooMode m;
+    m.cap = (int)M + 1;
+    m.n_used = cnt[0]; m.n_rejected = cnt[1];
+    const size_t nx = (size_t)c->L.Nx;
+    const size_t state_bytes = 6 * nx * sizeof(double) + 4 * sizeof(long long) + nx * sizeof(int32_t);
+    if (hipMalloc(&m.d_state, state_bytes) != hipSuccess) { (void)hipGetLastError(); return TAMCMC_E_NOMEM; }
+    if (hipMalloc(&m.d_heap, (size_t)m.cap * nx * sizeof(double)) != hipSuccess) { (void)hipGetLastError(); (void)hipFree(m.d_state); return TAMCMC_E_NOMEM; }
+    m.body = reinterpret_cast<double *>(m.d_state);
+    m.elpd = m.body + 3 * nx;
+    m.khat = m.elpd + nx;
+    m.cutoff = m.khat + nx;
+    m.cnt = reinterpret_cast<long long *>(m.cutoff + nx);
+    m.tail_len = reinterpret_cast<int32_t *>(m.cnt + 4);
+    m.on = true;
+    s->loo = m;
+    c->enq_seq++;
+    if (loo_pass_clear(s) != TAMCMC_OK) { (void)hipStreamSynchronize(c->stream); loo_free(s); return TAMCMC_E_HIP; }
+    return TAMCMC_OK;
+}
+
+extern "C" int tamcmc_summary_loo_result(tamcmc_summary *s, tamcmc_summary_loo_totals *totals, double *elpd_loo, double *pareto_k,
+                                         double *cutoff, int32_t *tail_len)
+{
+    if (!s || !s->loo.on || s->c->in_flight || s->c->armed) return TAMCMC_E_INVALID;
+    tamcmc_ctx *c = s->c;
+    TmLooMode &m = s->loo;
+    TM_HIP(hipSetDevice(c->device));
+    TM_HIP(tm_ctx_stream_sync(c));
+    c->enq_seq++;
+    long long cnt[2] = {0, 0};
+    TM_HIP(hipMemcpy(cnt, m.cnt + 2 * m.parity, sizeof(cnt), hipMemcpyDeviceToHost));
+    if (cnt[0] != m.n_used || cnt[1] != m.n_rejected) {                 // not the fold pass's samples: the pass is discarded
+        const int rc = loo_pass_clear(s);
+        return rc != TAMCMC_OK ? rc : TAMCMC_E_INVALID;
+    }
+    const size_t nx = (size_t)c->L.Nx;
+    std::vector<double> out, lse;
+    std::vector<int32_t> tl;
+    try { out.resize(3 * nx); lse.resize(2 * nx); tl.resize(nx); } catch (const std::bad_alloc &) { return TAMCMC_E_NOMEM; }
+    TmLooArgs a = loo_args(s);
+    a.n = m.n_used;
+    int rc = TAMCMC_OK;
+    if (s->profile) { rc = s->timer.begin(c->stream); if (rc != TAMCMC_OK) return rc; }
+    const int hr = tm_launch_loo_finalize(a, c->stream);
+    if (hr != 0) return tm_launch_failed("summary loo finalize", hr);
+    if (s->profile) { rc = s->timer.end(c->stream); if (rc != TAMCMC_OK) return rc; }
+    TM_HIP(hipMemcpyAsync(out.data(), m.elpd, 3 * nx * sizeof(double), hipMemcpyDeviceToHost, c->stream));      // elpd | khat | cutoff
+    TM_HIP(hipMemcpyAsync(tl.data(), m.tail_len, nx * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    TM_HIP(hipMemcpyAsync(lse.data(), s->d_state + (size_t)TM_SUM_LSE_A * nx, 2 * nx * sizeof(double), hipMemcpyDeviceToHost, c->stream));   // a | r
+    TM_HIP(hipStreamSynchronize(c->stream));
+    const double dn = (double)m.n_used;
+    long double lppd_total = 0.0L, elpd_total = 0.0L;
+    double k_max = std::nan("");
+    int64_t n_high = 0, n_inf = 0;
+    for (size_t i = 0; i < nx; i++) {
+        const double k = out[nx + i];
+        lppd_total += (long double)(lse[i] + std::log(lse[nx + i] / dn));     // as tamcmc_summary_result, in bin order
+        elpd_total += (long double)out[i];
+        if (!(k <= k_max)) k_max = std::isnan(k) ? k_max : k;                 // (a NaN k-hat is never the maximum)
+        if (k > 0.7) n_high++;
+        if (std::isinf(k) && k > 0.0) n_inf++;
+    }
+    if (elpd_loo) std::memcpy(elpd_loo, out.data(), nx * sizeof(double));
+    if (pareto_k) std::memcpy(pareto_k, out.data() + nx, nx * sizeof(double));
+    if (cutoff) std::memcpy(cutoff, out.data() + 2 * nx, nx * sizeof(double));
+    if (tail_len) std::memcpy(tail_len, tl.data(), nx * sizeof(int32_t));
+    if (totals) {
+        totals->n_used = m.n_used;
+        totals->n_rejected = m.n_rejected;
+        totals->elpd_loo = (double)elpd_total;
+        totals->p_loo = (double)(lppd_total - elpd_total);
+        totals->looic = (double)(-2.0L * elpd_total);
+        totals->k_max = k_max;
+        totals->n_k_high = n_high;
+        totals->n_k_inf = n_inf;
+    }
+    return TAMCMC_OK;
+}
+
+extern "C" int tamcmc_summary_loo_end(tamcmc_summary *s)
+{
+    if (!s || !s->loo.on || s->c->in_flight || s->c->armed) return TAMCMC_E_INVALID;
+    TM_HIP(hipSetDevice(s->c->device));
+    TM_HIP(tm_ctx_stream_sync(s->c));
+    loo_free(s);
     return TAMCMC_OK;
 }

@@ -1,0 +1,73 @@
+"""PSIS-LOO of a stored chain (tamcmc_summary_loo_*, include/tamcmc_accel.h), the part that needs no GPU: the symbols exist
+with the declared prototypes, a NULL handle is refused before any device is touched, the command-line tool knows the option,
+and the per-bin arithmetic (tamcmc_loo.h, shared by the kernels) -- the rule for M, the top-(M+1) structure, the Pareto
+fit, the smoothed tail and elpd_loo -- agrees on the CPU with a sort and with a long-double transcription of the definition
+(tests/cpp/loo_core_check.cpp, plain g++)."""
+import ctypes as C
+import os
+import re
+import subprocess
+
+import numpy as np
+
+from test_summary_host import prototypes, tool
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+NAMES = ["tamcmc_summary_loo_begin", "tamcmc_summary_loo_result", "tamcmc_summary_loo_end"]
+
+
+def test_symbols_and_signatures(accel_mod):
+    lib = accel_mod.load_library()
+    protos, txt = prototypes()
+    for n in NAMES:
+        assert hasattr(lib, n) and n in accel_mod.capi.EXPORTS, n
+    assert protos["tamcmc_summary_loo_begin"] == ["tamcmc_summary*"]
+    assert protos["tamcmc_summary_loo_result"] == ["tamcmc_summary*", "tamcmc_summary_loo_totals*", "double*", "double*", "double*", "int32_t*"]
+    assert protos["tamcmc_summary_loo_end"] == ["tamcmc_summary*"]
+    assert "#define TAMCMC_SUMMARY_LOO_MAX_TAIL 2048" in txt and accel_mod.capi.Summary.LOO_MAX_TAIL == 2048
+    m = re.search(r"typedef struct \{([^}]*)\}\s*tamcmc_summary_loo_totals;", txt)
+    assert m and " ".join(m.group(1).split()) == \
+        "int64_t n_used, n_rejected; double elpd_loo, p_loo, looic, k_max; int64_t n_k_high, n_k_inf;"
+    t = accel_mod.capi.SummaryLooTotals
+    assert [f[0] for f in t._fields_] == ["n_used", "n_rejected", "elpd_loo", "p_loo", "looic", "k_max", "n_k_high", "n_k_inf"]
+    assert C.sizeof(t) == 64
+    for meth in ("loo_begin", "loo_result", "loo_end", "loo"):
+        assert callable(getattr(accel_mod.Summary, meth))
+    # what the earlier modes expose stays as it is
+    assert accel_mod.Summary.ARRAYS == ("mean_M", "var_M", "min_M", "max_M", "mean_l", "var_l", "lppd")
+    assert C.sizeof(accel_mod.capi.SummaryTotals) == 40
+
+
+def test_null_handle_is_refused_without_a_device(accel_mod):
+    lib = accel_mod.load_library()
+    E = accel_mod.capi.E_INVALID
+    x = np.full(8, 7.0)
+    xp = x.ctypes.data_as(C.POINTER(C.c_double))
+    tl = np.full(8, 7, dtype=np.int32)
+    t = accel_mod.capi.SummaryLooTotals()
+    assert lib.tamcmc_summary_loo_begin(None) == E
+    assert lib.tamcmc_summary_loo_result(None, C.byref(t), xp, xp, xp, tl.ctypes.data_as(C.POINTER(C.c_int32))) == E
+    assert np.all(x == 7.0) and np.all(tl == 7)
+    assert lib.tamcmc_summary_loo_result(None, None, None, None, None, None) == E
+    assert lib.tamcmc_summary_loo_end(None) == E
+
+
+def test_tool_knows_the_option():
+    exe = tool()
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=60)
+    assert r.returncode != 0 and "--loo" in r.stderr and "pareto_k" in r.stderr and r.stdout == ""
+    r = subprocess.run([exe, "a", "b", "c", "d", "e", "--loo", "--thin"], capture_output=True, text=True, timeout=60)
+    assert r.returncode != 0 and "Usage: chainsummary_hip" in r.stderr
+    r = subprocess.run([exe, "a", "b", "c", "d", "e", "--loo"], capture_output=True, text=True, timeout=60)
+    assert r.returncode != 0 and "Usage" not in r.stderr and "cannot read the default configuration" in r.stderr      # the option is taken
+
+
+def test_core_arithmetic_against_a_sort_and_the_definition(tmp_path):
+    """The header compiles as plain C++17 under g++: M for n = 1 ... 30, 70 001, 466 033 and 466 034; columns of 1 ... 300
+    values (random, ties, +-0, descending, ascending) against a sort; steps 3-4 with one lane against long double."""
+    exe = str(tmp_path / "loo_core_check")
+    r = subprocess.run(["g++", "-std=c++17", "-O1", "-I", os.path.join(ROOT, "tamcmc-c-_amd", "csrc"),
+                        os.path.join(ROOT, "tests", "cpp", "loo_core_check.cpp"), "-o", exe], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stderr[-3000:]
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0 and r.stdout.startswith("ok loo_core_check") and r.stdout.count("\n") == 1, (r.stdout, r.stderr[-3000:])

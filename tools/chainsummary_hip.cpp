@@ -3,7 +3,7 @@
 //
 //   chainsummary_hip <config dir> <model file> <data file> <params root> <output file>
 //                    [--chain m] [--slice s] [--first i] [--last j] [--thin k] [--block B]
-//                    [--quantiles q1,q2,...] [--qbits b]
+//                    [--quantiles q1,q2,...] [--qbits b] [--loo]
 //
 // <config dir> is the reference's Config/default; model id, likelihood, p, plength, the inputs row and the relax mask
 // come from the setup it describes (tamcmc_setup_create / tamcmc_setup_load, slice s counted from 0).  The samples are
@@ -17,6 +17,9 @@
 // selection (tamcmc_summary_quantiles_*; b bits per pass, 0: the library's default), the header gains a line
 // `# quantiles= q1,q2,...  passes= N`, and one column per quantile follows var_l: the order statistic of the model in that
 // bin, numpy's "inverted_cdf".
+// With --loo the selected samples are read once more for PSIS-LOO (tamcmc_summary_loo_*), the header gains a line
+// `# elpd_loo= ...  p_loo= ...  looic= ...  k_max= ...  n_k_high= ...  n_k_inf= ...`, and two last columns follow:
+// elpd_loo and pareto_k, the bin's leave-one-out log predictive density and its Pareto k-hat (above 0.7: not to be trusted).
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -32,16 +35,18 @@ static int usage()
 {
     fprintf(stderr, " Usage: chainsummary_hip <config dir> <model file> <data file> <params root> <output file>\n"
                     "                         [--chain m] [--slice s] [--first i] [--last j] [--thin k] [--block B]\n"
-                    "                         [--quantiles q1,q2,...] [--qbits b]\n"
+                    "                         [--quantiles q1,q2,...] [--qbits b] [--loo]\n"
                     "     [1] The directory of config_default.cfg, errors_default.cfg and the *_ctrl.list files (Config/default)\n"
                     "     [2] The .model file and [3] the .data file of the fit\n"
                     "     [4] The root of the parameter files: <root>_chain-<m>.bin and <root>.hdr\n"
-                    "     [5] The output file (ASCII): x y mean_M sd_M min_M max_M lppd var_l [one column per quantile]\n"
+                    "     [5] The output file (ASCII): x y mean_M sd_M min_M max_M lppd var_l [one column per quantile] [elpd_loo pareto_k]\n"
                     "     --chain m   chain to read (default 0, the coldest)     --slice s   slice of the .model file, from 0 (default 0)\n"
                     "     --first i / --last j / --thin k   samples i, i + k, ... <= j, counted from 0 (default: all)\n"
                     "     --block B   samples per block on the GPU (default 0: chosen by the library)\n"
                     "     --quantiles q1,q2,...   up to 8 values in [0, 1]: one more column each, the exact quantile of the model per bin\n"
                     "                             (the samples are read again once per pass)     --qbits b   bits per pass, 1 ... 6 (default 0: the library's)\n"
+                    "     --loo   PSIS-LOO: two last columns, elpd_loo and the Pareto k-hat per bin, and their totals in the header\n"
+                    "             (the samples are read once more)\n"
                     " chainsummary_hip version   prints the library version\n");
     return EXIT_FAILURE;
 }
@@ -78,8 +83,10 @@ int main(int argc, char *argv[])
     long chain = 0, slice = 0, first = 0, last = -1, thin = 1, block = 0, qbits = 0;
     std::vector<double> quant;
     std::string quant_text;
+    bool loo = false;
     for (int i = 6; i < argc; i++) {
         const std::string a = argv[i];
+        if (a == "--loo") { loo = true; continue; }
         if (a == "--quantiles") {                   // a comma-separated list of numbers in [0, 1]
             if (i + 1 >= argc || !quant.empty()) return usage();
             quant_text = argv[++i];
@@ -185,6 +192,18 @@ int main(int argc, char *argv[])
         if (rc != TAMCMC_OK) return qfail("tamcmc_summary_quantiles_result");
         tamcmc_summary_quantiles_end(sum);
     }
+    // PSIS-LOO: the same samples once more
+    tamcmc_summary_loo_totals lt{};
+    std::vector<double> elpd(loo ? (size_t)Nx : 0), khat(loo ? (size_t)Nx : 0);
+    if (loo) {
+        auto lfail = [&](const char *what) { return fail(std::string(what) + ": " + tamcmc_strerror(rc) + " " + tamcmc_last_hip_error()); };
+        rc = tamcmc_summary_loo_begin(sum);
+        if (rc != TAMCMC_OK) return lfail("tamcmc_summary_loo_begin");
+        if (push_selected() != 0) return EXIT_FAILURE;
+        rc = tamcmc_summary_loo_result(sum, &lt, elpd.data(), khat.data(), nullptr, nullptr);
+        if (rc != TAMCMC_OK) return lfail("tamcmc_summary_loo_result");
+        tamcmc_summary_loo_end(sum);
+    }
     tamcmc_summary_destroy(sum);
     tamcmc_ctx_destroy(ctx);
 
@@ -196,13 +215,17 @@ int main(int argc, char *argv[])
     fprintf(o, "# n_used= %lld  n_rejected= %lld\n", (long long)t.n_used, (long long)t.n_rejected);
     fprintf(o, "# lppd_total= %.12g  p_waic= %.12g  waic= %.12g\n", t.lppd_total, t.p_waic, t.waic);
     if (Nq) fprintf(o, "# quantiles= %s  passes= %d\n", quant_text.c_str(), passes);
+    if (loo) fprintf(o, "# elpd_loo= %.12g  p_loo= %.12g  looic= %.12g  k_max= %.12g  n_k_high= %lld  n_k_inf= %lld\n", lt.elpd_loo, lt.p_loo, lt.looic,
+                     lt.k_max, (long long)lt.n_k_high, (long long)lt.n_k_inf);
     fprintf(o, "# x y mean_M sd_M min_M max_M lppd var_l");
     for (size_t j = 0; j < Nq; j++) fprintf(o, " q%.6g", quant[j]);
+    if (loo) fprintf(o, " elpd_loo pareto_k");
     fprintf(o, "\n");
     for (int64_t i = 0; i < Nx; i++) {
         fprintf(o, "%.12g %.12g %.12g %.12g %.12g %.12g %.12g %.12g", x[i], y[i], mean_M[i], std::sqrt(var_M[i]), min_M[i], max_M[i],
                 lppd[i], var_l[i]);
         for (size_t j = 0; j < Nq; j++) fprintf(o, " %.12g", qlo[j * (size_t)Nx + (size_t)i]);
+        if (loo) fprintf(o, " %.12g %.12g", elpd[(size_t)i], khat[(size_t)i]);
         fprintf(o, "\n");
     }
     fclose(o);

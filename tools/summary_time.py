@@ -12,6 +12,9 @@ Prints one JSON line:
   d_quantile_*              quantile mode (Summary.quantiles_*) at --quantiles quantiles and --qbits bits per pass, after leg
                             (a)'s fold pass: seconds per pass per 1000 samples through Summary.push (the step included), the
                             histogram kernel alone from the same HIP-event hooks, and the number of passes to exactness
+  e_loo_*                   LOO mode (Summary.loo_*) after a fold pass of the same rows: the tail pass in seconds per 1000
+                            samples through Summary.push, the tail kernel alone per block and the finalize kernel alone,
+                            once, from the same HIP-event hooks, M, and the device memory the mode allocates
 Every timed shape is warmed up first (--warmup pushes); host clocks stop after calls that end in a device synchronise.
 """
 import argparse
@@ -128,6 +131,42 @@ def main():
                        d_quantile_total_s_per_1000=float(np.sum(pass_times)) * 1000.0 / a.samples,
                        d_quantile_hist_us_per_block=ms * 1e3 / launches, d_quantile_hist_s_per_1000=ms * 1e-3 * 1000.0 / a.samples,
                        d_quantile_hist_bytes=len(q) * (1 << (a.qbits or 6)) * a.nx * 4)
+            # (e) LOO mode: the same rows once more, then the finalize kernel
+            s.reset()
+            s.push(P)
+            tail_times = []
+            for k in range(a.warmup + a.steps):             # every pass in a mode of its own: begin, push, (result,) end
+                s.loo_begin()
+                acc.synchronize()
+                t0 = time.perf_counter()
+                s.push(P)
+                if k >= a.warmup:
+                    tail_times.append(time.perf_counter() - t0)
+                if k + 1 < a.warmup + a.steps:
+                    s.loo_end()
+            acc.synchronize()
+            t0 = time.perf_counter()
+            loo = s.loo_result()
+            t_result = time.perf_counter() - t0
+            s.profile(True)                                 # the finalize kernel alone: a second result without another pass
+            s.loo_result()
+            fin_ms, fin_launches = s.kernel_time()
+            s.profile(False)
+            s.loo_end()
+            s.loo_begin()                                   # the tail kernel alone, over one pass
+            s.profile(True)
+            s.push(P)
+            ms, launches = s.kernel_time()
+            s.profile(False)
+            s.loo_end()
+            M = int(np.ceil(min(res["n_used"] / 5.0, 3.0 * np.sqrt(float(res["n_used"])))))
+            out.update(e_loo_M=M, e_loo_tail_s_per_1000=float(np.median(tail_times)) * 1000.0 / a.samples,
+                       e_loo_tail_spread=[float(min(tail_times)) * 1000.0 / a.samples, float(max(tail_times)) * 1000.0 / a.samples],
+                       e_loo_tail_us_per_block=ms * 1e3 / launches, e_loo_tail_kernel_s_per_1000=ms * 1e-3 * 1000.0 / a.samples,
+                       e_loo_result_s=t_result, e_loo_finalize_ms=fin_ms / max(fin_launches, 1),
+                       e_loo_bytes=(M + 1) * a.nx * 8 + 52 * a.nx + 32,
+                       e_loo_k_max=loo["k_max"], e_loo_n_k_high=loo["n_k_high"], e_loo_n_k_inf=loo["n_k_inf"],
+                       e_loo_elpd=loo["elpd_loo_total"], e_loo_p_loo=loo["p_loo"], e_p_waic=res["p_waic"])
         # (b) the host route, on fewer rows
         Pb = P[:a.samples_b]
         host_fold(acc, Pb[:64], y)
