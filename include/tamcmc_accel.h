@@ -273,7 +273,53 @@ int tamcmc_group_members(const tamcmc_group *g, int32_t *n_members, int32_t *Npa
  *   loo_end      frees the mode's memory and goes back to fold mode: the running statistics are untouched and further
  *                pushes fold as before.  tamcmc_summary_reset also leaves the mode; tamcmc_summary_destroy works in any.
  *                _result and _end outside the mode return TAMCMC_E_INVALID.
- *   profile / kernel_time in LOO mode: the tail kernel of every block, and the finalize kernel of every loo_result. */
+ *   profile / kernel_time in LOO mode: the tail kernel of every block, and the finalize kernel of every loo_result.
+ *
+ * POSTERIOR PREDICTIVE CHECK: is the residual spectrum distributed as the likelihood claims, and in which bins is it not?
+ * Per bin the predictive CDF of the datum averaged over the chain -- its probability integral transform (PIT) -- and both
+ * tail probabilities as logarithms, which stay meaningful far below 1e-300: a missed mode has y / M of a few thousand.
+ * (The classical residual is y / M at the best fit with the false-alarm probability exp(-y / M); this is its posterior
+ * version.)  Not a mode and no pass of its own: a setting of the object under which every fold-mode block runs one more
+ * kernel (tamcmc_predictive.hip) behind the fold kernel, on the same rows and the same stream.
+ *   Definition, per bin i, over the n = n_used accepted samples s, M = M_is:
+ *     chi(2,2p)    p = likelihood_p truncated as everywhere in this library, an integer in 1 ... 64.  Under the sample's
+ *                  model the datum is Gamma-distributed with shape p and scale M / p: with z = p y_i / M_is,
+ *                  P_is = P(p, z), the regularised lower incomplete gamma function, Q_is = Q(p, z) = exp(-z) sum_{k<p}
+ *                  z^k / k!, the upper one.  z <= 0 (y_i <= 0): P = 0, Q = 1.
+ *     chi_square   the library's l = -(y - M)^2 / sigma^2 is the logarithm of a Gaussian density with standard deviation
+ *                  sigma / sqrt(2), not sigma; the check takes the likelihood at its word: with r = (y_i - M_is) / sigma_i,
+ *                  P_is = erfc(-r) / 2 and Q_is = erfc(r) / 2.
+ *     log_cdf_i = log((1/n) sum_s P_is)        log_sf_i = log((1/n) sum_s Q_is)
+ *                  Both tails of a sample are computed as logarithms and directly, each by adding terms of one sign, never
+ *                  as 1 - the other where that cancels, for any finite z >= 0 and any |r| < 1.3e154 (tamcmc_predictive.h
+ *                  has the forms and their measured error: a few ulp of max(1, |value|) for p = 1 and chi_square, 2^-42
+ *                  for p > 1).  Each sum is a running-maximum log-sum-exp in push order by the fold kernel's recurrence,
+ *                  with four additions: a term of -inf adds nothing; a sum without a finite term is -inf; (-inf) -
+ *                  (-inf) is never formed; the sum is Kahan-compensated (a bin the model explains has log_cdf of order
+ *                  -1e-9, which n plain additions of terms near 1 would blur by n 2^-53).  So y_i = 0 gives log_cdf =
+ *                  -inf, log_sf = 0 and pit = 0 exactly.
+ *     mean_resid_i the mean (Welford) of y_i / M_is for chi(2,2p), of r for chi_square.
+ *     pit_i        from the smaller tail, on the host: exp(log_cdf) if log_cdf < log_sf, else -expm1(log_sf).
+ *     With n = 0 everything is NaN (and the two bins of the totals are -1).
+ *   Totals, on the host in long double and in bin order: n_used, n_rejected; ks_D = max_k max((k + 1) / Nx - u_k, u_k -
+ *   k / Nx) over the pit sorted ascending as u_0 <= ... <= u_{Nx-1}, the Kolmogorov distance from uniform; pit_hist, the
+ *   count of bins in cell min(19, floor(20 pit)); min_log_sf with its bin (the strongest unexplained excess) and
+ *   min_log_cdf with its bin (the strongest deficit), the first bin winning a tie.
+ *   predictive_enable   allowed only while the object holds no sample (fresh, or after tamcmc_summary_reset) and is in fold
+ *                mode.  Allocates 56 Nx bytes of state; TAMCMC_E_NOMEM when that fails, and the object stays as it was.
+ *                Refused with TAMCMC_E_INVALID: a chi(2,2p) context with p < 1 or p > TAMCMC_SUMMARY_PREDICTIVE_MAX_P, a
+ *                second call, samples already pushed, quantile or LOO mode, a context with a batch armed or in flight.
+ *                Stays on until tamcmc_summary_destroy; tamcmc_summary_reset clears the state and keeps the setting.
+ *   While enabled, the fold kernel runs unchanged -- every result of tamcmc_summary_result keeps its bits -- and passes
+ *   pushed in quantile mode or LOO mode do not touch the predictive state.  Every result is bit for bit independent of
+ *   block_chains and of how the samples are split over pushes.
+ *   predictive_result   synchronises the stream; may be called between pushes, in any mode and repeatedly, and disturbs
+ *                nothing.  totals and four arrays of Nx doubles on the host, any of them may be NULL.  TAMCMC_E_INVALID
+ *                when the check is not enabled, and (as tamcmc_summary_result) with a batch in flight or armed.
+ *   predictive_kernel_time   as tamcmc_summary_kernel_time, for the predictive kernel alone, under the same
+ *                tamcmc_summary_profile switch; tamcmc_summary_kernel_time keeps reporting the fold kernel alone.
+ *                Refused exactly as tamcmc_summary_kernel_time is (NULL arguments, a batch armed; a batch in flight is
+ *                not refused: its stream is waited for), and with TAMCMC_E_INVALID when the check is not enabled. */
 typedef struct tamcmc_summary tamcmc_summary;
 typedef struct {
     int64_t n_used, n_rejected;
@@ -306,6 +352,18 @@ int tamcmc_summary_loo_begin(tamcmc_summary *s);
 int tamcmc_summary_loo_result(tamcmc_summary *s, tamcmc_summary_loo_totals *totals,
                               double *elpd_loo, double *pareto_k, double *cutoff, int32_t *tail_len);
 int tamcmc_summary_loo_end(tamcmc_summary *s);
+#define TAMCMC_SUMMARY_PREDICTIVE_MAX_P 64
+#define TAMCMC_SUMMARY_PIT_CELLS 20
+typedef struct {
+    int64_t n_used, n_rejected;
+    double ks_D, min_log_sf, min_log_cdf;
+    int64_t bin_min_log_sf, bin_min_log_cdf;
+    int64_t pit_hist[TAMCMC_SUMMARY_PIT_CELLS];
+} tamcmc_summary_predictive_totals;
+int tamcmc_summary_predictive_enable(tamcmc_summary *s);
+int tamcmc_summary_predictive_result(tamcmc_summary *s, tamcmc_summary_predictive_totals *totals,
+                                     double *pit, double *log_cdf, double *log_sf, double *mean_resid);
+int tamcmc_summary_predictive_kernel_time(tamcmc_summary *s, double *total_ms, int64_t *launches);
 
 /* Replaces: the `for chain` loop of generate_model() calls (MALA.cpp:632-639, model_def.cpp:139-143).
  * Host pointers, row-major.  Synchronous: results are valid on return.

@@ -33,6 +33,7 @@ EXPORTS = [
     "tamcmc_summary_quantiles_begin", "tamcmc_summary_quantiles_step", "tamcmc_summary_quantiles_result",
     "tamcmc_summary_quantiles_end",
     "tamcmc_summary_loo_begin", "tamcmc_summary_loo_result", "tamcmc_summary_loo_end",
+    "tamcmc_summary_predictive_enable", "tamcmc_summary_predictive_result", "tamcmc_summary_predictive_kernel_time",
 ]
 
 
@@ -46,6 +47,16 @@ class SummaryLooTotals(C.Structure):
     """tamcmc_summary_loo_totals"""
     _fields_ = [("n_used", C.c_int64), ("n_rejected", C.c_int64), ("elpd_loo", C.c_double), ("p_loo", C.c_double),
                 ("looic", C.c_double), ("k_max", C.c_double), ("n_k_high", C.c_int64), ("n_k_inf", C.c_int64)]
+
+
+PIT_CELLS = 20          # TAMCMC_SUMMARY_PIT_CELLS
+
+
+class SummaryPredictiveTotals(C.Structure):
+    """tamcmc_summary_predictive_totals"""
+    _fields_ = [("n_used", C.c_int64), ("n_rejected", C.c_int64), ("ks_D", C.c_double), ("min_log_sf", C.c_double),
+                ("min_log_cdf", C.c_double), ("bin_min_log_sf", C.c_int64), ("bin_min_log_cdf", C.c_int64),
+                ("pit_hist", C.c_int64 * PIT_CELLS)]
 
 
 class AccelError(RuntimeError):
@@ -115,6 +126,9 @@ def load_library():
     lib.tamcmc_summary_loo_begin.argtypes = [vp]
     lib.tamcmc_summary_loo_result.argtypes = [vp, C.POINTER(SummaryLooTotals), dp, dp, dp, ip]
     lib.tamcmc_summary_loo_end.argtypes = [vp]
+    lib.tamcmc_summary_predictive_enable.argtypes = [vp]
+    lib.tamcmc_summary_predictive_result.argtypes = [vp, C.POINTER(SummaryPredictiveTotals), dp, dp, dp, dp]
+    lib.tamcmc_summary_predictive_kernel_time.argtypes = [vp, dp, C.POINTER(C.c_int64)]
     for name in EXPORTS:
         fn = getattr(lib, name)
         if fn.restype is not C.c_char_p:
@@ -423,15 +437,23 @@ class Summary:
     and of the pointwise log-likelihood over the parameter rows pushed so far, kept on the device.  Results do not depend,
     bit for bit, on block_chains or on how the rows are split over pushes.  quantiles() gives the exact per-bin quantiles
     of the model (credible bands) by pushing the same rows again a few times; loo() gives PSIS-LOO (elpd_loo and the
-    Pareto k-hat per bin) by pushing them once more.  The Accel cannot be closed while the summary is open."""
+    Pareto k-hat per bin) by pushing them once more.  With predictive=True every fold pass also accumulates the
+    posterior predictive check (predictive_result(): PIT and both log tail probabilities per bin).  The Accel cannot be
+    closed while the summary is open."""
 
     ARRAYS = ("mean_M", "var_M", "min_M", "max_M", "mean_l", "var_l", "lppd")
 
-    def __init__(self, accel, block_chains=0):
+    def __init__(self, accel, block_chains=0, predictive=False):
         self._lib = load_library()
         self.accel = accel
         self._s = C.c_void_p()
         self._check(self._lib.tamcmc_summary_create(C.byref(self._s), accel._ctx, int(block_chains)), "tamcmc_summary_create")
+        if predictive:
+            try:
+                self.predictive_enable()
+            except AccelError:
+                self.close()
+                raise
 
     _check = Accel._check
 
@@ -571,6 +593,36 @@ class Summary:
         finally:
             if getattr(self, "_loo", False):
                 self.loo_end()
+
+    # ---- posterior predictive check: PIT and both log tail probabilities per bin, beside every fold pass ----
+    PREDICTIVE_MAX_P = 64
+    PIT_CELLS = PIT_CELLS
+    PREDICTIVE_ARRAYS = ("pit", "log_cdf", "log_sf", "mean_resid")
+    PREDICTIVE_TOTALS = ("n_used", "n_rejected", "ks_D", "min_log_sf", "min_log_cdf", "bin_min_log_sf", "bin_min_log_cdf")
+
+    def predictive_enable(self):
+        """Turns the check on for the life of the object; allowed only while it holds no sample and is in fold mode."""
+        self._check(self._lib.tamcmc_summary_predictive_enable(self._s), "tamcmc_summary_predictive_enable")
+
+    def predictive_result(self):
+        """dict: pit, log_cdf, log_sf, mean_resid (Nx doubles), pit_hist (20 int64) and the totals n_used, n_rejected,
+        ks_D, min_log_sf, min_log_cdf, bin_min_log_sf, bin_min_log_cdf."""
+        out = {k: np.empty(self.accel.Nx) for k in self.PREDICTIVE_ARRAYS}
+        t = SummaryPredictiveTotals()
+        self._check(self._lib.tamcmc_summary_predictive_result(self._s, C.byref(t), *[_dptr(out[k]) for k in self.PREDICTIVE_ARRAYS]),
+                    "tamcmc_summary_predictive_result")
+        out.update(n_used=int(t.n_used), n_rejected=int(t.n_rejected), ks_D=t.ks_D, min_log_sf=t.min_log_sf, min_log_cdf=t.min_log_cdf,
+                   bin_min_log_sf=int(t.bin_min_log_sf), bin_min_log_cdf=int(t.bin_min_log_cdf),
+                   pit_hist=np.array(list(t.pit_hist), dtype=np.int64))
+        return out
+
+    def predictive_kernel_time(self):
+        """(summed milliseconds, launches) of the predictive kernel since profile(True); kernel_time() stays the fold kernel's."""
+        ms = C.c_double(0.0)
+        n = C.c_int64(0)
+        self._check(self._lib.tamcmc_summary_predictive_kernel_time(self._s, C.byref(ms), C.byref(n)),
+                    "tamcmc_summary_predictive_kernel_time")
+        return ms.value, n.value
 
     def close(self):
         if getattr(self, "_s", None) is not None and self._s.value:

@@ -3,12 +3,16 @@
 // context's own launches (tamcmc_host.h: tm_enqueue) with a row map covering every chain (stage 1) +
 // tamcmc_summary_fold_kernel (stage 2), both on the context's stream.  While the object selects quantiles
 // (tamcmc_summary_quantiles_*, tamcmc_quantile.h) stage 2 is the histogram kernel instead and the fold state is frozen;
-// in LOO mode (tamcmc_summary_loo_*, tamcmc_loo.h) it is the tail kernel.
+// in LOO mode (tamcmc_summary_loo_*, tamcmc_loo.h) it is the tail kernel.  With the predictive check enabled
+// (tamcmc_summary_predictive_*, tamcmc_predictive.h) a fold-mode block has a stage 3: tamcmc_summary_predictive_kernel on
+// the same rows; the other two modes never touch its state.
+#include <algorithm>
 #include <cmath>
 #include <new>
 
 #include "tamcmc_host.h"
 #include "tamcmc_loo.h"
+#include "tamcmc_predictive.h"
 #include "tamcmc_quantile.h"
 #include "tamcmc_summary.h"
 
@@ -41,6 +45,15 @@ struct TmLooMode {
     int parity = 0;
 };
 
+// The predictive check: a setting of the object (on from _enable until destroy), not a mode.
+struct TmPredictive {
+    bool on = false;
+    double *d_state = nullptr;           // [TM_PRED_NSTATE][Nx]
+    int p = 1, nterms = 0;               // chi(2,2p): (int)like_p and tmp_series_terms(p)
+    double lf_pm1 = 0.0, lf_p = 0.0;     // log (p-1)!, log p!
+    TmTimer timer;                       // the predictive kernel alone (tamcmc_summary_predictive_kernel_time)
+};
+
 struct tamcmc_summary {
     tamcmc_ctx *c = nullptr;
     int B = 0;                           // samples per block
@@ -62,6 +75,7 @@ struct tamcmc_summary {
     TmTimer timer;
     TmQuantMode q;
     TmLooMode loo;
+    TmPredictive pred;
 };
 
 static size_t summary_stage_out(const tamcmc_summary *s) { return (size_t)s->B * (size_t)s->c->L.Nparams * sizeof(double); }
@@ -182,12 +196,24 @@ static int summary_block(tamcmc_summary *s, int n, const double *d_params, doubl
     const int hr = tm_launch_summary_fold(a, c->stream);
     if (hr != 0) return tm_launch_failed("summary fold", hr);
     s->parity ^= 1;
-    return s->profile ? s->timer.end(c->stream) : TAMCMC_OK;
+    if (s->profile) { rc = s->timer.end(c->stream); if (rc != TAMCMC_OK) return rc; }
+    if (!s->pred.on) return TAMCMC_OK;
+    // stage 3: the predictive kernel on the same rows, counting on from the pair the fold launch read
+    TmPredArgs pa{};
+    pa.rows = s->d_model; pa.status = d_status; pa.y = c->d_y; pa.isig2 = c->d_isig2; pa.state = s->pred.d_state;
+    pa.cnt_in = a.cnt_in;
+    pa.Nx = c->L.Nx; pa.B = n; pa.likelihood_case = c->L.likelihood_case; pa.p = s->pred.p; pa.nterms = s->pred.nterms;
+    pa.lf_pm1 = s->pred.lf_pm1; pa.lf_p = s->pred.lf_p;
+    if (s->profile) { rc = s->pred.timer.begin(c->stream); if (rc != TAMCMC_OK) return rc; }
+    const int pr = tm_launch_predictive(pa, c->stream);
+    if (pr != 0) return tm_launch_failed("summary predictive", pr);
+    return s->profile ? s->pred.timer.end(c->stream) : TAMCMC_OK;
 }
 
 static int summary_clear(tamcmc_summary *s)
 {
     const tamcmc_ctx *c = s->c;
+    if (s->pred.on) TM_HIP(hipMemsetAsync(s->pred.d_state, 0, (size_t)TM_PRED_NSTATE * (size_t)c->L.Nx * sizeof(double), c->stream));
     TM_HIP(hipMemsetAsync(s->d_state, 0, (size_t)TM_SUM_NSTATE * (size_t)c->L.Nx * sizeof(double), c->stream));
     TM_HIP(hipMemsetAsync(s->d_cnt, 0, 4 * sizeof(long long), c->stream));
     s->parity = 0;
@@ -245,12 +271,13 @@ extern "C" int tamcmc_summary_destroy(tamcmc_summary *s)
     quantile_free(s);
     loo_free(s);
     (void)hipFree(s->d_model); (void)hipFree(s->d_state); (void)hipFree(s->d_cnt); (void)hipFree(s->d_rows);
-    (void)hipFree(s->d_T); (void)hipFree(s->d_logL); (void)hipFree(s->d_status);
+    (void)hipFree(s->d_T); (void)hipFree(s->d_logL); (void)hipFree(s->d_status); (void)hipFree(s->pred.d_state);
     for (int p = 0; p < 2; p++) {
         s->stage[p].release();
         if (s->ev_stage[p]) (void)hipEventDestroy(s->ev_stage[p]);
     }
     s->timer.destroy();
+    s->pred.timer.destroy();
     delete s;
     return TAMCMC_OK;
 }
@@ -386,6 +413,7 @@ extern "C" int tamcmc_summary_profile(tamcmc_summary *s, int enable)
     TM_HIP(tm_ctx_stream_sync(s->c));
     s->profile = enable != 0;
     s->timer.used = 0;
+    s->pred.timer.used = 0;
     return TAMCMC_OK;
 }
 
@@ -624,4 +652,97 @@ extern "C" int tamcmc_summary_loo_end(tamcmc_summary *s)
     TM_HIP(tm_ctx_stream_sync(s->c));
     loo_free(s);
     return TAMCMC_OK;
+}
+
+// ---- posterior predictive check (tamcmc_predictive.h) ----
+
+extern "C" int tamcmc_summary_predictive_enable(tamcmc_summary *s)
+{
+    if (!s) return TAMCMC_E_INVALID;
+    tamcmc_ctx *c = s->c;
+    if (s->pred.on || s->q.on || s->loo.on || c->in_flight || c->armed) return TAMCMC_E_INVALID;
+    const bool chi = c->L.likelihood_case == 0;
+    if (chi && !(c->L.like_p >= 1.0 && c->L.like_p <= (double)TAMCMC_SUMMARY_PREDICTIVE_MAX_P)) return TAMCMC_E_INVALID;
+    TM_HIP(hipSetDevice(c->device));
+    TM_HIP(tm_ctx_stream_sync(c));
+    long long cnt[2] = {0, 0};
+    TM_HIP(hipMemcpy(cnt, s->d_cnt + 2 * s->parity, sizeof(cnt), hipMemcpyDeviceToHost));
+    if (cnt[0] != 0 || cnt[1] != 0) return TAMCMC_E_INVALID;            // the object holds samples: reset first
+    TmPredictive &m = s->pred;
+    const size_t bytes = (size_t)TM_PRED_NSTATE * (size_t)c->L.Nx * sizeof(double);
+    if (hipMalloc(&m.d_state, bytes) != hipSuccess) { (void)hipGetLastError(); m.d_state = nullptr; return TAMCMC_E_NOMEM; }
+    m.p = chi ? (int)c->L.like_p : 1;
+    m.nterms = tmp_series_terms(m.p);
+    m.lf_pm1 = tmp_log_factorial(m.p - 1);
+    m.lf_p = tmp_log_factorial(m.p);
+    c->enq_seq++;
+    if (hipMemsetAsync(m.d_state, 0, bytes, c->stream) != hipSuccess) {
+        (void)hipStreamSynchronize(c->stream);
+        (void)hipFree(m.d_state);
+        m.d_state = nullptr;
+        return TAMCMC_E_HIP;
+    }
+    m.on = true;
+    return TAMCMC_OK;
+}
+
+extern "C" int tamcmc_summary_predictive_result(tamcmc_summary *s, tamcmc_summary_predictive_totals *totals,
+                                                double *pit, double *log_cdf, double *log_sf, double *mean_resid)
+{
+    if (!s || !s->pred.on || s->c->in_flight || s->c->armed) return TAMCMC_E_INVALID;
+    tamcmc_ctx *c = s->c;
+    TM_HIP(hipSetDevice(c->device));
+    TM_HIP(tm_ctx_stream_sync(c));
+    const size_t nx = (size_t)c->L.Nx;
+    long long cnt[2] = {0, 0};
+    std::vector<double> st, u;
+    try { st.resize(TM_PRED_NSTATE * nx); u.reserve(nx); } catch (const std::bad_alloc &) { return TAMCMC_E_NOMEM; }
+    // the fold pass's counts: frozen copies while a mode is on (its passes do not touch the predictive state either)
+    if (s->q.on) { cnt[0] = s->q.n_used; cnt[1] = s->q.n_rejected; }
+    else if (s->loo.on) { cnt[0] = s->loo.n_used; cnt[1] = s->loo.n_rejected; }
+    else TM_HIP(hipMemcpy(cnt, s->d_cnt + 2 * s->parity, sizeof(cnt), hipMemcpyDeviceToHost));
+    TM_HIP(hipMemcpy(st.data(), s->pred.d_state, st.size() * sizeof(double), hipMemcpyDeviceToHost));
+    const long long n = cnt[0];
+    const double nan = std::nan("");
+    tamcmc_summary_predictive_totals t{};
+    t.n_used = n; t.n_rejected = cnt[1];
+    t.ks_D = nan; t.min_log_sf = nan; t.min_log_cdf = nan;
+    t.bin_min_log_sf = -1; t.bin_min_log_cdf = -1;
+    for (size_t i = 0; i < nx; i++) {
+        const double lc = tmp_lse_result(st[TM_PRED_CDF_A * nx + i], st[TM_PRED_CDF_R * nx + i], st[TM_PRED_CDF_C * nx + i], n);
+        const double ls = tmp_lse_result(st[TM_PRED_SF_A * nx + i], st[TM_PRED_SF_R * nx + i], st[TM_PRED_SF_C * nx + i], n);
+        const double pv = n >= 1 ? (lc < ls ? std::exp(lc) : -std::expm1(ls)) : nan;       // from the smaller tail
+        if (pit) pit[i] = pv;
+        if (log_cdf) log_cdf[i] = lc;
+        if (log_sf) log_sf[i] = ls;
+        if (mean_resid) mean_resid[i] = n >= 1 ? st[TM_PRED_MEAN_RESID * nx + i] : nan;
+        if (n < 1) continue;
+        if (t.bin_min_log_sf < 0 ? !std::isnan(ls) : ls < t.min_log_sf) { t.min_log_sf = ls; t.bin_min_log_sf = (int64_t)i; }      // the first bin wins a tie
+        if (t.bin_min_log_cdf < 0 ? !std::isnan(lc) : lc < t.min_log_cdf) { t.min_log_cdf = lc; t.bin_min_log_cdf = (int64_t)i; }
+        if (std::isnan(pv)) continue;
+        const int cell = (int)std::floor(20.0 * pv);
+        t.pit_hist[cell > TAMCMC_SUMMARY_PIT_CELLS - 1 ? TAMCMC_SUMMARY_PIT_CELLS - 1 : (cell < 0 ? 0 : cell)]++;
+        u.push_back(pv);
+    }
+    if (!u.empty()) {                   // Kolmogorov distance of the pit_i from uniform, in long double
+        std::sort(u.begin(), u.end());
+        const long double N = (long double)u.size();
+        long double D = 0.0L;
+        for (size_t k = 0; k < u.size(); k++) {
+            const long double up = (long double)(k + 1) / N - (long double)u[k], dn = (long double)u[k] - (long double)k / N;
+            D = up > D ? up : D;
+            D = dn > D ? dn : D;
+        }
+        t.ks_D = (double)D;
+    }
+    if (totals) *totals = t;
+    return TAMCMC_OK;
+}
+
+extern "C" int tamcmc_summary_predictive_kernel_time(tamcmc_summary *s, double *total_ms, int64_t *launches)
+{
+    if (!s || !total_ms || !launches || !s->pred.on || s->c->armed) return TAMCMC_E_INVALID;
+    TM_HIP(hipSetDevice(s->c->device));
+    TM_HIP(tm_ctx_stream_sync(s->c));
+    return s->pred.timer.total(total_ms, launches);
 }

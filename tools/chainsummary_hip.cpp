@@ -3,7 +3,7 @@
 //
 //   chainsummary_hip <config dir> <model file> <data file> <params root> <output file>
 //                    [--chain m] [--slice s] [--first i] [--last j] [--thin k] [--block B]
-//                    [--quantiles q1,q2,...] [--qbits b] [--loo]
+//                    [--quantiles q1,q2,...] [--qbits b] [--loo] [--predictive]
 //
 // <config dir> is the reference's Config/default; model id, likelihood, p, plength, the inputs row and the relax mask
 // come from the setup it describes (tamcmc_setup_create / tamcmc_setup_load, slice s counted from 0).  The samples are
@@ -18,8 +18,14 @@
 // `# quantiles= q1,q2,...  passes= N`, and one column per quantile follows var_l: the order statistic of the model in that
 // bin, numpy's "inverted_cdf".
 // With --loo the selected samples are read once more for PSIS-LOO (tamcmc_summary_loo_*), the header gains a line
-// `# elpd_loo= ...  p_loo= ...  looic= ...  k_max= ...  n_k_high= ...  n_k_inf= ...`, and two last columns follow:
-// elpd_loo and pareto_k, the bin's leave-one-out log predictive density and its Pareto k-hat (above 0.7: not to be trusted).
+// `# elpd_loo= ...  p_loo= ...  looic= ...  k_max= ...  n_k_high= ...  n_k_inf= ...`, and two more columns follow the
+// quantiles: elpd_loo and pareto_k, the bin's leave-one-out log predictive density and its Pareto k-hat (above 0.7: not to
+// be trusted).
+// With --predictive the first pass also accumulates the posterior predictive check (tamcmc_summary_predictive_*; no further
+// pass), the header gains two lines, `# ks_D= ...  min_log_sf= ...  bin_min_log_sf= ...  min_log_cdf= ...
+// bin_min_log_cdf= ...` and `# pit_hist= c0 c1 ... c19`, and four columns follow all the others: pit, log_cdf, log_sf and
+// mean_resid -- the bin's probability integral transform, the logarithms of its two predictive tail probabilities (log_sf
+// far below 0: power the model does not explain) and its mean residual.
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -35,18 +41,21 @@ static int usage()
 {
     fprintf(stderr, " Usage: chainsummary_hip <config dir> <model file> <data file> <params root> <output file>\n"
                     "                         [--chain m] [--slice s] [--first i] [--last j] [--thin k] [--block B]\n"
-                    "                         [--quantiles q1,q2,...] [--qbits b] [--loo]\n"
+                    "                         [--quantiles q1,q2,...] [--qbits b] [--loo] [--predictive]\n"
                     "     [1] The directory of config_default.cfg, errors_default.cfg and the *_ctrl.list files (Config/default)\n"
                     "     [2] The .model file and [3] the .data file of the fit\n"
                     "     [4] The root of the parameter files: <root>_chain-<m>.bin and <root>.hdr\n"
                     "     [5] The output file (ASCII): x y mean_M sd_M min_M max_M lppd var_l [one column per quantile] [elpd_loo pareto_k]\n"
+                    "         [pit log_cdf log_sf mean_resid]\n"
                     "     --chain m   chain to read (default 0, the coldest)     --slice s   slice of the .model file, from 0 (default 0)\n"
                     "     --first i / --last j / --thin k   samples i, i + k, ... <= j, counted from 0 (default: all)\n"
                     "     --block B   samples per block on the GPU (default 0: chosen by the library)\n"
                     "     --quantiles q1,q2,...   up to 8 values in [0, 1]: one more column each, the exact quantile of the model per bin\n"
                     "                             (the samples are read again once per pass)     --qbits b   bits per pass, 1 ... 6 (default 0: the library's)\n"
-                    "     --loo   PSIS-LOO: two last columns, elpd_loo and the Pareto k-hat per bin, and their totals in the header\n"
+                    "     --loo   PSIS-LOO: two more columns, elpd_loo and the Pareto k-hat per bin, and their totals in the header\n"
                     "             (the samples are read once more)\n"
+                    "     --predictive   posterior predictive check: four last columns, pit, log_cdf, log_sf and mean_resid per bin, and\n"
+                    "             two header lines with the totals and the PIT histogram (no further pass)\n"
                     " chainsummary_hip version   prints the library version\n");
     return EXIT_FAILURE;
 }
@@ -83,10 +92,11 @@ int main(int argc, char *argv[])
     long chain = 0, slice = 0, first = 0, last = -1, thin = 1, block = 0, qbits = 0;
     std::vector<double> quant;
     std::string quant_text;
-    bool loo = false;
+    bool loo = false, predictive = false;
     for (int i = 6; i < argc; i++) {
         const std::string a = argv[i];
         if (a == "--loo") { loo = true; continue; }
+        if (a == "--predictive") { predictive = true; continue; }
         if (a == "--quantiles") {                   // a comma-separated list of numbers in [0, 1]
             if (i + 1 >= argc || !quant.empty()) return usage();
             quant_text = argv[++i];
@@ -148,6 +158,10 @@ int main(int argc, char *argv[])
     tamcmc_summary *sum = nullptr;
     rc = tamcmc_summary_create(&sum, ctx, (int32_t)block);
     if (rc != TAMCMC_OK) return fail(std::string("tamcmc_summary_create: ") + tamcmc_strerror(rc) + " " + tamcmc_last_hip_error());
+    if (predictive) {
+        rc = tamcmc_summary_predictive_enable(sum);
+        if (rc != TAMCMC_OK) return fail(std::string("tamcmc_summary_predictive_enable: ") + tamcmc_strerror(rc) + " " + tamcmc_last_hip_error());
+    }
     // One pass over the selected samples, a few thousand rows per push: the library cuts them into its blocks.
     const long long chunk = 4096;
     std::vector<double> vars((size_t)Nvars), P;
@@ -175,6 +189,13 @@ int main(int argc, char *argv[])
     std::vector<double> mean_M(Nx), var_M(Nx), min_M(Nx), max_M(Nx), var_l(Nx), lppd(Nx);
     rc = tamcmc_summary_result(sum, &t, mean_M.data(), var_M.data(), min_M.data(), max_M.data(), nullptr, var_l.data(), lppd.data());
     if (rc != TAMCMC_OK) return fail(std::string("tamcmc_summary_result: ") + tamcmc_strerror(rc) + " " + tamcmc_last_hip_error());
+    tamcmc_summary_predictive_totals pt{};
+    const size_t Np = predictive ? (size_t)Nx : 0;
+    std::vector<double> pit(Np), log_cdf(Np), log_sf(Np), mean_resid(Np);
+    if (predictive) {
+        rc = tamcmc_summary_predictive_result(sum, &pt, pit.data(), log_cdf.data(), log_sf.data(), mean_resid.data());
+        if (rc != TAMCMC_OK) return fail(std::string("tamcmc_summary_predictive_result: ") + tamcmc_strerror(rc) + " " + tamcmc_last_hip_error());
+    }
     // quantiles: the same samples again, once per pass, until every value is exact
     const size_t Nq = quant.size();
     std::vector<double> qlo(Nq * (size_t)Nx);
@@ -217,15 +238,24 @@ int main(int argc, char *argv[])
     if (Nq) fprintf(o, "# quantiles= %s  passes= %d\n", quant_text.c_str(), passes);
     if (loo) fprintf(o, "# elpd_loo= %.12g  p_loo= %.12g  looic= %.12g  k_max= %.12g  n_k_high= %lld  n_k_inf= %lld\n", lt.elpd_loo, lt.p_loo, lt.looic,
                      lt.k_max, (long long)lt.n_k_high, (long long)lt.n_k_inf);
+    if (predictive) {
+        fprintf(o, "# ks_D= %.12g  min_log_sf= %.12g  bin_min_log_sf= %lld  min_log_cdf= %.12g  bin_min_log_cdf= %lld\n", pt.ks_D, pt.min_log_sf,
+                (long long)pt.bin_min_log_sf, pt.min_log_cdf, (long long)pt.bin_min_log_cdf);
+        fprintf(o, "# pit_hist=");
+        for (int k = 0; k < TAMCMC_SUMMARY_PIT_CELLS; k++) fprintf(o, " %lld", (long long)pt.pit_hist[k]);
+        fprintf(o, "\n");
+    }
     fprintf(o, "# x y mean_M sd_M min_M max_M lppd var_l");
     for (size_t j = 0; j < Nq; j++) fprintf(o, " q%.6g", quant[j]);
     if (loo) fprintf(o, " elpd_loo pareto_k");
+    if (predictive) fprintf(o, " pit log_cdf log_sf mean_resid");
     fprintf(o, "\n");
     for (int64_t i = 0; i < Nx; i++) {
         fprintf(o, "%.12g %.12g %.12g %.12g %.12g %.12g %.12g %.12g", x[i], y[i], mean_M[i], std::sqrt(var_M[i]), min_M[i], max_M[i],
                 lppd[i], var_l[i]);
         for (size_t j = 0; j < Nq; j++) fprintf(o, " %.12g", qlo[j * (size_t)Nx + (size_t)i]);
         if (loo) fprintf(o, " %.12g %.12g", elpd[(size_t)i], khat[(size_t)i]);
+        if (predictive) fprintf(o, " %.12g %.12g %.12g %.12g", pit[(size_t)i], log_cdf[(size_t)i], log_sf[(size_t)i], mean_resid[(size_t)i]);
         fprintf(o, "\n");
     }
     fclose(o);

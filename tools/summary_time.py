@@ -15,6 +15,11 @@ Prints one JSON line:
   e_loo_*                   LOO mode (Summary.loo_*) after a fold pass of the same rows: the tail pass in seconds per 1000
                             samples through Summary.push, the tail kernel alone per block and the finalize kernel alone,
                             once, from the same HIP-event hooks, M, and the device memory the mode allocates
+  f_predictive_*            with --predictive (and --like-p p, default 1): in one run, the fold pass through Summary.push with
+                            the predictive check off and on (two summary objects on one context, alternating, seconds per
+                            1000 samples), and from a profiled pass of the second object the fold kernel alone
+                            (Summary.kernel_time) beside the predictive kernel alone (Summary.predictive_kernel_time) and
+                            the eval launches of the same blocks (Accel.kernel_time).  Only this leg runs.
 Every timed shape is warmed up first (--warmup pushes); host clocks stop after calls that end in a device synchronise.
 """
 import argparse
@@ -60,6 +65,42 @@ def host_fold(acc, P, y, like_p=1.0, block=64):
     return dict(mean_M=mean, var_M=M2 / (n - 1), lppd=a + np.log(r / n), var_l=M2l / (n - 1), n_used=n)
 
 
+def predictive_leg(a, w, y, P):
+    """(f) the fold pass with the predictive check off and on, and the kernels' own times."""
+    out = dict(f_predictive_like_p=a.like_p)
+    with tamcmc_amd.Accel(2, w["plength"], w["x"], y, likelihood_p=float(a.like_p)) as acc:
+        with tamcmc_amd.Summary(acc, a.block) as s0, tamcmc_amd.Summary(acc, a.block, predictive=True) as s1:
+            times = {0: [], 1: []}
+            for k in range(a.warmup + a.steps):
+                for on, s in ((0, s0), (1, s1)):
+                    s.reset()
+                    acc.synchronize()
+                    t0 = time.perf_counter()
+                    s.push(P)                               # synchronous: results are on the host on return
+                    if k >= a.warmup:
+                        times[on].append(time.perf_counter() - t0)
+            for on, key in ((0, "off"), (1, "on")):
+                out[f"f_predictive_{key}_s_per_1000"] = float(np.median(times[on])) * 1000.0 / a.samples
+                out[f"f_predictive_{key}_spread"] = [float(min(times[on])) * 1000.0 / a.samples, float(max(times[on])) * 1000.0 / a.samples]
+            s1.reset()
+            s1.profile(True)
+            acc.profile(True)
+            s1.push(P)
+            fold_ms, launches = s1.kernel_time()
+            pred_ms, pred_launches = s1.predictive_kernel_time()
+            eval_ms, eval_launches = acc.kernel_time()
+            acc.profile(False)
+            s1.profile(False)
+            r = s1.predictive_result()
+            out.update(f_predictive_launches=pred_launches, f_fold_us_per_block=fold_ms * 1e3 / launches,
+                       f_predictive_us_per_block=pred_ms * 1e3 / pred_launches, f_eval_us_per_block=eval_ms * 1e3 / max(eval_launches, 1),
+                       f_fold_kernel_s_per_1000=fold_ms * 1e-3 * 1000.0 / a.samples,
+                       f_predictive_kernel_s_per_1000=pred_ms * 1e-3 * 1000.0 / a.samples,
+                       f_eval_kernel_s_per_1000=eval_ms * 1e-3 * 1000.0 / a.samples,
+                       f_predictive_ks_D=r["ks_D"], f_predictive_min_log_sf=r["min_log_sf"], n_used=r["n_used"])
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--samples", type=int, default=4096)
@@ -70,6 +111,8 @@ def main():
     ap.add_argument("--nx", type=int, default=100000)
     ap.add_argument("--quantiles", type=int, default=3)
     ap.add_argument("--qbits", type=int, default=0)
+    ap.add_argument("--predictive", action="store_true")
+    ap.add_argument("--like-p", type=int, default=1)
     a = ap.parse_args()
     if a.steps < 1 or a.warmup < 0 or a.samples < 1 or a.samples_b < 2:
         ap.error("--steps >= 1, --warmup >= 0, --samples >= 1, --samples-b >= 2")
@@ -80,6 +123,10 @@ def main():
     assert st == 0
     y = synth.make_spectrum(m_true)
     out = dict(tool="summary_time", Nx=a.nx, samples=a.samples, steps=a.steps, warmup=a.warmup, version=tamcmc_amd.capi.version())
+    if a.predictive:
+        out.update(predictive_leg(a, w, y, P))
+        print(json.dumps(out))
+        return
     with tamcmc_amd.Accel(2, w["plength"], w["x"], y) as acc:
         with tamcmc_amd.Summary(acc, a.block) as s:
             for _ in range(a.warmup):
