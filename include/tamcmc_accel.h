@@ -319,7 +319,54 @@ int tamcmc_group_members(const tamcmc_group *g, int32_t *n_members, int32_t *Npa
  *   predictive_kernel_time   as tamcmc_summary_kernel_time, for the predictive kernel alone, under the same
  *                tamcmc_summary_profile switch; tamcmc_summary_kernel_time keeps reporting the fold kernel alone.
  *                Refused exactly as tamcmc_summary_kernel_time is (NULL arguments, a batch armed; a batch in flight is
- *                not refused: its stream is waited for), and with TAMCMC_E_INVALID when the check is not enabled. */
+ *                not refused: its stream is waited for), and with TAMCMC_E_INVALID when the check is not enabled.
+ *
+ * WINDOWED PREDICTIVE CHECK: the same question over groups of bins.  An unfitted mode of modest height is tens to hundreds
+ * of bins wide with y / M of 2 ... 4 in each: per bin that is log_sf of -2 ... -4, and on a 1e5-bin grid the model's own
+ * noise reaches -11.5 somewhere.  The sum over a window of len independent bins is Gamma-distributed with shape p len (the
+ * H0 test on binned spectra, Appourchaux 2004; this is its posterior version): twenty bins at a mean ratio of 2 give
+ * log Q(20, 40) = -8.6, at a ratio of 4 log Q(20, 80) = -35.8.  Like the per-bin check a setting of the object and no pass
+ * of its own: every fold-mode block runs three more kernels (tamcmc_window.hip) behind the fold kernel -- and behind the
+ * predictive kernel where that is on -- on the same rows and the same stream.
+ *   Windows: disjoint, covering the grid.  W = bins per window, 1 ... TAMCMC_SUMMARY_WINDOW_MAX_BINS; first = the length of
+ *   the first window, 1 ... W, 0 meaning W (a second object or run with another `first` has staggered windows, so that a
+ *   feature cut by a boundary in one is whole in the other).  Window 0 is bins [0, min(first, Nx)), window w >= 1 is
+ *   [first + (w-1) W, min(first + w W, Nx)), len_w its number of bins, n_windows = 1 + ceil(max(Nx - first, 0) / W).
+ *   Definition, per window w, over the n = n_used accepted samples s (exactly the samples the fold kernel counts):
+ *     chi(2,2p)    S_sw = sum_{i in w} y_i / M_is, one division per bin, added in ascending bin order without FMA
+ *                  contraction; z = (double)p S_sw; shape a_w = p len_w; P_sw = P(a_w, z), Q_sw = Q(a_w, z), the regularised
+ *                  incomplete gamma functions; z <= 0: P = 0, Q = 1.  p = likelihood_p truncated, as everywhere.
+ *     chi_square   R_sw = sum_{i in w} (y_i - M_is) sqrt(isig2_i) in the same order; g = R_sw c_w with c_w = 1 /
+ *                  sqrt((double)len_w) formed on the host; P_sw = erfc(-g) / 2, Q_sw = erfc(g) / 2.  The likelihood is taken
+ *                  at its word as per bin: each r has standard deviation 1 / sqrt(2), and so has g.
+ *     log_cdf_w = log((1/n) sum_s P_sw)        log_sf_w = log((1/n) sum_s Q_sw)
+ *                  the per-bin check's guarded, compensated log-sum-exp in push order, unchanged; both tails of a sample as
+ *                  logarithms by the per-bin check's forms at shape a_w, the largest term written about its maximum
+ *                  where a window has two or more bins (tamcmc_window.h has the forms and their measured error: a few
+ *                  ulp of max(1, |value|) at shape 1 and for chi_square, 3.2e-14 at shape 512).
+ *     mean_resid_w the mean (Welford) over s of S_sw / len_w (chi(2,2p)) or R_sw / len_w (chi_square).
+ *     pit_w        from the smaller tail, on the host, as per bin.   With n = 0 everything is NaN (the two windows of the
+ *                  totals are -1).
+ *   W = 1 is the per-bin check: c_1 = 1.0, S / 1 = S, and p (y / M) = (p y) / M where p is a power of two -- bit for bit then.
+ *   Totals, on the host in long double and in window order: n_used, n_rejected, n_windows, W, first (as resolved: never 0);
+ *   ks_D and pit_hist over the window PITs as for the bins; min_log_sf with win_min_log_sf and min_log_cdf with
+ *   win_min_log_cdf, the first window winning a tie.
+ *   window_enable   allowed only while the object holds no sample (fresh, or after tamcmc_summary_reset) and is in fold mode,
+ *                once per object; *n_windows (may be NULL) gets the number of windows.  Allocates 7 n_windows doubles of
+ *                state plus 3 block_chains n_windows doubles of scratch on the device; TAMCMC_E_NOMEM when that fails, and
+ *                the object stays as it was.  Refused with TAMCMC_E_INVALID: W outside 1 ... TAMCMC_SUMMARY_WINDOW_MAX_BINS,
+ *                first outside 0 ... W, a chi(2,2p) context with p < 1 or p W > TAMCMC_SUMMARY_WINDOW_MAX_SHAPE (the form of
+ *                Q in use overflows past a shape of about 700), a second call, samples already pushed, quantile or LOO mode,
+ *                a context with a batch armed or in flight.  Stays on until tamcmc_summary_destroy; tamcmc_summary_reset
+ *                clears the state and keeps the setting.  Independent of predictive_enable: either, both, in either order.
+ *   While enabled, the fold kernel and the predictive kernel run unchanged -- tamcmc_summary_result and
+ *   tamcmc_summary_predictive_result keep their bits -- and passes pushed in quantile mode or LOO mode do not touch the
+ *   windows' state.  Every result is bit for bit independent of block_chains and of how the samples are split over pushes.
+ *   window_result   as predictive_result, with arrays of n_windows doubles: synchronises the stream; may be called between
+ *                pushes, in any mode and repeatedly, and disturbs nothing; totals and any array may be NULL.
+ *                TAMCMC_E_INVALID when the check is not enabled, and with a batch in flight or armed.
+ *   window_kernel_time   as predictive_kernel_time, for the three window kernels of a block together (one event pair per
+ *                block), under the same tamcmc_summary_profile switch, refused in the same cases. */
 typedef struct tamcmc_summary tamcmc_summary;
 typedef struct {
     int64_t n_used, n_rejected;
@@ -364,6 +411,18 @@ int tamcmc_summary_predictive_enable(tamcmc_summary *s);
 int tamcmc_summary_predictive_result(tamcmc_summary *s, tamcmc_summary_predictive_totals *totals,
                                      double *pit, double *log_cdf, double *log_sf, double *mean_resid);
 int tamcmc_summary_predictive_kernel_time(tamcmc_summary *s, double *total_ms, int64_t *launches);
+#define TAMCMC_SUMMARY_WINDOW_MAX_BINS 512
+#define TAMCMC_SUMMARY_WINDOW_MAX_SHAPE 512
+typedef struct {
+    int64_t n_used, n_rejected, n_windows, W, first;
+    double ks_D, min_log_sf, min_log_cdf;
+    int64_t win_min_log_sf, win_min_log_cdf;
+    int64_t pit_hist[TAMCMC_SUMMARY_PIT_CELLS];
+} tamcmc_summary_window_totals;
+int tamcmc_summary_window_enable(tamcmc_summary *s, int32_t W, int32_t first, int32_t *n_windows);
+int tamcmc_summary_window_result(tamcmc_summary *s, tamcmc_summary_window_totals *totals,
+                                 double *pit, double *log_cdf, double *log_sf, double *mean_resid);
+int tamcmc_summary_window_kernel_time(tamcmc_summary *s, double *total_ms, int64_t *launches);
 
 /* Replaces: the `for chain` loop of generate_model() calls (MALA.cpp:632-639, model_def.cpp:139-143).
  * Host pointers, row-major.  Synchronous: results are valid on return.

@@ -34,6 +34,7 @@ EXPORTS = [
     "tamcmc_summary_quantiles_end",
     "tamcmc_summary_loo_begin", "tamcmc_summary_loo_result", "tamcmc_summary_loo_end",
     "tamcmc_summary_predictive_enable", "tamcmc_summary_predictive_result", "tamcmc_summary_predictive_kernel_time",
+    "tamcmc_summary_window_enable", "tamcmc_summary_window_result", "tamcmc_summary_window_kernel_time",
 ]
 
 
@@ -57,6 +58,13 @@ class SummaryPredictiveTotals(C.Structure):
     _fields_ = [("n_used", C.c_int64), ("n_rejected", C.c_int64), ("ks_D", C.c_double), ("min_log_sf", C.c_double),
                 ("min_log_cdf", C.c_double), ("bin_min_log_sf", C.c_int64), ("bin_min_log_cdf", C.c_int64),
                 ("pit_hist", C.c_int64 * PIT_CELLS)]
+
+
+class SummaryWindowTotals(C.Structure):
+    """tamcmc_summary_window_totals"""
+    _fields_ = [("n_used", C.c_int64), ("n_rejected", C.c_int64), ("n_windows", C.c_int64), ("W", C.c_int64), ("first", C.c_int64),
+                ("ks_D", C.c_double), ("min_log_sf", C.c_double), ("min_log_cdf", C.c_double),
+                ("win_min_log_sf", C.c_int64), ("win_min_log_cdf", C.c_int64), ("pit_hist", C.c_int64 * PIT_CELLS)]
 
 
 class AccelError(RuntimeError):
@@ -129,6 +137,9 @@ def load_library():
     lib.tamcmc_summary_predictive_enable.argtypes = [vp]
     lib.tamcmc_summary_predictive_result.argtypes = [vp, C.POINTER(SummaryPredictiveTotals), dp, dp, dp, dp]
     lib.tamcmc_summary_predictive_kernel_time.argtypes = [vp, dp, C.POINTER(C.c_int64)]
+    lib.tamcmc_summary_window_enable.argtypes = [vp, C.c_int32, C.c_int32, ip]
+    lib.tamcmc_summary_window_result.argtypes = [vp, C.POINTER(SummaryWindowTotals), dp, dp, dp, dp]
+    lib.tamcmc_summary_window_kernel_time.argtypes = [vp, dp, C.POINTER(C.c_int64)]
     for name in EXPORTS:
         fn = getattr(lib, name)
         if fn.restype is not C.c_char_p:
@@ -438,22 +449,25 @@ class Summary:
     bit for bit, on block_chains or on how the rows are split over pushes.  quantiles() gives the exact per-bin quantiles
     of the model (credible bands) by pushing the same rows again a few times; loo() gives PSIS-LOO (elpd_loo and the
     Pareto k-hat per bin) by pushing them once more.  With predictive=True every fold pass also accumulates the
-    posterior predictive check (predictive_result(): PIT and both log tail probabilities per bin).  The Accel cannot be
-    closed while the summary is open."""
+    posterior predictive check (predictive_result(): PIT and both log tail probabilities per bin), and with window=W or
+    window=(W, first) the same check over disjoint windows of W bins (window_result()).  The Accel cannot be closed while
+    the summary is open."""
 
     ARRAYS = ("mean_M", "var_M", "min_M", "max_M", "mean_l", "var_l", "lppd")
 
-    def __init__(self, accel, block_chains=0, predictive=False):
+    def __init__(self, accel, block_chains=0, predictive=False, window=None):
         self._lib = load_library()
         self.accel = accel
         self._s = C.c_void_p()
         self._check(self._lib.tamcmc_summary_create(C.byref(self._s), accel._ctx, int(block_chains)), "tamcmc_summary_create")
-        if predictive:
-            try:
+        try:
+            if predictive:
                 self.predictive_enable()
-            except AccelError:
-                self.close()
-                raise
+            if window is not None:
+                self.window_enable(*np.atleast_1d(window).tolist())
+        except (AccelError, TypeError, ValueError):
+            self.close()
+            raise
 
     _check = Accel._check
 
@@ -622,6 +636,45 @@ class Summary:
         n = C.c_int64(0)
         self._check(self._lib.tamcmc_summary_predictive_kernel_time(self._s, C.byref(ms), C.byref(n)),
                     "tamcmc_summary_predictive_kernel_time")
+        return ms.value, n.value
+
+    # ---- windowed predictive check: the same over disjoint windows of W bins, the first one `first` bins long ----
+    WINDOW_MAX_BINS = 512
+    WINDOW_MAX_SHAPE = 512
+    WINDOW_ARRAYS = ("pit", "log_cdf", "log_sf", "mean_resid")
+    WINDOW_TOTALS = ("n_used", "n_rejected", "n_windows", "W", "first", "ks_D", "min_log_sf", "min_log_cdf", "win_min_log_sf",
+                     "win_min_log_cdf")
+
+    def window_enable(self, W, first=0):
+        """Turns the windowed check on for the life of the object (W bins per window, the first window `first` bins, 0 = W);
+        allowed only while it holds no sample and is in fold mode.  Returns the number of windows."""
+        nw = C.c_int32(0)
+        self._check(self._lib.tamcmc_summary_window_enable(self._s, int(W), int(first), C.byref(nw)), "tamcmc_summary_window_enable")
+        self._n_windows = int(nw.value)
+        return self._n_windows
+
+    def window_result(self):
+        """dict: pit, log_cdf, log_sf, mean_resid (n_windows doubles), first_bin and last_bin (n_windows int64, inclusive),
+        pit_hist (20 int64) and the totals n_used, n_rejected, n_windows, W, first, ks_D, min_log_sf, min_log_cdf,
+        win_min_log_sf, win_min_log_cdf."""
+        nw = max(getattr(self, "_n_windows", 0), 1)             # (not enabled: the library refuses before it writes)
+        out = {k: np.empty(nw) for k in self.WINDOW_ARRAYS}
+        t = SummaryWindowTotals()
+        self._check(self._lib.tamcmc_summary_window_result(self._s, C.byref(t), *[_dptr(out[k]) for k in self.WINDOW_ARRAYS]),
+                    "tamcmc_summary_window_result")
+        out.update({k: (getattr(t, k) if k in ("ks_D", "min_log_sf", "min_log_cdf") else int(getattr(t, k))) for k in self.WINDOW_TOTALS})
+        w = np.arange(nw, dtype=np.int64)
+        out["first_bin"] = np.where(w == 0, 0, int(t.first) + (w - 1) * int(t.W))
+        out["last_bin"] = np.minimum(int(t.first) + w * int(t.W), self.accel.Nx) - 1
+        out["pit_hist"] = np.array(list(t.pit_hist), dtype=np.int64)
+        return out
+
+    def window_kernel_time(self):
+        """(summed milliseconds, blocks) of the window kernels since profile(True); kernel_time() stays the fold kernel's."""
+        ms = C.c_double(0.0)
+        n = C.c_int64(0)
+        self._check(self._lib.tamcmc_summary_window_kernel_time(self._s, C.byref(ms), C.byref(n)),
+                    "tamcmc_summary_window_kernel_time")
         return ms.value, n.value
 
     def close(self):

@@ -5,7 +5,8 @@
 // (tamcmc_summary_quantiles_*, tamcmc_quantile.h) stage 2 is the histogram kernel instead and the fold state is frozen;
 // in LOO mode (tamcmc_summary_loo_*, tamcmc_loo.h) it is the tail kernel.  With the predictive check enabled
 // (tamcmc_summary_predictive_*, tamcmc_predictive.h) a fold-mode block has a stage 3: tamcmc_summary_predictive_kernel on
-// the same rows; the other two modes never touch its state.
+// the same rows; the other two modes never touch its state.  With the windowed check enabled (tamcmc_summary_window_*,
+// tamcmc_window.h) a stage 4 follows: the sums, tails and fold kernels of tamcmc_window.hip, again on the same rows.
 #include <algorithm>
 #include <cmath>
 #include <new>
@@ -15,6 +16,7 @@
 #include "tamcmc_predictive.h"
 #include "tamcmc_quantile.h"
 #include "tamcmc_summary.h"
+#include "tamcmc_window.h"
 
 // Quantile mode: the selection's state on the device and what the host remembers of it.
 struct TmQuantMode {
@@ -54,6 +56,16 @@ struct TmPredictive {
     TmTimer timer;                       // the predictive kernel alone (tamcmc_summary_predictive_kernel_time)
 };
 
+// The windowed predictive check: a setting like TmPredictive, and independent of it.
+struct TmWindow {
+    bool on = false;
+    double *d_state = nullptr;           // [TM_PRED_NSTATE][n_windows]
+    double *d_scratch = nullptr;         // [3][B][n_windows]
+    int W = 0, first = 0, n_windows = 0, p = 1;
+    TmWinShape shape[3] = {};            // first window, full windows, last window
+    TmTimer timer;                       // the three window kernels of a block together (tamcmc_summary_window_kernel_time)
+};
+
 struct tamcmc_summary {
     tamcmc_ctx *c = nullptr;
     int B = 0;                           // samples per block
@@ -76,6 +88,7 @@ struct tamcmc_summary {
     TmQuantMode q;
     TmLooMode loo;
     TmPredictive pred;
+    TmWindow win;
 };
 
 static size_t summary_stage_out(const tamcmc_summary *s) { return (size_t)s->B * (size_t)s->c->L.Nparams * sizeof(double); }
@@ -176,6 +189,40 @@ static void loo_free(tamcmc_summary *s)
     s->loo = TmLooMode();
 }
 
+// stage 3 of a fold-mode block: the predictive kernel on the same rows, counting on from the pair the fold launch read
+static int predictive_block(tamcmc_summary *s, int n, const int32_t *d_status, const long long *cnt_in)
+{
+    tamcmc_ctx *c = s->c;
+    int rc = TAMCMC_OK;
+    TmPredArgs pa{};
+    pa.rows = s->d_model; pa.status = d_status; pa.y = c->d_y; pa.isig2 = c->d_isig2; pa.state = s->pred.d_state;
+    pa.cnt_in = cnt_in;
+    pa.Nx = c->L.Nx; pa.B = n; pa.likelihood_case = c->L.likelihood_case; pa.p = s->pred.p; pa.nterms = s->pred.nterms;
+    pa.lf_pm1 = s->pred.lf_pm1; pa.lf_p = s->pred.lf_p;
+    if (s->profile) { rc = s->pred.timer.begin(c->stream); if (rc != TAMCMC_OK) return rc; }
+    const int pr = tm_launch_predictive(pa, c->stream);
+    if (pr != 0) return tm_launch_failed("summary predictive", pr);
+    return s->profile ? s->pred.timer.end(c->stream) : TAMCMC_OK;
+}
+
+// stage 4: the windowed check's three kernels on the same rows, counting on from the same pair
+static int window_block(tamcmc_summary *s, int n, const int32_t *d_status, const long long *cnt_in)
+{
+    tamcmc_ctx *c = s->c;
+    const TmWindow &m = s->win;
+    int rc = TAMCMC_OK;
+    TmWinArgs wa{};
+    wa.rows = s->d_model; wa.status = d_status; wa.y = c->d_y; wa.isig2 = c->d_isig2; wa.state = m.d_state; wa.scratch = m.d_scratch;
+    wa.cnt_in = cnt_in;
+    wa.Nx = c->L.Nx; wa.B = n; wa.Bcap = s->B; wa.n_windows = m.n_windows; wa.W = m.W; wa.first = m.first;
+    wa.likelihood_case = c->L.likelihood_case; wa.p = m.p;
+    for (int k = 0; k < 3; k++) wa.shape[k] = m.shape[k];
+    if (s->profile) { rc = s->win.timer.begin(c->stream); if (rc != TAMCMC_OK) return rc; }
+    const int wr = tm_launch_window(wa, c->stream);
+    if (wr != 0) return tm_launch_failed("summary window", wr);
+    return s->profile ? s->win.timer.end(c->stream) : TAMCMC_OK;
+}
+
 // One block of n <= B samples, device pointers, enqueued on the context's stream.
 static int summary_block(tamcmc_summary *s, int n, const double *d_params, double *d_logL, int32_t *d_status)
 {
@@ -197,23 +244,15 @@ static int summary_block(tamcmc_summary *s, int n, const double *d_params, doubl
     if (hr != 0) return tm_launch_failed("summary fold", hr);
     s->parity ^= 1;
     if (s->profile) { rc = s->timer.end(c->stream); if (rc != TAMCMC_OK) return rc; }
-    if (!s->pred.on) return TAMCMC_OK;
-    // stage 3: the predictive kernel on the same rows, counting on from the pair the fold launch read
-    TmPredArgs pa{};
-    pa.rows = s->d_model; pa.status = d_status; pa.y = c->d_y; pa.isig2 = c->d_isig2; pa.state = s->pred.d_state;
-    pa.cnt_in = a.cnt_in;
-    pa.Nx = c->L.Nx; pa.B = n; pa.likelihood_case = c->L.likelihood_case; pa.p = s->pred.p; pa.nterms = s->pred.nterms;
-    pa.lf_pm1 = s->pred.lf_pm1; pa.lf_p = s->pred.lf_p;
-    if (s->profile) { rc = s->pred.timer.begin(c->stream); if (rc != TAMCMC_OK) return rc; }
-    const int pr = tm_launch_predictive(pa, c->stream);
-    if (pr != 0) return tm_launch_failed("summary predictive", pr);
-    return s->profile ? s->pred.timer.end(c->stream) : TAMCMC_OK;
+    if (s->pred.on) { rc = predictive_block(s, n, d_status, a.cnt_in); if (rc != TAMCMC_OK) return rc; }
+    return s->win.on ? window_block(s, n, d_status, a.cnt_in) : TAMCMC_OK;
 }
 
 static int summary_clear(tamcmc_summary *s)
 {
     const tamcmc_ctx *c = s->c;
     if (s->pred.on) TM_HIP(hipMemsetAsync(s->pred.d_state, 0, (size_t)TM_PRED_NSTATE * (size_t)c->L.Nx * sizeof(double), c->stream));
+    if (s->win.on) TM_HIP(hipMemsetAsync(s->win.d_state, 0, (size_t)TM_PRED_NSTATE * (size_t)s->win.n_windows * sizeof(double), c->stream));
     TM_HIP(hipMemsetAsync(s->d_state, 0, (size_t)TM_SUM_NSTATE * (size_t)c->L.Nx * sizeof(double), c->stream));
     TM_HIP(hipMemsetAsync(s->d_cnt, 0, 4 * sizeof(long long), c->stream));
     s->parity = 0;
@@ -272,12 +311,14 @@ extern "C" int tamcmc_summary_destroy(tamcmc_summary *s)
     loo_free(s);
     (void)hipFree(s->d_model); (void)hipFree(s->d_state); (void)hipFree(s->d_cnt); (void)hipFree(s->d_rows);
     (void)hipFree(s->d_T); (void)hipFree(s->d_logL); (void)hipFree(s->d_status); (void)hipFree(s->pred.d_state);
+    (void)hipFree(s->win.d_state); (void)hipFree(s->win.d_scratch);
     for (int p = 0; p < 2; p++) {
         s->stage[p].release();
         if (s->ev_stage[p]) (void)hipEventDestroy(s->ev_stage[p]);
     }
     s->timer.destroy();
     s->pred.timer.destroy();
+    s->win.timer.destroy();
     delete s;
     return TAMCMC_OK;
 }
@@ -414,6 +455,7 @@ extern "C" int tamcmc_summary_profile(tamcmc_summary *s, int enable)
     s->profile = enable != 0;
     s->timer.used = 0;
     s->pred.timer.used = 0;
+    s->win.timer.used = 0;
     return TAMCMC_OK;
 }
 
@@ -686,39 +728,34 @@ extern "C" int tamcmc_summary_predictive_enable(tamcmc_summary *s)
     return TAMCMC_OK;
 }
 
-extern "C" int tamcmc_summary_predictive_result(tamcmc_summary *s, tamcmc_summary_predictive_totals *totals,
-                                                double *pit, double *log_cdf, double *log_sf, double *mean_resid)
+// What the per-bin and the windowed check share on the host: from the state st[TM_PRED_NSTATE][m] of m items (bins or
+// windows) and n accepted samples, the four arrays (any may be NULL) and the totals over the items, in item order.
+struct TmTailTotals {
+    double ks_D, min_log_sf, min_log_cdf;
+    int64_t at_min_log_sf, at_min_log_cdf;
+    int64_t pit_hist[TAMCMC_SUMMARY_PIT_CELLS];
+};
+
+static int tails_finish(const std::vector<double> &st, const size_t m, const long long n, double *pit, double *log_cdf, double *log_sf,
+                        double *mean_resid, TmTailTotals *out)
 {
-    if (!s || !s->pred.on || s->c->in_flight || s->c->armed) return TAMCMC_E_INVALID;
-    tamcmc_ctx *c = s->c;
-    TM_HIP(hipSetDevice(c->device));
-    TM_HIP(tm_ctx_stream_sync(c));
-    const size_t nx = (size_t)c->L.Nx;
-    long long cnt[2] = {0, 0};
-    std::vector<double> st, u;
-    try { st.resize(TM_PRED_NSTATE * nx); u.reserve(nx); } catch (const std::bad_alloc &) { return TAMCMC_E_NOMEM; }
-    // the fold pass's counts: frozen copies while a mode is on (its passes do not touch the predictive state either)
-    if (s->q.on) { cnt[0] = s->q.n_used; cnt[1] = s->q.n_rejected; }
-    else if (s->loo.on) { cnt[0] = s->loo.n_used; cnt[1] = s->loo.n_rejected; }
-    else TM_HIP(hipMemcpy(cnt, s->d_cnt + 2 * s->parity, sizeof(cnt), hipMemcpyDeviceToHost));
-    TM_HIP(hipMemcpy(st.data(), s->pred.d_state, st.size() * sizeof(double), hipMemcpyDeviceToHost));
-    const long long n = cnt[0];
     const double nan = std::nan("");
-    tamcmc_summary_predictive_totals t{};
-    t.n_used = n; t.n_rejected = cnt[1];
+    std::vector<double> u;
+    try { u.reserve(m); } catch (const std::bad_alloc &) { return TAMCMC_E_NOMEM; }
+    TmTailTotals t{};
     t.ks_D = nan; t.min_log_sf = nan; t.min_log_cdf = nan;
-    t.bin_min_log_sf = -1; t.bin_min_log_cdf = -1;
-    for (size_t i = 0; i < nx; i++) {
-        const double lc = tmp_lse_result(st[TM_PRED_CDF_A * nx + i], st[TM_PRED_CDF_R * nx + i], st[TM_PRED_CDF_C * nx + i], n);
-        const double ls = tmp_lse_result(st[TM_PRED_SF_A * nx + i], st[TM_PRED_SF_R * nx + i], st[TM_PRED_SF_C * nx + i], n);
+    t.at_min_log_sf = -1; t.at_min_log_cdf = -1;
+    for (size_t i = 0; i < m; i++) {
+        const double lc = tmp_lse_result(st[TM_PRED_CDF_A * m + i], st[TM_PRED_CDF_R * m + i], st[TM_PRED_CDF_C * m + i], n);
+        const double ls = tmp_lse_result(st[TM_PRED_SF_A * m + i], st[TM_PRED_SF_R * m + i], st[TM_PRED_SF_C * m + i], n);
         const double pv = n >= 1 ? (lc < ls ? std::exp(lc) : -std::expm1(ls)) : nan;       // from the smaller tail
         if (pit) pit[i] = pv;
         if (log_cdf) log_cdf[i] = lc;
         if (log_sf) log_sf[i] = ls;
-        if (mean_resid) mean_resid[i] = n >= 1 ? st[TM_PRED_MEAN_RESID * nx + i] : nan;
+        if (mean_resid) mean_resid[i] = n >= 1 ? st[TM_PRED_MEAN_RESID * m + i] : nan;
         if (n < 1) continue;
-        if (t.bin_min_log_sf < 0 ? !std::isnan(ls) : ls < t.min_log_sf) { t.min_log_sf = ls; t.bin_min_log_sf = (int64_t)i; }      // the first bin wins a tie
-        if (t.bin_min_log_cdf < 0 ? !std::isnan(lc) : lc < t.min_log_cdf) { t.min_log_cdf = lc; t.bin_min_log_cdf = (int64_t)i; }
+        if (t.at_min_log_sf < 0 ? !std::isnan(ls) : ls < t.min_log_sf) { t.min_log_sf = ls; t.at_min_log_sf = (int64_t)i; }      // the first item wins a tie
+        if (t.at_min_log_cdf < 0 ? !std::isnan(lc) : lc < t.min_log_cdf) { t.min_log_cdf = lc; t.at_min_log_cdf = (int64_t)i; }
         if (std::isnan(pv)) continue;
         const int cell = (int)std::floor(20.0 * pv);
         t.pit_hist[cell > TAMCMC_SUMMARY_PIT_CELLS - 1 ? TAMCMC_SUMMARY_PIT_CELLS - 1 : (cell < 0 ? 0 : cell)]++;
@@ -735,7 +772,44 @@ extern "C" int tamcmc_summary_predictive_result(tamcmc_summary *s, tamcmc_summar
         }
         t.ks_D = (double)D;
     }
-    if (totals) *totals = t;
+    *out = t;
+    return TAMCMC_OK;
+}
+
+// the fold pass's counts: frozen copies while a mode is on (its passes touch neither check's state)
+static int fold_counts(const tamcmc_summary *s, long long cnt[2])
+{
+    if (s->q.on) { cnt[0] = s->q.n_used; cnt[1] = s->q.n_rejected; }
+    else if (s->loo.on) { cnt[0] = s->loo.n_used; cnt[1] = s->loo.n_rejected; }
+    else TM_HIP(hipMemcpy(cnt, s->d_cnt + 2 * s->parity, 2 * sizeof(long long), hipMemcpyDeviceToHost));
+    return TAMCMC_OK;
+}
+
+extern "C" int tamcmc_summary_predictive_result(tamcmc_summary *s, tamcmc_summary_predictive_totals *totals,
+                                                double *pit, double *log_cdf, double *log_sf, double *mean_resid)
+{
+    if (!s || !s->pred.on || s->c->in_flight || s->c->armed) return TAMCMC_E_INVALID;
+    tamcmc_ctx *c = s->c;
+    TM_HIP(hipSetDevice(c->device));
+    TM_HIP(tm_ctx_stream_sync(c));
+    const size_t nx = (size_t)c->L.Nx;
+    long long cnt[2] = {0, 0};
+    std::vector<double> st;
+    try { st.resize(TM_PRED_NSTATE * nx); } catch (const std::bad_alloc &) { return TAMCMC_E_NOMEM; }
+    int rc = fold_counts(s, cnt);
+    if (rc != TAMCMC_OK) return rc;
+    TM_HIP(hipMemcpy(st.data(), s->pred.d_state, st.size() * sizeof(double), hipMemcpyDeviceToHost));
+    TmTailTotals f;
+    rc = tails_finish(st, nx, cnt[0], pit, log_cdf, log_sf, mean_resid, &f);
+    if (rc != TAMCMC_OK) return rc;
+    if (totals) {
+        tamcmc_summary_predictive_totals t{};
+        t.n_used = cnt[0]; t.n_rejected = cnt[1];
+        t.ks_D = f.ks_D; t.min_log_sf = f.min_log_sf; t.min_log_cdf = f.min_log_cdf;
+        t.bin_min_log_sf = f.at_min_log_sf; t.bin_min_log_cdf = f.at_min_log_cdf;
+        std::memcpy(t.pit_hist, f.pit_hist, sizeof(t.pit_hist));
+        *totals = t;
+    }
     return TAMCMC_OK;
 }
 
@@ -745,4 +819,79 @@ extern "C" int tamcmc_summary_predictive_kernel_time(tamcmc_summary *s, double *
     TM_HIP(hipSetDevice(s->c->device));
     TM_HIP(tm_ctx_stream_sync(s->c));
     return s->pred.timer.total(total_ms, launches);
+}
+
+// ---- windowed posterior predictive check (tamcmc_window.h) ----
+
+extern "C" int tamcmc_summary_window_enable(tamcmc_summary *s, int32_t W, int32_t first, int32_t *n_windows)
+{
+    if (!s || W < 1 || W > TAMCMC_SUMMARY_WINDOW_MAX_BINS || first < 0 || first > W) return TAMCMC_E_INVALID;
+    tamcmc_ctx *c = s->c;
+    if (s->win.on || s->q.on || s->loo.on || c->in_flight || c->armed) return TAMCMC_E_INVALID;
+    const bool chi = c->L.likelihood_case == 0;
+    if (chi && !(c->L.like_p >= 1.0 && c->L.like_p <= (double)TAMCMC_SUMMARY_WINDOW_MAX_SHAPE && (int)c->L.like_p * W <= TAMCMC_SUMMARY_WINDOW_MAX_SHAPE))
+        return TAMCMC_E_INVALID;
+    TM_HIP(hipSetDevice(c->device));
+    TM_HIP(tm_ctx_stream_sync(c));
+    long long cnt[2] = {0, 0};
+    TM_HIP(hipMemcpy(cnt, s->d_cnt + 2 * s->parity, sizeof(cnt), hipMemcpyDeviceToHost));
+    if (cnt[0] != 0 || cnt[1] != 0) return TAMCMC_E_INVALID;            // the object holds samples: reset first
+    TmWindow &m = s->win;
+    int f = first, len[3];
+    const long long nw = tmw_partition((long long)c->L.Nx, W, &f, len);
+    const size_t state_bytes = (size_t)TM_PRED_NSTATE * (size_t)nw * sizeof(double);
+    const size_t scratch_bytes = 3 * (size_t)s->B * (size_t)nw * sizeof(double);
+    double *d_state = nullptr, *d_scratch = nullptr;
+    if (hipMalloc(&d_state, state_bytes) != hipSuccess) { (void)hipGetLastError(); return TAMCMC_E_NOMEM; }
+    if (hipMalloc(&d_scratch, scratch_bytes) != hipSuccess) { (void)hipGetLastError(); (void)hipFree(d_state); return TAMCMC_E_NOMEM; }
+    c->enq_seq++;
+    if (hipMemsetAsync(d_state, 0, state_bytes, c->stream) != hipSuccess) {
+        (void)hipStreamSynchronize(c->stream);
+        (void)hipFree(d_state); (void)hipFree(d_scratch);
+        return TAMCMC_E_HIP;
+    }
+    m.d_state = d_state; m.d_scratch = d_scratch;
+    m.W = W; m.first = f; m.n_windows = (int)nw;
+    m.p = chi ? (int)c->L.like_p : 1;
+    for (int k = 0; k < 3; k++) m.shape[k] = tmw_shape(len[k], m.p);
+    m.on = true;
+    if (n_windows) *n_windows = (int32_t)nw;
+    return TAMCMC_OK;
+}
+
+extern "C" int tamcmc_summary_window_result(tamcmc_summary *s, tamcmc_summary_window_totals *totals,
+                                            double *pit, double *log_cdf, double *log_sf, double *mean_resid)
+{
+    if (!s || !s->win.on || s->c->in_flight || s->c->armed) return TAMCMC_E_INVALID;
+    tamcmc_ctx *c = s->c;
+    TM_HIP(hipSetDevice(c->device));
+    TM_HIP(tm_ctx_stream_sync(c));
+    const size_t nw = (size_t)s->win.n_windows;
+    long long cnt[2] = {0, 0};
+    std::vector<double> st;
+    try { st.resize(TM_PRED_NSTATE * nw); } catch (const std::bad_alloc &) { return TAMCMC_E_NOMEM; }
+    int rc = fold_counts(s, cnt);
+    if (rc != TAMCMC_OK) return rc;
+    TM_HIP(hipMemcpy(st.data(), s->win.d_state, st.size() * sizeof(double), hipMemcpyDeviceToHost));
+    TmTailTotals f;
+    rc = tails_finish(st, nw, cnt[0], pit, log_cdf, log_sf, mean_resid, &f);
+    if (rc != TAMCMC_OK) return rc;
+    if (totals) {
+        tamcmc_summary_window_totals t{};
+        t.n_used = cnt[0]; t.n_rejected = cnt[1];
+        t.n_windows = (int64_t)nw; t.W = s->win.W; t.first = s->win.first;
+        t.ks_D = f.ks_D; t.min_log_sf = f.min_log_sf; t.min_log_cdf = f.min_log_cdf;
+        t.win_min_log_sf = f.at_min_log_sf; t.win_min_log_cdf = f.at_min_log_cdf;
+        std::memcpy(t.pit_hist, f.pit_hist, sizeof(t.pit_hist));
+        *totals = t;
+    }
+    return TAMCMC_OK;
+}
+
+extern "C" int tamcmc_summary_window_kernel_time(tamcmc_summary *s, double *total_ms, int64_t *launches)
+{
+    if (!s || !total_ms || !launches || !s->win.on || s->c->armed) return TAMCMC_E_INVALID;
+    TM_HIP(hipSetDevice(s->c->device));
+    TM_HIP(tm_ctx_stream_sync(s->c));
+    return s->win.timer.total(total_ms, launches);
 }

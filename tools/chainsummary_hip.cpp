@@ -3,7 +3,7 @@
 //
 //   chainsummary_hip <config dir> <model file> <data file> <params root> <output file>
 //                    [--chain m] [--slice s] [--first i] [--last j] [--thin k] [--block B]
-//                    [--quantiles q1,q2,...] [--qbits b] [--loo] [--predictive]
+//                    [--quantiles q1,q2,...] [--qbits b] [--loo] [--predictive] [--window W[,first]]
 //
 // <config dir> is the reference's Config/default; model id, likelihood, p, plength, the inputs row and the relax mask
 // come from the setup it describes (tamcmc_setup_create / tamcmc_setup_load, slice s counted from 0).  The samples are
@@ -26,6 +26,12 @@
 // bin_min_log_cdf= ...` and `# pit_hist= c0 c1 ... c19`, and four columns follow all the others: pit, log_cdf, log_sf and
 // mean_resid -- the bin's probability integral transform, the logarithms of its two predictive tail probabilities (log_sf
 // far below 0: power the model does not explain) and its mean residual.
+// With --window W[,first] the first pass also accumulates the same check over disjoint windows of W bins, the first window
+// `first` bins long (tamcmc_summary_window_*; no further pass).  The output file keeps every byte; the windows go to
+// <output file>.windows: `#` header lines -- the version, `# W= ...  first= ...  n_windows= ...`, `# n_used= ...
+// n_rejected= ...`, `# ks_D= ...  min_log_sf= ...  win_min_log_sf= ...  min_log_cdf= ...  win_min_log_cdf= ...`,
+// `# pit_hist= c0 c1 ... c19` -- then one row per window:
+//   w  first_bin  last_bin  x_first  x_last  pit  log_cdf  log_sf  mean_resid
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -41,7 +47,7 @@ static int usage()
 {
     fprintf(stderr, " Usage: chainsummary_hip <config dir> <model file> <data file> <params root> <output file>\n"
                     "                         [--chain m] [--slice s] [--first i] [--last j] [--thin k] [--block B]\n"
-                    "                         [--quantiles q1,q2,...] [--qbits b] [--loo] [--predictive]\n"
+                    "                         [--quantiles q1,q2,...] [--qbits b] [--loo] [--predictive] [--window W[,first]]\n"
                     "     [1] The directory of config_default.cfg, errors_default.cfg and the *_ctrl.list files (Config/default)\n"
                     "     [2] The .model file and [3] the .data file of the fit\n"
                     "     [4] The root of the parameter files: <root>_chain-<m>.bin and <root>.hdr\n"
@@ -56,6 +62,9 @@ static int usage()
                     "             (the samples are read once more)\n"
                     "     --predictive   posterior predictive check: four last columns, pit, log_cdf, log_sf and mean_resid per bin, and\n"
                     "             two header lines with the totals and the PIT histogram (no further pass)\n"
+                    "     --window W[,first]   the same check over disjoint windows of W bins (1 ... 512; likelihood p times W at most 512),\n"
+                    "             the first window `first` bins long (1 ... W, default W): written to <output file>.windows, one row per\n"
+                    "             window, w first_bin last_bin x_first x_last pit log_cdf log_sf mean_resid (no further pass; [5] is unchanged)\n"
                     " chainsummary_hip version   prints the library version\n");
     return EXIT_FAILURE;
 }
@@ -93,10 +102,26 @@ int main(int argc, char *argv[])
     std::vector<double> quant;
     std::string quant_text;
     bool loo = false, predictive = false;
+    long win_W = 0, win_first = 0;
     for (int i = 6; i < argc; i++) {
         const std::string a = argv[i];
         if (a == "--loo") { loo = true; continue; }
         if (a == "--predictive") { predictive = true; continue; }
+        if (a == "--window") {                      // W or W,first
+            if (i + 1 >= argc || win_W != 0) return usage();
+            char *end = nullptr;
+            const char *p = argv[++i];
+            win_W = strtol(p, &end, 10);
+            if (end == p || win_W < 1 || win_W > TAMCMC_SUMMARY_WINDOW_MAX_BINS) return usage();
+            win_first = win_W;
+            if (*end == ',') {
+                p = end + 1;
+                win_first = strtol(p, &end, 10);
+                if (end == p || win_first < 1 || win_first > win_W) return usage();
+            }
+            if (*end != '\0') return usage();
+            continue;
+        }
         if (a == "--quantiles") {                   // a comma-separated list of numbers in [0, 1]
             if (i + 1 >= argc || !quant.empty()) return usage();
             quant_text = argv[++i];
@@ -162,6 +187,11 @@ int main(int argc, char *argv[])
         rc = tamcmc_summary_predictive_enable(sum);
         if (rc != TAMCMC_OK) return fail(std::string("tamcmc_summary_predictive_enable: ") + tamcmc_strerror(rc) + " " + tamcmc_last_hip_error());
     }
+    int32_t n_windows = 0;
+    if (win_W) {
+        rc = tamcmc_summary_window_enable(sum, (int32_t)win_W, (int32_t)win_first, &n_windows);
+        if (rc != TAMCMC_OK) return fail(std::string("tamcmc_summary_window_enable: ") + tamcmc_strerror(rc) + " " + tamcmc_last_hip_error());
+    }
     // One pass over the selected samples, a few thousand rows per push: the library cuts them into its blocks.
     const long long chunk = 4096;
     std::vector<double> vars((size_t)Nvars), P;
@@ -195,6 +225,12 @@ int main(int argc, char *argv[])
     if (predictive) {
         rc = tamcmc_summary_predictive_result(sum, &pt, pit.data(), log_cdf.data(), log_sf.data(), mean_resid.data());
         if (rc != TAMCMC_OK) return fail(std::string("tamcmc_summary_predictive_result: ") + tamcmc_strerror(rc) + " " + tamcmc_last_hip_error());
+    }
+    tamcmc_summary_window_totals wt{};
+    std::vector<double> wpit((size_t)n_windows), wlog_cdf((size_t)n_windows), wlog_sf((size_t)n_windows), wmean_resid((size_t)n_windows);
+    if (win_W) {
+        rc = tamcmc_summary_window_result(sum, &wt, wpit.data(), wlog_cdf.data(), wlog_sf.data(), wmean_resid.data());
+        if (rc != TAMCMC_OK) return fail(std::string("tamcmc_summary_window_result: ") + tamcmc_strerror(rc) + " " + tamcmc_last_hip_error());
     }
     // quantiles: the same samples again, once per pass, until every value is exact
     const size_t Nq = quant.size();
@@ -259,6 +295,25 @@ int main(int argc, char *argv[])
         fprintf(o, "\n");
     }
     fclose(o);
+    if (win_W) {
+        const std::string win_file = out_file + ".windows";
+        FILE *ow = fopen(win_file.c_str(), "w");
+        if (!ow) return fail("unable to open the output file " + win_file);
+        fprintf(ow, "# chainsummary_hip (%s)\n", tamcmc_version());
+        fprintf(ow, "# W= %lld  first= %lld  n_windows= %lld\n", (long long)wt.W, (long long)wt.first, (long long)wt.n_windows);
+        fprintf(ow, "# n_used= %lld  n_rejected= %lld\n", (long long)wt.n_used, (long long)wt.n_rejected);
+        fprintf(ow, "# ks_D= %.12g  min_log_sf= %.12g  win_min_log_sf= %lld  min_log_cdf= %.12g  win_min_log_cdf= %lld\n", wt.ks_D, wt.min_log_sf,
+                (long long)wt.win_min_log_sf, wt.min_log_cdf, (long long)wt.win_min_log_cdf);
+        fprintf(ow, "# pit_hist=");
+        for (int k = 0; k < TAMCMC_SUMMARY_PIT_CELLS; k++) fprintf(ow, " %lld", (long long)wt.pit_hist[k]);
+        fprintf(ow, "\n# w first_bin last_bin x_first x_last pit log_cdf log_sf mean_resid\n");
+        for (int64_t w = 0; w < wt.n_windows; w++) {
+            const int64_t b = w == 0 ? 0 : wt.first + (w - 1) * wt.W, e = wt.first + w * wt.W < Nx ? wt.first + w * wt.W : Nx;
+            fprintf(ow, "%lld %lld %lld %.12g %.12g %.12g %.12g %.12g %.12g\n", (long long)w, (long long)b, (long long)(e - 1), x[(size_t)b],
+                    x[(size_t)(e - 1)], wpit[(size_t)w], wlog_cdf[(size_t)w], wlog_sf[(size_t)w], wmean_resid[(size_t)w]);
+        }
+        fclose(ow);
+    }
     printf("Summary of %lld samples (%lld rejected) written to %s\n", (long long)t.n_used, (long long)t.n_rejected, out_file.c_str());
     return 0;
 }

@@ -20,6 +20,10 @@ Prints one JSON line:
                             1000 samples), and from a profiled pass of the second object the fold kernel alone
                             (Summary.kernel_time) beside the predictive kernel alone (Summary.predictive_kernel_time) and
                             the eval launches of the same blocks (Accel.kernel_time).  Only this leg runs.
+  g_window_*                with --window W (and --like-p p, default 1; p W <= 512): the same for the windowed check -- the fold
+                            pass with the check off and on, alternating in one run, and from a profiled pass the fold kernel
+                            alone beside the three window kernels together (Summary.window_kernel_time) and the eval launches.
+                            Only this leg runs.
 Every timed shape is warmed up first (--warmup pushes); host clocks stop after calls that end in a device synchronise.
 """
 import argparse
@@ -101,6 +105,42 @@ def predictive_leg(a, w, y, P):
     return out
 
 
+def window_leg(a, w, y, P):
+    """(g) the fold pass with the windowed check off and on, and the kernels' own times."""
+    out = dict(g_window_W=a.window, g_window_like_p=a.like_p)
+    with tamcmc_amd.Accel(2, w["plength"], w["x"], y, likelihood_p=float(a.like_p)) as acc:
+        with tamcmc_amd.Summary(acc, a.block) as s0, tamcmc_amd.Summary(acc, a.block, window=a.window) as s1:
+            times = {0: [], 1: []}
+            for k in range(a.warmup + a.steps):
+                for on, s in ((0, s0), (1, s1)):
+                    s.reset()
+                    acc.synchronize()
+                    t0 = time.perf_counter()
+                    s.push(P)                               # synchronous: results are on the host on return
+                    if k >= a.warmup:
+                        times[on].append(time.perf_counter() - t0)
+            for on, key in ((0, "off"), (1, "on")):
+                out[f"g_window_{key}_s_per_1000"] = float(np.median(times[on])) * 1000.0 / a.samples
+                out[f"g_window_{key}_spread"] = [float(min(times[on])) * 1000.0 / a.samples, float(max(times[on])) * 1000.0 / a.samples]
+            s1.reset()
+            s1.profile(True)
+            acc.profile(True)
+            s1.push(P)
+            fold_ms, launches = s1.kernel_time()
+            win_ms, win_blocks = s1.window_kernel_time()
+            eval_ms, eval_launches = acc.kernel_time()
+            acc.profile(False)
+            s1.profile(False)
+            r = s1.window_result()
+            out.update(g_window_blocks=win_blocks, g_window_n_windows=r["n_windows"], g_fold_us_per_block=fold_ms * 1e3 / launches,
+                       g_window_us_per_block=win_ms * 1e3 / win_blocks, g_eval_us_per_block=eval_ms * 1e3 / max(eval_launches, 1),
+                       g_fold_kernel_s_per_1000=fold_ms * 1e-3 * 1000.0 / a.samples,
+                       g_window_kernel_s_per_1000=win_ms * 1e-3 * 1000.0 / a.samples,
+                       g_eval_kernel_s_per_1000=eval_ms * 1e-3 * 1000.0 / a.samples,
+                       g_window_ks_D=r["ks_D"], g_window_min_log_sf=r["min_log_sf"], n_used=r["n_used"])
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--samples", type=int, default=4096)
@@ -113,6 +153,7 @@ def main():
     ap.add_argument("--qbits", type=int, default=0)
     ap.add_argument("--predictive", action="store_true")
     ap.add_argument("--like-p", type=int, default=1)
+    ap.add_argument("--window", type=int, default=0)
     a = ap.parse_args()
     if a.steps < 1 or a.warmup < 0 or a.samples < 1 or a.samples_b < 2:
         ap.error("--steps >= 1, --warmup >= 0, --samples >= 1, --samples-b >= 2")
@@ -123,8 +164,8 @@ def main():
     assert st == 0
     y = synth.make_spectrum(m_true)
     out = dict(tool="summary_time", Nx=a.nx, samples=a.samples, steps=a.steps, warmup=a.warmup, version=tamcmc_amd.capi.version())
-    if a.predictive:
-        out.update(predictive_leg(a, w, y, P))
+    if a.predictive or a.window:
+        out.update(window_leg(a, w, y, P) if a.window else predictive_leg(a, w, y, P))
         print(json.dumps(out))
         return
     with tamcmc_amd.Accel(2, w["plength"], w["x"], y) as acc:
