@@ -366,7 +366,62 @@ int tamcmc_group_members(const tamcmc_group *g, int32_t *n_members, int32_t *Npa
  *                pushes, in any mode and repeatedly, and disturbs nothing; totals and any array may be NULL.
  *                TAMCMC_E_INVALID when the check is not enabled, and with a batch in flight or armed.
  *   window_kernel_time   as predictive_kernel_time, for the three window kernels of a block together (one event pair per
- *                block), under the same tamcmc_summary_profile switch, refused in the same cases. */
+ *                block), under the same tamcmc_summary_profile switch, refused in the same cases.
+ *
+ * EFFECTIVE SAMPLE SIZE, MCSE AND SPLIT R-HAT: every number above is a Monte-Carlo estimate over an autocorrelated chain;
+ * this says per bin how many independent draws the chain is worth (Geyer's initial monotone sequence on the
+ * autocorrelation over the sample order, as Stan uses for one chain), the Monte-Carlo standard error of mean_M that
+ * follows, the split R-hat of the two halves of the chain, and the relative efficiency r_eff the `loo` literature expects
+ * beside k-hat.  A fourth mode beside fold, quantile and LOO mode: after the fold pass the caller pushes the SAME samples
+ * once more, in the same order.
+ *   Definition, per bin i, with n = n_used and t = 0 ... n - 1 counting the accepted samples in push order (a rejected
+ *   sample is skipped and counted and does not advance t: lags are counted in accepted samples):
+ *     1. Two series, centred with the frozen fold results (the very doubles tamcmc_summary_result returns):
+ *          model        a_t = M_it - mean_M_i
+ *          likelihood   u_t = exp(l_it - lppd_i) - 1.0, l restated without FMA contraction as in LOO mode.  The mean of
+ *                       exp(l - lppd) is 1 by construction and l - lppd <= log n: nothing overflows.
+ *     2. Lag limit: L = the largest odd number <= min(max_lag | 1, n - 1); max_lag = 0 picks the library's default, 255.
+ *     3. Lag products, for each series d: A_k = sum_{t=k}^{n-1} d_t d_{t-k}, k = 0 ... L, each accumulated from +0.0 in
+ *        ascending t by A = fma(d_t, d_{t-k}, A): the product is not rounded before it is added (tamcmc_ess.h).
+ *     4. Finish, in double, in this order, without contraction: rho_k = A_k / A_0; P_m = rho_{2m} + rho_{2m+1} for
+ *        m = 0 ... (L-1)/2; K = the first m for which P_m >= 0 does not hold (a NaN stops the sum too), K = (L+1)/2 if there
+ *        is none; P_m = min(P_m, P_{m-1}) for m = 1 ... K-1; tau = -1 + 2 sum_{m<K} P_m in ascending m; tau = max(tau,
+ *        1 / log10(n)), the log10 evaluated on the host; ess = n / tau; cut = 2K, and cut = L + 1 says the bin was truncated:
+ *        the sequence had not turned negative within L lags and ess is an upper bound.  A_0 zero or not finite: ess = tau
+ *        = NaN, cut = 0.
+ *     5. Split R-hat of the model series: h = floor(n / 2), the halves t in [0, h) and [n - h, n), each with its own
+ *        Welford mean m and sum of squared deviations M2 of M_it accumulated in push order on the device; on the host
+ *        s^2 = M2 / (h - 1), W = (s1^2 + s2^2) / 2, Bn = (m1 - mb)^2 + (m2 - mb)^2 with mb = (m1 + m2) / 2,
+ *        rhat = sqrt(((h - 1) / h * W + Bn) / W); W = 0: NaN.
+ *     6. Per bin: ess_M, tau_M, cut_M; mcse_M = sqrt(var_M / ess_M) with the frozen var_M; rhat_M; ess_l, cut_l,
+ *        r_eff = ess_l / n.
+ *     7. Totals, on the host in bin order, the first bin winning a tie and a NaN skipped (a bin of -1: every value was NaN):
+ *        n_used, n_rejected, lag = L; min_ess_M with bin_min_ess_M, min_ess_l with bin_min_ess_l, max_rhat with
+ *        bin_max_rhat; n_truncated_M, n_truncated_l = bins with cut = L + 1; n_rhat_high = bins with rhat > 1.01.
+ *   ess_begin    freezes the fold state as loo_begin does, resolves L (*lag_used, may be NULL) and allocates on the device,
+ *                per series, (L + 1) x Nx accumulators and a ring of L + 64 centred values per bin (the last L are the carry
+ *                that bridges blocks and pushes, 64 is the number of samples one pair of launches takes), plus 4 Nx doubles
+ *                of half-chain moments, Nx of lppd and 5 Nx of results: (32 L + 1120) Nx + 32 bytes in all -- 0.93 GB for Nx =
+ *                1e5 at L = 255.  TAMCMC_E_NOMEM when that fails, and the object stays as it was.  Refused with
+ *                TAMCMC_E_INVALID: n_used < 4, max_lag outside 0 ... TAMCMC_SUMMARY_ESS_MAX_LAG, any mode already on
+ *                (tamcmc_summary_quantiles_begin and tamcmc_summary_loo_begin are likewise refused while ESS mode is on, and
+ *                so are predictive_enable and window_enable), a context with a batch in flight or armed.
+ *   While the mode is on, push and push_device evaluate the rows as before and hand out the same logL and status bits, but
+ *   feed the ESS kernels (tamcmc_ess.hip) instead of the fold kernel; tamcmc_summary_result keeps returning the frozen fold
+ *   results, and the predictive and window states are not touched.  Every (bin, lag) accumulator is advanced by one
+ *   thread in sample order, so every result is bit for bit independent of block_chains and of how the pass is split over
+ *   pushes -- pushes shorter than L and pushes of one sample included.
+ *   ess_result   totals and eight arrays of Nx on the host, any of them may be NULL.  If the pass did not see exactly the
+ *                fold pass's accepted and rejected counts: TAMCMC_E_INVALID, the pass is discarded and may be repeated.  May
+ *                be called again without another pass.
+ *   ess_acov     the lag products of a complete pass: which = 0 the model series, 1 the likelihood series; acov is
+ *                (L + 1) x Nx on the host, A_k of bin i at acov[k * Nx + i].  TAMCMC_E_INVALID for an incomplete pass (which
+ *                it leaves alone), a NULL acov, which outside 0 ... 1.
+ *   ess_end      frees the mode's memory and goes back to fold mode: the running statistics are untouched and further
+ *                pushes fold as before.  tamcmc_summary_reset also leaves the mode; tamcmc_summary_destroy works in any.
+ *                _result, _acov and _end outside the mode return TAMCMC_E_INVALID.
+ *   profile / kernel_time in ESS mode: the centre and lag kernels of every block together (one event pair per block), and
+ *   the finish kernel of every ess_result. */
 typedef struct tamcmc_summary tamcmc_summary;
 typedef struct {
     int64_t n_used, n_rejected;
@@ -423,6 +478,19 @@ int tamcmc_summary_window_enable(tamcmc_summary *s, int32_t W, int32_t first, in
 int tamcmc_summary_window_result(tamcmc_summary *s, tamcmc_summary_window_totals *totals,
                                  double *pit, double *log_cdf, double *log_sf, double *mean_resid);
 int tamcmc_summary_window_kernel_time(tamcmc_summary *s, double *total_ms, int64_t *launches);
+#define TAMCMC_SUMMARY_ESS_MAX_LAG 1023
+typedef struct {
+    int64_t n_used, n_rejected, lag;
+    double min_ess_M, min_ess_l, max_rhat;
+    int64_t bin_min_ess_M, bin_min_ess_l, bin_max_rhat;
+    int64_t n_truncated_M, n_truncated_l, n_rhat_high;
+} tamcmc_summary_ess_totals;
+int tamcmc_summary_ess_begin(tamcmc_summary *s, int32_t max_lag, int32_t *lag_used);
+int tamcmc_summary_ess_result(tamcmc_summary *s, tamcmc_summary_ess_totals *totals,
+                              double *ess_M, double *tau_M, double *mcse_M, double *rhat_M, int32_t *cut_M,
+                              double *ess_l, double *r_eff, int32_t *cut_l);
+int tamcmc_summary_ess_acov(tamcmc_summary *s, int32_t which, double *acov);
+int tamcmc_summary_ess_end(tamcmc_summary *s);
 
 /* Replaces: the `for chain` loop of generate_model() calls (MALA.cpp:632-639, model_def.cpp:139-143).
  * Host pointers, row-major.  Synchronous: results are valid on return.

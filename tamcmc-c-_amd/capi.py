@@ -35,6 +35,7 @@ EXPORTS = [
     "tamcmc_summary_loo_begin", "tamcmc_summary_loo_result", "tamcmc_summary_loo_end",
     "tamcmc_summary_predictive_enable", "tamcmc_summary_predictive_result", "tamcmc_summary_predictive_kernel_time",
     "tamcmc_summary_window_enable", "tamcmc_summary_window_result", "tamcmc_summary_window_kernel_time",
+    "tamcmc_summary_ess_begin", "tamcmc_summary_ess_result", "tamcmc_summary_ess_acov", "tamcmc_summary_ess_end",
 ]
 
 
@@ -65,6 +66,14 @@ class SummaryWindowTotals(C.Structure):
     _fields_ = [("n_used", C.c_int64), ("n_rejected", C.c_int64), ("n_windows", C.c_int64), ("W", C.c_int64), ("first", C.c_int64),
                 ("ks_D", C.c_double), ("min_log_sf", C.c_double), ("min_log_cdf", C.c_double),
                 ("win_min_log_sf", C.c_int64), ("win_min_log_cdf", C.c_int64), ("pit_hist", C.c_int64 * PIT_CELLS)]
+
+
+class SummaryEssTotals(C.Structure):
+    """tamcmc_summary_ess_totals"""
+    _fields_ = [("n_used", C.c_int64), ("n_rejected", C.c_int64), ("lag", C.c_int64),
+                ("min_ess_M", C.c_double), ("min_ess_l", C.c_double), ("max_rhat", C.c_double),
+                ("bin_min_ess_M", C.c_int64), ("bin_min_ess_l", C.c_int64), ("bin_max_rhat", C.c_int64),
+                ("n_truncated_M", C.c_int64), ("n_truncated_l", C.c_int64), ("n_rhat_high", C.c_int64)]
 
 
 class AccelError(RuntimeError):
@@ -140,6 +149,10 @@ def load_library():
     lib.tamcmc_summary_window_enable.argtypes = [vp, C.c_int32, C.c_int32, ip]
     lib.tamcmc_summary_window_result.argtypes = [vp, C.POINTER(SummaryWindowTotals), dp, dp, dp, dp]
     lib.tamcmc_summary_window_kernel_time.argtypes = [vp, dp, C.POINTER(C.c_int64)]
+    lib.tamcmc_summary_ess_begin.argtypes = [vp, C.c_int32, ip]
+    lib.tamcmc_summary_ess_result.argtypes = [vp, C.POINTER(SummaryEssTotals), dp, dp, dp, dp, ip, dp, dp, ip]
+    lib.tamcmc_summary_ess_acov.argtypes = [vp, C.c_int32, dp]
+    lib.tamcmc_summary_ess_end.argtypes = [vp]
     for name in EXPORTS:
         fn = getattr(lib, name)
         if fn.restype is not C.c_char_p:
@@ -448,7 +461,8 @@ class Summary:
     and of the pointwise log-likelihood over the parameter rows pushed so far, kept on the device.  Results do not depend,
     bit for bit, on block_chains or on how the rows are split over pushes.  quantiles() gives the exact per-bin quantiles
     of the model (credible bands) by pushing the same rows again a few times; loo() gives PSIS-LOO (elpd_loo and the
-    Pareto k-hat per bin) by pushing them once more.  With predictive=True every fold pass also accumulates the
+    Pareto k-hat per bin) by pushing them once more, and ess() the effective sample size, Monte-Carlo standard error and
+    split R-hat per bin by pushing them once more in the same order.  With predictive=True every fold pass also accumulates the
     posterior predictive check (predictive_result(): PIT and both log tail probabilities per bin), and with window=W or
     window=(W, first) the same check over disjoint windows of W bins (window_result()).  The Accel cannot be closed while
     the summary is open."""
@@ -503,6 +517,7 @@ class Summary:
         self._check(self._lib.tamcmc_summary_reset(self._s), "tamcmc_summary_reset")
         self._nq = 0                                            # reset leaves quantile mode
         self._loo = False                                       # and LOO mode
+        self._ess_lag = 0                                       # and ESS mode
 
     def profile(self, enable=True):
         self._check(self._lib.tamcmc_summary_profile(self._s, int(enable)), "tamcmc_summary_profile")
@@ -676,6 +691,52 @@ class Summary:
         self._check(self._lib.tamcmc_summary_window_kernel_time(self._s, C.byref(ms), C.byref(n)),
                     "tamcmc_summary_window_kernel_time")
         return ms.value, n.value
+
+    # ---- effective sample size, MCSE and split R-hat per bin, one more pass over the same rows in the same order ----
+    ESS_MAX_LAG = 1023
+    ESS_ARRAYS = ("ess_M", "tau_M", "mcse_M", "rhat_M", "cut_M", "ess_l", "r_eff", "cut_l")
+    ESS_TOTALS = ("n_used", "n_rejected", "lag", "min_ess_M", "min_ess_l", "max_rhat", "bin_min_ess_M", "bin_min_ess_l",
+                  "bin_max_rhat", "n_truncated_M", "n_truncated_l", "n_rhat_high")
+
+    def ess_begin(self, max_lag=0):
+        """Enters ESS mode with lags up to max_lag (0 = the library's default, 255); returns the lag limit L in use.  From
+        here on push / push_device feed the ESS kernels: push the same rows again in the same order, then ess_result()."""
+        lag = C.c_int32(0)
+        self._check(self._lib.tamcmc_summary_ess_begin(self._s, int(max_lag), C.byref(lag)), "tamcmc_summary_ess_begin")
+        self._ess_lag = int(lag.value)
+        return self._ess_lag
+
+    def ess_result(self):
+        """dict: ess_M, tau_M, mcse_M, rhat_M, ess_l, r_eff (Nx doubles), cut_M, cut_l (Nx int32) and the totals n_used,
+        n_rejected, lag, min_ess_M, min_ess_l, max_rhat with their bins, n_truncated_M, n_truncated_l, n_rhat_high."""
+        out = {k: np.empty(self.accel.Nx, dtype=np.int32 if k.startswith("cut") else np.float64) for k in self.ESS_ARRAYS}
+        t = SummaryEssTotals()
+        args = [(_iptr if k.startswith("cut") else _dptr)(out[k]) for k in self.ESS_ARRAYS]
+        self._check(self._lib.tamcmc_summary_ess_result(self._s, C.byref(t), *args), "tamcmc_summary_ess_result")
+        kinds = dict(SummaryEssTotals._fields_)
+        out.update({k: (getattr(t, k) if kinds[k] is C.c_double else int(getattr(t, k))) for k in self.ESS_TOTALS})
+        return out
+
+    def ess_acov(self, which):
+        """The lag products A_0 ... A_L of a complete pass, (L + 1, Nx): which = 0 the model series, 1 the likelihood series."""
+        acov = np.empty((max(getattr(self, "_ess_lag", 0), 0) + 1, self.accel.Nx))
+        self._check(self._lib.tamcmc_summary_ess_acov(self._s, int(which), _dptr(acov)), "tamcmc_summary_ess_acov")
+        return acov
+
+    def ess_end(self):
+        self._check(self._lib.tamcmc_summary_ess_end(self._s), "tamcmc_summary_ess_end")
+        self._ess_lag = 0
+
+    def ess(self, params, max_lag=0):
+        """ESS, MCSE and split R-hat over the rows already pushed, `params` being those rows in the same order: begin, one
+        push, result, end.  Returns the dict of ess_result() and always leaves the mode."""
+        self.ess_begin(max_lag)
+        try:
+            self.push(params)
+            return self.ess_result()
+        finally:
+            if getattr(self, "_ess_lag", 0):
+                self.ess_end()
 
     def close(self):
         if getattr(self, "_s", None) is not None and self._s.value:

@@ -7,10 +7,13 @@
 // (tamcmc_summary_predictive_*, tamcmc_predictive.h) a fold-mode block has a stage 3: tamcmc_summary_predictive_kernel on
 // the same rows; the other two modes never touch its state.  With the windowed check enabled (tamcmc_summary_window_*,
 // tamcmc_window.h) a stage 4 follows: the sums, tails and fold kernels of tamcmc_window.hip, again on the same rows.
+// In ESS mode (tamcmc_summary_ess_*, tamcmc_ess.h) stage 2 is the centre and lag kernels of tamcmc_ess.hip, once per chunk of
+// the block.
 #include <algorithm>
 #include <cmath>
 #include <new>
 
+#include "tamcmc_ess.h"
 #include "tamcmc_host.h"
 #include "tamcmc_loo.h"
 #include "tamcmc_predictive.h"
@@ -44,6 +47,21 @@ struct TmLooMode {
     double *body = nullptr, *elpd = nullptr, *khat = nullptr, *cutoff = nullptr;
     long long *cnt = nullptr;            // as tamcmc_summary::d_cnt, for the samples of the pass under way
     int32_t *tail_len = nullptr;
+    int parity = 0;
+};
+
+// ESS mode: the lag products, the rings of centred values and the half-chain moments of the pass on the device, and what the
+// host remembers of the fold pass.
+struct TmEssMode {
+    bool on = false;
+    int L = 0, R = 0;
+    long long n_used = 0, n_rejected = 0;   // of the fold pass, frozen by _begin
+    double *d_acc = nullptr;             // [2][L + 1][Nx]
+    double *d_ring = nullptr;            // [2][R][Nx]
+    char *d_state = nullptr;             // one allocation: half[4][Nx] | lppd | tau[2][Nx] | ess[2][Nx] | cnt[2][2] | cut[2][Nx]
+    double *half = nullptr, *lppd = nullptr, *tau = nullptr, *ess = nullptr;
+    long long *cnt = nullptr;            // as tamcmc_summary::d_cnt, for the samples of the pass under way
+    int32_t *cut = nullptr;
     int parity = 0;
 };
 
@@ -87,6 +105,7 @@ struct tamcmc_summary {
     TmTimer timer;
     TmQuantMode q;
     TmLooMode loo;
+    TmEssMode ess;
     TmPredictive pred;
     TmWindow win;
 };
@@ -189,6 +208,56 @@ static void loo_free(tamcmc_summary *s)
     s->loo = TmLooMode();
 }
 
+static TmEssArgs ess_args(const tamcmc_summary *s)
+{
+    const TmEssMode &m = s->ess;
+    const tamcmc_ctx *c = s->c;
+    TmEssArgs a{};
+    a.y = c->d_y; a.isig2 = c->d_isig2; a.mean_M = s->d_state + (size_t)TM_SUM_MEAN_M * (size_t)c->L.Nx; a.lppd = m.lppd;
+    a.ring = m.d_ring; a.acc = m.d_acc; a.half = m.half; a.tau = m.tau; a.ess = m.ess; a.cut = m.cut;
+    a.cnt_in = m.cnt + 2 * m.parity; a.cnt_out = m.cnt + 2 * (m.parity ^ 1);
+    a.n = m.n_used; a.h = m.n_used / 2;
+    a.Nx = c->L.Nx; a.L = m.L; a.R = m.R; a.likelihood_case = c->L.likelihood_case; a.like_p = c->L.like_p;
+    a.tau_floor = 1.0 / std::log10((double)m.n_used);
+    return a;
+}
+
+// stage 2 of a block in ESS mode: per chunk of the block the centre kernel and the lag kernel in the fold kernel's place
+static int ess_block(tamcmc_summary *s, int n, const int32_t *d_status)
+{
+    tamcmc_ctx *c = s->c;
+    int rc = TAMCMC_OK;
+    if (s->profile) { rc = s->timer.begin(c->stream); if (rc != TAMCMC_OK) return rc; }
+    for (int k = 0; k < n; k += TM_ESS_CHUNK) {
+        TmEssArgs a = ess_args(s);
+        a.rows = s->d_model + (size_t)k * (size_t)c->L.Nx; a.status = d_status + k;
+        a.B = n - k < TM_ESS_CHUNK ? n - k : TM_ESS_CHUNK;
+        const int hr = tm_launch_ess_chunk(a, c->stream);
+        if (hr != 0) return tm_launch_failed("summary ess chunk", hr);
+        s->ess.parity ^= 1;
+    }
+    return s->profile ? s->timer.end(c->stream) : TAMCMC_OK;
+}
+
+// a pass starts from empty counts, lag products and half-chain moments (a ring slot is written before it is read)
+static int ess_pass_clear(tamcmc_summary *s)
+{
+    TmEssMode &m = s->ess;
+    const size_t nx = (size_t)s->c->L.Nx;
+    TM_HIP(hipMemsetAsync(m.cnt, 0, 4 * sizeof(long long), s->c->stream));
+    TM_HIP(hipMemsetAsync(m.d_acc, 0, 2 * (size_t)(m.L + 1) * nx * sizeof(double), s->c->stream));
+    TM_HIP(hipMemsetAsync(m.half, 0, (size_t)TM_ESS_NHALF * nx * sizeof(double), s->c->stream));
+    m.parity = 0;
+    return TAMCMC_OK;
+}
+
+// the stream must be idle
+static void ess_free(tamcmc_summary *s)
+{
+    (void)hipFree(s->ess.d_state); (void)hipFree(s->ess.d_acc); (void)hipFree(s->ess.d_ring);
+    s->ess = TmEssMode();
+}
+
 // stage 3 of a fold-mode block: the predictive kernel on the same rows, counting on from the pair the fold launch read
 static int predictive_block(tamcmc_summary *s, int n, const int32_t *d_status, const long long *cnt_in)
 {
@@ -235,6 +304,7 @@ static int summary_block(tamcmc_summary *s, int n, const double *d_params, doubl
     if (rc != TAMCMC_OK) return rc;
     if (s->q.on) return quantile_block(s, n, d_status);
     if (s->loo.on) return loo_block(s, n, d_status);
+    if (s->ess.on) return ess_block(s, n, d_status);
     TmSummaryArgs a{};
     a.rows = s->d_model; a.status = d_status; a.y = c->d_y; a.isig2 = c->d_isig2; a.state = s->d_state;
     a.cnt_in = s->d_cnt + 2 * s->parity; a.cnt_out = s->d_cnt + 2 * (s->parity ^ 1);
@@ -309,6 +379,7 @@ extern "C" int tamcmc_summary_destroy(tamcmc_summary *s)
     if (s->counted) c->summaries--;
     quantile_free(s);
     loo_free(s);
+    ess_free(s);
     (void)hipFree(s->d_model); (void)hipFree(s->d_state); (void)hipFree(s->d_cnt); (void)hipFree(s->d_rows);
     (void)hipFree(s->d_T); (void)hipFree(s->d_logL); (void)hipFree(s->d_status); (void)hipFree(s->pred.d_state);
     (void)hipFree(s->win.d_state); (void)hipFree(s->win.d_scratch);
@@ -328,10 +399,11 @@ extern "C" int tamcmc_summary_reset(tamcmc_summary *s)
     if (!s || s->c->in_flight || s->c->armed) return TAMCMC_E_INVALID;
     tamcmc_ctx *c = s->c;
     TM_HIP(hipSetDevice(c->device));
-    if (s->q.on || s->loo.on) {                     // reset leaves quantile mode and LOO mode
+    if (s->q.on || s->loo.on || s->ess.on) {        // reset leaves quantile mode, LOO mode and ESS mode
         TM_HIP(tm_ctx_stream_sync(c));
         quantile_free(s);
         loo_free(s);
+        ess_free(s);
     }
     TM_HIP(tm_ctx_settle(c));
     c->enq_seq++;
@@ -473,7 +545,7 @@ extern "C" int tamcmc_summary_quantiles_begin(tamcmc_summary *s, int32_t Nq, con
 {
     if (!s || !q || Nq < 1 || Nq > TAMCMC_SUMMARY_MAX_QUANTILES || bits_per_pass < 0 || bits_per_pass > TM_Q_MAXBITS) return TAMCMC_E_INVALID;
     tamcmc_ctx *c = s->c;
-    if (s->q.on || s->loo.on || c->in_flight || c->armed) return TAMCMC_E_INVALID;
+    if (s->q.on || s->loo.on || s->ess.on || c->in_flight || c->armed) return TAMCMC_E_INVALID;
     for (int j = 0; j < Nq; j++)
         if (!(q[j] >= 0.0 && q[j] <= 1.0)) return TAMCMC_E_INVALID;        // (a NaN fails both comparisons)
     TM_HIP(hipSetDevice(c->device));
@@ -600,7 +672,7 @@ extern "C" int tamcmc_summary_loo_begin(tamcmc_summary *s)
 {
     if (!s) return TAMCMC_E_INVALID;
     tamcmc_ctx *c = s->c;
-    if (s->q.on || s->loo.on || c->in_flight || c->armed) return TAMCMC_E_INVALID;
+    if (s->q.on || s->loo.on || s->ess.on || c->in_flight || c->armed) return TAMCMC_E_INVALID;
     TM_HIP(hipSetDevice(c->device));
     TM_HIP(tm_ctx_stream_sync(c));
     long long cnt[2] = {0, 0};
@@ -702,7 +774,7 @@ extern "C" int tamcmc_summary_predictive_enable(tamcmc_summary *s)
 {
     if (!s) return TAMCMC_E_INVALID;
     tamcmc_ctx *c = s->c;
-    if (s->pred.on || s->q.on || s->loo.on || c->in_flight || c->armed) return TAMCMC_E_INVALID;
+    if (s->pred.on || s->q.on || s->loo.on || s->ess.on || c->in_flight || c->armed) return TAMCMC_E_INVALID;
     const bool chi = c->L.likelihood_case == 0;
     if (chi && !(c->L.like_p >= 1.0 && c->L.like_p <= (double)TAMCMC_SUMMARY_PREDICTIVE_MAX_P)) return TAMCMC_E_INVALID;
     TM_HIP(hipSetDevice(c->device));
@@ -781,6 +853,7 @@ static int fold_counts(const tamcmc_summary *s, long long cnt[2])
 {
     if (s->q.on) { cnt[0] = s->q.n_used; cnt[1] = s->q.n_rejected; }
     else if (s->loo.on) { cnt[0] = s->loo.n_used; cnt[1] = s->loo.n_rejected; }
+    else if (s->ess.on) { cnt[0] = s->ess.n_used; cnt[1] = s->ess.n_rejected; }
     else TM_HIP(hipMemcpy(cnt, s->d_cnt + 2 * s->parity, 2 * sizeof(long long), hipMemcpyDeviceToHost));
     return TAMCMC_OK;
 }
@@ -827,7 +900,7 @@ extern "C" int tamcmc_summary_window_enable(tamcmc_summary *s, int32_t W, int32_
 {
     if (!s || W < 1 || W > TAMCMC_SUMMARY_WINDOW_MAX_BINS || first < 0 || first > W) return TAMCMC_E_INVALID;
     tamcmc_ctx *c = s->c;
-    if (s->win.on || s->q.on || s->loo.on || c->in_flight || c->armed) return TAMCMC_E_INVALID;
+    if (s->win.on || s->q.on || s->loo.on || s->ess.on || c->in_flight || c->armed) return TAMCMC_E_INVALID;
     const bool chi = c->L.likelihood_case == 0;
     if (chi && !(c->L.like_p >= 1.0 && c->L.like_p <= (double)TAMCMC_SUMMARY_WINDOW_MAX_SHAPE && (int)c->L.like_p * W <= TAMCMC_SUMMARY_WINDOW_MAX_SHAPE))
         return TAMCMC_E_INVALID;
@@ -894,4 +967,146 @@ extern "C" int tamcmc_summary_window_kernel_time(tamcmc_summary *s, double *tota
     TM_HIP(hipSetDevice(s->c->device));
     TM_HIP(tm_ctx_stream_sync(s->c));
     return s->win.timer.total(total_ms, launches);
+}
+
+// ---- effective sample size, MCSE and split R-hat (tamcmc_ess.h) ----
+
+extern "C" int tamcmc_summary_ess_begin(tamcmc_summary *s, int32_t max_lag, int32_t *lag_used)
+{
+    if (!s || max_lag < 0 || max_lag > TAMCMC_SUMMARY_ESS_MAX_LAG) return TAMCMC_E_INVALID;
+    tamcmc_ctx *c = s->c;
+    if (s->q.on || s->loo.on || s->ess.on || c->in_flight || c->armed) return TAMCMC_E_INVALID;
+    TM_HIP(hipSetDevice(c->device));
+    TM_HIP(tm_ctx_stream_sync(c));
+    long long cnt[2] = {0, 0};
+    TM_HIP(hipMemcpy(cnt, s->d_cnt + 2 * s->parity, sizeof(cnt), hipMemcpyDeviceToHost));
+    if (cnt[0] < 4) return TAMCMC_E_INVALID;
+    const size_t nx = (size_t)c->L.Nx;
+    std::vector<double> lse;
+    try { lse.resize(2 * nx); } catch (const std::bad_alloc &) { return TAMCMC_E_NOMEM; }
+    TM_HIP(hipMemcpy(lse.data(), s->d_state + (size_t)TM_SUM_LSE_A * nx, 2 * nx * sizeof(double), hipMemcpyDeviceToHost));   // a | r
+    const double dn = (double)cnt[0];
+    for (size_t i = 0; i < nx; i++) lse[i] = lse[i] + std::log(lse[nx + i] / dn);       // lppd_i, as tamcmc_summary_result
+    TmEssMode m;
+    m.L = tme_lag_limit(max_lag, cnt[0]);
+    m.R = tme_ring_slots(m.L);
+    m.n_used = cnt[0]; m.n_rejected = cnt[1];
+    const size_t state_bytes = (TM_ESS_NHALF + 1 + 4) * nx * sizeof(double) + 4 * sizeof(long long) + 2 * nx * sizeof(int32_t);
+    if (hipMalloc(&m.d_state, state_bytes) != hipSuccess) { (void)hipGetLastError(); return TAMCMC_E_NOMEM; }
+    if (hipMalloc(&m.d_acc, 2 * (size_t)(m.L + 1) * nx * sizeof(double)) != hipSuccess) { (void)hipGetLastError(); (void)hipFree(m.d_state); return TAMCMC_E_NOMEM; }
+    if (hipMalloc(&m.d_ring, 2 * (size_t)m.R * nx * sizeof(double)) != hipSuccess) {
+        (void)hipGetLastError(); (void)hipFree(m.d_state); (void)hipFree(m.d_acc);
+        return TAMCMC_E_NOMEM;
+    }
+    m.half = reinterpret_cast<double *>(m.d_state);
+    m.lppd = m.half + TM_ESS_NHALF * nx;
+    m.tau = m.lppd + nx;
+    m.ess = m.tau + 2 * nx;
+    m.cnt = reinterpret_cast<long long *>(m.ess + 2 * nx);
+    m.cut = reinterpret_cast<int32_t *>(m.cnt + 4);
+    m.on = true;
+    s->ess = m;
+    c->enq_seq++;
+    if (hipMemcpy(m.lppd, lse.data(), nx * sizeof(double), hipMemcpyHostToDevice) != hipSuccess || ess_pass_clear(s) != TAMCMC_OK) {
+        (void)hipStreamSynchronize(c->stream);
+        ess_free(s);
+        return TAMCMC_E_HIP;
+    }
+    if (lag_used) *lag_used = m.L;
+    return TAMCMC_OK;
+}
+
+// the pass under way saw exactly the fold pass's samples
+static int ess_pass_complete(tamcmc_summary *s, bool *complete)
+{
+    long long cnt[2] = {0, 0};
+    TM_HIP(hipMemcpy(cnt, s->ess.cnt + 2 * s->ess.parity, sizeof(cnt), hipMemcpyDeviceToHost));
+    *complete = cnt[0] == s->ess.n_used && cnt[1] == s->ess.n_rejected;
+    return TAMCMC_OK;
+}
+
+extern "C" int tamcmc_summary_ess_result(tamcmc_summary *s, tamcmc_summary_ess_totals *totals,
+                                         double *ess_M, double *tau_M, double *mcse_M, double *rhat_M, int32_t *cut_M,
+                                         double *ess_l, double *r_eff, int32_t *cut_l)
+{
+    if (!s || !s->ess.on || s->c->in_flight || s->c->armed) return TAMCMC_E_INVALID;
+    tamcmc_ctx *c = s->c;
+    TmEssMode &m = s->ess;
+    TM_HIP(hipSetDevice(c->device));
+    TM_HIP(tm_ctx_stream_sync(c));
+    c->enq_seq++;
+    bool complete = false;
+    int rc = ess_pass_complete(s, &complete);
+    if (rc != TAMCMC_OK) return rc;
+    if (!complete) {                                                    // not the fold pass's samples: the pass is discarded
+        rc = ess_pass_clear(s);
+        return rc != TAMCMC_OK ? rc : TAMCMC_E_INVALID;
+    }
+    const size_t nx = (size_t)c->L.Nx;
+    std::vector<double> out, half, m2;
+    std::vector<int32_t> cut;
+    try { out.resize(4 * nx); half.resize(TM_ESS_NHALF * nx); m2.resize(nx); cut.resize(2 * nx); } catch (const std::bad_alloc &) { return TAMCMC_E_NOMEM; }
+    const TmEssArgs a = ess_args(s);
+    if (s->profile) { rc = s->timer.begin(c->stream); if (rc != TAMCMC_OK) return rc; }
+    const int hr = tm_launch_ess_finish(a, c->stream);
+    if (hr != 0) return tm_launch_failed("summary ess finish", hr);
+    if (s->profile) { rc = s->timer.end(c->stream); if (rc != TAMCMC_OK) return rc; }
+    TM_HIP(hipMemcpyAsync(out.data(), m.tau, 4 * nx * sizeof(double), hipMemcpyDeviceToHost, c->stream));        // tau[2] | ess[2]
+    TM_HIP(hipMemcpyAsync(cut.data(), m.cut, 2 * nx * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    TM_HIP(hipMemcpyAsync(half.data(), m.half, half.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    TM_HIP(hipMemcpyAsync(m2.data(), s->d_state + (size_t)TM_SUM_M2_M * nx, nx * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    TM_HIP(hipStreamSynchronize(c->stream));
+    const double dn = (double)m.n_used, nan = std::nan("");
+    const double *tau = out.data(), *ess = out.data() + 2 * nx;
+    tamcmc_summary_ess_totals t{};
+    t.n_used = m.n_used; t.n_rejected = m.n_rejected; t.lag = m.L;
+    t.min_ess_M = nan; t.min_ess_l = nan; t.max_rhat = nan;
+    t.bin_min_ess_M = -1; t.bin_min_ess_l = -1; t.bin_max_rhat = -1;
+    for (size_t i = 0; i < nx; i++) {
+        const double eM = ess[i], el = ess[nx + i];
+        const double var_M = m2[i] / (dn - 1.0);                        // the frozen var_M of tamcmc_summary_result
+        const double rh = tme_rhat(half[TM_ESS_H1_MEAN * nx + i], half[TM_ESS_H1_M2 * nx + i], half[TM_ESS_H2_MEAN * nx + i],
+                                   half[TM_ESS_H2_M2 * nx + i], m.n_used / 2);
+        if (ess_M) ess_M[i] = eM;
+        if (tau_M) tau_M[i] = tau[i];
+        if (mcse_M) mcse_M[i] = std::sqrt(var_M / eM);
+        if (rhat_M) rhat_M[i] = rh;
+        if (cut_M) cut_M[i] = cut[i];
+        if (ess_l) ess_l[i] = el;
+        if (r_eff) r_eff[i] = el / dn;
+        if (cut_l) cut_l[i] = cut[nx + i];
+        // the first bin wins a tie, a NaN is skipped
+        if (t.bin_min_ess_M < 0 ? !std::isnan(eM) : eM < t.min_ess_M) { t.min_ess_M = eM; t.bin_min_ess_M = (int64_t)i; }
+        if (t.bin_min_ess_l < 0 ? !std::isnan(el) : el < t.min_ess_l) { t.min_ess_l = el; t.bin_min_ess_l = (int64_t)i; }
+        if (t.bin_max_rhat < 0 ? !std::isnan(rh) : rh > t.max_rhat) { t.max_rhat = rh; t.bin_max_rhat = (int64_t)i; }
+        if (cut[i] == m.L + 1) t.n_truncated_M++;
+        if (cut[nx + i] == m.L + 1) t.n_truncated_l++;
+        if (rh > 1.01) t.n_rhat_high++;
+    }
+    if (totals) *totals = t;
+    return TAMCMC_OK;
+}
+
+extern "C" int tamcmc_summary_ess_acov(tamcmc_summary *s, int32_t which, double *acov)
+{
+    if (!s || !s->ess.on || !acov || which < 0 || which > 1 || s->c->in_flight || s->c->armed) return TAMCMC_E_INVALID;
+    tamcmc_ctx *c = s->c;
+    TM_HIP(hipSetDevice(c->device));
+    TM_HIP(tm_ctx_stream_sync(c));
+    bool complete = false;
+    const int rc = ess_pass_complete(s, &complete);
+    if (rc != TAMCMC_OK) return rc;
+    if (!complete) return TAMCMC_E_INVALID;                             // (the pass stays: tamcmc_summary_ess_result discards it)
+    const size_t len = (size_t)(s->ess.L + 1) * (size_t)c->L.Nx;
+    TM_HIP(hipMemcpy(acov, s->ess.d_acc + (size_t)which * len, len * sizeof(double), hipMemcpyDeviceToHost));
+    return TAMCMC_OK;
+}
+
+extern "C" int tamcmc_summary_ess_end(tamcmc_summary *s)
+{
+    if (!s || !s->ess.on || s->c->in_flight || s->c->armed) return TAMCMC_E_INVALID;
+    TM_HIP(hipSetDevice(s->c->device));
+    TM_HIP(tm_ctx_stream_sync(s->c));
+    ess_free(s);
+    return TAMCMC_OK;
 }

@@ -3,7 +3,7 @@
 //
 //   chainsummary_hip <config dir> <model file> <data file> <params root> <output file>
 //                    [--chain m] [--slice s] [--first i] [--last j] [--thin k] [--block B]
-//                    [--quantiles q1,q2,...] [--qbits b] [--loo] [--predictive] [--window W[,first]]
+//                    [--quantiles q1,q2,...] [--qbits b] [--loo] [--predictive] [--window W[,first]] [--ess [L]]
 //
 // <config dir> is the reference's Config/default; model id, likelihood, p, plength, the inputs row and the relax mask
 // come from the setup it describes (tamcmc_setup_create / tamcmc_setup_load, slice s counted from 0).  The samples are
@@ -32,6 +32,12 @@
 // n_rejected= ...`, `# ks_D= ...  min_log_sf= ...  win_min_log_sf= ...  min_log_cdf= ...  win_min_log_cdf= ...`,
 // `# pit_hist= c0 c1 ... c19` -- then one row per window:
 //   w  first_bin  last_bin  x_first  x_last  pit  log_cdf  log_sf  mean_resid
+// With --ess [L] the selected samples are read once more for the effective sample size, the Monte-Carlo standard error and
+// the split R-hat per bin (tamcmc_summary_ess_*; lags up to L, 0 ... 1023, default 0: the library's 255).  The output file
+// keeps every byte; the results go to <output file>.ess: `#` header lines -- the version, `# n_used= ...  n_rejected= ...
+// lag= ...`, `# min_ess_M= ...  bin_min_ess_M= ...  min_ess_l= ...  bin_min_ess_l= ...`, `# max_rhat= ...  bin_max_rhat= ...
+// n_rhat_high= ...`, `# n_truncated_M= ...  n_truncated_l= ...` -- then one row per bin:
+//   x  ess_M  tau_M  mcse_M  rhat_M  cut_M  ess_l  r_eff  cut_l
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -47,7 +53,7 @@ static int usage()
 {
     fprintf(stderr, " Usage: chainsummary_hip <config dir> <model file> <data file> <params root> <output file>\n"
                     "                         [--chain m] [--slice s] [--first i] [--last j] [--thin k] [--block B]\n"
-                    "                         [--quantiles q1,q2,...] [--qbits b] [--loo] [--predictive] [--window W[,first]]\n"
+                    "                         [--quantiles q1,q2,...] [--qbits b] [--loo] [--predictive] [--window W[,first]] [--ess [L]]\n"
                     "     [1] The directory of config_default.cfg, errors_default.cfg and the *_ctrl.list files (Config/default)\n"
                     "     [2] The .model file and [3] the .data file of the fit\n"
                     "     [4] The root of the parameter files: <root>_chain-<m>.bin and <root>.hdr\n"
@@ -65,6 +71,9 @@ static int usage()
                     "     --window W[,first]   the same check over disjoint windows of W bins (1 ... 512; likelihood p times W at most 512),\n"
                     "             the first window `first` bins long (1 ... W, default W): written to <output file>.windows, one row per\n"
                     "             window, w first_bin last_bin x_first x_last pit log_cdf log_sf mean_resid (no further pass; [5] is unchanged)\n"
+                    "     --ess [L]   effective sample size, Monte-Carlo standard error and split R-hat per bin from the autocorrelation up\n"
+                    "             to lag L (0 ... 1023, default 0: the library's 255): written to <output file>.ess, one row per bin,\n"
+                    "             x ess_M tau_M mcse_M rhat_M cut_M ess_l r_eff cut_l (the samples are read once more; [5] is unchanged)\n"
                     " chainsummary_hip version   prints the library version\n");
     return EXIT_FAILURE;
 }
@@ -102,11 +111,21 @@ int main(int argc, char *argv[])
     std::vector<double> quant;
     std::string quant_text;
     bool loo = false, predictive = false;
-    long win_W = 0, win_first = 0;
+    long win_W = 0, win_first = 0, ess_lag = -1;            // ess_lag < 0: no --ess
     for (int i = 6; i < argc; i++) {
         const std::string a = argv[i];
         if (a == "--loo") { loo = true; continue; }
         if (a == "--predictive") { predictive = true; continue; }
+        if (a == "--ess") {                         // alone, or followed by the lag limit
+            if (ess_lag >= 0) return usage();
+            ess_lag = 0;
+            if (i + 1 < argc && argv[i + 1][0] >= '0' && argv[i + 1][0] <= '9') {
+                char *end = nullptr;
+                ess_lag = strtol(argv[++i], &end, 10);
+                if (*end != '\0' || ess_lag > TAMCMC_SUMMARY_ESS_MAX_LAG) return usage();
+            }
+            continue;
+        }
         if (a == "--window") {                      // W or W,first
             if (i + 1 >= argc || win_W != 0) return usage();
             char *end = nullptr;
@@ -261,6 +280,21 @@ int main(int argc, char *argv[])
         if (rc != TAMCMC_OK) return lfail("tamcmc_summary_loo_result");
         tamcmc_summary_loo_end(sum);
     }
+    // ESS, MCSE and split R-hat: the same samples once more, in the same order
+    tamcmc_summary_ess_totals et{};
+    const size_t Ne = ess_lag >= 0 ? (size_t)Nx : 0;
+    std::vector<double> ess_M(Ne), tau_M(Ne), mcse_M(Ne), rhat_M(Ne), ess_l(Ne), r_eff(Ne);
+    std::vector<int32_t> cut_M(Ne), cut_l(Ne);
+    if (ess_lag >= 0) {
+        auto efail = [&](const char *what) { return fail(std::string(what) + ": " + tamcmc_strerror(rc) + " " + tamcmc_last_hip_error()); };
+        rc = tamcmc_summary_ess_begin(sum, (int32_t)ess_lag, nullptr);
+        if (rc != TAMCMC_OK) return efail("tamcmc_summary_ess_begin");
+        if (push_selected() != 0) return EXIT_FAILURE;
+        rc = tamcmc_summary_ess_result(sum, &et, ess_M.data(), tau_M.data(), mcse_M.data(), rhat_M.data(), cut_M.data(), ess_l.data(), r_eff.data(),
+                                       cut_l.data());
+        if (rc != TAMCMC_OK) return efail("tamcmc_summary_ess_result");
+        tamcmc_summary_ess_end(sum);
+    }
     tamcmc_summary_destroy(sum);
     tamcmc_ctx_destroy(ctx);
 
@@ -313,6 +347,22 @@ int main(int argc, char *argv[])
                     x[(size_t)(e - 1)], wpit[(size_t)w], wlog_cdf[(size_t)w], wlog_sf[(size_t)w], wmean_resid[(size_t)w]);
         }
         fclose(ow);
+    }
+    if (ess_lag >= 0) {
+        const std::string ess_file = out_file + ".ess";
+        FILE *oe = fopen(ess_file.c_str(), "w");
+        if (!oe) return fail("unable to open the output file " + ess_file);
+        fprintf(oe, "# chainsummary_hip (%s)\n", tamcmc_version());
+        fprintf(oe, "# n_used= %lld  n_rejected= %lld  lag= %lld\n", (long long)et.n_used, (long long)et.n_rejected, (long long)et.lag);
+        fprintf(oe, "# min_ess_M= %.12g  bin_min_ess_M= %lld  min_ess_l= %.12g  bin_min_ess_l= %lld\n", et.min_ess_M, (long long)et.bin_min_ess_M,
+                et.min_ess_l, (long long)et.bin_min_ess_l);
+        fprintf(oe, "# max_rhat= %.12g  bin_max_rhat= %lld  n_rhat_high= %lld\n", et.max_rhat, (long long)et.bin_max_rhat, (long long)et.n_rhat_high);
+        fprintf(oe, "# n_truncated_M= %lld  n_truncated_l= %lld\n", (long long)et.n_truncated_M, (long long)et.n_truncated_l);
+        fprintf(oe, "# x ess_M tau_M mcse_M rhat_M cut_M ess_l r_eff cut_l\n");
+        for (int64_t i = 0; i < Nx; i++)
+            fprintf(oe, "%.12g %.12g %.12g %.12g %.12g %d %.12g %.12g %d\n", x[(size_t)i], ess_M[(size_t)i], tau_M[(size_t)i], mcse_M[(size_t)i],
+                    rhat_M[(size_t)i], (int)cut_M[(size_t)i], ess_l[(size_t)i], r_eff[(size_t)i], (int)cut_l[(size_t)i]);
+        fclose(oe);
     }
     printf("Summary of %lld samples (%lld rejected) written to %s\n", (long long)t.n_used, (long long)t.n_rejected, out_file.c_str());
     return 0;

@@ -24,6 +24,11 @@ Prints one JSON line:
                             pass with the check off and on, alternating in one run, and from a profiled pass the fold kernel
                             alone beside the three window kernels together (Summary.window_kernel_time) and the eval launches.
                             Only this leg runs.
+  h_ess_*                   with --ess L (0: the library's default lag limit): the fold pass and the ESS pass of the same rows
+                            through Summary.push, alternating in one run (seconds per 1000 samples), and from profiled passes the
+                            fold kernel alone beside the ESS kernels alone (centre and lag kernels of every block,
+                            Summary.kernel_time in ESS mode) and the eval launches, the finish kernel, ess_result on the host
+                            clock, and the device memory the mode allocates.  Only this leg runs.
 Every timed shape is warmed up first (--warmup pushes); host clocks stop after calls that end in a device synchronise.
 """
 import argparse
@@ -141,6 +146,66 @@ def window_leg(a, w, y, P):
     return out
 
 
+def ess_leg(a, w, y, P):
+    """(h) the fold pass beside the ESS pass of the same rows, and the kernels' own times."""
+    out = {}
+    with tamcmc_amd.Accel(2, w["plength"], w["x"], y) as acc:
+        with tamcmc_amd.Summary(acc, a.block) as s:
+            times = {"fold": [], "ess": []}
+            for k in range(a.warmup + a.steps):
+                s.reset()
+                acc.synchronize()
+                t0 = time.perf_counter()
+                s.push(P)                                   # synchronous: results are on the host on return
+                t1 = time.perf_counter()
+                L = s.ess_begin(a.ess)
+                acc.synchronize()
+                t2 = time.perf_counter()
+                s.push(P)
+                t3 = time.perf_counter()
+                if k >= a.warmup:
+                    times["fold"].append(t1 - t0)
+                    times["ess"].append(t3 - t2)
+                if k + 1 < a.warmup + a.steps:
+                    s.ess_end()
+            for key, v in times.items():
+                out[f"h_ess_{key}_pass_s_per_1000"] = float(np.median(v)) * 1000.0 / a.samples
+                out[f"h_ess_{key}_pass_spread"] = [float(min(v)) * 1000.0 / a.samples, float(max(v)) * 1000.0 / a.samples]
+            acc.synchronize()
+            t0 = time.perf_counter()
+            r = s.ess_result()
+            t_result = time.perf_counter() - t0
+            s.profile(True)                                 # the finish kernel alone: a second result without another pass
+            s.ess_result()
+            fin_ms, fin_launches = s.kernel_time()
+            s.profile(False)
+            s.ess_end()
+            s.reset()                                       # the kernels alone: a profiled fold pass, then a profiled ESS pass
+            s.profile(True)
+            acc.profile(True)
+            s.push(P)
+            fold_ms, fold_launches = s.kernel_time()
+            eval_ms, eval_launches = acc.kernel_time()
+            acc.profile(False)
+            s.profile(False)
+            s.ess_begin(a.ess)
+            s.profile(True)
+            s.push(P)
+            ess_ms, ess_blocks = s.kernel_time()
+            s.profile(False)
+            s.ess_end()
+            out.update(h_ess_lag=L, h_ess_blocks=ess_blocks, h_ess_us_per_block=ess_ms * 1e3 / ess_blocks,
+                       h_ess_kernels_s_per_1000=ess_ms * 1e-3 * 1000.0 / a.samples,
+                       h_fold_kernel_s_per_1000=fold_ms * 1e-3 * 1000.0 / a.samples,
+                       h_eval_kernel_s_per_1000=eval_ms * 1e-3 * 1000.0 / a.samples,
+                       h_ess_fma_per_s=2.0 * (L + 1) * a.nx * a.samples / (ess_ms * 1e-3),
+                       h_ess_result_s=t_result, h_ess_finish_ms=fin_ms / max(fin_launches, 1),
+                       h_ess_bytes=(32 * L + 1120) * a.nx + 32,
+                       h_ess_min_ess_M=r["min_ess_M"], h_ess_min_ess_l=r["min_ess_l"], h_ess_max_rhat=r["max_rhat"],
+                       h_ess_n_truncated_M=r["n_truncated_M"], n_used=r["n_used"])
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--samples", type=int, default=4096)
@@ -154,6 +219,7 @@ def main():
     ap.add_argument("--predictive", action="store_true")
     ap.add_argument("--like-p", type=int, default=1)
     ap.add_argument("--window", type=int, default=0)
+    ap.add_argument("--ess", type=int, default=-1)
     a = ap.parse_args()
     if a.steps < 1 or a.warmup < 0 or a.samples < 1 or a.samples_b < 2:
         ap.error("--steps >= 1, --warmup >= 0, --samples >= 1, --samples-b >= 2")
@@ -164,8 +230,8 @@ def main():
     assert st == 0
     y = synth.make_spectrum(m_true)
     out = dict(tool="summary_time", Nx=a.nx, samples=a.samples, steps=a.steps, warmup=a.warmup, version=tamcmc_amd.capi.version())
-    if a.predictive or a.window:
-        out.update(window_leg(a, w, y, P) if a.window else predictive_leg(a, w, y, P))
+    if a.predictive or a.window or a.ess >= 0:
+        out.update(ess_leg(a, w, y, P) if a.ess >= 0 else window_leg(a, w, y, P) if a.window else predictive_leg(a, w, y, P))
         print(json.dumps(out))
         return
     with tamcmc_amd.Accel(2, w["plength"], w["x"], y) as acc:
