@@ -8,7 +8,7 @@
 // compiler: the only fused operation is the one written out as fma() in tme_acc.
 //
 //   series   model        a_t = M_t - mean_M                                                              tme_centre_model
-//            likelihood   u_t = exp(l_t - lppd) - 1.0, l as the fold kernel computes it                   tme_like, tme_centre_like
+//            likelihood   u_t = exp(l_t - lppd) - 1.0, l = tms_like (tamcmc_summary_walk.h)                tme_centre_like
 //            t = 0 ... n - 1 counts ACCEPTED samples in push order; mean_M and lppd are the frozen fold results
 //   lags     L = the largest odd number <= min(max_lag | 1, n - 1), max_lag = 0 meaning TM_ESS_DEFAULT_LAG   tme_lag_limit
 //   A_k      = sum_{t=k}^{n-1} d_t d_{t-k}, k = 0 ... L.  ACCUMULATION RULE: one accumulator per (bin, k), started at +0.0 and
@@ -51,13 +51,6 @@ TME_FN int tme_lag_limit(const int max_lag, const long long n)
 }
 
 TME_FN int tme_ring_slots(const int L) { return L + TM_ESS_CHUNK; }
-
-// l of one (sample, bin), as tamcmc_summary.hip and tamcmc_loo.hip state it
-TME_FN double tme_like(const bool chi_square, const double y, const double M, const double isig2, const double p)
-{
-    if (chi_square) { const double dd = y - M; return -((dd * dd) * isig2); }
-    return -p * (y / M + log(M));
-}
 
 TME_FN double tme_centre_model(const double M, const double mean_M) { return M - mean_M; }
 TME_FN double tme_centre_like(const double l, const double lppd) { return exp(l - lppd) - 1.0; }

@@ -4,7 +4,8 @@
 // A block is cut into chunks of at most TM_ESS_CHUNK pushed samples; a chunk is two launches.
 //
 // Centre kernel.  One thread owns one bin, as in the fold kernel (tamcmc_summary.hip): rows are read coalesced with 64-bit
-// row offsets; the status words come from device memory and a sample that is not OK is skipped and counted.  For every
+// row offsets; the status words come from device memory and a sample that is not OK is skipped and counted.  The loop is the
+// kernel's own, one load at a time: tms_walk (tamcmc_summary_walk.h) changes its registers; l is tms_like.  For every
 // accepted sample t the thread writes the two centred values a_t = M - mean_M and u_t = exp(l - lppd) - 1 into slot t mod R
 // of the two rings (R = L + TM_ESS_CHUNK: the chunk's values land behind the L values before them, which stay readable), and
 // folds M into the Welford moments of the half-chain t belongs to.  Thread 0 stores the new {accepted, rejected} pair into
@@ -22,11 +23,12 @@
 #include <hip/hip_runtime.h>
 #include <cmath>
 
-// no FMA contraction anywhere in this file: l must round as the fold kernel's does, and the shared arithmetic of
-// tamcmc_ess.h is compiled under the same rule (its one fused operation is written out)
+// no FMA contraction anywhere in this file: the shared arithmetic of tamcmc_ess.h is compiled under that rule (its one
+// fused operation is written out)
 #pragma clang fp contract(off)
 
 #include "tamcmc_ess.h"
+#include "tamcmc_summary_walk.h"
 
 __global__ __launch_bounds__(TM_ESS_THREADS) void tamcmc_ess_centre_kernel(const TmEssArgs a)
 {
@@ -36,10 +38,7 @@ __global__ __launch_bounds__(TM_ESS_THREADS) void tamcmc_ess_centre_kernel(const
     long long t = a.cnt_in[0], rej = a.cnt_in[1];
     const int R = a.R;
     int slot = (int)(t % R);
-    const double y = a.y[bin];
-    const bool chi2 = a.likelihood_case != 0;
-    const double is2 = chi2 ? a.isig2[bin] : 0.0;
-    const double p = a.like_p;
+    const TmsBinLike lk(a, bin);
     const double mean_M = a.mean_M[bin], lppd = a.lppd[bin];
     double *const hs = a.half + bin;
     double m1 = hs[TM_ESS_H1_MEAN * nx], q1 = hs[TM_ESS_H1_M2 * nx], m2 = hs[TM_ESS_H2_MEAN * nx], q2 = hs[TM_ESS_H2_M2 * nx];
@@ -50,7 +49,7 @@ __global__ __launch_bounds__(TM_ESS_THREADS) void tamcmc_ess_centre_kernel(const
         const double v = rows[(size_t)s * nx];                               // (a rejected sample's row is loaded and dropped)
         if (a.status[s] != 0) { rej++; continue; }
         ring_M[(size_t)slot * nx] = tme_centre_model(v, mean_M);
-        ring_l[(size_t)slot * nx] = tme_centre_like(tme_like(chi2, y, v, is2, p), lppd);
+        ring_l[(size_t)slot * nx] = tme_centre_like(lk.l(v), lppd);
         if (t < a.h) tme_welford(&m1, &q1, t + 1, v);
         if (t >= a.n - a.h && t < a.n) tme_welford(&m2, &q2, t - (a.n - a.h) + 1, v);
         t++;
@@ -92,12 +91,11 @@ static bool ess_args_ok(const TmEssArgs &a)
 int tm_launch_ess_chunk(const TmEssArgs &a, void *stream)
 {
     if (!ess_args_ok(a) || a.B < 1 || a.B > TM_ESS_CHUNK) return (int)hipErrorInvalidValue;
-    const unsigned blocks = (unsigned)(((long long)a.Nx + TM_ESS_THREADS - 1) / TM_ESS_THREADS);
-    hipLaunchKernelGGL(tamcmc_ess_centre_kernel, dim3(blocks), dim3(TM_ESS_THREADS), 0, (hipStream_t)stream, a);
+    hipLaunchKernelGGL(tamcmc_ess_centre_kernel, dim3(tms_blocks(a.Nx, TM_ESS_THREADS)), dim3(TM_ESS_THREADS), 0, (hipStream_t)stream, a);
     int rc = (int)hipGetLastError();
     if (rc != 0) return rc;
     const int groups = (a.L + 1 + TM_ESS_G - 1) / TM_ESS_G;
-    const dim3 grid((unsigned)(((long long)a.Nx + TM_ESS_BINS - 1) / TM_ESS_BINS), (unsigned)((groups + TM_ESS_GROUPS - 1) / TM_ESS_GROUPS), 2);
+    const dim3 grid(tms_blocks(a.Nx, TM_ESS_BINS), (unsigned)((groups + TM_ESS_GROUPS - 1) / TM_ESS_GROUPS), 2);
     hipLaunchKernelGGL(tamcmc_ess_lag_kernel, grid, dim3(TM_ESS_BINS, TM_ESS_GROUPS), 0, (hipStream_t)stream, a);
     return (int)hipGetLastError();
 }
@@ -105,7 +103,6 @@ int tm_launch_ess_chunk(const TmEssArgs &a, void *stream)
 int tm_launch_ess_finish(const TmEssArgs &a, void *stream)
 {
     if (!ess_args_ok(a) || a.n < 1) return (int)hipErrorInvalidValue;
-    const unsigned blocks = (unsigned)(((long long)a.Nx + TM_ESS_THREADS - 1) / TM_ESS_THREADS);
-    hipLaunchKernelGGL(tamcmc_ess_finish_kernel, dim3(blocks, 2), dim3(TM_ESS_THREADS), 0, (hipStream_t)stream, a);
+    hipLaunchKernelGGL(tamcmc_ess_finish_kernel, dim3(tms_blocks(a.Nx, TM_ESS_THREADS), 2), dim3(TM_ESS_THREADS), 0, (hipStream_t)stream, a);
     return (int)hipGetLastError();
 }

@@ -6,7 +6,7 @@
 // (tests/cpp/loo_core_check.cpp, built with g++) call these same functions.  tamcmc_loo.hip includes this header under
 // `#pragma clang fp contract(off)`, so on the device none of it is contracted into FMAs.
 //
-//   x_s = -l_is over the n accepted samples (l as the fold kernel computes it), xmax = max x, z = x - xmax
+//   x_s = -l_is over the n accepted samples (l = tms_like, tamcmc_summary_walk.h), xmax = max x, z = x - xmax
 //   M        = (int64)ceil(fmin(n / 5.0, 3.0 * sqrt((double)n)))                                         tml_tail_M
 //   top set  the exact multiset of the M + 1 largest x seen so far: a binary min-heap of M + 1 slots, slot k of bin i at
 //            heap[k * stride + i]; its root (the (M+1)-th largest = the cutoff) is also kept in a register by the caller,

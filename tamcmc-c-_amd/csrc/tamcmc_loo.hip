@@ -1,19 +1,17 @@
 // tamcmc_loo.hip -- stage 2 of a block of samples while a summary object is in LOO mode (tamcmc_loo.h), and the kernel that
 // turns the pass into per-bin PSIS-LOO results.
 //
-// Tail kernel.  One thread owns one bin, as in the fold kernel (tamcmc_summary.hip): rows are read coalesced with 64-bit
-// row offsets, TM_LOO_UNROLL loads requested before the first is used; the status words come from device memory and a
-// sample that is not OK is skipped and counted.  Per bin the thread keeps the exact multiset of the M + 1 largest
-// x = -l seen so far in a binary min-heap laid out [slot][Nx] (a wave's accesses to one slot are consecutive), with the
-// root in a register: the common sample (x <= root) goes into the body's running-maximum log-sum-exp (a Kahan sum whose
-// maximum follows lazily: tamcmc_loo.h) and touches no memory.
+// Tail kernel.  One thread owns one bin and walks the block's rows as the fold kernel does: rows are read coalesced with
+// 64-bit row offsets, TM_LOO_UNROLL loads requested before the first is used; the status words come from device memory and
+// a sample that is not OK is skipped and counted.  The loop is written out here and is not tms_walk
+// (tamcmc_summary_walk.h): DESIGN.md has the measurement.  Per bin the thread keeps the exact multiset of the M + 1
+// largest x = -l seen so far in a binary min-heap laid out [slot][Nx] (a wave's accesses to one slot are consecutive),
+// with the root in a register: the common sample (x <= root) goes into the body's running-maximum log-sum-exp (a Kahan sum
+// whose maximum follows lazily: tamcmc_loo.h) and touches no memory.
 // While the heap fills, every thread writes the same slots (the number of accepted samples is the same for every bin); a
 // replacement walks down a path of its own.  No LDS, no atomics, no cross-thread reduction: a bin's state after a pass is
 // bit for bit independent of the block size and of how the pass was split over pushes.
-// l is the fold kernel's, restated (tests/test_summary_loo_gpu.py pins that the two agree bit for bit), without FMA
-// contraction:
-//     chi(2,2p)    l = -p (y / M + log M)
-//     chi_square   l = -(y - M)^2 / sigma^2
+// l is the fold kernel's: both call tms_like (tamcmc_summary_walk.h).
 //
 // Finalize kernel.  One wave per bin.  The bin's heap goes into LDS (the M <= 2048 values above the root, padded with
 // +inf to a power of two), is sorted ascending by a bitonic network, and tml_finalize (tamcmc_loo.h) does the rest with
@@ -23,11 +21,12 @@
 #include <hip/hip_runtime.h>
 #include <cmath>
 
-// no FMA contraction anywhere in this file: the two formulas for l must round as the fold kernel's do, and the shared
-// arithmetic of tamcmc_loo.h (heap, body sum, tml_finalize) is compiled under the same rule
+// no FMA contraction anywhere in this file: the shared arithmetic of tamcmc_loo.h (heap, body sum, tml_finalize) is
+// compiled under that rule
 #pragma clang fp contract(off)
 
 #include "tamcmc_loo.h"
+#include "tamcmc_summary_walk.h"
 
 __global__ __launch_bounds__(TM_LOO_THREADS) void tamcmc_loo_tail_kernel(const TmLooArgs a)
 {
@@ -38,12 +37,8 @@ __global__ __launch_bounds__(TM_LOO_THREADS) void tamcmc_loo_tail_kernel(const T
     double *const heap = a.heap + bin;
     double root = n > 0 ? heap[0] : 0.0;
     double ba = a.body[bin], br = a.body[nx + bin], bc = a.body[2 * nx + bin];
-    const double y = a.y[bin];
-    const bool chi2 = a.likelihood_case != 0;
-    const double is2 = chi2 ? a.isig2[bin] : 0.0;
-    const double p = a.like_p;
+    const TmsBinLike lk(a, bin);
     const double *__restrict__ rows = a.rows + bin;
-
     for (int s0 = 0; s0 < a.B; s0 += TM_LOO_UNROLL) {
         double v[TM_LOO_UNROLL];
 #pragma unroll
@@ -53,10 +48,7 @@ __global__ __launch_bounds__(TM_LOO_THREADS) void tamcmc_loo_tail_kernel(const T
         for (int k = 0; k < TM_LOO_UNROLL; k++) {
             if (s0 + k >= a.B) break;
             if (a.status[s0 + k] != 0) { rej++; continue; }
-            double l;
-            if (chi2) { const double dd = y - v[k]; l = -((dd * dd) * is2); }
-            else l = -p * (y / v[k] + log(v[k]));
-            tml_top_push(heap, nx, a.cap, n, -l, &root, &ba, &br, &bc);
+            tml_top_push(heap, nx, a.cap, n, -lk.l(v[k]), &root, &ba, &br, &bc);
             n++;
         }
     }
@@ -112,8 +104,7 @@ __global__ __launch_bounds__(TM_LOO_THREADS) void tamcmc_loo_finalize_kernel(con
 int tm_launch_loo_tail(const TmLooArgs &a, void *stream)
 {
     if (a.cap < 2 || a.cap > TM_LOO_MAX_TAIL + 1) return (int)hipErrorInvalidValue;
-    const unsigned blocks = (unsigned)(((long long)a.Nx + TM_LOO_THREADS - 1) / TM_LOO_THREADS);
-    hipLaunchKernelGGL(tamcmc_loo_tail_kernel, dim3(blocks), dim3(TM_LOO_THREADS), 0, (hipStream_t)stream, a);
+    hipLaunchKernelGGL(tamcmc_loo_tail_kernel, dim3(tms_blocks(a.Nx, TM_LOO_THREADS)), dim3(TM_LOO_THREADS), 0, (hipStream_t)stream, a);
     return (int)hipGetLastError();
 }
 

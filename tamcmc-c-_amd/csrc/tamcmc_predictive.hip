@@ -5,9 +5,10 @@
 // Shaped like the fold kernel (tamcmc_summary.hip).  One thread owns one bin: it loads the bin's seven state words, walks
 // the block's rows ONE SAMPLE AT A TIME IN PUSH ORDER and stores the state back.  Rows are read coalesced with 64-bit row
 // offsets, TM_PRED_UNROLL loads requested before the first is used; the status words come from device memory and a sample
-// that is not OK is skipped (a wave-uniform test).  No LDS, no barrier, no atomics, no cross-lane work: a bin's results
-// are bit for bit independent of the block size and of how the samples were split over pushes.  The number of accepted
-// samples before the block is the pair the block's fold launch read; this kernel writes no count.
+// that is not OK is skipped (a wave-uniform test).  The loop is written out here and is not tms_walk
+// (tamcmc_summary_walk.h): DESIGN.md has the measurement.  No LDS, no barrier, no atomics, no cross-lane work: a bin's
+// results are bit for bit independent of the block size and of how the samples were split over pushes.  The number of
+// accepted samples before the block is the pair the block's fold launch read; this kernel writes no count.
 //
 // Which of the three per-sample routines runs is decided by launch arguments alone (likelihood, p): chi_square; p = 1,
 // which has no loop; p > 1, whose two loops have trip counts fixed by p (tamcmc_predictive.h says how its lane-dependent
@@ -18,6 +19,7 @@
 #pragma clang fp contract(off)
 
 #include "tamcmc_predictive.h"
+#include "tamcmc_summary_walk.h"
 
 __global__ __launch_bounds__(TM_PRED_THREADS) void tamcmc_summary_predictive_kernel(const TmPredArgs a)
 {
@@ -46,12 +48,12 @@ __global__ __launch_bounds__(TM_PRED_THREADS) void tamcmc_summary_predictive_ker
             if (s0 + k >= a.B) break;
             if (a.status[s0 + k] != 0) continue;
             n++;
-            double resid, lP, lQ;
+            double resid, lP, lQ;                             // (the residual is formed inside its branch: see DESIGN.md)
             if (gauss) {
-                resid = (y - v[k]) * isig;
+                resid = tms_resid(true, y, v[k], isig);
                 tmp_gauss(resid, &lP, &lQ);
             } else {
-                resid = y / v[k];
+                resid = tms_resid(false, y, v[k], isig);
                 if (p == 1) tmp_chi_p1(resid, &lP, &lQ);
                 else tmp_chi_p(p, a.lf_pm1, a.lf_p, a.nterms, dp * y / v[k], &lP, &lQ);
             }
@@ -69,7 +71,6 @@ __global__ __launch_bounds__(TM_PRED_THREADS) void tamcmc_summary_predictive_ker
 int tm_launch_predictive(const TmPredArgs &a, void *stream)
 {
     if (a.likelihood_case == 0 && (a.p < 1 || a.p > TM_PRED_MAX_P)) return (int)hipErrorInvalidValue;
-    const unsigned blocks = (unsigned)(((long long)a.Nx + TM_PRED_THREADS - 1) / TM_PRED_THREADS);
-    hipLaunchKernelGGL(tamcmc_summary_predictive_kernel, dim3(blocks), dim3(TM_PRED_THREADS), 0, (hipStream_t)stream, a);
+    hipLaunchKernelGGL(tamcmc_summary_predictive_kernel, dim3(tms_blocks(a.Nx, TM_PRED_THREADS)), dim3(TM_PRED_THREADS), 0, (hipStream_t)stream, a);
     return (int)hipGetLastError();
 }

@@ -1,14 +1,13 @@
 // tamcmc_quantile.hip -- stage 2 of a block of samples while a summary object selects quantiles (tamcmc_quantile.h): count
 // the block's model rows into per-bin histograms of the next few key bits, and, between passes, narrow every bracket.
 //
-// Histogram kernel.  One thread owns one bin, as in the fold kernel (tamcmc_summary.hip): rows are read coalesced with
-// 64-bit row offsets, TM_Q_UNROLL loads requested before the first is used; the status words come from device memory and a
-// sample that is not OK is skipped and counted.  A workgroup is one wave.  The block's counts go into 16-bit LDS counters
-// laid out [quantile][cell][thread]: a thread only ever touches its own column, so there is no barrier, no atomic and no
-// bank conflict (64 threads x 2 bytes = 32 consecutive banks, two threads per word).  The sample loop is cut into runs of
-// TM_Q_RUN = 65535 samples, each followed by a flush, so a counter cannot wrap.  A flush adds the thread's column into the
-// global uint32 histogram [Nq][2^bits][Nx]: coalesced over the wave, owner-only read-modify-write, cells the run left at
-// zero are not touched.  No per-sample update goes to global memory.
+// Histogram kernel.  One thread owns one bin and walks the block's rows as the fold kernel does (tms_walk,
+// tamcmc_summary_walk.h, TM_Q_UNROLL loads in flight).  A workgroup is one wave.  The block's counts go into 16-bit LDS
+// counters laid out [quantile][cell][thread]: a thread only ever touches its own column, so there is no barrier, no atomic
+// and no bank conflict (64 threads x 2 bytes = 32 consecutive banks, two threads per word).  The sample loop is cut into
+// runs of TM_Q_RUN = 65535 samples, each followed by a flush, so a counter cannot wrap.  A flush adds the thread's column
+// into the global uint32 histogram [Nq][2^bits][Nx]: coalesced over the wave, owner-only read-modify-write, cells the run
+// left at zero are not touched.  No per-sample update goes to global memory.
 // LDS: Nq x 2^bits columns of 128 bytes, at most 8 x 64 x 128 = 64 KiB; the kernel is instantiated for 64, 128, 256 and
 // 512 columns (8 ... 64 KiB) and the launch picks the smallest that holds Nq << bits, for the sake of occupancy.
 //
@@ -35,9 +34,8 @@ __global__ __launch_bounds__(TM_Q_THREADS) void tamcmc_quantile_hist_kernel(cons
     uint64_t prefix[TM_Q_MAXQ];
 #pragma unroll
     for (int j = 0; j < TM_Q_MAXQ; j++) prefix[j] = j < a.Nq ? a.prefix[(size_t)j * nx + bin] : (uint64_t)0;
-    long long n = a.cnt_in[0], rej = a.cnt_in[1];
+    TmsCount cnt{a.cnt_in[0], a.cnt_in[1]};
     bool outside = false;
-    const double *__restrict__ rows = a.rows + bin;
     uint16_t *const col = lds + threadIdx.x;
     uint32_t *const hist = a.hist + bin;
 
@@ -46,26 +44,16 @@ __global__ __launch_bounds__(TM_Q_THREADS) void tamcmc_quantile_hist_kernel(cons
         if (u > 0)
             for (int j = 0; j < a.Nq; j++)
                 for (int c = 0; c < used; c++) col[(j * ncell + c) * TM_Q_THREADS] = 0;
-        for (int s0 = b0; s0 < b1; s0 += TM_Q_UNROLL) {
-            double v[TM_Q_UNROLL];
+        cnt = tms_walk<TM_Q_UNROLL>(a.rows + bin, a.status, b0, b1, nx, cnt, [&](const double v, long long) {
+            const uint64_t D = tmq_key(v) - kmin;
+            if (D > R) { outside = true; return; }
+            if (u == 0) return;
 #pragma unroll
-            for (int k = 0; k < TM_Q_UNROLL; k++)
-                v[k] = (s0 + k < b1) ? rows[(size_t)(s0 + k) * nx] : 1.0;        // (a rejected sample's row is loaded and dropped)
-#pragma unroll
-            for (int k = 0; k < TM_Q_UNROLL; k++) {
-                if (s0 + k >= b1) break;
-                if (a.status[s0 + k] != 0) { rej++; continue; }
-                n++;
-                const uint64_t D = tmq_key(v[k]) - kmin;
-                if (D > R) { outside = true; continue; }
-                if (u == 0) continue;
-#pragma unroll
-                for (int j = 0; j < TM_Q_MAXQ; j++) {
-                    unsigned cell;
-                    if (j < a.Nq && tmq_match(D, prefix[j], u, d, &cell)) col[(j * ncell + (int)cell) * TM_Q_THREADS]++;
-                }
+            for (int j = 0; j < TM_Q_MAXQ; j++) {
+                unsigned cell;
+                if (j < a.Nq && tmq_match(D, prefix[j], u, d, &cell)) col[(j * ncell + (int)cell) * TM_Q_THREADS]++;
             }
-        }
+        });
         if (u > 0)
             for (int j = 0; j < a.Nq; j++)
                 for (int c = 0; c < used; c++) {
@@ -74,7 +62,7 @@ __global__ __launch_bounds__(TM_Q_THREADS) void tamcmc_quantile_hist_kernel(cons
                 }
     }
     if (outside) *a.flag = 1u;
-    if (bin == 0) { a.cnt_out[0] = n; a.cnt_out[1] = rej; }
+    if (bin == 0) { a.cnt_out[0] = cnt.n; a.cnt_out[1] = cnt.rej; }
 }
 
 __global__ __launch_bounds__(TM_Q_NARROW_THREADS) void tamcmc_quantile_narrow_kernel(const TmQuantArgs a)
@@ -111,17 +99,15 @@ __global__ __launch_bounds__(TM_Q_NARROW_THREADS) void tamcmc_quantile_init_kern
     }
 }
 
-static unsigned tmq_blocks(int Nx, int threads) { return (unsigned)(((long long)Nx + threads - 1) / threads); }
-
 int tm_launch_quantile_init(const TmQuantArgs &a, void *stream)
 {
-    hipLaunchKernelGGL(tamcmc_quantile_init_kernel, dim3(tmq_blocks(a.Nx, TM_Q_NARROW_THREADS)), dim3(TM_Q_NARROW_THREADS), 0, (hipStream_t)stream, a);
+    hipLaunchKernelGGL(tamcmc_quantile_init_kernel, dim3(tms_blocks(a.Nx, TM_Q_NARROW_THREADS)), dim3(TM_Q_NARROW_THREADS), 0, (hipStream_t)stream, a);
     return (int)hipGetLastError();
 }
 
 int tm_launch_quantile_narrow(const TmQuantArgs &a, void *stream)
 {
-    hipLaunchKernelGGL(tamcmc_quantile_narrow_kernel, dim3(tmq_blocks(a.Nx, TM_Q_NARROW_THREADS)), dim3(TM_Q_NARROW_THREADS), 0, (hipStream_t)stream, a);
+    hipLaunchKernelGGL(tamcmc_quantile_narrow_kernel, dim3(tms_blocks(a.Nx, TM_Q_NARROW_THREADS)), dim3(TM_Q_NARROW_THREADS), 0, (hipStream_t)stream, a);
     return (int)hipGetLastError();
 }
 
@@ -129,7 +115,7 @@ int tm_launch_quantile_hist(const TmQuantArgs &a, void *stream)
 {
     if (a.Nq < 1 || a.Nq > TM_Q_MAXQ || a.bits < 1 || a.bits > TM_Q_MAXBITS) return (int)hipErrorInvalidValue;
     const int cols = a.Nq << a.bits;
-    const dim3 grid(tmq_blocks(a.Nx, TM_Q_THREADS)), block(TM_Q_THREADS);
+    const dim3 grid(tms_blocks(a.Nx, TM_Q_THREADS)), block(TM_Q_THREADS);
     if (cols <= 64) hipLaunchKernelGGL(tamcmc_quantile_hist_kernel<64>, grid, block, 0, (hipStream_t)stream, a);
     else if (cols <= 128) hipLaunchKernelGGL(tamcmc_quantile_hist_kernel<128>, grid, block, 0, (hipStream_t)stream, a);
     else if (cols <= 256) hipLaunchKernelGGL(tamcmc_quantile_hist_kernel<256>, grid, block, 0, (hipStream_t)stream, a);

@@ -8,8 +8,10 @@
 // Running state, structure of arrays, TM_SUM_NSTATE blocks of Nx doubles.  The ninth quantity of the recurrences, the
 // number of accepted samples, is the same for every bin and is kept once (TmSummaryArgs::cnt_in / cnt_out).
 #pragma once
+#include <math.h>
 #include <stddef.h>
 #include <stdint.h>
+#include "tamcmc_summary_walk.h"
 
 enum {
     TM_SUM_MEAN_M = 0, TM_SUM_M2_M, TM_SUM_MIN_M, TM_SUM_MAX_M,   // Welford mean / sum of squared deviations, envelope
@@ -33,5 +35,8 @@ struct TmSummaryArgs {
     int32_t likelihood_case, pad;
     double like_p;                // already truncated (TmLayout::like_p)
 };
+
+// host: lppd_i = log((1/n) sum_s exp l_is) from the bin's running-maximum log-sum-exp (a, r) and n accepted samples
+inline double tm_lppd(const double a, const double r, const double n) { return a + log(r / n); }
 
 int tm_launch_summary_fold(const TmSummaryArgs &a, void *stream);      // tamcmc_summary.hip; returns a hipError_t

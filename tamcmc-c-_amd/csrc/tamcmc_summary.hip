@@ -7,20 +7,17 @@
 // of how the samples were split over pushes (the tests pin this).  The formulas are compiled without FMA contraction:
 // they are part of that contract, not a matter of the optimiser's mood.
 //
-//   model value v = M_is, pointwise log-likelihood l = l_is:
-//     chi(2,2p)    l = -p (y / M + log M)                      likelihoods.cpp:17-29, per bin
-//     chi_square   l = -(y - M)^2 / sigma^2                    likelihoods.cpp:31-39 (the reference's convention: no 1/2)
+//   model value v = M_is, pointwise log-likelihood l = l_is: tms_like (tamcmc_summary_walk.h)
 //   Welford, for v and for l:      d = v - mean;  mean += d / n;  M2 += d (v - mean)
 //   envelope:                      min, max
 //   running-maximum log-sum-exp:   first sample a = l, r = 1;  then  l > a:  r = r exp(a - l) + 1, a = l;  else r += exp(l - a)
 //
-// Rejected samples (status != TAMCMC_CHAIN_OK) are skipped: the status words are read from device memory, the test is
-// wave-uniform, and the host never looks at them.  The number of accepted samples is the same for every bin: every thread
-// starts from the pair {accepted, rejected} the previous launch left and counts on through the block's statuses by
-// itself; thread 0 of the launch stores the new pair into the OTHER pair of words, which the next launch reads.
+// The walk over the block's rows is tms_walk (tamcmc_summary_walk.h): rejected samples (status != TAMCMC_CHAIN_OK) are
+// skipped and counted from the pair {accepted, rejected} the previous launch left, and the host never looks at the
+// status words; thread 0 of the launch stores the new pair into the OTHER pair of words, which the next launch reads.
 //
 // The kernel is a stream over B x Nx doubles read once: TM_SUM_UNROLL row loads are requested per thread before the
-// first of them is folded (64-bit row offsets; the rows of a block sit in one buffer of up to 64 MiB by default).
+// first of them is folded (the rows of a block sit in one buffer of up to 64 MiB by default).
 #include <hip/hip_runtime.h>
 #include <cmath>
 
@@ -57,46 +54,25 @@ __global__ __launch_bounds__(TM_SUM_THREADS) void tamcmc_summary_fold_kernel(con
     const int bin = (int)(blockIdx.x * TM_SUM_THREADS + threadIdx.x);
     if (bin >= a.Nx) return;
     const size_t nx = (size_t)a.Nx;
-    long long n = a.cnt_in[0], rej = a.cnt_in[1];
     double *__restrict__ st = a.state + bin;
     TmSumState s;
     s.mean_M = st[TM_SUM_MEAN_M * nx]; s.M2_M = st[TM_SUM_M2_M * nx];
     s.min_M = st[TM_SUM_MIN_M * nx]; s.max_M = st[TM_SUM_MAX_M * nx];
     s.mean_l = st[TM_SUM_MEAN_L * nx]; s.M2_l = st[TM_SUM_M2_L * nx];
     s.a = st[TM_SUM_LSE_A * nx]; s.r = st[TM_SUM_LSE_R * nx];
-    const double y = a.y[bin];
-    const bool chi2 = a.likelihood_case != 0;
-    const double is2 = chi2 ? a.isig2[bin] : 0.0;
-    const double p = a.like_p;
-    const double *__restrict__ rows = a.rows + bin;
-
-    for (int s0 = 0; s0 < a.B; s0 += TM_SUM_UNROLL) {
-        double v[TM_SUM_UNROLL];
-#pragma unroll
-        for (int k = 0; k < TM_SUM_UNROLL; k++)
-            v[k] = (s0 + k < a.B) ? rows[(size_t)(s0 + k) * nx] : 1.0;       // (a rejected sample's row is loaded and dropped)
-#pragma unroll
-        for (int k = 0; k < TM_SUM_UNROLL; k++) {
-            if (s0 + k >= a.B) break;
-            if (a.status[s0 + k] != 0) { rej++; continue; }
-            n++;
-            double l;
-            if (chi2) { const double dd = y - v[k]; l = -((dd * dd) * is2); }
-            else l = -p * (y / v[k] + log(v[k]));
-            tm_summary_fold_one(s, n, v[k], l);
-        }
-    }
+    const TmsBinLike lk(a, bin);
+    const TmsCount cnt = tms_walk<TM_SUM_UNROLL>(a.rows + bin, a.status, 0, a.B, nx, TmsCount{a.cnt_in[0], a.cnt_in[1]},
+                                                 [&](const double v, const long long n) { tm_summary_fold_one(s, n, v, lk.l(v)); });
 
     st[TM_SUM_MEAN_M * nx] = s.mean_M; st[TM_SUM_M2_M * nx] = s.M2_M;
     st[TM_SUM_MIN_M * nx] = s.min_M; st[TM_SUM_MAX_M * nx] = s.max_M;
     st[TM_SUM_MEAN_L * nx] = s.mean_l; st[TM_SUM_M2_L * nx] = s.M2_l;
     st[TM_SUM_LSE_A * nx] = s.a; st[TM_SUM_LSE_R * nx] = s.r;
-    if (bin == 0) { a.cnt_out[0] = n; a.cnt_out[1] = rej; }
+    if (bin == 0) { a.cnt_out[0] = cnt.n; a.cnt_out[1] = cnt.rej; }
 }
 
 int tm_launch_summary_fold(const TmSummaryArgs &a, void *stream)
 {
-    const unsigned blocks = (unsigned)(((long long)a.Nx + TM_SUM_THREADS - 1) / TM_SUM_THREADS);
-    hipLaunchKernelGGL(tamcmc_summary_fold_kernel, dim3(blocks), dim3(TM_SUM_THREADS), 0, (hipStream_t)stream, a);
+    hipLaunchKernelGGL(tamcmc_summary_fold_kernel, dim3(tms_blocks(a.Nx, TM_SUM_THREADS)), dim3(TM_SUM_THREADS), 0, (hipStream_t)stream, a);
     return (int)hipGetLastError();
 }

@@ -21,48 +21,55 @@
 #include "tamcmc_summary.h"
 #include "tamcmc_window.h"
 
-// Quantile mode: the selection's state on the device and what the host remembers of it.
-struct TmQuantMode {
+// {accepted, rejected} of a pass on the device, [2][2] words: launch k reads pair k & 1 and writes the other, so no
+// workgroup reads a word that another workgroup of the same launch writes (TmSummaryArgs::cnt_in / cnt_out).  read(): idle stream.
+struct TmCountPair {
+    long long *d = nullptr;
+    int parity = 0;
+    const long long *in() const { return d + 2 * parity; }
+    long long *out() const { return d + 2 * (parity ^ 1); }
+    void flip() { parity ^= 1; }         // after a launch that wrote out()
+    int clear(hipStream_t stream) { TM_HIP(hipMemsetAsync(d, 0, 4 * sizeof(long long), stream)); parity = 0; return TAMCMC_OK; }
+    int read(long long cnt[2]) const { TM_HIP(hipMemcpy(cnt, in(), 2 * sizeof(long long), hipMemcpyDeviceToHost)); return TAMCMC_OK; }
+};
+
+// What the three modes share: the counts of the fold pass, frozen by _begin, and those of the mode's pass under way.
+struct TmMode {
     bool on = false;
+    long long n_used = 0, n_rejected = 0;
+    TmCountPair cnt;
+};
+
+// Quantile mode: the selection's state on the device and what the host remembers of it.
+struct TmQuantMode : TmMode {
     int Nq = 0, bits = 0, passes = 0;
     int u0max = 0;                       // the largest number of unresolved bits over the bins, before the first step
-    long long n_used = 0, n_rejected = 0;   // of the fold pass, frozen by _begin
     int64_t ranks[TM_Q_MAXQ] = {};
     char *d_state = nullptr;             // one allocation: kmin | R | prefix | below | ranks | cnt[2][2] | u | flag
     uint32_t *d_hist = nullptr;          // [Nq][2^bits][Nx]
     size_t hist_bytes = 0;
     uint64_t *kmin = nullptr, *R = nullptr, *prefix = nullptr, *below = nullptr, *d_ranks = nullptr;
-    long long *cnt = nullptr;            // as tamcmc_summary::d_cnt, for the samples of the pass under way
     uint32_t *u = nullptr, *flag = nullptr;
-    int parity = 0;
 };
 
 // LOO mode: the top sets and the body sums of the pass on the device, and what the host remembers of the fold pass.
-struct TmLooMode {
-    bool on = false;
+struct TmLooMode : TmMode {
     int cap = 0;                         // M + 1 heap slots per bin
-    long long n_used = 0, n_rejected = 0;   // of the fold pass, frozen by _begin
     double *d_heap = nullptr;            // [cap][Nx]
     char *d_state = nullptr;             // one allocation: body[3][Nx] | elpd | khat | cutoff | cnt[2][2] | tail_len
     double *body = nullptr, *elpd = nullptr, *khat = nullptr, *cutoff = nullptr;
-    long long *cnt = nullptr;            // as tamcmc_summary::d_cnt, for the samples of the pass under way
     int32_t *tail_len = nullptr;
-    int parity = 0;
 };
 
 // ESS mode: the lag products, the rings of centred values and the half-chain moments of the pass on the device, and what the
 // host remembers of the fold pass.
-struct TmEssMode {
-    bool on = false;
+struct TmEssMode : TmMode {
     int L = 0, R = 0;
-    long long n_used = 0, n_rejected = 0;   // of the fold pass, frozen by _begin
     double *d_acc = nullptr;             // [2][L + 1][Nx]
     double *d_ring = nullptr;            // [2][R][Nx]
     char *d_state = nullptr;             // one allocation: half[4][Nx] | lppd | tau[2][Nx] | ess[2][Nx] | cnt[2][2] | cut[2][Nx]
     double *half = nullptr, *lppd = nullptr, *tau = nullptr, *ess = nullptr;
-    long long *cnt = nullptr;            // as tamcmc_summary::d_cnt, for the samples of the pass under way
     int32_t *cut = nullptr;
-    int parity = 0;
 };
 
 // The predictive check: a setting of the object (on from _enable until destroy), not a mode.
@@ -90,8 +97,7 @@ struct tamcmc_summary {
     bool counted = false;                // the context's count includes this object
     double *d_model = nullptr;           // [B][Nx] model rows of the block in flight (the context's d_model is not touched)
     double *d_state = nullptr;           // [TM_SUM_NSTATE][Nx]
-    long long *d_cnt = nullptr;          // [2][2] {accepted, rejected}: launch k reads pair k & 1 and writes the other
-    int parity = 0;
+    TmCountPair cnt;                     // of the fold pass
     int32_t *d_rows = nullptr;           // [B] the identity row map
     double *d_T = nullptr;               // [B] ones: samples are evaluated at temperature 1
     double *d_logL = nullptr;            // [B] / [B]: where a block's logL / status go when the caller wants none
@@ -122,13 +128,54 @@ static int summary_check(const tamcmc_summary *s, int32_t Nsamples, int32_t Npar
     return TAMCMC_OK;
 }
 
+// What most entry points open with: no object, or a context whose stream cannot be waited for, is refused; then the stream
+// is idle.  (_create and _reset settle without waiting; _destroy and the _kernel_time functions have their own preludes.)
+// fold_cnt: where the fold pass's counts go, read from the device, for the callers that want them.
+static int summary_enter(tamcmc_summary *s, long long *fold_cnt = nullptr)
+{
+    if (!s || s->c->in_flight || s->c->armed) return TAMCMC_E_INVALID;
+    TM_HIP(hipSetDevice(s->c->device));
+    TM_HIP(tm_ctx_stream_sync(s->c));
+    return fold_cnt ? s->cnt.read(fold_cnt) : TAMCMC_OK;
+}
+
+// the mode the object is in (at most one), or NULL in fold mode
+static const TmMode *active_mode(const tamcmc_summary *s)
+{
+    if (s->q.on) return &s->q;
+    if (s->loo.on) return &s->loo;
+    return s->ess.on ? &s->ess : nullptr;
+}
+
+// the pass under way saw exactly the fold pass's samples (the stream must be idle)
+static int pass_complete(const TmMode &m, bool *complete)
+{
+    long long cnt[2] = {0, 0};
+    const int rc = m.cnt.read(cnt);
+    *complete = rc == TAMCMC_OK && cnt[0] == m.n_used && cnt[1] == m.n_rejected;
+    return rc;
+}
+
+// One stage of a block, or a result kernel, on the context's stream, between two events of `timer` while the object is
+// profiled.  launch() returns a hipError_t; `wrote`, the count pair the launch writes, flips once it has succeeded.
+template <class F>
+static int timed_launch(tamcmc_summary *s, TmTimer &timer, const char *what, F &&launch, TmCountPair *wrote = nullptr)
+{
+    const hipStream_t stream = s->c->stream;
+    if (s->profile) { const int rc = timer.begin(stream); if (rc != TAMCMC_OK) return rc; }
+    const int hr = launch();
+    if (hr != 0) return tm_launch_failed(what, hr);
+    if (wrote) wrote->flip();
+    return s->profile ? timer.end(stream) : TAMCMC_OK;
+}
+
 static TmQuantArgs quantile_args(const tamcmc_summary *s)
 {
     const TmQuantMode &q = s->q;
     TmQuantArgs a{};
     a.rows = s->d_model; a.fold_state = s->d_state;
     a.kmin = q.kmin; a.R = q.R; a.u = q.u; a.prefix = q.prefix; a.below = q.below; a.ranks = q.d_ranks; a.hist = q.d_hist;
-    a.cnt_in = q.cnt + 2 * q.parity; a.cnt_out = q.cnt + 2 * (q.parity ^ 1); a.flag = q.flag;
+    a.cnt_in = q.cnt.in(); a.cnt_out = q.cnt.out(); a.flag = q.flag;
     a.Nx = s->c->L.Nx; a.Nq = q.Nq; a.bits = q.bits;
     return a;
 }
@@ -136,26 +183,18 @@ static TmQuantArgs quantile_args(const tamcmc_summary *s)
 // stage 2 of a block in quantile mode: the histogram kernel in the fold kernel's place
 static int quantile_block(tamcmc_summary *s, int n, const int32_t *d_status)
 {
-    tamcmc_ctx *c = s->c;
     TmQuantArgs a = quantile_args(s);
     a.status = d_status; a.B = n;
-    int rc = TAMCMC_OK;
-    if (s->profile) { rc = s->timer.begin(c->stream); if (rc != TAMCMC_OK) return rc; }
-    const int hr = tm_launch_quantile_hist(a, c->stream);
-    if (hr != 0) return tm_launch_failed("summary quantile histogram", hr);
-    s->q.parity ^= 1;
-    return s->profile ? s->timer.end(c->stream) : TAMCMC_OK;
+    return timed_launch(s, s->timer, "summary quantile histogram", [&] { return tm_launch_quantile_hist(a, s->c->stream); }, &s->q.cnt);
 }
 
 // a pass starts from empty counts and a clear flag (the cells are cleared by whoever read them last)
 static int quantile_pass_clear(tamcmc_summary *s, bool cells)
 {
     TmQuantMode &q = s->q;
-    TM_HIP(hipMemsetAsync(q.cnt, 0, 4 * sizeof(long long), s->c->stream));
     TM_HIP(hipMemsetAsync(q.flag, 0, sizeof(uint32_t), s->c->stream));
     if (cells) TM_HIP(hipMemsetAsync(q.d_hist, 0, q.hist_bytes, s->c->stream));
-    q.parity = 0;
-    return TAMCMC_OK;
+    return q.cnt.clear(s->c->stream);
 }
 
 // the stream must be idle
@@ -171,7 +210,7 @@ static TmLooArgs loo_args(const tamcmc_summary *s)
     const tamcmc_ctx *c = s->c;
     TmLooArgs a{};
     a.rows = s->d_model; a.y = c->d_y; a.isig2 = c->d_isig2; a.heap = m.d_heap; a.body = m.body;
-    a.cnt_in = m.cnt + 2 * m.parity; a.cnt_out = m.cnt + 2 * (m.parity ^ 1);
+    a.cnt_in = m.cnt.in(); a.cnt_out = m.cnt.out();
     a.elpd = m.elpd; a.khat = m.khat; a.cutoff = m.cutoff; a.tail_len = m.tail_len;
     a.Nx = c->L.Nx; a.likelihood_case = c->L.likelihood_case; a.cap = m.cap; a.like_p = c->L.like_p;
     return a;
@@ -180,25 +219,17 @@ static TmLooArgs loo_args(const tamcmc_summary *s)
 // stage 2 of a block in LOO mode: the tail kernel in the fold kernel's place
 static int loo_block(tamcmc_summary *s, int n, const int32_t *d_status)
 {
-    tamcmc_ctx *c = s->c;
     TmLooArgs a = loo_args(s);
     a.status = d_status; a.B = n;
-    int rc = TAMCMC_OK;
-    if (s->profile) { rc = s->timer.begin(c->stream); if (rc != TAMCMC_OK) return rc; }
-    const int hr = tm_launch_loo_tail(a, c->stream);
-    if (hr != 0) return tm_launch_failed("summary loo tail", hr);
-    s->loo.parity ^= 1;
-    return s->profile ? s->timer.end(c->stream) : TAMCMC_OK;
+    return timed_launch(s, s->timer, "summary loo tail", [&] { return tm_launch_loo_tail(a, s->c->stream); }, &s->loo.cnt);
 }
 
 // a pass starts from empty counts and empty body sums (with no sample counted the heap holds nothing)
 static int loo_pass_clear(tamcmc_summary *s)
 {
     TmLooMode &m = s->loo;
-    TM_HIP(hipMemsetAsync(m.cnt, 0, 4 * sizeof(long long), s->c->stream));
     TM_HIP(hipMemsetAsync(m.body, 0, 3 * (size_t)s->c->L.Nx * sizeof(double), s->c->stream));
-    m.parity = 0;
-    return TAMCMC_OK;
+    return m.cnt.clear(s->c->stream);
 }
 
 // the stream must be idle
@@ -215,7 +246,7 @@ static TmEssArgs ess_args(const tamcmc_summary *s)
     TmEssArgs a{};
     a.y = c->d_y; a.isig2 = c->d_isig2; a.mean_M = s->d_state + (size_t)TM_SUM_MEAN_M * (size_t)c->L.Nx; a.lppd = m.lppd;
     a.ring = m.d_ring; a.acc = m.d_acc; a.half = m.half; a.tau = m.tau; a.ess = m.ess; a.cut = m.cut;
-    a.cnt_in = m.cnt + 2 * m.parity; a.cnt_out = m.cnt + 2 * (m.parity ^ 1);
+    a.cnt_in = m.cnt.in(); a.cnt_out = m.cnt.out();
     a.n = m.n_used; a.h = m.n_used / 2;
     a.Nx = c->L.Nx; a.L = m.L; a.R = m.R; a.likelihood_case = c->L.likelihood_case; a.like_p = c->L.like_p;
     a.tau_floor = 1.0 / std::log10((double)m.n_used);
@@ -226,17 +257,17 @@ static TmEssArgs ess_args(const tamcmc_summary *s)
 static int ess_block(tamcmc_summary *s, int n, const int32_t *d_status)
 {
     tamcmc_ctx *c = s->c;
-    int rc = TAMCMC_OK;
-    if (s->profile) { rc = s->timer.begin(c->stream); if (rc != TAMCMC_OK) return rc; }
-    for (int k = 0; k < n; k += TM_ESS_CHUNK) {
-        TmEssArgs a = ess_args(s);
-        a.rows = s->d_model + (size_t)k * (size_t)c->L.Nx; a.status = d_status + k;
-        a.B = n - k < TM_ESS_CHUNK ? n - k : TM_ESS_CHUNK;
-        const int hr = tm_launch_ess_chunk(a, c->stream);
-        if (hr != 0) return tm_launch_failed("summary ess chunk", hr);
-        s->ess.parity ^= 1;
-    }
-    return s->profile ? s->timer.end(c->stream) : TAMCMC_OK;
+    return timed_launch(s, s->timer, "summary ess chunk", [&] {
+        int hr = 0;
+        for (int k = 0; k < n && hr == 0; k += TM_ESS_CHUNK) {
+            TmEssArgs a = ess_args(s);
+            a.rows = s->d_model + (size_t)k * (size_t)c->L.Nx; a.status = d_status + k;
+            a.B = n - k < TM_ESS_CHUNK ? n - k : TM_ESS_CHUNK;
+            hr = tm_launch_ess_chunk(a, c->stream);
+            if (hr == 0) s->ess.cnt.flip();                 // per chunk: timed_launch's `wrote` would flip once per block
+        }
+        return hr;
+    });
 }
 
 // a pass starts from empty counts, lag products and half-chain moments (a ring slot is written before it is read)
@@ -244,11 +275,9 @@ static int ess_pass_clear(tamcmc_summary *s)
 {
     TmEssMode &m = s->ess;
     const size_t nx = (size_t)s->c->L.Nx;
-    TM_HIP(hipMemsetAsync(m.cnt, 0, 4 * sizeof(long long), s->c->stream));
     TM_HIP(hipMemsetAsync(m.d_acc, 0, 2 * (size_t)(m.L + 1) * nx * sizeof(double), s->c->stream));
     TM_HIP(hipMemsetAsync(m.half, 0, (size_t)TM_ESS_NHALF * nx * sizeof(double), s->c->stream));
-    m.parity = 0;
-    return TAMCMC_OK;
+    return m.cnt.clear(s->c->stream);
 }
 
 // the stream must be idle
@@ -262,16 +291,12 @@ static void ess_free(tamcmc_summary *s)
 static int predictive_block(tamcmc_summary *s, int n, const int32_t *d_status, const long long *cnt_in)
 {
     tamcmc_ctx *c = s->c;
-    int rc = TAMCMC_OK;
     TmPredArgs pa{};
     pa.rows = s->d_model; pa.status = d_status; pa.y = c->d_y; pa.isig2 = c->d_isig2; pa.state = s->pred.d_state;
     pa.cnt_in = cnt_in;
     pa.Nx = c->L.Nx; pa.B = n; pa.likelihood_case = c->L.likelihood_case; pa.p = s->pred.p; pa.nterms = s->pred.nterms;
     pa.lf_pm1 = s->pred.lf_pm1; pa.lf_p = s->pred.lf_p;
-    if (s->profile) { rc = s->pred.timer.begin(c->stream); if (rc != TAMCMC_OK) return rc; }
-    const int pr = tm_launch_predictive(pa, c->stream);
-    if (pr != 0) return tm_launch_failed("summary predictive", pr);
-    return s->profile ? s->pred.timer.end(c->stream) : TAMCMC_OK;
+    return timed_launch(s, s->pred.timer, "summary predictive", [&] { return tm_launch_predictive(pa, c->stream); });
 }
 
 // stage 4: the windowed check's three kernels on the same rows, counting on from the same pair
@@ -279,17 +304,13 @@ static int window_block(tamcmc_summary *s, int n, const int32_t *d_status, const
 {
     tamcmc_ctx *c = s->c;
     const TmWindow &m = s->win;
-    int rc = TAMCMC_OK;
     TmWinArgs wa{};
     wa.rows = s->d_model; wa.status = d_status; wa.y = c->d_y; wa.isig2 = c->d_isig2; wa.state = m.d_state; wa.scratch = m.d_scratch;
     wa.cnt_in = cnt_in;
     wa.Nx = c->L.Nx; wa.B = n; wa.Bcap = s->B; wa.n_windows = m.n_windows; wa.W = m.W; wa.first = m.first;
     wa.likelihood_case = c->L.likelihood_case; wa.p = m.p;
     for (int k = 0; k < 3; k++) wa.shape[k] = m.shape[k];
-    if (s->profile) { rc = s->win.timer.begin(c->stream); if (rc != TAMCMC_OK) return rc; }
-    const int wr = tm_launch_window(wa, c->stream);
-    if (wr != 0) return tm_launch_failed("summary window", wr);
-    return s->profile ? s->win.timer.end(c->stream) : TAMCMC_OK;
+    return timed_launch(s, s->win.timer, "summary window", [&] { return tm_launch_window(wa, c->stream); });
 }
 
 // One block of n <= B samples, device pointers, enqueued on the context's stream.
@@ -307,13 +328,10 @@ static int summary_block(tamcmc_summary *s, int n, const double *d_params, doubl
     if (s->ess.on) return ess_block(s, n, d_status);
     TmSummaryArgs a{};
     a.rows = s->d_model; a.status = d_status; a.y = c->d_y; a.isig2 = c->d_isig2; a.state = s->d_state;
-    a.cnt_in = s->d_cnt + 2 * s->parity; a.cnt_out = s->d_cnt + 2 * (s->parity ^ 1);
+    a.cnt_in = s->cnt.in(); a.cnt_out = s->cnt.out();
     a.Nx = c->L.Nx; a.B = n; a.likelihood_case = c->L.likelihood_case; a.like_p = c->L.like_p;
-    if (s->profile) { rc = s->timer.begin(c->stream); if (rc != TAMCMC_OK) return rc; }
-    const int hr = tm_launch_summary_fold(a, c->stream);
-    if (hr != 0) return tm_launch_failed("summary fold", hr);
-    s->parity ^= 1;
-    if (s->profile) { rc = s->timer.end(c->stream); if (rc != TAMCMC_OK) return rc; }
+    rc = timed_launch(s, s->timer, "summary fold", [&] { return tm_launch_summary_fold(a, c->stream); }, &s->cnt);
+    if (rc != TAMCMC_OK) return rc;
     if (s->pred.on) { rc = predictive_block(s, n, d_status, a.cnt_in); if (rc != TAMCMC_OK) return rc; }
     return s->win.on ? window_block(s, n, d_status, a.cnt_in) : TAMCMC_OK;
 }
@@ -324,9 +342,7 @@ static int summary_clear(tamcmc_summary *s)
     if (s->pred.on) TM_HIP(hipMemsetAsync(s->pred.d_state, 0, (size_t)TM_PRED_NSTATE * (size_t)c->L.Nx * sizeof(double), c->stream));
     if (s->win.on) TM_HIP(hipMemsetAsync(s->win.d_state, 0, (size_t)TM_PRED_NSTATE * (size_t)s->win.n_windows * sizeof(double), c->stream));
     TM_HIP(hipMemsetAsync(s->d_state, 0, (size_t)TM_SUM_NSTATE * (size_t)c->L.Nx * sizeof(double), c->stream));
-    TM_HIP(hipMemsetAsync(s->d_cnt, 0, 4 * sizeof(long long), c->stream));
-    s->parity = 0;
-    return TAMCMC_OK;
+    return s->cnt.clear(c->stream);
 }
 
 extern "C" int tamcmc_summary_create(tamcmc_summary **out, tamcmc_ctx *c, int32_t block_chains)
@@ -349,7 +365,7 @@ extern "C" int tamcmc_summary_create(tamcmc_summary **out, tamcmc_ctx *c, int32_
     if (hipSetDevice(c->device) != hipSuccess) return fail(TAMCMC_E_NODEVICE);
     const size_t b = (size_t)B;
     if (hipMalloc(&s->d_model, b * nx * sizeof(double)) != hipSuccess || hipMalloc(&s->d_state, TM_SUM_NSTATE * nx * sizeof(double)) != hipSuccess ||
-        hipMalloc(&s->d_cnt, 4 * sizeof(long long)) != hipSuccess || hipMalloc(&s->d_rows, b * sizeof(int32_t)) != hipSuccess ||
+        hipMalloc(&s->cnt.d, 4 * sizeof(long long)) != hipSuccess || hipMalloc(&s->d_rows, b * sizeof(int32_t)) != hipSuccess ||
         hipMalloc(&s->d_T, b * sizeof(double)) != hipSuccess || hipMalloc(&s->d_logL, b * sizeof(double)) != hipSuccess ||
         hipMalloc(&s->d_status, b * sizeof(int32_t)) != hipSuccess)
         return fail(TAMCMC_E_NOMEM);
@@ -380,7 +396,7 @@ extern "C" int tamcmc_summary_destroy(tamcmc_summary *s)
     quantile_free(s);
     loo_free(s);
     ess_free(s);
-    (void)hipFree(s->d_model); (void)hipFree(s->d_state); (void)hipFree(s->d_cnt); (void)hipFree(s->d_rows);
+    (void)hipFree(s->d_model); (void)hipFree(s->d_state); (void)hipFree(s->cnt.d); (void)hipFree(s->d_rows);
     (void)hipFree(s->d_T); (void)hipFree(s->d_logL); (void)hipFree(s->d_status); (void)hipFree(s->pred.d_state);
     (void)hipFree(s->win.d_state); (void)hipFree(s->win.d_scratch);
     for (int p = 0; p < 2; p++) {
@@ -399,7 +415,7 @@ extern "C" int tamcmc_summary_reset(tamcmc_summary *s)
     if (!s || s->c->in_flight || s->c->armed) return TAMCMC_E_INVALID;
     tamcmc_ctx *c = s->c;
     TM_HIP(hipSetDevice(c->device));
-    if (s->q.on || s->loo.on || s->ess.on) {        // reset leaves quantile mode, LOO mode and ESS mode
+    if (active_mode(s)) {                           // reset leaves quantile mode, LOO mode and ESS mode
         TM_HIP(tm_ctx_stream_sync(c));
         quantile_free(s);
         loo_free(s);
@@ -482,15 +498,12 @@ extern "C" int tamcmc_summary_result(tamcmc_summary *s, tamcmc_summary_totals *t
                                      double *mean_M, double *var_M, double *min_M, double *max_M,
                                      double *mean_l, double *var_l, double *lppd)
 {
-    if (!s || s->c->in_flight || s->c->armed) return TAMCMC_E_INVALID;
-    tamcmc_ctx *c = s->c;
-    TM_HIP(hipSetDevice(c->device));
-    TM_HIP(tm_ctx_stream_sync(c));
-    const size_t nx = (size_t)c->L.Nx;
     long long cnt[2] = {0, 0};
+    const int rc = summary_enter(s, cnt);
+    if (rc != TAMCMC_OK) return rc;
+    const size_t nx = (size_t)s->c->L.Nx;
     std::vector<double> st;
     try { st.resize(TM_SUM_NSTATE * nx); } catch (const std::bad_alloc &) { return TAMCMC_E_NOMEM; }
-    TM_HIP(hipMemcpy(cnt, s->d_cnt + 2 * s->parity, sizeof(cnt), hipMemcpyDeviceToHost));
     TM_HIP(hipMemcpy(st.data(), s->d_state, st.size() * sizeof(double), hipMemcpyDeviceToHost));
     const long long n = cnt[0];
     const double nan = std::nan(""), dn = (double)n;
@@ -498,7 +511,7 @@ extern "C" int tamcmc_summary_result(tamcmc_summary *s, tamcmc_summary_totals *t
     for (size_t i = 0; i < nx; i++) {
         const double vM = n >= 2 ? st[TM_SUM_M2_M * nx + i] / (dn - 1.0) : nan;
         const double vl = n >= 2 ? st[TM_SUM_M2_L * nx + i] / (dn - 1.0) : nan;
-        const double lp = n >= 1 ? st[TM_SUM_LSE_A * nx + i] + std::log(st[TM_SUM_LSE_R * nx + i] / dn) : nan;
+        const double lp = n >= 1 ? tm_lppd(st[TM_SUM_LSE_A * nx + i], st[TM_SUM_LSE_R * nx + i], dn) : nan;
         if (mean_M) mean_M[i] = n >= 1 ? st[TM_SUM_MEAN_M * nx + i] : nan;
         if (var_M) var_M[i] = vM;
         if (min_M) min_M[i] = n >= 1 ? st[TM_SUM_MIN_M * nx + i] : nan;
@@ -545,13 +558,12 @@ extern "C" int tamcmc_summary_quantiles_begin(tamcmc_summary *s, int32_t Nq, con
 {
     if (!s || !q || Nq < 1 || Nq > TAMCMC_SUMMARY_MAX_QUANTILES || bits_per_pass < 0 || bits_per_pass > TM_Q_MAXBITS) return TAMCMC_E_INVALID;
     tamcmc_ctx *c = s->c;
-    if (s->q.on || s->loo.on || s->ess.on || c->in_flight || c->armed) return TAMCMC_E_INVALID;
+    if (active_mode(s)) return TAMCMC_E_INVALID;
     for (int j = 0; j < Nq; j++)
         if (!(q[j] >= 0.0 && q[j] <= 1.0)) return TAMCMC_E_INVALID;        // (a NaN fails both comparisons)
-    TM_HIP(hipSetDevice(c->device));
-    TM_HIP(tm_ctx_stream_sync(c));
     long long cnt[2] = {0, 0};
-    TM_HIP(hipMemcpy(cnt, s->d_cnt + 2 * s->parity, sizeof(cnt), hipMemcpyDeviceToHost));
+    const int rc = summary_enter(s, cnt);
+    if (rc != TAMCMC_OK) return rc;
     if (cnt[0] < 1 || cnt[0] >= ((long long)1 << 32)) return TAMCMC_E_INVALID;
     TmQuantMode m;
     m.Nq = Nq;
@@ -572,8 +584,8 @@ extern "C" int tamcmc_summary_quantiles_begin(tamcmc_summary *s, int32_t Nq, con
     m.prefix = m.R + nx;
     m.below = m.prefix + nq * nx;
     m.d_ranks = m.below + nq * nx;
-    m.cnt = reinterpret_cast<long long *>(m.d_ranks + TM_Q_MAXQ);
-    m.u = reinterpret_cast<uint32_t *>(m.cnt + 4);
+    m.cnt.d = reinterpret_cast<long long *>(m.d_ranks + TM_Q_MAXQ);
+    m.u = reinterpret_cast<uint32_t *>(m.cnt.d + 4);
     m.flag = m.u + nx;
     m.on = true;
     s->q = m;
@@ -600,40 +612,41 @@ static int quantile_bits_left(const TmQuantMode &q)
 
 extern "C" int tamcmc_summary_quantiles_step(tamcmc_summary *s, int32_t *bits_left)
 {
-    if (!s || !s->q.on || s->c->in_flight || s->c->armed) return TAMCMC_E_INVALID;
+    if (!s || !s->q.on) return TAMCMC_E_INVALID;
+    int rc = summary_enter(s);
+    if (rc != TAMCMC_OK) return rc;
     tamcmc_ctx *c = s->c;
     TmQuantMode &q = s->q;
-    TM_HIP(hipSetDevice(c->device));
-    TM_HIP(tm_ctx_stream_sync(c));
     c->enq_seq++;
     if (quantile_bits_left(q) == 0) {                  // nothing to resolve: whatever was pushed is dropped
-        const int rc = quantile_pass_clear(s, false);
+        rc = quantile_pass_clear(s, false);
         if (bits_left) *bits_left = 0;
         return rc;
     }
-    long long cnt[2] = {0, 0};
+    bool complete = false;
     uint32_t flag = 0;
-    TM_HIP(hipMemcpy(cnt, q.cnt + 2 * q.parity, sizeof(cnt), hipMemcpyDeviceToHost));
+    rc = pass_complete(q, &complete);
+    if (rc != TAMCMC_OK) return rc;
     TM_HIP(hipMemcpy(&flag, q.flag, sizeof(flag), hipMemcpyDeviceToHost));
-    if (cnt[0] != q.n_used || cnt[1] != q.n_rejected || flag != 0) {      // not the fold pass's samples: the pass is discarded
-        const int rc = quantile_pass_clear(s, true);
+    if (!complete || flag != 0) {                      // not the fold pass's samples: the pass is discarded
+        rc = quantile_pass_clear(s, true);
         return rc != TAMCMC_OK ? rc : TAMCMC_E_INVALID;
     }
     const int hr = tm_launch_quantile_narrow(quantile_args(s), c->stream);
     if (hr != 0) return tm_launch_failed("summary quantile narrow", hr);
     q.passes++;
-    const int rc = quantile_pass_clear(s, false);      // the narrow kernel cleared the cells it read; the others were never written
+    rc = quantile_pass_clear(s, false);                // the narrow kernel cleared the cells it read; the others were never written
     if (bits_left) *bits_left = quantile_bits_left(q);
     return rc;
 }
 
 extern "C" int tamcmc_summary_quantiles_result(tamcmc_summary *s, int64_t *ranks, double *lo, double *hi)
 {
-    if (!s || !s->q.on || s->c->in_flight || s->c->armed) return TAMCMC_E_INVALID;
+    if (!s || !s->q.on) return TAMCMC_E_INVALID;
+    const int rc = summary_enter(s);
+    if (rc != TAMCMC_OK) return rc;
     tamcmc_ctx *c = s->c;
     const TmQuantMode &q = s->q;
-    TM_HIP(hipSetDevice(c->device));
-    TM_HIP(tm_ctx_stream_sync(c));
     if (ranks) for (int j = 0; j < q.Nq; j++) ranks[j] = q.ranks[j];
     if (!lo && !hi) return TAMCMC_OK;
     const size_t nx = (size_t)c->L.Nx, nq = (size_t)q.Nq;
@@ -659,24 +672,21 @@ extern "C" int tamcmc_summary_quantiles_result(tamcmc_summary *s, int64_t *ranks
 
 extern "C" int tamcmc_summary_quantiles_end(tamcmc_summary *s)
 {
-    if (!s || !s->q.on || s->c->in_flight || s->c->armed) return TAMCMC_E_INVALID;
-    TM_HIP(hipSetDevice(s->c->device));
-    TM_HIP(tm_ctx_stream_sync(s->c));
-    quantile_free(s);
-    return TAMCMC_OK;
+    if (!s || !s->q.on) return TAMCMC_E_INVALID;
+    const int rc = summary_enter(s);
+    if (rc == TAMCMC_OK) quantile_free(s);
+    return rc;
 }
 
 // ---- PSIS-LOO (tamcmc_loo.h) ----
 
 extern "C" int tamcmc_summary_loo_begin(tamcmc_summary *s)
 {
-    if (!s) return TAMCMC_E_INVALID;
+    if (!s || active_mode(s)) return TAMCMC_E_INVALID;
     tamcmc_ctx *c = s->c;
-    if (s->q.on || s->loo.on || s->ess.on || c->in_flight || c->armed) return TAMCMC_E_INVALID;
-    TM_HIP(hipSetDevice(c->device));
-    TM_HIP(tm_ctx_stream_sync(c));
     long long cnt[2] = {0, 0};
-    TM_HIP(hipMemcpy(cnt, s->d_cnt + 2 * s->parity, sizeof(cnt), hipMemcpyDeviceToHost));
+    const int rc = summary_enter(s, cnt);
+    if (rc != TAMCMC_OK) return rc;
     if (cnt[0] < 1) return TAMCMC_E_INVALID;
     const int64_t M = tml_tail_M((int64_t)cnt[0]);
     if (M > TAMCMC_SUMMARY_LOO_MAX_TAIL) return TAMCMC_E_INVALID;       // thin the chain
@@ -691,8 +701,8 @@ extern "C" int tamcmc_summary_loo_begin(tamcmc_summary *s)
     m.elpd = m.body + 3 * nx;
     m.khat = m.elpd + nx;
     m.cutoff = m.khat + nx;
-    m.cnt = reinterpret_cast<long long *>(m.cutoff + nx);
-    m.tail_len = reinterpret_cast<int32_t *>(m.cnt + 4);
+    m.cnt.d = reinterpret_cast<long long *>(m.cutoff + nx);
+    m.tail_len = reinterpret_cast<int32_t *>(m.cnt.d + 4);
     m.on = true;
     s->loo = m;
     c->enq_seq++;
@@ -703,16 +713,17 @@ extern "C" int tamcmc_summary_loo_begin(tamcmc_summary *s)
 extern "C" int tamcmc_summary_loo_result(tamcmc_summary *s, tamcmc_summary_loo_totals *totals, double *elpd_loo, double *pareto_k,
                                          double *cutoff, int32_t *tail_len)
 {
-    if (!s || !s->loo.on || s->c->in_flight || s->c->armed) return TAMCMC_E_INVALID;
+    if (!s || !s->loo.on) return TAMCMC_E_INVALID;
+    int rc = summary_enter(s);
+    if (rc != TAMCMC_OK) return rc;
     tamcmc_ctx *c = s->c;
     TmLooMode &m = s->loo;
-    TM_HIP(hipSetDevice(c->device));
-    TM_HIP(tm_ctx_stream_sync(c));
     c->enq_seq++;
-    long long cnt[2] = {0, 0};
-    TM_HIP(hipMemcpy(cnt, m.cnt + 2 * m.parity, sizeof(cnt), hipMemcpyDeviceToHost));
-    if (cnt[0] != m.n_used || cnt[1] != m.n_rejected) {                 // not the fold pass's samples: the pass is discarded
-        const int rc = loo_pass_clear(s);
+    bool complete = false;
+    rc = pass_complete(m, &complete);
+    if (rc != TAMCMC_OK) return rc;
+    if (!complete) {                                                    // not the fold pass's samples: the pass is discarded
+        rc = loo_pass_clear(s);
         return rc != TAMCMC_OK ? rc : TAMCMC_E_INVALID;
     }
     const size_t nx = (size_t)c->L.Nx;
@@ -721,11 +732,8 @@ extern "C" int tamcmc_summary_loo_result(tamcmc_summary *s, tamcmc_summary_loo_t
     try { out.resize(3 * nx); lse.resize(2 * nx); tl.resize(nx); } catch (const std::bad_alloc &) { return TAMCMC_E_NOMEM; }
     TmLooArgs a = loo_args(s);
     a.n = m.n_used;
-    int rc = TAMCMC_OK;
-    if (s->profile) { rc = s->timer.begin(c->stream); if (rc != TAMCMC_OK) return rc; }
-    const int hr = tm_launch_loo_finalize(a, c->stream);
-    if (hr != 0) return tm_launch_failed("summary loo finalize", hr);
-    if (s->profile) { rc = s->timer.end(c->stream); if (rc != TAMCMC_OK) return rc; }
+    rc = timed_launch(s, s->timer, "summary loo finalize", [&] { return tm_launch_loo_finalize(a, c->stream); });
+    if (rc != TAMCMC_OK) return rc;
     TM_HIP(hipMemcpyAsync(out.data(), m.elpd, 3 * nx * sizeof(double), hipMemcpyDeviceToHost, c->stream));      // elpd | khat | cutoff
     TM_HIP(hipMemcpyAsync(tl.data(), m.tail_len, nx * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
     TM_HIP(hipMemcpyAsync(lse.data(), s->d_state + (size_t)TM_SUM_LSE_A * nx, 2 * nx * sizeof(double), hipMemcpyDeviceToHost, c->stream));   // a | r
@@ -736,7 +744,7 @@ extern "C" int tamcmc_summary_loo_result(tamcmc_summary *s, tamcmc_summary_loo_t
     int64_t n_high = 0, n_inf = 0;
     for (size_t i = 0; i < nx; i++) {
         const double k = out[nx + i];
-        lppd_total += (long double)(lse[i] + std::log(lse[nx + i] / dn));     // as tamcmc_summary_result, in bin order
+        lppd_total += (long double)tm_lppd(lse[i], lse[nx + i], dn);          // as tamcmc_summary_result, in bin order
         elpd_total += (long double)out[i];
         if (!(k <= k_max)) k_max = std::isnan(k) ? k_max : k;                 // (a NaN k-hat is never the maximum)
         if (k > 0.7) n_high++;
@@ -761,27 +769,30 @@ extern "C" int tamcmc_summary_loo_result(tamcmc_summary *s, tamcmc_summary_loo_t
 
 extern "C" int tamcmc_summary_loo_end(tamcmc_summary *s)
 {
-    if (!s || !s->loo.on || s->c->in_flight || s->c->armed) return TAMCMC_E_INVALID;
-    TM_HIP(hipSetDevice(s->c->device));
-    TM_HIP(tm_ctx_stream_sync(s->c));
-    loo_free(s);
-    return TAMCMC_OK;
+    if (!s || !s->loo.on) return TAMCMC_E_INVALID;
+    const int rc = summary_enter(s);
+    if (rc == TAMCMC_OK) loo_free(s);
+    return rc;
 }
 
 // ---- posterior predictive check (tamcmc_predictive.h) ----
 
+// A check is enabled on an object that holds no samples yet (otherwise: reset first).  Opens both _enable functions.
+static int summary_enter_empty(tamcmc_summary *s)
+{
+    long long cnt[2] = {0, 0};
+    const int rc = summary_enter(s, cnt);
+    return rc != TAMCMC_OK ? rc : (cnt[0] != 0 || cnt[1] != 0 ? TAMCMC_E_INVALID : TAMCMC_OK);
+}
+
 extern "C" int tamcmc_summary_predictive_enable(tamcmc_summary *s)
 {
-    if (!s) return TAMCMC_E_INVALID;
+    if (!s || s->pred.on || active_mode(s)) return TAMCMC_E_INVALID;
     tamcmc_ctx *c = s->c;
-    if (s->pred.on || s->q.on || s->loo.on || s->ess.on || c->in_flight || c->armed) return TAMCMC_E_INVALID;
     const bool chi = c->L.likelihood_case == 0;
     if (chi && !(c->L.like_p >= 1.0 && c->L.like_p <= (double)TAMCMC_SUMMARY_PREDICTIVE_MAX_P)) return TAMCMC_E_INVALID;
-    TM_HIP(hipSetDevice(c->device));
-    TM_HIP(tm_ctx_stream_sync(c));
-    long long cnt[2] = {0, 0};
-    TM_HIP(hipMemcpy(cnt, s->d_cnt + 2 * s->parity, sizeof(cnt), hipMemcpyDeviceToHost));
-    if (cnt[0] != 0 || cnt[1] != 0) return TAMCMC_E_INVALID;            // the object holds samples: reset first
+    const int rc = summary_enter_empty(s);
+    if (rc != TAMCMC_OK) return rc;
     TmPredictive &m = s->pred;
     const size_t bytes = (size_t)TM_PRED_NSTATE * (size_t)c->L.Nx * sizeof(double);
     if (hipMalloc(&m.d_state, bytes) != hipSuccess) { (void)hipGetLastError(); m.d_state = nullptr; return TAMCMC_E_NOMEM; }
@@ -803,6 +814,7 @@ extern "C" int tamcmc_summary_predictive_enable(tamcmc_summary *s)
 // What the per-bin and the windowed check share on the host: from the state st[TM_PRED_NSTATE][m] of m items (bins or
 // windows) and n accepted samples, the four arrays (any may be NULL) and the totals over the items, in item order.
 struct TmTailTotals {
+    long long n_used, n_rejected;
     double ks_D, min_log_sf, min_log_cdf;
     int64_t at_min_log_sf, at_min_log_cdf;
     int64_t pit_hist[TAMCMC_SUMMARY_PIT_CELLS];
@@ -851,33 +863,39 @@ static int tails_finish(const std::vector<double> &st, const size_t m, const lon
 // the fold pass's counts: frozen copies while a mode is on (its passes touch neither check's state)
 static int fold_counts(const tamcmc_summary *s, long long cnt[2])
 {
-    if (s->q.on) { cnt[0] = s->q.n_used; cnt[1] = s->q.n_rejected; }
-    else if (s->loo.on) { cnt[0] = s->loo.n_used; cnt[1] = s->loo.n_rejected; }
-    else if (s->ess.on) { cnt[0] = s->ess.n_used; cnt[1] = s->ess.n_rejected; }
-    else TM_HIP(hipMemcpy(cnt, s->d_cnt + 2 * s->parity, 2 * sizeof(long long), hipMemcpyDeviceToHost));
+    const TmMode *m = active_mode(s);
+    if (!m) return s->cnt.read(cnt);
+    cnt[0] = m->n_used; cnt[1] = m->n_rejected;
     return TAMCMC_OK;
+}
+
+// _predictive_result and _window_result once their check is known to be on: d_state[TM_PRED_NSTATE][m], m bins or windows
+static int tails_result(tamcmc_summary *s, const double *d_state, const size_t m, double *pit, double *log_cdf, double *log_sf,
+                        double *mean_resid, TmTailTotals *out)
+{
+    int rc = summary_enter(s);
+    if (rc != TAMCMC_OK) return rc;
+    long long cnt[2] = {0, 0};
+    std::vector<double> st;
+    try { st.resize(TM_PRED_NSTATE * m); } catch (const std::bad_alloc &) { return TAMCMC_E_NOMEM; }
+    rc = fold_counts(s, cnt);
+    if (rc != TAMCMC_OK) return rc;
+    TM_HIP(hipMemcpy(st.data(), d_state, st.size() * sizeof(double), hipMemcpyDeviceToHost));
+    rc = tails_finish(st, m, cnt[0], pit, log_cdf, log_sf, mean_resid, out);
+    out->n_used = cnt[0]; out->n_rejected = cnt[1];
+    return rc;
 }
 
 extern "C" int tamcmc_summary_predictive_result(tamcmc_summary *s, tamcmc_summary_predictive_totals *totals,
                                                 double *pit, double *log_cdf, double *log_sf, double *mean_resid)
 {
-    if (!s || !s->pred.on || s->c->in_flight || s->c->armed) return TAMCMC_E_INVALID;
-    tamcmc_ctx *c = s->c;
-    TM_HIP(hipSetDevice(c->device));
-    TM_HIP(tm_ctx_stream_sync(c));
-    const size_t nx = (size_t)c->L.Nx;
-    long long cnt[2] = {0, 0};
-    std::vector<double> st;
-    try { st.resize(TM_PRED_NSTATE * nx); } catch (const std::bad_alloc &) { return TAMCMC_E_NOMEM; }
-    int rc = fold_counts(s, cnt);
-    if (rc != TAMCMC_OK) return rc;
-    TM_HIP(hipMemcpy(st.data(), s->pred.d_state, st.size() * sizeof(double), hipMemcpyDeviceToHost));
+    if (!s || !s->pred.on) return TAMCMC_E_INVALID;
     TmTailTotals f;
-    rc = tails_finish(st, nx, cnt[0], pit, log_cdf, log_sf, mean_resid, &f);
+    const int rc = tails_result(s, s->pred.d_state, (size_t)s->c->L.Nx, pit, log_cdf, log_sf, mean_resid, &f);
     if (rc != TAMCMC_OK) return rc;
     if (totals) {
         tamcmc_summary_predictive_totals t{};
-        t.n_used = cnt[0]; t.n_rejected = cnt[1];
+        t.n_used = f.n_used; t.n_rejected = f.n_rejected;
         t.ks_D = f.ks_D; t.min_log_sf = f.min_log_sf; t.min_log_cdf = f.min_log_cdf;
         t.bin_min_log_sf = f.at_min_log_sf; t.bin_min_log_cdf = f.at_min_log_cdf;
         std::memcpy(t.pit_hist, f.pit_hist, sizeof(t.pit_hist));
@@ -900,15 +918,12 @@ extern "C" int tamcmc_summary_window_enable(tamcmc_summary *s, int32_t W, int32_
 {
     if (!s || W < 1 || W > TAMCMC_SUMMARY_WINDOW_MAX_BINS || first < 0 || first > W) return TAMCMC_E_INVALID;
     tamcmc_ctx *c = s->c;
-    if (s->win.on || s->q.on || s->loo.on || s->ess.on || c->in_flight || c->armed) return TAMCMC_E_INVALID;
+    if (s->win.on || active_mode(s)) return TAMCMC_E_INVALID;
     const bool chi = c->L.likelihood_case == 0;
     if (chi && !(c->L.like_p >= 1.0 && c->L.like_p <= (double)TAMCMC_SUMMARY_WINDOW_MAX_SHAPE && (int)c->L.like_p * W <= TAMCMC_SUMMARY_WINDOW_MAX_SHAPE))
         return TAMCMC_E_INVALID;
-    TM_HIP(hipSetDevice(c->device));
-    TM_HIP(tm_ctx_stream_sync(c));
-    long long cnt[2] = {0, 0};
-    TM_HIP(hipMemcpy(cnt, s->d_cnt + 2 * s->parity, sizeof(cnt), hipMemcpyDeviceToHost));
-    if (cnt[0] != 0 || cnt[1] != 0) return TAMCMC_E_INVALID;            // the object holds samples: reset first
+    const int rc = summary_enter_empty(s);
+    if (rc != TAMCMC_OK) return rc;
     TmWindow &m = s->win;
     int f = first, len[3];
     const long long nw = tmw_partition((long long)c->L.Nx, W, &f, len);
@@ -935,23 +950,14 @@ extern "C" int tamcmc_summary_window_enable(tamcmc_summary *s, int32_t W, int32_
 extern "C" int tamcmc_summary_window_result(tamcmc_summary *s, tamcmc_summary_window_totals *totals,
                                             double *pit, double *log_cdf, double *log_sf, double *mean_resid)
 {
-    if (!s || !s->win.on || s->c->in_flight || s->c->armed) return TAMCMC_E_INVALID;
-    tamcmc_ctx *c = s->c;
-    TM_HIP(hipSetDevice(c->device));
-    TM_HIP(tm_ctx_stream_sync(c));
+    if (!s || !s->win.on) return TAMCMC_E_INVALID;
     const size_t nw = (size_t)s->win.n_windows;
-    long long cnt[2] = {0, 0};
-    std::vector<double> st;
-    try { st.resize(TM_PRED_NSTATE * nw); } catch (const std::bad_alloc &) { return TAMCMC_E_NOMEM; }
-    int rc = fold_counts(s, cnt);
-    if (rc != TAMCMC_OK) return rc;
-    TM_HIP(hipMemcpy(st.data(), s->win.d_state, st.size() * sizeof(double), hipMemcpyDeviceToHost));
     TmTailTotals f;
-    rc = tails_finish(st, nw, cnt[0], pit, log_cdf, log_sf, mean_resid, &f);
+    const int rc = tails_result(s, s->win.d_state, nw, pit, log_cdf, log_sf, mean_resid, &f);
     if (rc != TAMCMC_OK) return rc;
     if (totals) {
         tamcmc_summary_window_totals t{};
-        t.n_used = cnt[0]; t.n_rejected = cnt[1];
+        t.n_used = f.n_used; t.n_rejected = f.n_rejected;
         t.n_windows = (int64_t)nw; t.W = s->win.W; t.first = s->win.first;
         t.ks_D = f.ks_D; t.min_log_sf = f.min_log_sf; t.min_log_cdf = f.min_log_cdf;
         t.win_min_log_sf = f.at_min_log_sf; t.win_min_log_cdf = f.at_min_log_cdf;
@@ -975,18 +981,17 @@ extern "C" int tamcmc_summary_ess_begin(tamcmc_summary *s, int32_t max_lag, int3
 {
     if (!s || max_lag < 0 || max_lag > TAMCMC_SUMMARY_ESS_MAX_LAG) return TAMCMC_E_INVALID;
     tamcmc_ctx *c = s->c;
-    if (s->q.on || s->loo.on || s->ess.on || c->in_flight || c->armed) return TAMCMC_E_INVALID;
-    TM_HIP(hipSetDevice(c->device));
-    TM_HIP(tm_ctx_stream_sync(c));
+    if (active_mode(s)) return TAMCMC_E_INVALID;
     long long cnt[2] = {0, 0};
-    TM_HIP(hipMemcpy(cnt, s->d_cnt + 2 * s->parity, sizeof(cnt), hipMemcpyDeviceToHost));
+    const int rc = summary_enter(s, cnt);
+    if (rc != TAMCMC_OK) return rc;
     if (cnt[0] < 4) return TAMCMC_E_INVALID;
     const size_t nx = (size_t)c->L.Nx;
     std::vector<double> lse;
     try { lse.resize(2 * nx); } catch (const std::bad_alloc &) { return TAMCMC_E_NOMEM; }
     TM_HIP(hipMemcpy(lse.data(), s->d_state + (size_t)TM_SUM_LSE_A * nx, 2 * nx * sizeof(double), hipMemcpyDeviceToHost));   // a | r
     const double dn = (double)cnt[0];
-    for (size_t i = 0; i < nx; i++) lse[i] = lse[i] + std::log(lse[nx + i] / dn);       // lppd_i, as tamcmc_summary_result
+    for (size_t i = 0; i < nx; i++) lse[i] = tm_lppd(lse[i], lse[nx + i], dn);          // as tamcmc_summary_result
     TmEssMode m;
     m.L = tme_lag_limit(max_lag, cnt[0]);
     m.R = tme_ring_slots(m.L);
@@ -1002,8 +1007,8 @@ extern "C" int tamcmc_summary_ess_begin(tamcmc_summary *s, int32_t max_lag, int3
     m.lppd = m.half + TM_ESS_NHALF * nx;
     m.tau = m.lppd + nx;
     m.ess = m.tau + 2 * nx;
-    m.cnt = reinterpret_cast<long long *>(m.ess + 2 * nx);
-    m.cut = reinterpret_cast<int32_t *>(m.cnt + 4);
+    m.cnt.d = reinterpret_cast<long long *>(m.ess + 2 * nx);
+    m.cut = reinterpret_cast<int32_t *>(m.cnt.d + 4);
     m.on = true;
     s->ess = m;
     c->enq_seq++;
@@ -1016,27 +1021,18 @@ extern "C" int tamcmc_summary_ess_begin(tamcmc_summary *s, int32_t max_lag, int3
     return TAMCMC_OK;
 }
 
-// the pass under way saw exactly the fold pass's samples
-static int ess_pass_complete(tamcmc_summary *s, bool *complete)
-{
-    long long cnt[2] = {0, 0};
-    TM_HIP(hipMemcpy(cnt, s->ess.cnt + 2 * s->ess.parity, sizeof(cnt), hipMemcpyDeviceToHost));
-    *complete = cnt[0] == s->ess.n_used && cnt[1] == s->ess.n_rejected;
-    return TAMCMC_OK;
-}
-
 extern "C" int tamcmc_summary_ess_result(tamcmc_summary *s, tamcmc_summary_ess_totals *totals,
                                          double *ess_M, double *tau_M, double *mcse_M, double *rhat_M, int32_t *cut_M,
                                          double *ess_l, double *r_eff, int32_t *cut_l)
 {
-    if (!s || !s->ess.on || s->c->in_flight || s->c->armed) return TAMCMC_E_INVALID;
+    if (!s || !s->ess.on) return TAMCMC_E_INVALID;
+    int rc = summary_enter(s);
+    if (rc != TAMCMC_OK) return rc;
     tamcmc_ctx *c = s->c;
     TmEssMode &m = s->ess;
-    TM_HIP(hipSetDevice(c->device));
-    TM_HIP(tm_ctx_stream_sync(c));
     c->enq_seq++;
     bool complete = false;
-    int rc = ess_pass_complete(s, &complete);
+    rc = pass_complete(m, &complete);
     if (rc != TAMCMC_OK) return rc;
     if (!complete) {                                                    // not the fold pass's samples: the pass is discarded
         rc = ess_pass_clear(s);
@@ -1047,10 +1043,8 @@ extern "C" int tamcmc_summary_ess_result(tamcmc_summary *s, tamcmc_summary_ess_t
     std::vector<int32_t> cut;
     try { out.resize(4 * nx); half.resize(TM_ESS_NHALF * nx); m2.resize(nx); cut.resize(2 * nx); } catch (const std::bad_alloc &) { return TAMCMC_E_NOMEM; }
     const TmEssArgs a = ess_args(s);
-    if (s->profile) { rc = s->timer.begin(c->stream); if (rc != TAMCMC_OK) return rc; }
-    const int hr = tm_launch_ess_finish(a, c->stream);
-    if (hr != 0) return tm_launch_failed("summary ess finish", hr);
-    if (s->profile) { rc = s->timer.end(c->stream); if (rc != TAMCMC_OK) return rc; }
+    rc = timed_launch(s, s->timer, "summary ess finish", [&] { return tm_launch_ess_finish(a, c->stream); });
+    if (rc != TAMCMC_OK) return rc;
     TM_HIP(hipMemcpyAsync(out.data(), m.tau, 4 * nx * sizeof(double), hipMemcpyDeviceToHost, c->stream));        // tau[2] | ess[2]
     TM_HIP(hipMemcpyAsync(cut.data(), m.cut, 2 * nx * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
     TM_HIP(hipMemcpyAsync(half.data(), m.half, half.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream));
@@ -1089,13 +1083,12 @@ extern "C" int tamcmc_summary_ess_result(tamcmc_summary *s, tamcmc_summary_ess_t
 
 extern "C" int tamcmc_summary_ess_acov(tamcmc_summary *s, int32_t which, double *acov)
 {
-    if (!s || !s->ess.on || !acov || which < 0 || which > 1 || s->c->in_flight || s->c->armed) return TAMCMC_E_INVALID;
-    tamcmc_ctx *c = s->c;
-    TM_HIP(hipSetDevice(c->device));
-    TM_HIP(tm_ctx_stream_sync(c));
+    if (!s || !s->ess.on || !acov || which < 0 || which > 1) return TAMCMC_E_INVALID;
     bool complete = false;
-    const int rc = ess_pass_complete(s, &complete);
+    int rc = summary_enter(s);
+    if (rc == TAMCMC_OK) rc = pass_complete(s->ess, &complete);
     if (rc != TAMCMC_OK) return rc;
+    tamcmc_ctx *c = s->c;
     if (!complete) return TAMCMC_E_INVALID;                             // (the pass stays: tamcmc_summary_ess_result discards it)
     const size_t len = (size_t)(s->ess.L + 1) * (size_t)c->L.Nx;
     TM_HIP(hipMemcpy(acov, s->ess.d_acc + (size_t)which * len, len * sizeof(double), hipMemcpyDeviceToHost));
@@ -1104,9 +1097,8 @@ extern "C" int tamcmc_summary_ess_acov(tamcmc_summary *s, int32_t which, double 
 
 extern "C" int tamcmc_summary_ess_end(tamcmc_summary *s)
 {
-    if (!s || !s->ess.on || s->c->in_flight || s->c->armed) return TAMCMC_E_INVALID;
-    TM_HIP(hipSetDevice(s->c->device));
-    TM_HIP(tm_ctx_stream_sync(s->c));
-    ess_free(s);
-    return TAMCMC_OK;
+    if (!s || !s->ess.on) return TAMCMC_E_INVALID;
+    const int rc = summary_enter(s);
+    if (rc == TAMCMC_OK) ess_free(s);
+    return rc;
 }

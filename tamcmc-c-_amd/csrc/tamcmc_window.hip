@@ -4,7 +4,7 @@
 //
 //   sums    one workgroup per (sample, tile of whole windows).  The tile's bins of the sample's row are read coalesced
 //           (64-bit row offsets), turned into q_i = y_i / M_is (chi(2,2p)) or r_i = (y_i - M_is) sqrt(isig2_i)
-//           (chi_square) and stored into LDS, every window in a slot of its own of W | 1 doubles; then one thread per
+//           (chi_square: tms_resid) and stored into LDS, every window in a slot of its own of W | 1 doubles; then one thread per
 //           window adds its slot up in ascending order.  A tile starts at a window start and holds min(256, 4096 / W)
 //           windows, so no window straddles two tiles; 34 KiB of LDS.  The odd slot stride puts the 32 lanes of a
 //           half-wave on 32 different bank pairs.  A sample that is not OK is skipped by its whole workgroup.
@@ -25,6 +25,7 @@
 
 #pragma clang fp contract(off)
 
+#include "tamcmc_summary_walk.h"
 #include "tamcmc_window.h"
 
 #define TM_WIN_UNROLL 4           // samples whose three scratch words the fold kernel requests before it uses the first
@@ -68,7 +69,7 @@ __global__ __launch_bounds__(TM_WIN_THREADS) void tamcmc_summary_window_sums_ker
         const int j = rest < 0 ? 0 : 1 + rest / a.W - w0;
         const int i = rest < 0 ? (int)g : rest % a.W;
         const double M = row[g], y = a.y[g];
-        q[j * Wp + i] = gauss ? (y - M) * sqrt(a.isig2[g]) : y / M;
+        q[j * Wp + i] = tms_resid(gauss, y, M, gauss ? sqrt(a.isig2[g]) : 0.0);
     }
     __syncthreads();
     if (tid >= nw) return;
@@ -152,7 +153,6 @@ int tm_launch_window(const TmWinArgs &a, void *stream)
         const unsigned blocks = (unsigned)((ns * a.n_windows + TM_WIN_THREADS - 1) / TM_WIN_THREADS);
         hipLaunchKernelGGL(tamcmc_summary_window_tails_kernel, dim3(blocks), dim3(TM_WIN_THREADS), 0, st, a, (int)s0, (int)ns);
     }
-    const unsigned blocks = (unsigned)(((long long)a.n_windows + TM_WIN_THREADS - 1) / TM_WIN_THREADS);
-    hipLaunchKernelGGL(tamcmc_summary_window_fold_kernel, dim3(blocks), dim3(TM_WIN_THREADS), 0, st, a);
+    hipLaunchKernelGGL(tamcmc_summary_window_fold_kernel, dim3(tms_blocks(a.n_windows, TM_WIN_THREADS)), dim3(TM_WIN_THREADS), 0, st, a);
     return (int)hipGetLastError();
 }
