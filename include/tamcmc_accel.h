@@ -368,6 +368,52 @@ int tamcmc_group_members(const tamcmc_group *g, int32_t *n_members, int32_t *Npa
  *   window_kernel_time   as predictive_kernel_time, for the three window kernels of a block together (one event pair per
  *                block), under the same tamcmc_summary_profile switch, refused in the same cases.
  *
+ * SLIDING-WINDOW PREDICTIVE SCAN: the windowed check at every start position and for several widths at once.  The disjoint
+ * windows above dilute a feature that one of their boundaries cuts, and take one width per object; the documented remedy, a
+ * second pass with another `first` or another W, costs a pass over the chain each.  The scan is a third setting of the
+ * object beside predictive_enable and window_enable: every fold-mode block runs the kernels of tamcmc_scan.hip behind the
+ * window kernels, on the same rows and the same stream.
+ *   Widths: a strictly ascending list W_0 < ... < W_{K-1}, 1 <= K <= TAMCMC_SUMMARY_SCAN_MAX_WIDTHS, each 1 ...
+ *   TAMCMC_SUMMARY_WINDOW_MAX_BINS and at most Nx.  Width k has the positions j = 0 ... Nx - W_k, n_pos_k = Nx - W_k + 1 of them;
+ *   the window of position j is the bins [j, j + W_k).  Every window is full.
+ *   Definition, per (accepted sample s, width k, position j), exactly as for a full window of W_k bins of the disjoint check:
+ *   the sum S (R) over the window's bins in ascending bin order starting from the first term, without FMA contraction -- the
+ *   sums of all widths at one position are prefixes of one ascending sum, so their bits are those of separate sums --, the
+ *   two tails at the shape p W_k (c = 1 / sqrt((double)W_k)), log_cdf and log_sf by the guarded, compensated log-sum-exp in
+ *   push order, mean_resid the Welford mean of S / (double)W_k, pit from the smaller tail on the host.  Position j of width W
+ *   equals window w of window_enable(W, first) wherever that window is full and starts at bin j, bit for bit in all four
+ *   arrays.  With n = 0 everything is NaN.
+ *   Totals per width, on the host in position order, the first position winning a tie and a NaN skipped: n_used, n_rejected,
+ *   W, n_positions; min_log_sf with pos_min_log_sf and min_log_cdf with pos_min_log_cdf (a position of -1: every value was NaN).
+ *   There is no ks_D and no pit_hist: overlapping windows are not independent, and a uniformity test over them would mislead.
+ *   Regions, on the host: for a width k, a side `which` (0: log_sf, an excess; 1: log_cdf, a deficit) and a line log_below < 0,
+ *   a region is a maximal run of consecutive positions whose value is below the line (a NaN is never below it): {pos_first,
+ *   pos_last, bin_first = pos_first, bin_last = pos_last + W_k - 1, pos_min = the first position of the run's minimum,
+ *   min_log, mean_resid_at_min}, in position order.  log_below = NaN picks log(0.01 * (double)W_k / (double)Nx), the Bonferroni
+ *   line at 1 % over Nx / W_k independent windows.
+ *   scan_enable  allowed only while the object holds no sample (fresh, or after tamcmc_summary_reset) and is in fold mode, once
+ *                per object.  With total = sum_k n_pos_k it allocates 56 total bytes of state plus 24 C total bytes of scratch
+ *                on the device, C = max(1, min(block_chains, 4096, 256 MiB / (24 total bytes))) samples: a block with more
+ *                samples is worked in chunks of C, which cannot change a bit.  At most 256 MiB of scratch, or 24 total bytes
+ *                where one sample takes more -- Nx = 1e5 with eight widths: 19 MB a sample, C = 13, and 45 MB of state.
+ *                TAMCMC_E_NOMEM when that fails, and the object stays as it was.  Refused with TAMCMC_E_INVALID: n_widths
+ *                outside 1 ... TAMCMC_SUMMARY_SCAN_MAX_WIDTHS, a NULL list, a width outside 1 ... TAMCMC_SUMMARY_WINDOW_MAX_BINS
+ *                or above Nx, widths not strictly ascending, a chi(2,2p) context with p < 1 or p W_{K-1} >
+ *                TAMCMC_SUMMARY_WINDOW_MAX_SHAPE, a second call, samples already pushed, quantile, LOO or ESS mode, a context
+ *                with a batch armed or in flight.  Stays on until tamcmc_summary_destroy; tamcmc_summary_reset clears the state
+ *                and keeps the setting.  Independent of predictive_enable and window_enable: any combination, in any order.
+ *   While enabled, the fold, predictive and window kernels run unchanged -- their results keep their bits -- and passes pushed
+ *   in quantile, LOO or ESS mode do not touch the scan's state.  Every scan result is bit for bit independent of block_chains,
+ *   of how the samples are split over pushes, and of which other widths are in the list.
+ *   scan_result  width k = 0 ... K-1: totals and four arrays of n_pos_k doubles on the host, any of them may be NULL.
+ *                Synchronises the stream; may be called between pushes, in any mode and repeatedly, and disturbs nothing.
+ *                TAMCMC_E_INVALID: k out of range, the scan not enabled, a batch in flight or armed.
+ *   scan_regions as scan_result.  Always writes the number of regions to *n_regions and fills at most max_regions records, the
+ *                first ones in position order; regions == NULL with max_regions == 0 only counts.  TAMCMC_E_INVALID also for
+ *                which outside 0 ... 1, log_below >= 0, max_regions < 0, a NULL n_regions, NULL regions with max_regions > 0.
+ *   scan_kernel_time   as window_kernel_time, for all scan kernels of a block together (one event pair per block), under the
+ *                same tamcmc_summary_profile switch, refused in the same cases.
+ *
  * EFFECTIVE SAMPLE SIZE, MCSE AND SPLIT R-HAT: every number above is a Monte-Carlo estimate over an autocorrelated chain;
  * this says per bin how many independent draws the chain is worth (Geyer's initial monotone sequence on the
  * autocorrelation over the sample order, as Stan uses for one chain), the Monte-Carlo standard error of mean_M that
@@ -405,7 +451,7 @@ int tamcmc_group_members(const tamcmc_group *g, int32_t *n_members, int32_t *Npa
  *                1e5 at L = 255.  TAMCMC_E_NOMEM when that fails, and the object stays as it was.  Refused with
  *                TAMCMC_E_INVALID: n_used < 4, max_lag outside 0 ... TAMCMC_SUMMARY_ESS_MAX_LAG, any mode already on
  *                (tamcmc_summary_quantiles_begin and tamcmc_summary_loo_begin are likewise refused while ESS mode is on, and
- *                so are predictive_enable and window_enable), a context with a batch in flight or armed.
+ *                so are predictive_enable, window_enable and scan_enable), a context with a batch in flight or armed.
  *   While the mode is on, push and push_device evaluate the rows as before and hand out the same logL and status bits, but
  *   feed the ESS kernels (tamcmc_ess.hip) instead of the fold kernel; tamcmc_summary_result keeps returning the frozen fold
  *   results, and the predictive and window states are not touched.  Every (bin, lag) accumulator is advanced by one
@@ -478,6 +524,22 @@ int tamcmc_summary_window_enable(tamcmc_summary *s, int32_t W, int32_t first, in
 int tamcmc_summary_window_result(tamcmc_summary *s, tamcmc_summary_window_totals *totals,
                                  double *pit, double *log_cdf, double *log_sf, double *mean_resid);
 int tamcmc_summary_window_kernel_time(tamcmc_summary *s, double *total_ms, int64_t *launches);
+#define TAMCMC_SUMMARY_SCAN_MAX_WIDTHS 8
+typedef struct {
+    int64_t n_used, n_rejected, W, n_positions;
+    double min_log_sf, min_log_cdf;
+    int64_t pos_min_log_sf, pos_min_log_cdf;
+} tamcmc_summary_scan_totals;
+typedef struct {
+    int64_t pos_first, pos_last, bin_first, bin_last, pos_min;
+    double min_log, mean_resid_at_min;
+} tamcmc_summary_scan_region;
+int tamcmc_summary_scan_enable(tamcmc_summary *s, int32_t n_widths, const int32_t *W);
+int tamcmc_summary_scan_result(tamcmc_summary *s, int32_t k, tamcmc_summary_scan_totals *totals,
+                               double *pit, double *log_cdf, double *log_sf, double *mean_resid);
+int tamcmc_summary_scan_regions(tamcmc_summary *s, int32_t k, int32_t which, double log_below,
+                                int32_t max_regions, tamcmc_summary_scan_region *regions, int32_t *n_regions);
+int tamcmc_summary_scan_kernel_time(tamcmc_summary *s, double *total_ms, int64_t *launches);
 #define TAMCMC_SUMMARY_ESS_MAX_LAG 1023
 typedef struct {
     int64_t n_used, n_rejected, lag;

@@ -35,6 +35,7 @@ EXPORTS = [
     "tamcmc_summary_loo_begin", "tamcmc_summary_loo_result", "tamcmc_summary_loo_end",
     "tamcmc_summary_predictive_enable", "tamcmc_summary_predictive_result", "tamcmc_summary_predictive_kernel_time",
     "tamcmc_summary_window_enable", "tamcmc_summary_window_result", "tamcmc_summary_window_kernel_time",
+    "tamcmc_summary_scan_enable", "tamcmc_summary_scan_result", "tamcmc_summary_scan_regions", "tamcmc_summary_scan_kernel_time",
     "tamcmc_summary_ess_begin", "tamcmc_summary_ess_result", "tamcmc_summary_ess_acov", "tamcmc_summary_ess_end",
 ]
 
@@ -66,6 +67,18 @@ class SummaryWindowTotals(C.Structure):
     _fields_ = [("n_used", C.c_int64), ("n_rejected", C.c_int64), ("n_windows", C.c_int64), ("W", C.c_int64), ("first", C.c_int64),
                 ("ks_D", C.c_double), ("min_log_sf", C.c_double), ("min_log_cdf", C.c_double),
                 ("win_min_log_sf", C.c_int64), ("win_min_log_cdf", C.c_int64), ("pit_hist", C.c_int64 * PIT_CELLS)]
+
+
+class SummaryScanTotals(C.Structure):
+    """tamcmc_summary_scan_totals"""
+    _fields_ = [("n_used", C.c_int64), ("n_rejected", C.c_int64), ("W", C.c_int64), ("n_positions", C.c_int64),
+                ("min_log_sf", C.c_double), ("min_log_cdf", C.c_double), ("pos_min_log_sf", C.c_int64), ("pos_min_log_cdf", C.c_int64)]
+
+
+class SummaryScanRegion(C.Structure):
+    """tamcmc_summary_scan_region"""
+    _fields_ = [("pos_first", C.c_int64), ("pos_last", C.c_int64), ("bin_first", C.c_int64), ("bin_last", C.c_int64),
+                ("pos_min", C.c_int64), ("min_log", C.c_double), ("mean_resid_at_min", C.c_double)]
 
 
 class SummaryEssTotals(C.Structure):
@@ -149,6 +162,10 @@ def load_library():
     lib.tamcmc_summary_window_enable.argtypes = [vp, C.c_int32, C.c_int32, ip]
     lib.tamcmc_summary_window_result.argtypes = [vp, C.POINTER(SummaryWindowTotals), dp, dp, dp, dp]
     lib.tamcmc_summary_window_kernel_time.argtypes = [vp, dp, C.POINTER(C.c_int64)]
+    lib.tamcmc_summary_scan_enable.argtypes = [vp, C.c_int32, ip]
+    lib.tamcmc_summary_scan_result.argtypes = [vp, C.c_int32, C.POINTER(SummaryScanTotals), dp, dp, dp, dp]
+    lib.tamcmc_summary_scan_regions.argtypes = [vp, C.c_int32, C.c_int32, C.c_double, C.c_int32, C.POINTER(SummaryScanRegion), ip]
+    lib.tamcmc_summary_scan_kernel_time.argtypes = [vp, dp, C.POINTER(C.c_int64)]
     lib.tamcmc_summary_ess_begin.argtypes = [vp, C.c_int32, ip]
     lib.tamcmc_summary_ess_result.argtypes = [vp, C.POINTER(SummaryEssTotals), dp, dp, dp, dp, ip, dp, dp, ip]
     lib.tamcmc_summary_ess_acov.argtypes = [vp, C.c_int32, dp]
@@ -464,12 +481,13 @@ class Summary:
     Pareto k-hat per bin) by pushing them once more, and ess() the effective sample size, Monte-Carlo standard error and
     split R-hat per bin by pushing them once more in the same order.  With predictive=True every fold pass also accumulates the
     posterior predictive check (predictive_result(): PIT and both log tail probabilities per bin), and with window=W or
-    window=(W, first) the same check over disjoint windows of W bins (window_result()).  The Accel cannot be closed while
+    window=(W, first) the same check over disjoint windows of W bins (window_result()); with scan=W or scan=(W0, W1, ...) the
+    windowed check at every start position for up to eight widths at once (scan_result(k), scan_regions(k)).  The Accel cannot be closed while
     the summary is open."""
 
     ARRAYS = ("mean_M", "var_M", "min_M", "max_M", "mean_l", "var_l", "lppd")
 
-    def __init__(self, accel, block_chains=0, predictive=False, window=None):
+    def __init__(self, accel, block_chains=0, predictive=False, window=None, scan=None):
         self._lib = load_library()
         self.accel = accel
         self._s = C.c_void_p()
@@ -479,6 +497,8 @@ class Summary:
                 self.predictive_enable()
             if window is not None:
                 self.window_enable(*np.atleast_1d(window).tolist())
+            if scan is not None:
+                self.scan_enable(scan)
         except (AccelError, TypeError, ValueError):
             self.close()
             raise
@@ -690,6 +710,59 @@ class Summary:
         n = C.c_int64(0)
         self._check(self._lib.tamcmc_summary_window_kernel_time(self._s, C.byref(ms), C.byref(n)),
                     "tamcmc_summary_window_kernel_time")
+        return ms.value, n.value
+
+    # ---- sliding-window predictive scan: the windowed check at every start position, several widths at once ----
+    SCAN_MAX_WIDTHS = 8
+    SCAN_ARRAYS = ("pit", "log_cdf", "log_sf", "mean_resid")
+    SCAN_TOTALS = ("n_used", "n_rejected", "W", "n_positions", "min_log_sf", "min_log_cdf", "pos_min_log_sf", "pos_min_log_cdf")
+    SCAN_REGION = ("pos_first", "pos_last", "bin_first", "bin_last", "pos_min", "min_log", "mean_resid_at_min")
+
+    def scan_enable(self, widths):
+        """Turns the scan on for the life of the object: widths is W or a strictly ascending sequence of up to eight W;
+        allowed only while the object holds no sample and is in fold mode."""
+        W = np.ascontiguousarray(np.atleast_1d(widths), dtype=np.int32)
+        if W.ndim != 1:
+            raise ValueError("widths must be an integer or a sequence of integers")
+        self._check(self._lib.tamcmc_summary_scan_enable(self._s, int(W.size), _iptr(W) if W.size else None), "tamcmc_summary_scan_enable")
+        self._scan_W = tuple(int(w) for w in W)
+
+    def scan_result(self, k=0):
+        """Width k of the list.  dict: pit, log_cdf, log_sf, mean_resid (n_positions doubles), first_bin and last_bin
+        (n_positions int64, inclusive) and the totals n_used, n_rejected, W, n_positions, min_log_sf, min_log_cdf,
+        pos_min_log_sf, pos_min_log_cdf."""
+        W = getattr(self, "_scan_W", ())
+        npos = max(self.accel.Nx - W[k] + 1, 1) if 0 <= k < len(W) else 1      # (otherwise the library refuses before it writes)
+        out = {key: np.empty(npos) for key in self.SCAN_ARRAYS}
+        t = SummaryScanTotals()
+        self._check(self._lib.tamcmc_summary_scan_result(self._s, int(k), C.byref(t), *[_dptr(out[key]) for key in self.SCAN_ARRAYS]),
+                    "tamcmc_summary_scan_result")
+        out.update({key: (getattr(t, key) if key in ("min_log_sf", "min_log_cdf") else int(getattr(t, key))) for key in self.SCAN_TOTALS})
+        out["first_bin"] = np.arange(npos, dtype=np.int64)
+        out["last_bin"] = out["first_bin"] + (int(t.W) - 1)
+        return out
+
+    def scan_regions(self, k=0, which=0, log_below=None):
+        """The maximal runs of positions of width k whose log_sf (which = 0: an excess) or log_cdf (which = 1: a deficit) is
+        below log_below (None: log(0.01 W / Nx)), in position order: a list of dicts pos_first, pos_last, bin_first,
+        bin_last, pos_min, min_log, mean_resid_at_min."""
+        line = float("nan") if log_below is None else float(log_below)
+        n = C.c_int32(0)
+        self._check(self._lib.tamcmc_summary_scan_regions(self._s, int(k), int(which), line, 0, None, C.byref(n)), "tamcmc_summary_scan_regions")
+        if n.value == 0:
+            return []
+        buf = (SummaryScanRegion * n.value)()
+        cap = n.value
+        self._check(self._lib.tamcmc_summary_scan_regions(self._s, int(k), int(which), line, cap, buf, C.byref(n)), "tamcmc_summary_scan_regions")
+        return [{key: (getattr(r, key) if key in ("min_log", "mean_resid_at_min") else int(getattr(r, key))) for key in self.SCAN_REGION}
+                for r in buf[:min(cap, n.value)]]
+
+    def scan_kernel_time(self):
+        """(summed milliseconds, blocks) of the scan kernels since profile(True); kernel_time() stays the fold kernel's."""
+        ms = C.c_double(0.0)
+        n = C.c_int64(0)
+        self._check(self._lib.tamcmc_summary_scan_kernel_time(self._s, C.byref(ms), C.byref(n)),
+                    "tamcmc_summary_scan_kernel_time")
         return ms.value, n.value
 
     # ---- effective sample size, MCSE and split R-hat per bin, one more pass over the same rows in the same order ----

@@ -7,6 +7,8 @@
 // (tamcmc_summary_predictive_*, tamcmc_predictive.h) a fold-mode block has a stage 3: tamcmc_summary_predictive_kernel on
 // the same rows; the other two modes never touch its state.  With the windowed check enabled (tamcmc_summary_window_*,
 // tamcmc_window.h) a stage 4 follows: the sums, tails and fold kernels of tamcmc_window.hip, again on the same rows.
+// With the sliding-window scan enabled (tamcmc_summary_scan_*, tamcmc_scan.h) a stage 5 follows: the sums, tails and fold
+// kernels of tamcmc_scan.hip per chunk of the block, on the same rows.
 // In ESS mode (tamcmc_summary_ess_*, tamcmc_ess.h) stage 2 is the centre and lag kernels of tamcmc_ess.hip, once per chunk of
 // the block.
 #include <algorithm>
@@ -18,6 +20,7 @@
 #include "tamcmc_loo.h"
 #include "tamcmc_predictive.h"
 #include "tamcmc_quantile.h"
+#include "tamcmc_scan.h"
 #include "tamcmc_summary.h"
 #include "tamcmc_window.h"
 
@@ -91,6 +94,19 @@ struct TmWindow {
     TmTimer timer;                       // the three window kernels of a block together (tamcmc_summary_window_kernel_time)
 };
 
+// The sliding-window scan: a setting like TmWindow, and independent of it and of TmPredictive.
+struct TmScan {
+    bool on = false;
+    double *d_state = nullptr;           // [TM_PRED_NSTATE][total]
+    double *d_scratch = nullptr;         // [3][C][total]
+    int K = 0, C = 0, p = 1;
+    long long total = 0;                 // sum_k n_pos_k
+    int32_t W[TM_SCAN_MAX_WIDTHS] = {};
+    long long off[TM_SCAN_MAX_WIDTHS] = {};
+    TmWinShape shape[TM_SCAN_MAX_WIDTHS] = {};
+    TmTimer timer;                       // the scan kernels of a block together (tamcmc_summary_scan_kernel_time)
+};
+
 struct tamcmc_summary {
     tamcmc_ctx *c = nullptr;
     int B = 0;                           // samples per block
@@ -114,6 +130,7 @@ struct tamcmc_summary {
     TmEssMode ess;
     TmPredictive pred;
     TmWindow win;
+    TmScan scan;
 };
 
 static size_t summary_stage_out(const tamcmc_summary *s) { return (size_t)s->B * (size_t)s->c->L.Nparams * sizeof(double); }
@@ -313,6 +330,20 @@ static int window_block(tamcmc_summary *s, int n, const int32_t *d_status, const
     return timed_launch(s, s->win.timer, "summary window", [&] { return tm_launch_window(wa, c->stream); });
 }
 
+// stage 5: the scan's kernels on the same rows, per chunk of the block, counting on from the same pair
+static int scan_block(tamcmc_summary *s, int n, const int32_t *d_status, const long long *cnt_in)
+{
+    tamcmc_ctx *c = s->c;
+    const TmScan &m = s->scan;
+    TmScanArgs sa{};
+    sa.rows = s->d_model; sa.status = d_status; sa.y = c->d_y; sa.isig2 = c->d_isig2; sa.state = m.d_state; sa.scratch = m.d_scratch;
+    sa.cnt_in = cnt_in;
+    sa.total = m.total; sa.Nx = c->L.Nx; sa.B = n; sa.C = m.C; sa.K = m.K;
+    sa.likelihood_case = c->L.likelihood_case; sa.p = m.p;
+    for (int k = 0; k < m.K; k++) { sa.W[k] = m.W[k]; sa.off[k] = m.off[k]; sa.shape[k] = m.shape[k]; }
+    return timed_launch(s, s->scan.timer, "summary scan", [&] { return tm_launch_scan(sa, c->stream); });
+}
+
 // One block of n <= B samples, device pointers, enqueued on the context's stream.
 static int summary_block(tamcmc_summary *s, int n, const double *d_params, double *d_logL, int32_t *d_status)
 {
@@ -333,7 +364,8 @@ static int summary_block(tamcmc_summary *s, int n, const double *d_params, doubl
     rc = timed_launch(s, s->timer, "summary fold", [&] { return tm_launch_summary_fold(a, c->stream); }, &s->cnt);
     if (rc != TAMCMC_OK) return rc;
     if (s->pred.on) { rc = predictive_block(s, n, d_status, a.cnt_in); if (rc != TAMCMC_OK) return rc; }
-    return s->win.on ? window_block(s, n, d_status, a.cnt_in) : TAMCMC_OK;
+    if (s->win.on) { rc = window_block(s, n, d_status, a.cnt_in); if (rc != TAMCMC_OK) return rc; }
+    return s->scan.on ? scan_block(s, n, d_status, a.cnt_in) : TAMCMC_OK;
 }
 
 static int summary_clear(tamcmc_summary *s)
@@ -341,6 +373,7 @@ static int summary_clear(tamcmc_summary *s)
     const tamcmc_ctx *c = s->c;
     if (s->pred.on) TM_HIP(hipMemsetAsync(s->pred.d_state, 0, (size_t)TM_PRED_NSTATE * (size_t)c->L.Nx * sizeof(double), c->stream));
     if (s->win.on) TM_HIP(hipMemsetAsync(s->win.d_state, 0, (size_t)TM_PRED_NSTATE * (size_t)s->win.n_windows * sizeof(double), c->stream));
+    if (s->scan.on) TM_HIP(hipMemsetAsync(s->scan.d_state, 0, (size_t)TM_PRED_NSTATE * (size_t)s->scan.total * sizeof(double), c->stream));
     TM_HIP(hipMemsetAsync(s->d_state, 0, (size_t)TM_SUM_NSTATE * (size_t)c->L.Nx * sizeof(double), c->stream));
     return s->cnt.clear(c->stream);
 }
@@ -399,6 +432,7 @@ extern "C" int tamcmc_summary_destroy(tamcmc_summary *s)
     (void)hipFree(s->d_model); (void)hipFree(s->d_state); (void)hipFree(s->cnt.d); (void)hipFree(s->d_rows);
     (void)hipFree(s->d_T); (void)hipFree(s->d_logL); (void)hipFree(s->d_status); (void)hipFree(s->pred.d_state);
     (void)hipFree(s->win.d_state); (void)hipFree(s->win.d_scratch);
+    (void)hipFree(s->scan.d_state); (void)hipFree(s->scan.d_scratch);
     for (int p = 0; p < 2; p++) {
         s->stage[p].release();
         if (s->ev_stage[p]) (void)hipEventDestroy(s->ev_stage[p]);
@@ -406,6 +440,7 @@ extern "C" int tamcmc_summary_destroy(tamcmc_summary *s)
     s->timer.destroy();
     s->pred.timer.destroy();
     s->win.timer.destroy();
+    s->scan.timer.destroy();
     delete s;
     return TAMCMC_OK;
 }
@@ -541,6 +576,7 @@ extern "C" int tamcmc_summary_profile(tamcmc_summary *s, int enable)
     s->timer.used = 0;
     s->pred.timer.used = 0;
     s->win.timer.used = 0;
+    s->scan.timer.used = 0;
     return TAMCMC_OK;
 }
 
@@ -869,9 +905,10 @@ static int fold_counts(const tamcmc_summary *s, long long cnt[2])
     return TAMCMC_OK;
 }
 
-// _predictive_result and _window_result once their check is known to be on: d_state[TM_PRED_NSTATE][m], m bins or windows
+// _predictive_result, _window_result and _scan_result once their check is known to be on: d_state[TM_PRED_NSTATE][m], m bins,
+// windows or positions; pitch: the doubles from one state word's block to the next, where that is not m (0: m)
 static int tails_result(tamcmc_summary *s, const double *d_state, const size_t m, double *pit, double *log_cdf, double *log_sf,
-                        double *mean_resid, TmTailTotals *out)
+                        double *mean_resid, TmTailTotals *out, const size_t pitch = 0)
 {
     int rc = summary_enter(s);
     if (rc != TAMCMC_OK) return rc;
@@ -880,7 +917,8 @@ static int tails_result(tamcmc_summary *s, const double *d_state, const size_t m
     try { st.resize(TM_PRED_NSTATE * m); } catch (const std::bad_alloc &) { return TAMCMC_E_NOMEM; }
     rc = fold_counts(s, cnt);
     if (rc != TAMCMC_OK) return rc;
-    TM_HIP(hipMemcpy(st.data(), d_state, st.size() * sizeof(double), hipMemcpyDeviceToHost));
+    if (pitch == 0 || pitch == m) TM_HIP(hipMemcpy(st.data(), d_state, st.size() * sizeof(double), hipMemcpyDeviceToHost));
+    else TM_HIP(hipMemcpy2D(st.data(), m * sizeof(double), d_state, pitch * sizeof(double), m * sizeof(double), TM_PRED_NSTATE, hipMemcpyDeviceToHost));
     rc = tails_finish(st, m, cnt[0], pit, log_cdf, log_sf, mean_resid, out);
     out->n_used = cnt[0]; out->n_rejected = cnt[1];
     return rc;
@@ -973,6 +1011,106 @@ extern "C" int tamcmc_summary_window_kernel_time(tamcmc_summary *s, double *tota
     TM_HIP(hipSetDevice(s->c->device));
     TM_HIP(tm_ctx_stream_sync(s->c));
     return s->win.timer.total(total_ms, launches);
+}
+
+// ---- sliding-window predictive scan (tamcmc_scan.h) ----
+
+extern "C" int tamcmc_summary_scan_enable(tamcmc_summary *s, int32_t n_widths, const int32_t *W)
+{
+    if (!s || !W || n_widths < 1 || n_widths > TAMCMC_SUMMARY_SCAN_MAX_WIDTHS) return TAMCMC_E_INVALID;
+    tamcmc_ctx *c = s->c;
+    if (s->scan.on || active_mode(s)) return TAMCMC_E_INVALID;
+    for (int k = 0; k < n_widths; k++)
+        if (W[k] < 1 || W[k] > TAMCMC_SUMMARY_WINDOW_MAX_BINS || W[k] > c->L.Nx || (k > 0 && W[k] <= W[k - 1])) return TAMCMC_E_INVALID;
+    const bool chi = c->L.likelihood_case == 0;
+    if (chi && !(c->L.like_p >= 1.0 && c->L.like_p <= (double)TAMCMC_SUMMARY_WINDOW_MAX_SHAPE &&
+                 (int)c->L.like_p * W[n_widths - 1] <= TAMCMC_SUMMARY_WINDOW_MAX_SHAPE))
+        return TAMCMC_E_INVALID;
+    const int rc = summary_enter_empty(s);
+    if (rc != TAMCMC_OK) return rc;
+    TmScan m;
+    m.K = n_widths;
+    for (int k = 0; k < n_widths; k++) m.W[k] = W[k];
+    m.total = tmsc_layout((long long)c->L.Nx, m.K, m.W, m.off);
+    m.C = (int)tmsc_chunk((long long)s->B, m.total);
+    m.p = chi ? (int)c->L.like_p : 1;
+    for (int k = 0; k < n_widths; k++) m.shape[k] = tmw_shape(m.W[k], m.p);
+    const size_t state_bytes = (size_t)TM_PRED_NSTATE * (size_t)m.total * sizeof(double);
+    const size_t scratch_bytes = 3 * (size_t)m.C * (size_t)m.total * sizeof(double);
+    if (hipMalloc(&m.d_state, state_bytes) != hipSuccess) { (void)hipGetLastError(); return TAMCMC_E_NOMEM; }
+    if (hipMalloc(&m.d_scratch, scratch_bytes) != hipSuccess) { (void)hipGetLastError(); (void)hipFree(m.d_state); return TAMCMC_E_NOMEM; }
+    c->enq_seq++;
+    if (hipMemsetAsync(m.d_state, 0, state_bytes, c->stream) != hipSuccess) {
+        (void)hipStreamSynchronize(c->stream);
+        (void)hipFree(m.d_state); (void)hipFree(m.d_scratch);
+        return TAMCMC_E_HIP;
+    }
+    m.on = true;
+    s->scan = m;
+    return TAMCMC_OK;
+}
+
+// what _scan_result and _scan_regions share: width k's four arrays (any may be NULL) and its totals
+static int scan_width_result(tamcmc_summary *s, int32_t k, double *pit, double *log_cdf, double *log_sf, double *mean_resid, TmTailTotals *f)
+{
+    if (!s || !s->scan.on || k < 0 || k >= s->scan.K) return TAMCMC_E_INVALID;
+    const TmScan &m = s->scan;
+    const size_t n_pos = (size_t)tmsc_positions((long long)s->c->L.Nx, m.W[k]);
+    return tails_result(s, m.d_state + m.off[k], n_pos, pit, log_cdf, log_sf, mean_resid, f, (size_t)m.total);
+}
+
+extern "C" int tamcmc_summary_scan_result(tamcmc_summary *s, int32_t k, tamcmc_summary_scan_totals *totals,
+                                          double *pit, double *log_cdf, double *log_sf, double *mean_resid)
+{
+    TmTailTotals f;
+    const int rc = scan_width_result(s, k, pit, log_cdf, log_sf, mean_resid, &f);
+    if (rc != TAMCMC_OK) return rc;
+    if (totals) {
+        tamcmc_summary_scan_totals t{};
+        t.n_used = f.n_used; t.n_rejected = f.n_rejected;
+        t.W = s->scan.W[k]; t.n_positions = (int64_t)tmsc_positions((long long)s->c->L.Nx, s->scan.W[k]);
+        t.min_log_sf = f.min_log_sf; t.min_log_cdf = f.min_log_cdf;
+        t.pos_min_log_sf = f.at_min_log_sf; t.pos_min_log_cdf = f.at_min_log_cdf;
+        *totals = t;
+    }
+    return TAMCMC_OK;
+}
+
+extern "C" int tamcmc_summary_scan_regions(tamcmc_summary *s, int32_t k, int32_t which, double log_below,
+                                           int32_t max_regions, tamcmc_summary_scan_region *regions, int32_t *n_regions)
+{
+    if (!s || !s->scan.on || k < 0 || k >= s->scan.K || which < 0 || which > 1 || !n_regions || max_regions < 0 ||
+        (max_regions > 0 && !regions) || log_below >= 0.0)
+        return TAMCMC_E_INVALID;                    // (a NaN line passes: the default)
+    const long long nx = (long long)s->c->L.Nx;
+    const int W = s->scan.W[k];
+    const long long n_pos = tmsc_positions(nx, W);
+    std::vector<double> v, mr;
+    std::vector<TmScanRegion> found;
+    const long long room = max_regions < n_pos ? max_regions : n_pos;          // (there are at most n_pos regions)
+    try { v.resize((size_t)n_pos); mr.resize((size_t)n_pos); found.resize((size_t)room); } catch (const std::bad_alloc &) { return TAMCMC_E_NOMEM; }
+    TmTailTotals f;
+    const int rc = scan_width_result(s, k, nullptr, which == 1 ? v.data() : nullptr, which == 0 ? v.data() : nullptr, mr.data(), &f);
+    if (rc != TAMCMC_OK) return rc;
+    const double line = std::isnan(log_below) ? tmsc_default_line(W, nx) : log_below;
+    const long long count = tmsc_regions(v.data(), mr.data(), n_pos, W, line, room, found.data());
+    for (long long i = 0; i < count && i < room; i++) {
+        const TmScanRegion &r = found[(size_t)i];
+        tamcmc_summary_scan_region o{};
+        o.pos_first = r.pos_first; o.pos_last = r.pos_last; o.bin_first = r.bin_first; o.bin_last = r.bin_last; o.pos_min = r.pos_min;
+        o.min_log = r.min_log; o.mean_resid_at_min = r.mean_resid_at_min;
+        regions[i] = o;
+    }
+    *n_regions = (int32_t)count;
+    return TAMCMC_OK;
+}
+
+extern "C" int tamcmc_summary_scan_kernel_time(tamcmc_summary *s, double *total_ms, int64_t *launches)
+{
+    if (!s || !total_ms || !launches || !s->scan.on || s->c->armed) return TAMCMC_E_INVALID;
+    TM_HIP(hipSetDevice(s->c->device));
+    TM_HIP(tm_ctx_stream_sync(s->c));
+    return s->scan.timer.total(total_ms, launches);
 }
 
 // ---- effective sample size, MCSE and split R-hat (tamcmc_ess.h) ----

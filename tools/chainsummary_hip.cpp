@@ -4,6 +4,7 @@
 //   chainsummary_hip <config dir> <model file> <data file> <params root> <output file>
 //                    [--chain m] [--slice s] [--first i] [--last j] [--thin k] [--block B]
 //                    [--quantiles q1,q2,...] [--qbits b] [--loo] [--predictive] [--window W[,first]] [--ess [L]]
+//                    [--scan W0[,W1,...]] [--scan-below T]
 //
 // <config dir> is the reference's Config/default; model id, likelihood, p, plength, the inputs row and the relax mask
 // come from the setup it describes (tamcmc_setup_create / tamcmc_setup_load, slice s counted from 0).  The samples are
@@ -32,6 +33,16 @@
 // n_rejected= ...`, `# ks_D= ...  min_log_sf= ...  win_min_log_sf= ...  min_log_cdf= ...  win_min_log_cdf= ...`,
 // `# pit_hist= c0 c1 ... c19` -- then one row per window:
 //   w  first_bin  last_bin  x_first  x_last  pit  log_cdf  log_sf  mean_resid
+// With --scan W0[,W1,...] (up to 8 strictly ascending widths) the first pass also accumulates that check at every start
+// position j = 0 ... Nx - W of every width (tamcmc_summary_scan_*; no further pass).  The output file and .windows keep every
+// byte; the scan goes to <output file>.scan: `#` header lines -- the version, `# widths= W0,W1,...`, `# n_used= ...
+// n_rejected= ...`, per width `# W= ...  n_positions= ...  min_log_sf= ...  pos_min_log_sf= ...  min_log_cdf= ...
+// pos_min_log_cdf= ...` -- then one row per bin j, 17 significant digits, `nan` where width k has no position j:
+//   j  x_j  then for each width  pit  log_cdf  log_sf  mean_resid
+// and the regions -- the maximal runs of positions whose log_sf (which = 0) or log_cdf (which = 1) lies below the line -- to
+// <output file>.scan.regions, one row per region of either side, per width:
+//   W  which  pos_first  pos_last  bin_first  bin_last  x_first  x_last  pos_min  min_log  mean_resid_at_min
+// The line is T of --scan-below T (T < 0) for all widths, by default log(0.01 W / Nx) per width.
 // With --ess [L] the selected samples are read once more for the effective sample size, the Monte-Carlo standard error and
 // the split R-hat per bin (tamcmc_summary_ess_*; lags up to L, 0 ... 1023, default 0: the library's 255).  The output file
 // keeps every byte; the results go to <output file>.ess: `#` header lines -- the version, `# n_used= ...  n_rejected= ...
@@ -54,6 +65,7 @@ static int usage()
     fprintf(stderr, " Usage: chainsummary_hip <config dir> <model file> <data file> <params root> <output file>\n"
                     "                         [--chain m] [--slice s] [--first i] [--last j] [--thin k] [--block B]\n"
                     "                         [--quantiles q1,q2,...] [--qbits b] [--loo] [--predictive] [--window W[,first]] [--ess [L]]\n"
+                    "                         [--scan W0[,W1,...]] [--scan-below T]\n"
                     "     [1] The directory of config_default.cfg, errors_default.cfg and the *_ctrl.list files (Config/default)\n"
                     "     [2] The .model file and [3] the .data file of the fit\n"
                     "     [4] The root of the parameter files: <root>_chain-<m>.bin and <root>.hdr\n"
@@ -71,6 +83,12 @@ static int usage()
                     "     --window W[,first]   the same check over disjoint windows of W bins (1 ... 512; likelihood p times W at most 512),\n"
                     "             the first window `first` bins long (1 ... W, default W): written to <output file>.windows, one row per\n"
                     "             window, w first_bin last_bin x_first x_last pit log_cdf log_sf mean_resid (no further pass; [5] is unchanged)\n"
+                    "     --scan W0[,W1,...]   that check at every start position of up to 8 strictly ascending widths (each 1 ... 512 and at\n"
+                    "             most the number of bins; likelihood p times the largest at most 512): written to <output file>.scan, one\n"
+                    "             row per bin j, j x_j and per width pit log_cdf log_sf mean_resid, and the runs of positions below the line to\n"
+                    "             <output file>.scan.regions, W which pos_first pos_last bin_first bin_last x_first x_last pos_min min_log\n"
+                    "             mean_resid_at_min (no further pass; [5] and .windows are unchanged)\n"
+                    "     --scan-below T   the line of the regions for all widths, T < 0 (default: log(0.01 W / Nx) per width)\n"
                     "     --ess [L]   effective sample size, Monte-Carlo standard error and split R-hat per bin from the autocorrelation up\n"
                     "             to lag L (0 ... 1023, default 0: the library's 255): written to <output file>.ess, one row per bin,\n"
                     "             x ess_M tau_M mcse_M rhat_M cut_M ess_l r_eff cut_l (the samples are read once more; [5] is unchanged)\n"
@@ -112,6 +130,10 @@ int main(int argc, char *argv[])
     std::string quant_text;
     bool loo = false, predictive = false;
     long win_W = 0, win_first = 0, ess_lag = -1;            // ess_lag < 0: no --ess
+    std::vector<int32_t> scan_W;
+    std::string scan_text;
+    double scan_below = std::nan("");                       // NaN: the library's default line per width
+    bool have_below = false;
     for (int i = 6; i < argc; i++) {
         const std::string a = argv[i];
         if (a == "--loo") { loo = true; continue; }
@@ -141,6 +163,31 @@ int main(int argc, char *argv[])
             if (*end != '\0') return usage();
             continue;
         }
+        if (a == "--scan") {                        // a comma-separated, strictly ascending list of widths
+            if (i + 1 >= argc || !scan_W.empty()) return usage();
+            scan_text = argv[++i];
+            for (const char *p = scan_text.c_str();;) {
+                char *end = nullptr;
+                const long W = strtol(p, &end, 10);
+                if (end == p || W < 1 || W > TAMCMC_SUMMARY_WINDOW_MAX_BINS || scan_W.size() >= TAMCMC_SUMMARY_SCAN_MAX_WIDTHS ||
+                    (!scan_W.empty() && W <= scan_W.back()))
+                    return usage();
+                scan_W.push_back((int32_t)W);
+                if (*end == '\0') break;
+                if (*end != ',') return usage();
+                p = end + 1;
+            }
+            continue;
+        }
+        if (a == "--scan-below") {                  // a negative number
+            if (i + 1 >= argc || have_below) return usage();
+            char *end = nullptr;
+            const char *p = argv[++i];
+            scan_below = strtod(p, &end);
+            if (end == p || *end != '\0' || !(scan_below < 0.0)) return usage();
+            have_below = true;
+            continue;
+        }
         if (a == "--quantiles") {                   // a comma-separated list of numbers in [0, 1]
             if (i + 1 >= argc || !quant.empty()) return usage();
             quant_text = argv[++i];
@@ -163,6 +210,7 @@ int main(int argc, char *argv[])
         if (end == argv[i] || *end != '\0') return usage();
     }
     if (chain < 0 || slice < 0 || first < 0 || thin < 1 || block < 0 || block > 0x7FFFFFFF || qbits < 0 || qbits > 6) return usage();
+    if (have_below && scan_W.empty()) return usage();
 
     tamcmc_setup *S = nullptr;
     if (tamcmc_setup_create(&S, cfg_dir.c_str()) != TAMCMC_IO_OK) return fail("cannot read the default configuration in " + cfg_dir);
@@ -211,6 +259,10 @@ int main(int argc, char *argv[])
         rc = tamcmc_summary_window_enable(sum, (int32_t)win_W, (int32_t)win_first, &n_windows);
         if (rc != TAMCMC_OK) return fail(std::string("tamcmc_summary_window_enable: ") + tamcmc_strerror(rc) + " " + tamcmc_last_hip_error());
     }
+    if (!scan_W.empty()) {
+        rc = tamcmc_summary_scan_enable(sum, (int32_t)scan_W.size(), scan_W.data());
+        if (rc != TAMCMC_OK) return fail(std::string("tamcmc_summary_scan_enable: ") + tamcmc_strerror(rc) + " " + tamcmc_last_hip_error());
+    }
     // One pass over the selected samples, a few thousand rows per push: the library cuts them into its blocks.
     const long long chunk = 4096;
     std::vector<double> vars((size_t)Nvars), P;
@@ -250,6 +302,27 @@ int main(int argc, char *argv[])
     if (win_W) {
         rc = tamcmc_summary_window_result(sum, &wt, wpit.data(), wlog_cdf.data(), wlog_sf.data(), wmean_resid.data());
         if (rc != TAMCMC_OK) return fail(std::string("tamcmc_summary_window_result: ") + tamcmc_strerror(rc) + " " + tamcmc_last_hip_error());
+    }
+    // the scan: per width the four arrays over its positions and the regions of either side
+    const size_t Ks = scan_W.size();
+    std::vector<tamcmc_summary_scan_totals> st(Ks);
+    std::vector<std::vector<double>> sarr(4 * Ks);              // width k: pit, log_cdf, log_sf, mean_resid at 4 k ... 4 k + 3
+    std::vector<std::vector<tamcmc_summary_scan_region>> sreg(2 * Ks);      // width k, side `which` at 2 k + which
+    for (size_t k = 0; k < Ks; k++) {
+        auto sfail = [&](const char *what) { return fail(std::string(what) + ": " + tamcmc_strerror(rc) + " " + tamcmc_last_hip_error()); };
+        const size_t n_pos = (size_t)(Nx - scan_W[k] + 1);
+        for (int c = 0; c < 4; c++) sarr[4 * k + c].resize(n_pos);
+        rc = tamcmc_summary_scan_result(sum, (int32_t)k, &st[k], sarr[4 * k].data(), sarr[4 * k + 1].data(), sarr[4 * k + 2].data(), sarr[4 * k + 3].data());
+        if (rc != TAMCMC_OK) return sfail("tamcmc_summary_scan_result");
+        for (int which = 0; which < 2; which++) {
+            int32_t n_reg = 0;
+            rc = tamcmc_summary_scan_regions(sum, (int32_t)k, which, scan_below, 0, nullptr, &n_reg);
+            if (rc != TAMCMC_OK) return sfail("tamcmc_summary_scan_regions");
+            std::vector<tamcmc_summary_scan_region> &r = sreg[2 * k + (size_t)which];
+            r.resize((size_t)n_reg);
+            if (n_reg > 0) rc = tamcmc_summary_scan_regions(sum, (int32_t)k, which, scan_below, n_reg, r.data(), &n_reg);
+            if (rc != TAMCMC_OK) return sfail("tamcmc_summary_scan_regions");
+        }
     }
     // quantiles: the same samples again, once per pass, until every value is exact
     const size_t Nq = quant.size();
@@ -347,6 +420,43 @@ int main(int argc, char *argv[])
                     x[(size_t)(e - 1)], wpit[(size_t)w], wlog_cdf[(size_t)w], wlog_sf[(size_t)w], wmean_resid[(size_t)w]);
         }
         fclose(ow);
+    }
+    if (Ks) {
+        const std::string scan_file = out_file + ".scan", reg_file = scan_file + ".regions";
+        FILE *os = fopen(scan_file.c_str(), "w");
+        if (!os) return fail("unable to open the output file " + scan_file);
+        fprintf(os, "# chainsummary_hip (%s)\n", tamcmc_version());
+        fprintf(os, "# widths= %s\n", scan_text.c_str());
+        fprintf(os, "# n_used= %lld  n_rejected= %lld\n", (long long)st[0].n_used, (long long)st[0].n_rejected);
+        for (size_t k = 0; k < Ks; k++)
+            fprintf(os, "# W= %lld  n_positions= %lld  min_log_sf= %.17g  pos_min_log_sf= %lld  min_log_cdf= %.17g  pos_min_log_cdf= %lld\n",
+                    (long long)st[k].W, (long long)st[k].n_positions, st[k].min_log_sf, (long long)st[k].pos_min_log_sf, st[k].min_log_cdf,
+                    (long long)st[k].pos_min_log_cdf);
+        fprintf(os, "# j x");
+        for (size_t k = 0; k < Ks; k++) fprintf(os, " pit_%d log_cdf_%d log_sf_%d mean_resid_%d", (int)scan_W[k], (int)scan_W[k], (int)scan_W[k], (int)scan_W[k]);
+        fprintf(os, "\n");
+        for (int64_t j = 0; j < Nx; j++) {
+            fprintf(os, "%lld %.17g", (long long)j, x[(size_t)j]);
+            for (size_t k = 0; k < Ks; k++) {
+                if (j >= st[k].n_positions) { fprintf(os, " nan nan nan nan"); continue; }
+                for (int c = 0; c < 4; c++) fprintf(os, " %.17g", sarr[4 * k + c][(size_t)j]);
+            }
+            fprintf(os, "\n");
+        }
+        fclose(os);
+        FILE *org = fopen(reg_file.c_str(), "w");
+        if (!org) return fail("unable to open the output file " + reg_file);
+        fprintf(org, "# chainsummary_hip (%s)\n", tamcmc_version());
+        fprintf(org, "# widths= %s  log_below=", scan_text.c_str());
+        for (size_t k = 0; k < Ks; k++) fprintf(org, " %.17g", have_below ? scan_below : std::log(0.01 * (double)scan_W[k] / (double)Nx));
+        fprintf(org, "\n# W which pos_first pos_last bin_first bin_last x_first x_last pos_min min_log mean_resid_at_min\n");
+        for (size_t k = 0; k < Ks; k++)
+            for (int which = 0; which < 2; which++)
+                for (const tamcmc_summary_scan_region &r : sreg[2 * k + (size_t)which])
+                    fprintf(org, "%d %d %lld %lld %lld %lld %.17g %.17g %lld %.17g %.17g\n", (int)scan_W[k], which, (long long)r.pos_first,
+                            (long long)r.pos_last, (long long)r.bin_first, (long long)r.bin_last, x[(size_t)r.bin_first], x[(size_t)r.bin_last],
+                            (long long)r.pos_min, r.min_log, r.mean_resid_at_min);
+        fclose(org);
     }
     if (ess_lag >= 0) {
         const std::string ess_file = out_file + ".ess";

@@ -29,6 +29,11 @@ Prints one JSON line:
                             fold kernel alone beside the ESS kernels alone (centre and lag kernels of every block,
                             Summary.kernel_time in ESS mode) and the eval launches, the finish kernel, ess_result on the host
                             clock, and the device memory the mode allocates.  Only this leg runs.
+  i_scan_*                  with --scan W0[,W1,...] (and --like-p p, default 1; p times the largest width <= 512): the same as
+                            (g) for the sliding-window scan -- the fold pass with the scan off and on, alternating in one run,
+                            and from a profiled pass the fold kernel alone beside all scan kernels of a block together
+                            (Summary.scan_kernel_time) and the eval launches; per width the minima found and the number of
+                            regions below the default line.  Only this leg runs.
 Every timed shape is warmed up first (--warmup pushes); host clocks stop after calls that end in a device synchronise.
 """
 import argparse
@@ -146,6 +151,47 @@ def window_leg(a, w, y, P):
     return out
 
 
+def scan_leg(a, w, y, P):
+    """(i) the fold pass with the sliding-window scan off and on, and the kernels' own times."""
+    widths = [int(t) for t in a.scan.split(",")]
+    out = dict(i_scan_widths=widths, i_scan_like_p=a.like_p)
+    with tamcmc_amd.Accel(2, w["plength"], w["x"], y, likelihood_p=float(a.like_p)) as acc:
+        with tamcmc_amd.Summary(acc, a.block) as s0, tamcmc_amd.Summary(acc, a.block, scan=widths) as s1:
+            times = {0: [], 1: []}
+            for k in range(a.warmup + a.steps):
+                for on, s in ((0, s0), (1, s1)):
+                    s.reset()
+                    acc.synchronize()
+                    t0 = time.perf_counter()
+                    s.push(P)                               # synchronous: results are on the host on return
+                    if k >= a.warmup:
+                        times[on].append(time.perf_counter() - t0)
+            for on, key in ((0, "off"), (1, "on")):
+                out[f"i_scan_{key}_s_per_1000"] = float(np.median(times[on])) * 1000.0 / a.samples
+                out[f"i_scan_{key}_spread"] = [float(min(times[on])) * 1000.0 / a.samples, float(max(times[on])) * 1000.0 / a.samples]
+            s1.reset()
+            s1.profile(True)
+            acc.profile(True)
+            s1.push(P)
+            fold_ms, launches = s1.kernel_time()
+            scan_ms, scan_blocks = s1.scan_kernel_time()
+            eval_ms, eval_launches = acc.kernel_time()
+            acc.profile(False)
+            s1.profile(False)
+            res = [s1.scan_result(k) for k in range(len(widths))]
+            out.update(i_scan_blocks=scan_blocks, i_scan_n_positions=[r["n_positions"] for r in res],
+                       i_fold_us_per_block=fold_ms * 1e3 / launches, i_scan_us_per_block=scan_ms * 1e3 / scan_blocks,
+                       i_eval_us_per_block=eval_ms * 1e3 / max(eval_launches, 1),
+                       i_fold_kernel_s_per_1000=fold_ms * 1e-3 * 1000.0 / a.samples,
+                       i_scan_kernel_s_per_1000=scan_ms * 1e-3 * 1000.0 / a.samples,
+                       i_eval_kernel_s_per_1000=eval_ms * 1e-3 * 1000.0 / a.samples,
+                       i_scan_min_log_sf=[r["min_log_sf"] for r in res], i_scan_pos_min_log_sf=[r["pos_min_log_sf"] for r in res],
+                       i_scan_min_log_cdf=[r["min_log_cdf"] for r in res], i_scan_pos_min_log_cdf=[r["pos_min_log_cdf"] for r in res],
+                       i_scan_regions_sf=[len(s1.scan_regions(k, 0)) for k in range(len(widths))],
+                       i_scan_regions_cdf=[len(s1.scan_regions(k, 1)) for k in range(len(widths))], n_used=res[0]["n_used"])
+    return out
+
+
 def ess_leg(a, w, y, P):
     """(h) the fold pass beside the ESS pass of the same rows, and the kernels' own times."""
     out = {}
@@ -219,6 +265,7 @@ def main():
     ap.add_argument("--predictive", action="store_true")
     ap.add_argument("--like-p", type=int, default=1)
     ap.add_argument("--window", type=int, default=0)
+    ap.add_argument("--scan", default="", help="W0[,W1,...]: strictly ascending widths of the sliding-window scan")
     ap.add_argument("--ess", type=int, default=-1)
     a = ap.parse_args()
     if a.steps < 1 or a.warmup < 0 or a.samples < 1 or a.samples_b < 2:
@@ -230,8 +277,9 @@ def main():
     assert st == 0
     y = synth.make_spectrum(m_true)
     out = dict(tool="summary_time", Nx=a.nx, samples=a.samples, steps=a.steps, warmup=a.warmup, version=tamcmc_amd.capi.version())
-    if a.predictive or a.window or a.ess >= 0:
-        out.update(ess_leg(a, w, y, P) if a.ess >= 0 else window_leg(a, w, y, P) if a.window else predictive_leg(a, w, y, P))
+    if a.predictive or a.window or a.scan or a.ess >= 0:
+        out.update(ess_leg(a, w, y, P) if a.ess >= 0 else scan_leg(a, w, y, P) if a.scan else window_leg(a, w, y, P) if a.window
+                   else predictive_leg(a, w, y, P))
         print(json.dumps(out))
         return
     with tamcmc_amd.Accel(2, w["plength"], w["x"], y) as acc:
