@@ -554,6 +554,64 @@ int tamcmc_summary_ess_result(tamcmc_summary *s, tamcmc_summary_ess_totals *tota
 int tamcmc_summary_ess_acov(tamcmc_summary *s, int32_t which, double *acov);
 int tamcmc_summary_ess_end(tamcmc_summary *s);
 
+/* MONTE-CARLO NULL OF THE SCAN: the law of the sliding-window scan's extremes under a correctly specified model, and the
+ * lines and p-values that follow from it.  The scan's default line log(0.01 W / Nx) is Bonferroni over Nx / W independent
+ * windows, per width: neither the overlap of neighbouring positions nor the several widths enter it, and a pure-noise
+ * spectrum crosses it several times more often than the 1 % it names.  If the model is right, y_i / M_i is Gamma(p, 1 / p)
+ * for chi(2,2p) and r_i is N(0, 1/2) for chi_square, independent of the model: the null distribution of the scan's extremes
+ * depends on (likelihood, p, Nx, widths) alone.  An object of its own, bound to a device and to no context or chain; it
+ * simulates R replicate noise spectra on the device (tamcmc_scan_null.hip), the scan's own sums over them, and keeps per
+ * (replicate, width) the two extreme sums.  Nothing of size R x Nx ever exists in memory.
+ *   Generator: Philox4x32-10 -- multipliers 0xD2511F53 and 0xCD9E8D57, key increments 0x9E3779B9 and 0xBB67AE85, ten rounds --
+ *   with key = (seed low 32 bits, seed high 32 bits) and counter = (bin i, pair index t, replicate low 32 bits, replicate high
+ *   32 bits), the replicate being the GLOBAL one, first_replicate + r.  The output words (w0, w1, w2, w3) give two uniforms,
+ *     u = ((double)(((uint64_t)wa << 20) | (wb >> 12)) + 0.5) * 2^-52,   u_even from (w0, w1), u_odd from (w2, w3):
+ *   each exact and strictly inside (0, 1).
+ *   Variate of bin i, replicate r:
+ *     chi(2,2p)    e_k = -log(u_k), k = 0 ... p-1, u_k the (k & 1)-th uniform of call t = k >> 1; z = e_0 + e_1 + ... in
+ *                  ascending k without FMA contraction; q_i = z / (double)p.  p = likelihood_p truncated, as everywhere.
+ *     chi_square   q_i = sqrt(-log(u_even)) * cospi(2.0 * u_odd) of call t = 0: variance 1/2, the likelihood taken at its
+ *                  word as in the predictive check.
+ *   Sums: for width k and position j, S = the scan's ascending sum of q[j ... j + W_k), all widths prefixes of one walk.  Per
+ *   (replicate, width): S_max with its first position and S_min with its first position.
+ *   Statistic, on the host with the functions the scan's tails use, without FMA contraction: which = 0 (excess): min_log =
+ *   log Q at S_max, at the shape p W_k (c = 1 / sqrt((double)W_k)); which = 1 (deficit): log P at S_min.  The tails are
+ *   monotone in S, so this is the minimum over positions of what the scan computes for a chain of one sample.
+ *   Calibration: integer counting over the R replicates done so far, per side.  With m[r][k] = min_log and cnt[r][k] =
+ *   #{r' : m[r'][k] <= m[r][k]}:  vmin[r] = min_k cnt[r][k];  p_width(v) = (1 + n_v) / (R + 1) with n_v = #{r : m[r][k] <= v};
+ *   p_joint(v) = (1 + #{r : vmin[r] <= n_v}) / (R + 1).  The line at level alpha, with j = floor(alpha (R + 1)): per width the
+ *   j-th smallest m[.][k]; jointly the c-th smallest m[.][k], where c is the j-th smallest vmin.  The joint line is never
+ *   above the per-width line.
+ *   What it calibrates: the multiplicity over overlapping positions and several widths under a correctly specified model.
+ *   The chain's statistic is a posterior average of per-sample tails, never more extreme than the plug-in value simulated
+ *   here.  The fit's own degrees of freedom -- a window over a fitted mode -- are not accounted for.
+ *   create       widths, p and their limits exactly as tamcmc_summary_scan_enable, refused the same way (TAMCMC_E_INVALID; a
+ *                likelihood_case other than 0 or 1: TAMCMC_E_UNKNOWN_MODEL); Nx >= 1; first_replicate >= 0.  Every argument
+ *                is checked before a device is touched; TAMCMC_E_NODEVICE without a usable device.  Allocates the partials of
+ *                one chunk of replicates, at most 64 MiB, on the device.  chi_square ignores likelihood_p.
+ *   run          appends n_replicates >= 1 replicates; synchronous.  At most TAMCMC_SCAN_NULL_MAX_REPLICATES in all,
+ *                TAMCMC_E_INVALID beyond.  Replicate r is bit for bit the same however the replicates are split over runs,
+ *                whichever other widths are in the list, and for an object created at first_replicate = r.
+ *   result       width k, side which: R doubles / int64 each, any may be NULL.
+ *   line         TAMCMC_E_INVALID: k or which out of range, no replicate yet, a NULL log_below, j < 1 or j > R.
+ *   pvalue       TAMCMC_E_INVALID likewise, and for a NaN value.
+ *   variates     the Nx variates of replicate r >= 0 (run or not), generated on the device by the kernels' own function: for
+ *                tests and plots.
+ *   profile / kernel_time   as tamcmc_summary_profile / _kernel_time: one event pair around the kernels of each chunk. */
+#define TAMCMC_SCAN_NULL_MAX_REPLICATES 16777216
+typedef struct tamcmc_scan_null tamcmc_scan_null;
+int tamcmc_scan_null_create(tamcmc_scan_null **out, int device_id, int likelihood_case, double likelihood_p, int64_t Nx,
+                            int32_t n_widths, const int32_t *W, uint64_t seed, int64_t first_replicate);
+int tamcmc_scan_null_run(tamcmc_scan_null *h, int64_t n_replicates);
+int tamcmc_scan_null_replicates(const tamcmc_scan_null *h, int64_t *R);
+int tamcmc_scan_null_result(tamcmc_scan_null *h, int32_t k, int32_t which, double *ext_sum, int64_t *pos, double *min_log);
+int tamcmc_scan_null_line(tamcmc_scan_null *h, int32_t k, int32_t which, double alpha, int32_t joint, double *log_below);
+int tamcmc_scan_null_pvalue(tamcmc_scan_null *h, int32_t k, int32_t which, double value, double *p_width, double *p_joint);
+int tamcmc_scan_null_variates(tamcmc_scan_null *h, int64_t r, double *q);
+int tamcmc_scan_null_profile(tamcmc_scan_null *h, int enable);
+int tamcmc_scan_null_kernel_time(tamcmc_scan_null *h, double *total_ms, int64_t *launches);
+int tamcmc_scan_null_destroy(tamcmc_scan_null *h);
+
 /* Replaces: the `for chain` loop of generate_model() calls (MALA.cpp:632-639, model_def.cpp:139-143).
  * Host pointers, row-major.  Synchronous: results are valid on return.
  *   params      Nchains x Nparams

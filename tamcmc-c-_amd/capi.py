@@ -37,6 +37,9 @@ EXPORTS = [
     "tamcmc_summary_window_enable", "tamcmc_summary_window_result", "tamcmc_summary_window_kernel_time",
     "tamcmc_summary_scan_enable", "tamcmc_summary_scan_result", "tamcmc_summary_scan_regions", "tamcmc_summary_scan_kernel_time",
     "tamcmc_summary_ess_begin", "tamcmc_summary_ess_result", "tamcmc_summary_ess_acov", "tamcmc_summary_ess_end",
+    "tamcmc_scan_null_create", "tamcmc_scan_null_run", "tamcmc_scan_null_replicates", "tamcmc_scan_null_result",
+    "tamcmc_scan_null_line", "tamcmc_scan_null_pvalue", "tamcmc_scan_null_variates", "tamcmc_scan_null_profile",
+    "tamcmc_scan_null_kernel_time", "tamcmc_scan_null_destroy",
 ]
 
 
@@ -170,6 +173,17 @@ def load_library():
     lib.tamcmc_summary_ess_result.argtypes = [vp, C.POINTER(SummaryEssTotals), dp, dp, dp, dp, ip, dp, dp, ip]
     lib.tamcmc_summary_ess_acov.argtypes = [vp, C.c_int32, dp]
     lib.tamcmc_summary_ess_end.argtypes = [vp]
+    lp = C.POINTER(C.c_int64)
+    lib.tamcmc_scan_null_create.argtypes = [C.POINTER(vp), C.c_int, C.c_int, C.c_double, C.c_int64, C.c_int32, ip, C.c_uint64, C.c_int64]
+    lib.tamcmc_scan_null_run.argtypes = [vp, C.c_int64]
+    lib.tamcmc_scan_null_replicates.argtypes = [vp, lp]
+    lib.tamcmc_scan_null_result.argtypes = [vp, C.c_int32, C.c_int32, dp, lp, dp]
+    lib.tamcmc_scan_null_line.argtypes = [vp, C.c_int32, C.c_int32, C.c_double, C.c_int32, dp]
+    lib.tamcmc_scan_null_pvalue.argtypes = [vp, C.c_int32, C.c_int32, C.c_double, dp, dp]
+    lib.tamcmc_scan_null_variates.argtypes = [vp, C.c_int64, dp]
+    lib.tamcmc_scan_null_profile.argtypes = [vp, C.c_int]
+    lib.tamcmc_scan_null_kernel_time.argtypes = [vp, dp, lp]
+    lib.tamcmc_scan_null_destroy.argtypes = [vp]
     for name in EXPORTS:
         fn = getattr(lib, name)
         if fn.restype is not C.c_char_p:
@@ -815,6 +829,97 @@ class Summary:
         if getattr(self, "_s", None) is not None and self._s.value:
             self._check(self._lib.tamcmc_summary_destroy(self._s), "tamcmc_summary_destroy")
             self._s = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
+class ScanNull:
+    """Monte-Carlo null of the sliding-window scan (tamcmc_accel.h, tamcmc_scan_null_*): the law of the scan's extremes over
+    every position of every width under a correctly specified model, simulated on the device, and the lines and p-values
+    counted off it.  Bound to a device and to no Accel or chain: it depends on (likelihood_case, p, Nx, widths) alone.
+    run(n) appends n replicates; line() is what Summary.scan_regions takes as log_below.  Replicate r of the object is global
+    replicate first_replicate + r and does not depend on how the replicates are split over runs or objects."""
+
+    MAX_REPLICATES = 1 << 24      # TAMCMC_SCAN_NULL_MAX_REPLICATES
+
+    def __init__(self, likelihood_case, p, Nx, widths, seed, first_replicate=0, device_id=0):
+        self._lib = load_library()
+        self._h = C.c_void_p()
+        W = np.ascontiguousarray(np.atleast_1d(widths), dtype=np.int32)
+        if W.ndim != 1:
+            raise ValueError("widths must be an integer or a sequence of integers")
+        self.Nx = int(Nx)
+        self.widths = tuple(int(w) for w in W)
+        self._check(self._lib.tamcmc_scan_null_create(C.byref(self._h), int(device_id), int(likelihood_case), float(p), self.Nx, int(W.size),
+                                                      _iptr(W) if W.size else None, int(seed), int(first_replicate)), "tamcmc_scan_null_create")
+
+    _check = Accel._check
+
+    def run(self, n):
+        """Appends n replicates (synchronous); returns the number of replicates done."""
+        self._check(self._lib.tamcmc_scan_null_run(self._h, int(n)), "tamcmc_scan_null_run")
+        return self.replicates
+
+    @property
+    def replicates(self):
+        R = C.c_int64(0)
+        self._check(self._lib.tamcmc_scan_null_replicates(self._h, C.byref(R)), "tamcmc_scan_null_replicates")
+        return int(R.value)
+
+    def result(self, k, which):
+        """Width k, side which (0: the maximum sum / excess, 1: the minimum sum / deficit): dict of ext_sum, pos (int64) and
+        min_log, one entry per replicate."""
+        R = self.replicates
+        out = dict(ext_sum=np.empty(R), pos=np.empty(R, dtype=np.int64), min_log=np.empty(R))
+        self._check(self._lib.tamcmc_scan_null_result(self._h, int(k), int(which), _dptr(out["ext_sum"]),
+                                                      out["pos"].ctypes.data_as(C.POINTER(C.c_int64)), _dptr(out["min_log"])),
+                    "tamcmc_scan_null_result")
+        return out
+
+    def line(self, k, which=0, alpha=0.01, joint=True):
+        """The line at level alpha for width k: jointly over all widths and positions, or over the positions of this width."""
+        v = C.c_double(0.0)
+        self._check(self._lib.tamcmc_scan_null_line(self._h, int(k), int(which), float(alpha), int(bool(joint)), C.byref(v)),
+                    "tamcmc_scan_null_line")
+        return v.value
+
+    def pvalue(self, k, which, value):
+        """(p_width, p_joint) of a scan value (a log_sf for which = 0, a log_cdf for which = 1) of width k."""
+        pw, pj = C.c_double(0.0), C.c_double(0.0)
+        self._check(self._lib.tamcmc_scan_null_pvalue(self._h, int(k), int(which), float(value), C.byref(pw), C.byref(pj)),
+                    "tamcmc_scan_null_pvalue")
+        return pw.value, pj.value
+
+    def variates(self, r):
+        """The Nx variates of replicate r, generated on the device."""
+        q = np.empty(self.Nx)
+        self._check(self._lib.tamcmc_scan_null_variates(self._h, int(r), _dptr(q)), "tamcmc_scan_null_variates")
+        return q
+
+    def profile(self, enable=True):
+        self._check(self._lib.tamcmc_scan_null_profile(self._h, int(enable)), "tamcmc_scan_null_profile")
+
+    def kernel_time(self):
+        """(summed milliseconds, chunks) of the kernels since profile(True)."""
+        ms = C.c_double(0.0)
+        n = C.c_int64(0)
+        self._check(self._lib.tamcmc_scan_null_kernel_time(self._h, C.byref(ms), C.byref(n)), "tamcmc_scan_null_kernel_time")
+        return ms.value, n.value
+
+    def close(self):
+        if getattr(self, "_h", None) is not None and self._h.value:
+            self._check(self._lib.tamcmc_scan_null_destroy(self._h), "tamcmc_scan_null_destroy")
+            self._h = C.c_void_p()
 
     def __del__(self):
         try:

@@ -4,7 +4,7 @@
 //   chainsummary_hip <config dir> <model file> <data file> <params root> <output file>
 //                    [--chain m] [--slice s] [--first i] [--last j] [--thin k] [--block B]
 //                    [--quantiles q1,q2,...] [--qbits b] [--loo] [--predictive] [--window W[,first]] [--ess [L]]
-//                    [--scan W0[,W1,...]] [--scan-below T]
+//                    [--scan W0[,W1,...]] [--scan-below T] [--scan-null R[,seed]]
 //
 // <config dir> is the reference's Config/default; model id, likelihood, p, plength, the inputs row and the relax mask
 // come from the setup it describes (tamcmc_setup_create / tamcmc_setup_load, slice s counted from 0).  The samples are
@@ -43,6 +43,11 @@
 // <output file>.scan.regions, one row per region of either side, per width:
 //   W  which  pos_first  pos_last  bin_first  bin_last  x_first  x_last  pos_min  min_log  mean_resid_at_min
 // The line is T of --scan-below T (T < 0) for all widths, by default log(0.01 W / Nx) per width.
+// With --scan-null R[,seed] (needs --scan; R replicates with floor(0.01 (R + 1)) >= 1, seed default 0) the null distribution of
+// the scan's extremes is simulated on the device (tamcmc_scan_null_*): without --scan-below the regions' line becomes the
+// joint 1 % line of each width and side.  .scan keeps every byte; .scan.regions gains one header line, `# null= R seed
+// alpha= 0.01 joint_line= ...` (per width the excess side's line, then the deficit side's; `log_below=` lists the lines in
+// use in the same order unless --scan-below set one for all), and two trailing columns, p_width and p_joint of min_log.
 // With --ess [L] the selected samples are read once more for the effective sample size, the Monte-Carlo standard error and
 // the split R-hat per bin (tamcmc_summary_ess_*; lags up to L, 0 ... 1023, default 0: the library's 255).  The output file
 // keeps every byte; the results go to <output file>.ess: `#` header lines -- the version, `# n_used= ...  n_rejected= ...
@@ -65,7 +70,7 @@ static int usage()
     fprintf(stderr, " Usage: chainsummary_hip <config dir> <model file> <data file> <params root> <output file>\n"
                     "                         [--chain m] [--slice s] [--first i] [--last j] [--thin k] [--block B]\n"
                     "                         [--quantiles q1,q2,...] [--qbits b] [--loo] [--predictive] [--window W[,first]] [--ess [L]]\n"
-                    "                         [--scan W0[,W1,...]] [--scan-below T]\n"
+                    "                         [--scan W0[,W1,...]] [--scan-below T] [--scan-null R[,seed]]\n"
                     "     [1] The directory of config_default.cfg, errors_default.cfg and the *_ctrl.list files (Config/default)\n"
                     "     [2] The .model file and [3] the .data file of the fit\n"
                     "     [4] The root of the parameter files: <root>_chain-<m>.bin and <root>.hdr\n"
@@ -89,6 +94,9 @@ static int usage()
                     "             <output file>.scan.regions, W which pos_first pos_last bin_first bin_last x_first x_last pos_min min_log\n"
                     "             mean_resid_at_min (no further pass; [5] and .windows are unchanged)\n"
                     "     --scan-below T   the line of the regions for all widths, T < 0 (default: log(0.01 W / Nx) per width)\n"
+                    "     --scan-null R[,seed]   needs --scan: R >= 99 replicate noise spectra simulated on the device (seed default 0) give the\n"
+                    "             joint 1 %% line over all positions and widths, the regions' line unless --scan-below is given, one more header\n"
+                    "             line in .scan.regions, `# null= R seed alpha= 0.01 joint_line= ...`, and two trailing columns p_width p_joint\n"
                     "     --ess [L]   effective sample size, Monte-Carlo standard error and split R-hat per bin from the autocorrelation up\n"
                     "             to lag L (0 ... 1023, default 0: the library's 255): written to <output file>.ess, one row per bin,\n"
                     "             x ess_M tau_M mcse_M rhat_M cut_M ess_l r_eff cut_l (the samples are read once more; [5] is unchanged)\n"
@@ -134,6 +142,9 @@ int main(int argc, char *argv[])
     std::string scan_text;
     double scan_below = std::nan("");                       // NaN: the library's default line per width
     bool have_below = false;
+    long long null_R = 0;                                   // 0: no --scan-null
+    unsigned long long null_seed = 0;
+    const double null_alpha = 0.01;
     for (int i = 6; i < argc; i++) {
         const std::string a = argv[i];
         if (a == "--loo") { loo = true; continue; }
@@ -188,6 +199,21 @@ int main(int argc, char *argv[])
             have_below = true;
             continue;
         }
+        if (a == "--scan-null") {                   // R or R,seed
+            if (i + 1 >= argc || null_R != 0) return usage();
+            char *end = nullptr;
+            const char *p = argv[++i];
+            if (*p < '0' || *p > '9') return usage();
+            null_R = strtoll(p, &end, 10);
+            if (end == p || null_R > TAMCMC_SCAN_NULL_MAX_REPLICATES || std::floor(null_alpha * (double)(null_R + 1)) < 1.0) return usage();
+            if (*end == ',') {
+                p = end + 1;
+                if (*p < '0' || *p > '9') return usage();
+                null_seed = strtoull(p, &end, 10);
+            }
+            if (*end != '\0') return usage();
+            continue;
+        }
         if (a == "--quantiles") {                   // a comma-separated list of numbers in [0, 1]
             if (i + 1 >= argc || !quant.empty()) return usage();
             quant_text = argv[++i];
@@ -210,7 +236,7 @@ int main(int argc, char *argv[])
         if (end == argv[i] || *end != '\0') return usage();
     }
     if (chain < 0 || slice < 0 || first < 0 || thin < 1 || block < 0 || block > 0x7FFFFFFF || qbits < 0 || qbits > 6) return usage();
-    if (have_below && scan_W.empty()) return usage();
+    if ((have_below || null_R) && scan_W.empty()) return usage();
 
     tamcmc_setup *S = nullptr;
     if (tamcmc_setup_create(&S, cfg_dir.c_str()) != TAMCMC_IO_OK) return fail("cannot read the default configuration in " + cfg_dir);
@@ -308,6 +334,16 @@ int main(int argc, char *argv[])
     std::vector<tamcmc_summary_scan_totals> st(Ks);
     std::vector<std::vector<double>> sarr(4 * Ks);              // width k: pit, log_cdf, log_sf, mean_resid at 4 k ... 4 k + 3
     std::vector<std::vector<tamcmc_summary_scan_region>> sreg(2 * Ks);      // width k, side `which` at 2 k + which
+    // the null of the scan: the joint line of width k, side `which` at 2 k + which, and the two p-values of every region
+    std::vector<double> joint_line(2 * Ks, std::nan(""));
+    std::vector<std::vector<double>> sreg_p(2 * Ks);           // p_width, p_joint of region i at 2 i, 2 i + 1
+    tamcmc_scan_null *null = nullptr;
+    if (null_R) {
+        rc = tamcmc_scan_null_create(&null, 0, like_case, like_p, Nx, (int32_t)Ks, scan_W.data(), null_seed, 0);
+        if (rc == TAMCMC_OK) rc = tamcmc_scan_null_run(null, null_R);
+        for (size_t i = 0; i < 2 * Ks && rc == TAMCMC_OK; i++) rc = tamcmc_scan_null_line(null, (int32_t)(i / 2), (int32_t)(i % 2), null_alpha, 1, &joint_line[i]);
+        if (rc != TAMCMC_OK) return fail(std::string("tamcmc_scan_null: ") + tamcmc_strerror(rc) + " " + tamcmc_last_hip_error());
+    }
     for (size_t k = 0; k < Ks; k++) {
         auto sfail = [&](const char *what) { return fail(std::string(what) + ": " + tamcmc_strerror(rc) + " " + tamcmc_last_hip_error()); };
         const size_t n_pos = (size_t)(Nx - scan_W[k] + 1);
@@ -316,14 +352,22 @@ int main(int argc, char *argv[])
         if (rc != TAMCMC_OK) return sfail("tamcmc_summary_scan_result");
         for (int which = 0; which < 2; which++) {
             int32_t n_reg = 0;
-            rc = tamcmc_summary_scan_regions(sum, (int32_t)k, which, scan_below, 0, nullptr, &n_reg);
+            const double line = null_R && !have_below ? joint_line[2 * k + (size_t)which] : scan_below;
+            rc = tamcmc_summary_scan_regions(sum, (int32_t)k, which, line, 0, nullptr, &n_reg);
             if (rc != TAMCMC_OK) return sfail("tamcmc_summary_scan_regions");
             std::vector<tamcmc_summary_scan_region> &r = sreg[2 * k + (size_t)which];
             r.resize((size_t)n_reg);
-            if (n_reg > 0) rc = tamcmc_summary_scan_regions(sum, (int32_t)k, which, scan_below, n_reg, r.data(), &n_reg);
+            if (n_reg > 0) rc = tamcmc_summary_scan_regions(sum, (int32_t)k, which, line, n_reg, r.data(), &n_reg);
             if (rc != TAMCMC_OK) return sfail("tamcmc_summary_scan_regions");
+            std::vector<double> &pv = sreg_p[2 * k + (size_t)which];
+            pv.resize(null_R ? 2 * r.size() : 0);
+            for (size_t i = 0; null_R && i < r.size(); i++) {
+                rc = tamcmc_scan_null_pvalue(null, (int32_t)k, which, r[i].min_log, &pv[2 * i], &pv[2 * i + 1]);
+                if (rc != TAMCMC_OK) return sfail("tamcmc_scan_null_pvalue");
+            }
         }
     }
+    tamcmc_scan_null_destroy(null);
     // quantiles: the same samples again, once per pass, until every value is exact
     const size_t Nq = quant.size();
     std::vector<double> qlo(Nq * (size_t)Nx);
@@ -448,14 +492,25 @@ int main(int argc, char *argv[])
         if (!org) return fail("unable to open the output file " + reg_file);
         fprintf(org, "# chainsummary_hip (%s)\n", tamcmc_version());
         fprintf(org, "# widths= %s  log_below=", scan_text.c_str());
-        for (size_t k = 0; k < Ks; k++) fprintf(org, " %.17g", have_below ? scan_below : std::log(0.01 * (double)scan_W[k] / (double)Nx));
-        fprintf(org, "\n# W which pos_first pos_last bin_first bin_last x_first x_last pos_min min_log mean_resid_at_min\n");
+        if (null_R && !have_below) for (size_t i = 0; i < 2 * Ks; i++) fprintf(org, " %.17g", joint_line[i]);
+        else for (size_t k = 0; k < Ks; k++) fprintf(org, " %.17g", have_below ? scan_below : std::log(0.01 * (double)scan_W[k] / (double)Nx));
+        if (null_R) {
+            fprintf(org, "\n# null= %lld %llu alpha= %.17g joint_line=", null_R, null_seed, null_alpha);
+            for (size_t i = 0; i < 2 * Ks; i++) fprintf(org, " %.17g", joint_line[i]);
+        }
+        fprintf(org, "\n# W which pos_first pos_last bin_first bin_last x_first x_last pos_min min_log mean_resid_at_min%s\n", null_R ? " p_width p_joint" : "");
         for (size_t k = 0; k < Ks; k++)
-            for (int which = 0; which < 2; which++)
-                for (const tamcmc_summary_scan_region &r : sreg[2 * k + (size_t)which])
-                    fprintf(org, "%d %d %lld %lld %lld %lld %.17g %.17g %lld %.17g %.17g\n", (int)scan_W[k], which, (long long)r.pos_first,
+            for (int which = 0; which < 2; which++) {
+                const std::vector<tamcmc_summary_scan_region> &regs = sreg[2 * k + (size_t)which];
+                for (size_t i = 0; i < regs.size(); i++) {
+                    const tamcmc_summary_scan_region &r = regs[i];
+                    fprintf(org, "%d %d %lld %lld %lld %lld %.17g %.17g %lld %.17g %.17g", (int)scan_W[k], which, (long long)r.pos_first,
                             (long long)r.pos_last, (long long)r.bin_first, (long long)r.bin_last, x[(size_t)r.bin_first], x[(size_t)r.bin_last],
                             (long long)r.pos_min, r.min_log, r.mean_resid_at_min);
+                    if (null_R) fprintf(org, " %.17g %.17g", sreg_p[2 * k + (size_t)which][2 * i], sreg_p[2 * k + (size_t)which][2 * i + 1]);
+                    fprintf(org, "\n");
+                }
+            }
         fclose(org);
     }
     if (ess_lag >= 0) {

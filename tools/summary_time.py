@@ -34,6 +34,11 @@ Prints one JSON line:
                             and from a profiled pass the fold kernel alone beside all scan kernels of a block together
                             (Summary.scan_kernel_time) and the eval launches; per width the minima found and the number of
                             regions below the default line.  Only this leg runs.
+  j_scan_null_*             with --scan-null R (and --scan W0[,W1,...], default 10,20,40; --like-p p; --nx): the Monte-Carlo null of
+                            the scan (tamcmc_amd.ScanNull), no chain and no context: R replicates per run, --warmup + --steps
+                            runs appended to one object -- wall seconds per replicate through ScanNull.run (the copy back and the
+                            host's tail functions included) and the two kernels alone from HIP events around every chunk; the
+                            joint and the per-width 1 % line of the excess side beside the default line.  Only this leg runs.
 Every timed shape is warmed up first (--warmup pushes); host clocks stop after calls that end in a device synchronise.
 """
 import argparse
@@ -192,6 +197,33 @@ def scan_leg(a, w, y, P):
     return out
 
 
+def scan_null_leg(a):
+    """(j) the Monte-Carlo null of the scan: wall time and kernel time per replicate."""
+    widths = [int(t) for t in (a.scan or "10,20,40").split(",")]
+    out = dict(j_scan_null_widths=widths, j_scan_null_like_p=a.like_p, j_scan_null_R_per_run=a.scan_null)
+    with tamcmc_amd.ScanNull(0, a.like_p, a.nx, widths, 3) as null:
+        times = []
+        for k in range(a.warmup + a.steps):
+            if k == a.warmup:
+                null.profile(True)
+            t0 = time.perf_counter()
+            null.run(a.scan_null)                           # synchronous
+            if k >= a.warmup:
+                times.append(time.perf_counter() - t0)
+        ms, chunks = null.kernel_time()
+        null.profile(False)
+        R = null.replicates
+        out.update(j_scan_null_wall_s_per_replicate=float(np.median(times)) / a.scan_null,
+                   j_scan_null_wall_spread=[float(min(times)) / a.scan_null, float(max(times)) / a.scan_null],
+                   j_scan_null_kernel_s_per_replicate=ms * 1e-3 / (a.steps * a.scan_null), j_scan_null_chunks=chunks,
+                   j_scan_null_additions_per_s=float(a.nx) * widths[-1] * a.steps * a.scan_null / (ms * 1e-3),
+                   j_scan_null_replicates=R,
+                   j_scan_null_joint_line=[null.line(k, 0, 0.01, True) for k in range(len(widths))] if R >= 99 else None,
+                   j_scan_null_width_line=[null.line(k, 0, 0.01, False) for k in range(len(widths))] if R >= 99 else None,
+                   j_scan_null_default_line=[float(np.log(0.01 * W / a.nx)) for W in widths])
+    return out
+
+
 def ess_leg(a, w, y, P):
     """(h) the fold pass beside the ESS pass of the same rows, and the kernels' own times."""
     out = {}
@@ -267,9 +299,15 @@ def main():
     ap.add_argument("--window", type=int, default=0)
     ap.add_argument("--scan", default="", help="W0[,W1,...]: strictly ascending widths of the sliding-window scan")
     ap.add_argument("--ess", type=int, default=-1)
+    ap.add_argument("--scan-null", type=int, default=0, help="R: replicates per run of the scan's Monte-Carlo null (widths of --scan)")
     a = ap.parse_args()
-    if a.steps < 1 or a.warmup < 0 or a.samples < 1 or a.samples_b < 2:
-        ap.error("--steps >= 1, --warmup >= 0, --samples >= 1, --samples-b >= 2")
+    if a.steps < 1 or a.warmup < 0 or a.samples < 1 or a.samples_b < 2 or a.scan_null < 0:
+        ap.error("--steps >= 1, --warmup >= 0, --samples >= 1, --samples-b >= 2, --scan-null >= 0")
+    if a.scan_null:
+        out = dict(tool="summary_time", Nx=a.nx, steps=a.steps, warmup=a.warmup, version=tamcmc_amd.capi.version())
+        out.update(scan_null_leg(a))
+        print(json.dumps(out))
+        return
     w = synth.workload_c2(Nx=a.nx)
     P = synth.chain_params(w, a.samples)
     with tamcmc_amd.Accel(2, w["plength"], w["x"], np.ones(a.nx)) as acc:
