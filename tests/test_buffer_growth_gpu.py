@@ -12,10 +12,11 @@ import numpy as np
 import pytest
 
 import workloads as W
+from summary_support import same
+from support import bits
 from tamcmc_amd import capi, synth
 from test_grad_gpu import gradcheck
 from test_parity_gpu import check_logL, spectrum_for
-from test_summary_gpu import bits, same
 
 pytestmark = pytest.mark.gpu
 

@@ -19,14 +19,13 @@ suite) -- with 0 ... 6 chains per member, so that members own one workgroup, or 
 import ctypes as C
 import functools
 import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 
 import gradcheck
 import workloads as W
+from support import in_torch_process
 from tamcmc_amd import capi, synth
 from test_group_gpu import assert_group_matches_solo, bits_equal, close_all, mixed_members
 from test_parity_gpu import RTOL_MODEL, check_logL
@@ -267,11 +266,7 @@ def _device_check():
 
 
 def test_device_pointers():
-    here = os.path.dirname(os.path.abspath(__file__))
-    code = ("import torch, sys; sys.path[:0] = [%r, %r]; import test_chain_counts_gpu as t; t._device_check()"
-            % (os.path.dirname(here), here))
-    r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0 and "chain counts device path ok" in r.stdout, (r.stdout[-2000:], r.stderr[-3000:])
+    in_torch_process("test_chain_counts_gpu", "_device_check", "chain counts device path ok")
 
 
 @pytest.mark.parametrize("order", [None, "0"], ids=["default", "order-0"])

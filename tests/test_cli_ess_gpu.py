@@ -1,5 +1,5 @@
-"""chainsummary_hip --ess [L] on the GPU: the 23-sample chain of tests/test_summary_gpu.py::test_command_line on the golden
-local-model inputs.  <output file>.ess parses -- the totals in its header, one row per bin -- and holds the numbers
+"""chainsummary_hip --ess [L] on the GPU: the 23-sample chain of summary_support.stored_chain on the golden local-model
+inputs.  <output file>.ess parses -- the totals in its header, one row per bin -- and holds the numbers
 Summary.ess gives, to the 12 printed digits, with the default lag limit and with --ess 31 (both resolve to the chain's own
 limit, 21); the main output file is, byte for byte, what the same binary writes without the flag."""
 import os
@@ -8,8 +8,8 @@ import subprocess
 import numpy as np
 import pytest
 
+from summary_support import f12, header_values, stored_chain
 from tamcmc_amd import capi
-from test_summary_gpu import CFG, G, ROOT, pyorc
 
 pytestmark = pytest.mark.gpu
 
@@ -17,37 +17,13 @@ COLUMNS = ("x", "ess_M", "tau_M", "mcse_M", "rhat_M", "cut_M", "ess_l", "r_eff",
 
 
 def test_command_line(accel_mod, tmp_path):
-    from tamcmc_amd import outputs as O
-    from tamcmc_amd import sampler as S
-    from tamcmc_amd.setup_io import Setup
-    exe = os.path.join(ROOT, "bin", "chainsummary_hip")
-    model, data = os.path.join(G, "TF_3443483_local-v3.model"), os.path.join(G, "TF_3443483_local-v3.data")
-    out = str(tmp_path) + "/"
-    s = Setup(CFG).load(model, data, 0)
-    s.set("MALA", "Nchains", 2)
-    for k, v in (("output_dir", out), ("restore_dir", out), ("output_root_name", "TF_A_"), ("Nbuffer", 50), ("file_format", "binary")):
-        s.set("Outputs", k, v)
-    s.set("MALA", "Nt_learn", "10, 30, 100000")
-    s.apply_phase("Burn-in", 50, 1.8)
-    orc = pyorc()
-
-    def ev(P, T):
-        return orc.generate_batch(s.model_case, s.plength, s.x, s.y, P, T, likelihood_p=s.likelihood_p)[:2]
-    smp = S.Sampler(s.sampler_cfg(seed=5), ev, s.plength, s.inputs, s.relax, s.err, s.priors_names_switch, s.priors, s.extra_priors)
-    O.run_phase(s, smp)
-    root = out + "TF_A_params"
-    v, _ = O.read_params_bin(root, 0)
-    common = [exe, CFG, model, data, root]
-    sel = ["--thin", "2", "--first", "4", "--block", "7"]
-    rows = np.tile(s.inputs, (23, 1))
-    rows[:, s.index_to_relax] = v[4::2]
+    s, root, v, rows, common, sel = stored_chain(tmp_path)
     with accel_mod.Accel(s.model_case, s.plength, s.x, s.y, sigma_y=s.sigma_y, likelihood_case=s.likelihood_case,
                          likelihood_p=s.likelihood_p) as acc:
         with capi.Summary(acc) as sm:
             _, st = sm.push(rows)
             want = {0: sm.ess(rows), 31: sm.ess(rows, 31), 5: sm.ess(rows, 5)}
     assert np.all(st == 0) and want[0]["n_used"] == 23 and want[0]["lag"] == 21 and want[31]["lag"] == 21 and want[5]["lag"] == 5
-    f12 = lambda a: np.array([float("%.12g" % t) for t in np.atleast_1d(a)])       # noqa: E731
     plain = str(tmp_path / "plain.txt")
     r = subprocess.run(common + [plain] + sel + ["--loo"], capture_output=True, text=True, timeout=120)
     assert r.returncode == 0, r.stdout + r.stderr
@@ -60,11 +36,7 @@ def test_command_line(accel_mod, tmp_path):
             "the output file changed with --ess"
         d = want[lag]
         lines = open(table + ".ess").read().split("\n")
-        head = {}
-        for line in lines:
-            if line.startswith("#") and "=" in line:
-                tok = line[1:].split()
-                head.update({a[:-1]: b for a, b in zip(tok, tok[1:]) if a.endswith("=")})
+        head = header_values(line for line in lines if line.startswith("#") and "=" in line)
         assert lines[0].startswith("# chainsummary_hip (") and lines[5] == "# " + " ".join(COLUMNS)
         for k in ("n_used", "n_rejected", "lag", "bin_min_ess_M", "bin_min_ess_l", "bin_max_rhat", "n_rhat_high", "n_truncated_M", "n_truncated_l"):
             assert int(head[k]) == d[k], k

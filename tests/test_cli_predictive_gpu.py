@@ -1,15 +1,14 @@
-"""bin/chainsummary_hip --predictive on the GPU: the 23-sample chain of tests/test_summary_gpu.py::test_command_line on the
-golden local-model inputs, with and without --loo.  Two more header lines and four last columns, the numbers
+"""bin/chainsummary_hip --predictive on the GPU: the 23-sample chain of summary_support.stored_chain on the golden
+local-model inputs, with and without --loo.  Two more header lines and four last columns, the numbers
 Summary.predictive_result() gives to the 12 printed digits; everything else is, byte for byte, what the same binary writes
 without the flag."""
-import os
 import subprocess
 
 import numpy as np
 import pytest
 
+from summary_support import f12, header_values, stored_chain
 from tamcmc_amd import capi
-from test_summary_gpu import CFG, G, ROOT, pyorc
 
 pytestmark = pytest.mark.gpu
 
@@ -17,37 +16,13 @@ COLS = " pit log_cdf log_sf mean_resid"
 
 
 def test_command_line(accel_mod, tmp_path):
-    from tamcmc_amd import outputs as O
-    from tamcmc_amd import sampler as S
-    from tamcmc_amd.setup_io import Setup
-    exe = os.path.join(ROOT, "bin", "chainsummary_hip")
-    model, data = os.path.join(G, "TF_3443483_local-v3.model"), os.path.join(G, "TF_3443483_local-v3.data")
-    out = str(tmp_path) + "/"
-    s = Setup(CFG).load(model, data, 0)
-    s.set("MALA", "Nchains", 2)
-    for k, v in (("output_dir", out), ("restore_dir", out), ("output_root_name", "TF_A_"), ("Nbuffer", 50), ("file_format", "binary")):
-        s.set("Outputs", k, v)
-    s.set("MALA", "Nt_learn", "10, 30, 100000")
-    s.apply_phase("Burn-in", 50, 1.8)
-    orc = pyorc()
-
-    def ev(P, T):
-        return orc.generate_batch(s.model_case, s.plength, s.x, s.y, P, T, likelihood_p=s.likelihood_p)[:2]
-    smp = S.Sampler(s.sampler_cfg(seed=5), ev, s.plength, s.inputs, s.relax, s.err, s.priors_names_switch, s.priors, s.extra_priors)
-    O.run_phase(s, smp)
-    root = out + "TF_A_params"
-    v, _ = O.read_params_bin(root, 0)
-    common = [exe, CFG, model, data, root]
-    sel = ["--thin", "2", "--first", "4", "--block", "7"]
-    rows = np.tile(s.inputs, (23, 1))
-    rows[:, s.index_to_relax] = v[4::2]
+    s, root, v, rows, common, sel = stored_chain(tmp_path)
     with accel_mod.Accel(s.model_case, s.plength, s.x, s.y, sigma_y=s.sigma_y, likelihood_case=s.likelihood_case,
                          likelihood_p=s.likelihood_p) as acc:
         with capi.Summary(acc, predictive=True) as sm:
             _, st = sm.push(rows)
             d = sm.predictive_result()
     assert np.all(st == 0) and d["n_used"] == 23
-    f12 = lambda a: np.array([float("%.12g" % t) for t in np.atleast_1d(a)])       # noqa: E731
     for extra, ncol in (([], 8), (["--loo"], 10), (["--quantiles", "0.16,0.5,0.84", "--loo"], 13)):
         plain, table = str(tmp_path / f"plain{ncol}.txt"), str(tmp_path / f"pred{ncol}.txt")
         for path, flag in ((plain, []), (table, ["--predictive"])):
@@ -61,8 +36,7 @@ def test_command_line(accel_mod, tmp_path):
         added = [k for k, line in enumerate(lines) if line.startswith("# ks_D=") or line.startswith("# pit_hist=")]
         assert len(added) == 2 and added[1] == added[0] + 1 and lines[added[1] + 1].startswith("# x y ")
         assert lines[added[0] - 1].startswith("# elpd_loo=" if extra else "# lppd_total=")
-        tok = lines[added[0]][1:].split()
-        head = {a[:-1]: b for a, b in zip(tok, tok[1:]) if a.endswith("=")}
+        head = header_values([lines[added[0]]])
         for key in ("ks_D", "min_log_sf", "min_log_cdf"):
             assert head[key] == "%.12g" % d[key], key
         assert int(head["bin_min_log_sf"]) == d["bin_min_log_sf"] and int(head["bin_min_log_cdf"]) == d["bin_min_log_cdf"]

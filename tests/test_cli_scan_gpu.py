@@ -1,5 +1,5 @@
-"""bin/chainsummary_hip --scan on the GPU: the 23-sample chain of tests/test_summary_gpu.py::test_command_line on the
-golden local-model inputs.  --scan 7,20 writes <output file>.scan and <output file>.scan.regions, whose 17-digit numbers
+"""bin/chainsummary_hip --scan on the GPU: the 23-sample chain of summary_support.stored_chain on the golden local-model
+inputs.  --scan 7,20 writes <output file>.scan and <output file>.scan.regions, whose 17-digit numbers
 parse back to the bits of Summary(..., scan=(7, 20)).scan_result(k) and .scan_regions(k, which, line), at the default line and
 with --scan-below; the output file and <output file>.windows are, byte for byte, what the same binary writes without the
 flag."""
@@ -9,37 +9,15 @@ import subprocess
 import numpy as np
 import pytest
 
+from summary_support import header_values, stored_chain
+from support import bits
 from tamcmc_amd import capi
-from test_summary_gpu import CFG, G, ROOT, bits, pyorc
 
 pytestmark = pytest.mark.gpu
 
 
 def test_command_line(accel_mod, tmp_path):
-    from tamcmc_amd import outputs as O
-    from tamcmc_amd import sampler as S
-    from tamcmc_amd.setup_io import Setup
-    exe = os.path.join(ROOT, "bin", "chainsummary_hip")
-    model, data = os.path.join(G, "TF_3443483_local-v3.model"), os.path.join(G, "TF_3443483_local-v3.data")
-    out = str(tmp_path) + "/"
-    s = Setup(CFG).load(model, data, 0)
-    s.set("MALA", "Nchains", 2)
-    for k, v in (("output_dir", out), ("restore_dir", out), ("output_root_name", "TF_A_"), ("Nbuffer", 50), ("file_format", "binary")):
-        s.set("Outputs", k, v)
-    s.set("MALA", "Nt_learn", "10, 30, 100000")
-    s.apply_phase("Burn-in", 50, 1.8)
-    orc = pyorc()
-
-    def ev(P, T):
-        return orc.generate_batch(s.model_case, s.plength, s.x, s.y, P, T, likelihood_p=s.likelihood_p)[:2]
-    smp = S.Sampler(s.sampler_cfg(seed=5), ev, s.plength, s.inputs, s.relax, s.err, s.priors_names_switch, s.priors, s.extra_priors)
-    O.run_phase(s, smp)
-    root = out + "TF_A_params"
-    v, _ = O.read_params_bin(root, 0)
-    common = [exe, CFG, model, data, root]
-    sel = ["--thin", "2", "--first", "4", "--block", "7"]
-    rows = np.tile(s.inputs, (23, 1))
-    rows[:, s.index_to_relax] = v[4::2]
+    s, root, v, rows, common, sel = stored_chain(tmp_path)
     with accel_mod.Accel(s.model_case, s.plength, s.x, s.y, sigma_y=s.sigma_y, likelihood_case=s.likelihood_case,
                          likelihood_p=s.likelihood_p) as acc:
         with capi.Summary(acc, scan=(7, 20)) as sm:
@@ -63,8 +41,7 @@ def test_command_line(accel_mod, tmp_path):
     assert head[0].startswith("# chainsummary_hip (") and head[1] == "# widths= 7,20" and head[2] == "# n_used= 23  n_rejected= 0"
     assert len(head) == 6 and head[-1].startswith("# j x pit_7 log_cdf_7 log_sf_7 mean_resid_7 pit_20 ")
     for k in range(2):
-        tok = head[3 + k][1:].split()
-        val = {a[:-1]: b for a, b in zip(tok, tok[1:]) if a.endswith("=")}
+        val = header_values([head[3 + k]])
         for key in ("W", "n_positions", "pos_min_log_sf", "pos_min_log_cdf"):
             assert int(val[key]) == d[k][key], (k, key)
         for key in ("min_log_sf", "min_log_cdf"):

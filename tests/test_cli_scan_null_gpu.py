@@ -4,14 +4,14 @@ inputs.  Without the flag nothing is said about a null: the output file, .scan a
 .scan.regions carries the line `# null= R seed alpha= 0.01 joint_line= ...` and the two trailing columns p_width p_joint,
 whose 17-digit numbers parse back to the bits of ScanNull(...).line(k, which, 0.01, True) and .pvalue(k, which, min_log); the
 regions are those of Summary.scan_regions at the joint line, or at T with --scan-below T."""
-import os
 import subprocess
 
 import numpy as np
 import pytest
 
+from summary_support import stored_chain
+from support import bits
 from tamcmc_amd import capi
-from test_summary_gpu import CFG, G, ROOT, bits, pyorc
 
 pytestmark = pytest.mark.gpu
 
@@ -19,30 +19,7 @@ WIDTHS, R_NULL, SEED = (7, 20), 300, 9
 
 
 def test_command_line(accel_mod, tmp_path):
-    from tamcmc_amd import outputs as O
-    from tamcmc_amd import sampler as S
-    from tamcmc_amd.setup_io import Setup
-    exe = os.path.join(ROOT, "bin", "chainsummary_hip")
-    model, data = os.path.join(G, "TF_3443483_local-v3.model"), os.path.join(G, "TF_3443483_local-v3.data")
-    out = str(tmp_path) + "/"
-    s = Setup(CFG).load(model, data, 0)
-    s.set("MALA", "Nchains", 2)
-    for k, v in (("output_dir", out), ("restore_dir", out), ("output_root_name", "TF_A_"), ("Nbuffer", 50), ("file_format", "binary")):
-        s.set("Outputs", k, v)
-    s.set("MALA", "Nt_learn", "10, 30, 100000")
-    s.apply_phase("Burn-in", 50, 1.8)
-    orc = pyorc()
-
-    def ev(P, T):
-        return orc.generate_batch(s.model_case, s.plength, s.x, s.y, P, T, likelihood_p=s.likelihood_p)[:2]
-    smp = S.Sampler(s.sampler_cfg(seed=5), ev, s.plength, s.inputs, s.relax, s.err, s.priors_names_switch, s.priors, s.extra_priors)
-    O.run_phase(s, smp)
-    root = out + "TF_A_params"
-    v, _ = O.read_params_bin(root, 0)
-    common = [exe, CFG, model, data, root]
-    sel = ["--thin", "2", "--first", "4", "--block", "7"]
-    rows = np.tile(s.inputs, (23, 1))
-    rows[:, s.index_to_relax] = v[4::2]
+    s, root, v, rows, common, sel = stored_chain(tmp_path)
     with accel_mod.ScanNull(s.likelihood_case, s.likelihood_p, s.Nx, WIDTHS, SEED) as null:
         null.run(R_NULL)
         joint = [null.line(k, which, 0.01, True) for k in range(2) for which in (0, 1)]

@@ -19,14 +19,11 @@ bin; gradient rows (tests/gradcheck.py, unchanged) where the oracle's logL and w
 
 Every test prints its worst figures (logL, model bin, gradient entry in S_k and relative; part A also the residual of the
 scaling identity in ulp of |L(s)|)."""
-import os
-import subprocess
-import sys
-
 import numpy as np
 import pytest
 
 import datacases as D
+from support import in_torch_process
 from test_edges_gpu import Worst, check_grad, check_rows
 
 pytestmark = pytest.mark.gpu
@@ -370,8 +367,4 @@ def test_device_entry_with_gradient():
     """D: tamcmc_eval_batch_device with d_grad set (one fused and one tiled case of part A) equals eval_batch(grad=True) bit
     for bit in logL, status and every gradient entry: without and with a status buffer, and right behind a
     likelihood-only device call on the same context."""
-    here = os.path.dirname(os.path.abspath(__file__))
-    code = ("import torch, sys; sys.path[:0] = [%r, %r]; import test_data_values_gpu as t; t._device_grad_check()"
-            % (os.path.dirname(here), here))
-    r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0 and "device gradient path ok" in r.stdout, (r.stdout[-2000:], r.stderr[-3000:])
+    in_torch_process("test_data_values_gpu", "_device_grad_check", "device gradient path ok")

@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 import workloads as W
+from support import in_torch_process
 from tamcmc_amd import capi, synth
 from tamcmc_amd.setup_io import Setup, model_file_slices
 
@@ -176,13 +177,7 @@ def _device_check():
 
 
 def test_device_entry_point_equals_host_path():
-    import subprocess
-    import sys
-    here = os.path.dirname(os.path.abspath(__file__))
-    code = ("import torch, sys; sys.path[:0] = [%r, %r]; import test_group_gpu as t; t._device_check()"
-            % (os.path.dirname(here), here))
-    r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0 and "device path ok" in r.stdout, (r.stdout[-2000:], r.stderr[-3000:])
+    in_torch_process("test_group_gpu", "_device_check", "device path ok")
 
 
 def _stream_order_check():
@@ -239,18 +234,8 @@ def _stream_order_check():
     print("stream order ok")
 
 
-def _in_torch_process(fn):
-    import subprocess
-    import sys
-    here = os.path.dirname(os.path.abspath(__file__))
-    code = ("import torch, sys; sys.path[:0] = [%r, %r]; import test_group_gpu as t; t.%s()"
-            % (os.path.dirname(here), here, fn))
-    return subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=300)
-
-
 def test_solo_and_group_device_calls_need_no_synchronisation():
-    r = _in_torch_process("_stream_order_check")
-    assert r.returncode == 0 and "stream order ok" in r.stdout, (r.stdout[-2000:], r.stderr[-3000:])
+    in_torch_process("test_group_gpu", "_stream_order_check", "stream order ok")
 
 
 def test_solo_and_group_calls_alternate(accel_mod):

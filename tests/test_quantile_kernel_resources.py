@@ -1,26 +1,12 @@
 """Resources of the quantile kernels (tamcmc_quantile.hip), cross-compiled for gfx950 (make resource-usage-quantile): no
 kernel uses scratch or spills a VGPR, and the histogram kernel's LDS counters stay within 64 KiB per workgroup in every
 instantiation (the largest holds 8 quantiles x 64 cells x 64 threads x 2 bytes = exactly 64 KiB)."""
-import os
-import re
-import shutil
-import subprocess
-
-import pytest
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "tamcmc-c-_amd", "csrc")
+from support import kernel_usage, needs_hipcc
 
 
-@pytest.mark.skipif(shutil.which("hipcc") is None and not os.path.exists("/opt/rocm/bin/hipcc"), reason="hipcc not available")
+@needs_hipcc
 def test_quantile_kernel_resources():
-    r = subprocess.run(["make", "-s", "-C", CSRC, "resource-usage-quantile"], capture_output=True, text=True, timeout=600)
-    txt = r.stdout + r.stderr
-    assert r.returncode == 0, txt[-3000:]
-    usage = {}
-    for m in re.finditer(r"Function Name: (\S+).*?ScratchSize \[bytes/lane\]: (\d+).*?VGPRs Spill: (\d+).*?LDS Size \[bytes/block\]: (\d+)",
-                         txt, flags=re.S):
-        usage[m.group(1)] = (int(m.group(2)), int(m.group(3)), int(m.group(4)))      # scratch bytes, spilled VGPRs, LDS bytes
+    usage = {k: (v[0], v[2], v[3]) for k, v in kernel_usage("resource-usage-quantile").items()}      # scratch bytes, spilled VGPRs, LDS bytes
     hist = {k: v for k, v in usage.items() if "tamcmc_quantile_hist_kernel" in k}
     assert len(hist) == 4 and len(usage) == 6, sorted(usage)
     assert any("tamcmc_quantile_narrow_kernel" in k for k in usage) and any("tamcmc_quantile_init_kernel" in k for k in usage)

@@ -19,11 +19,9 @@ import numpy as np
 import pytest
 
 import scan_null_reference as R
+from summary_support import same, same_pred, same_scans, same_win, true_model
+from support import bits
 from tamcmc_amd import capi, synth
-from test_summary_gpu import bits, same
-from test_summary_predictive_gpu import same_pred, true_model
-from test_summary_scan_gpu import same_scans
-from test_summary_window_gpu import same_win
 
 pytestmark = pytest.mark.gpu
 

@@ -10,7 +10,8 @@ import subprocess
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from support import ROOT, tool
+
 H = "tamcmc_scan_null*"
 PROTOTYPES = {
     "tamcmc_scan_null_create": ["tamcmc_scan_null**", "int", "int", "double", "int64_t", "int32_t", "const int32_t*", "uint64_t", "int64_t"],
@@ -123,7 +124,6 @@ def test_bad_arguments_are_refused_before_any_device_use(accel_mod):
 
 def test_tool_knows_the_option():
     """chainsummary_hip --scan-null R[,seed]: needs --scan, R with floor(0.01 (R + 1)) >= 1, a usage error otherwise."""
-    from test_summary_host import tool
     exe = tool()
     r = subprocess.run([exe], capture_output=True, text=True, timeout=60)
     assert r.returncode != 0 and "--scan-null R[,seed]" in r.stderr and "p_width p_joint" in r.stderr and r.stdout == ""

@@ -4,13 +4,9 @@ extremes of a lane are indexed by unrolled loops and stay in registers), and LDS
 variates with their halo and the waves' partial extremes, TM_NULL_LDS_BYTES of tamcmc_scan_null.h to the byte."""
 import os
 import re
-import shutil
-import subprocess
 
-import pytest
+from support import CSRC, kernel_usage, needs_hipcc
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "tamcmc-c-_amd", "csrc")
 KERNELS = ("tamcmc_scan_null_extremes_kernel", "tamcmc_scan_null_combine_kernel", "tamcmc_scan_null_variates_kernel")
 
 
@@ -28,15 +24,9 @@ def stated_lds():
     return ((tile + bins - 1) * 8 + 15) // 16 * 16 + threads // 64 * widths * 2 * 12
 
 
-@pytest.mark.skipif(shutil.which("hipcc") is None and not os.path.exists("/opt/rocm/bin/hipcc"), reason="hipcc not available")
+@needs_hipcc
 def test_scan_null_kernel_resources():
-    r = subprocess.run(["make", "-s", "-C", CSRC, "resource-usage-scan_null"], capture_output=True, text=True, timeout=600)
-    txt = r.stdout + r.stderr
-    assert r.returncode == 0, txt[-3000:]
-    usage = {}
-    for m in re.finditer(r"Function Name: (\S+).*?ScratchSize \[bytes/lane\]: (\d+).*?SGPRs Spill: (\d+).*?VGPRs Spill: (\d+).*?"
-                         r"LDS Size \[bytes/block\]: (\d+)", txt, flags=re.S):
-        usage[m.group(1)] = tuple(int(m.group(k)) for k in (2, 3, 4, 5))     # scratch bytes, spilled SGPRs, spilled VGPRs, LDS bytes
+    usage = kernel_usage("resource-usage-scan_null")        # scratch bytes, spilled SGPRs, spilled VGPRs, LDS bytes
     assert len(usage) == len(KERNELS) and all(any(k in name for name in usage) for k in KERNELS), sorted(usage)
     lds = stated_lds()
     assert lds == 21248

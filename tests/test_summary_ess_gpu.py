@@ -20,17 +20,13 @@ Reference: tests/ess_reference.py, an independent numpy statement of the definit
 
 Worst ratios to the bound observed on an MI355X over all cases below: see README.md ("Effective sample size").
 """
-import functools
-import os
-import subprocess
-import sys
-
 import numpy as np
 import pytest
 
 import ess_reference as R
+from summary_support import c2_chain, gpu_rows, same, spectrum_for
+from support import LD, bits, in_torch_process
 from tamcmc_amd import capi, synth
-from test_summary_gpu import LD, bits, same, spectrum_for
 
 pytestmark = pytest.mark.gpu
 
@@ -38,10 +34,6 @@ ESS_KEYS = capi.Summary.ESS_ARRAYS
 ESS_TOTALS = capi.Summary.ESS_TOTALS
 PRED_KEYS = capi.Summary.PREDICTIVE_ARRAYS + capi.Summary.PREDICTIVE_TOTALS + ("pit_hist",)
 WIN_KEYS = capi.Summary.WINDOW_ARRAYS + capi.Summary.WINDOW_TOTALS + ("pit_hist",)
-
-
-def gpu_rows(acc, P):
-    return acc.eval_batch(P, np.ones(len(P)), model_rows=np.arange(len(P)))
 
 
 def run_ess(acc, pushes, max_lag=0, block=0, ess_pushes=None, acov=True):
@@ -141,16 +133,6 @@ def check_finish(tag, res, rows=None):
     assert res["n_truncated_M"] == int((res["cut_M"] == L + 1).sum()) and res["n_truncated_l"] == int((res["cut_l"] == L + 1).sum()), tag
     with np.errstate(invalid="ignore"):
         assert res["n_rhat_high"] == int((res["rhat_M"] > 1.01).sum()), tag
-
-
-@functools.lru_cache(maxsize=None)
-def c2_chain(Nx, S, scale=0.5):
-    w = synth.workload_c2(Nx=Nx)
-    y = spectrum_for(w)
-    P = synth.chain_params(w, S, scale=scale)
-    for a in (y, P):
-        a.setflags(write=False)
-    return w, y, P
 
 
 @pytest.mark.parametrize("n", [4, 5, 64, 1000])
@@ -489,8 +471,4 @@ def _device_check():
 
 
 def test_device_pointers():
-    here = os.path.dirname(os.path.abspath(__file__))
-    code = ("import torch, sys; sys.path[:0] = [%r, %r]; import test_summary_ess_gpu as t; t._device_check()"
-            % (os.path.dirname(here), here))
-    r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0 and "ess device path ok" in r.stdout, (r.stdout[-2000:], r.stderr[-3000:])
+    in_torch_process("test_summary_ess_gpu", "_device_check", "ess device path ok")

@@ -3,136 +3,24 @@
 Reference: the oracle's model rows (pyoracle.generate_batch(..., want_models=True)) reduced in numpy in long double --
 two-pass mean / variance, log-sum-exp with the exact maximum.
 
-Tolerances are derived, not tuned: the project's per-bin model bar eps = 1e-12 (RTOL_MODEL, tests/test_parity_gpu.py)
-propagated through each statistic, plus n 2^-52 (relative) for the accumulation over n samples, E = eps + n 2^-52:
-    |d mean_M| <= E mean|M|          |d var_M| <= 4 E mean(M^2)          min_M, max_M: eps relative
-    chi(2,2p)    |d l| <= p eps (y/M + 1)                      }  =: delta_i, the maximum over the samples,
-    chi_square   |d l| <= (2 |y - M| eps M + (eps M)^2) / s^2  }     plus n 2^-52 max|l|
-    |d mean_l|, |d lppd| <= delta_i          |d var_l| <= 2 delta_i sqrt(var_l) + delta_i^2
-    totals: the sum of the per-bin bounds (waic: twice the sum of the lppd and var_l bounds)
+The tolerances are derived, not tuned: reference() and check() of tests/summary_support.py, whose docstring states them.
 Every check prints its worst ratio to the bound (pytest -s shows them) before it asserts.
 
 Worst ratios observed on an MI355X over all cases below: lppd 6.0e-3 (chi_square, id 2), min_M / max_M 3.3e-3 (id 3,
 asymmetry 10), mean_M 1.0e-3, mean_l 1.2e-3, var_l 6.8e-4, var_M 2.2e-4, totals 1.3e-4.
 """
-import functools
-import os
 import subprocess
-import sys
 
 import numpy as np
 import pytest
 
 import workloads as W
+from summary_support import (ARRAYS, TOTALS, c2_case, check, f12, header_values, other_cases, reference, same, spectrum_for,
+                             stored_chain, summarize)
+from support import bits, in_torch_process
 from tamcmc_amd import capi, synth
 
 pytestmark = pytest.mark.gpu
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-G = os.path.join(ROOT, "tests", "golden", "ref_inputs")
-CFG = os.path.join(G, "Config_default")
-EPS = 1e-12
-ARRAYS = capi.Summary.ARRAYS
-TOTALS = ("n_used", "n_rejected", "lppd_total", "p_waic", "waic")
-LD = np.longdouble
-
-
-def pyorc():
-    from oracle import pyoracle
-    pyoracle.lib()
-    return pyoracle
-
-
-def spectrum_for(w, seed=17):
-    m, st = pyorc().model(w["model_case"], w["params_true"], w["plength"], w["x"])
-    assert st == 0
-    return synth.make_spectrum(m, seed=seed)
-
-
-def reference(w, y, P, sigma=None, like=0, p=1.0):
-    """Long-double reduction of the oracle's rows of the accepted samples, and the bounds above."""
-    mid = w["model_case"]
-    rL, rst, M = pyorc().generate_batch(mid, w["plength"], w["x"], y, P, np.ones(len(P)), sigma_y=sigma, likelihood_case=like,
-                                        likelihood_p=p, want_models=True)
-    ok = rst == 0
-    n = int(ok.sum())
-    Mq, yq = M[ok].astype(LD), y.astype(LD)
-    pt = float(int(p))                                  # `long p`, likelihoods.cpp:17
-    if like == 0:
-        l = -pt * (yq / Mq + np.log(Mq))
-        dl = pt * EPS * (yq / Mq + 1.0)
-    else:
-        s2 = sigma.astype(LD) ** 2
-        l = -((yq - Mq) ** 2) / s2
-        dl = (2.0 * np.abs(yq - Mq) * EPS * Mq + (EPS * Mq) ** 2) / s2
-    ref = dict(n_used=n, n_rejected=int((~ok).sum()), status=rst, logL=rL)
-    if n == 0:
-        return ref, {}
-    acc = n * 2.0 ** -52
-    E = EPS + acc
-    mean_M, mean_l = Mq.mean(axis=0), l.mean(axis=0)
-    a = l.max(axis=0)
-    ref.update(mean_M=mean_M, min_M=Mq.min(axis=0), max_M=Mq.max(axis=0), mean_l=mean_l,
-               lppd=a + np.log(np.exp(l - a).sum(axis=0) / n))
-    delta = dl.max(axis=0) + acc * np.abs(l).max(axis=0)
-    bound = dict(mean_M=E * np.abs(Mq).mean(axis=0), min_M=EPS * np.abs(ref["min_M"]), max_M=EPS * np.abs(ref["max_M"]),
-                 mean_l=delta, lppd=delta)
-    ref["lppd_total"] = ref["lppd"].sum()
-    bound["lppd_total"] = delta.sum()
-    if n >= 2:
-        ref["var_M"] = ((Mq - mean_M) ** 2).sum(axis=0) / (n - 1)
-        ref["var_l"] = ((l - mean_l) ** 2).sum(axis=0) / (n - 1)
-        bound["var_M"] = 4.0 * E * (Mq ** 2).mean(axis=0)
-        bound["var_l"] = 2.0 * delta * np.sqrt(ref["var_l"]) + delta ** 2
-        ref["p_waic"] = ref["var_l"].sum()
-        bound["p_waic"] = bound["var_l"].sum()
-        ref["waic"] = -2.0 * (ref["lppd_total"] - ref["p_waic"])
-        bound["waic"] = 2.0 * (bound["lppd_total"] + bound["p_waic"])
-    return ref, bound
-
-
-def check(tag, res, ref, bound):
-    """Every array and total of `res` within its bound; prints the worst ratio of each first."""
-    assert res["n_used"] == ref["n_used"] and res["n_rejected"] == ref["n_rejected"], (tag, res["n_used"], res["n_rejected"])
-    worst = {}
-    for k, b in bound.items():
-        err = np.abs(np.asarray(res[k], dtype=LD) - ref[k])
-        assert np.all(np.isfinite(np.asarray(res[k]))), (tag, k)
-        worst[k] = float(np.max(err / b)) if np.all(np.asarray(b) > 0) else (0.0 if np.all(err == 0) else np.inf)
-    print(f"RATIO {tag}: " + " ".join(f"{k}={v:.3g}" for k, v in worst.items()))
-    for k, v in worst.items():
-        assert v <= 1.0, (tag, k, v)
-    if ref["n_used"] < 2:
-        assert np.all(np.isnan(res["var_M"])) and np.all(np.isnan(res["var_l"])) and np.isnan(res["p_waic"]) and np.isnan(res["waic"])
-    return worst
-
-
-def bits(a):
-    return np.ascontiguousarray(a, dtype=np.float64).view(np.uint64)
-
-
-def same(r1, r2):
-    """Two results bit for bit: every array and every total (NaN == NaN when the bits agree)."""
-    return all(np.array_equal(bits(r1[k]), bits(r2[k])) for k in ARRAYS) and \
-        all(np.array_equal(bits(float(r1[k])), bits(float(r2[k]))) for k in TOTALS)
-
-
-def summarize(acc, pushes, block_chains=0):
-    with capi.Summary(acc, block_chains) as s:
-        out = [s.push(P) for P in pushes]
-        return s.result(), np.concatenate([o[0] for o in out]), np.concatenate([o[1] for o in out])
-
-
-@functools.lru_cache(maxsize=None)
-def c2_case(Nx, S=37):
-    """Id 2 on the C2 star's grid: workload, spectrum, S chain rows and the reference (computed once, never changed)."""
-    w = synth.workload_c2(Nx=Nx)
-    y = spectrum_for(w)
-    P = synth.chain_params(w, S)
-    ref, bound = reference(w, y, P)
-    for a in (y, P):
-        a.setflags(write=False)
-    return w, y, P, ref, bound
 
 
 @pytest.mark.parametrize("Nx", [2, 255, 256, 257, 700, 5000])
@@ -222,19 +110,6 @@ def test_rejected_samples(accel_mod):
     check("rejected", res, ref, bound)
 
 
-def other_cases():
-    sig = lambda n: 0.05 + 0.2 * np.abs(np.sin(np.arange(n)))       # noqa: E731  (tests/test_parity_gpu.py::test_chi_square_likelihood)
-    c1 = synth.workload_c1(Nx=1000)
-    return {
-        "c1-id11-fused": (c1, synth.chain_params(c1, 37), {}),
-        "id14": (W.any_model(14, Nx=3000), None, {}),
-        "id3-asym10": (synth.workload_c2(model_case=3, Nx=3000, asym=10.0), None, {}),
-        "p=2": (W.make(2, Nx=3000), None, dict(p=2.0)),
-        "chi-square-id0": (W.any_model(0, Nx=3000), None, dict(like=1, sigma=sig(3000))),
-        "chi-square-id2": (W.any_model(2, Nx=3000), None, dict(like=1, sigma=sig(3000))),
-    }
-
-
 @pytest.mark.parametrize("name", ["c1-id11-fused", "id14", "id3-asym10", "p=2", "chi-square-id0", "chi-square-id2"])
 def test_other_paths(accel_mod, name):
     w, P, kw = other_cases()[name]
@@ -282,11 +157,7 @@ def _device_check():
 
 
 def test_device_pointers():
-    here = os.path.dirname(os.path.abspath(__file__))
-    code = ("import torch, sys; sys.path[:0] = [%r, %r]; import test_summary_gpu as t; t._device_check()"
-            % (os.path.dirname(here), here))
-    r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0 and "summary device path ok" in r.stdout, (r.stdout[-2000:], r.stderr[-3000:])
+    in_torch_process("test_summary_gpu", "_device_check", "summary device path ok")
 
 
 def test_refusals_and_lifetime(accel_mod):
@@ -336,50 +207,21 @@ def test_command_line(accel_mod, tmp_path):
     """chainsummary_hip on a 50-sample chain of slice 1 of the reference's real spectrum, written by the phase driver
     (oracle evaluator, as tests/test_outputs.py): samples 4, 6, ..., 48 -- the table and the header totals are the
     Python Summary's on the same rows, to the 12 printed digits."""
-    from tamcmc_amd import outputs as O
-    from tamcmc_amd import sampler as S
-    from tamcmc_amd.setup_io import Setup
-    exe = os.path.join(ROOT, "bin", "chainsummary_hip")
-    if not os.path.exists(exe):
-        subprocess.run(["make", "-C", os.path.join(ROOT, "tamcmc-c-_amd", "csrc"), "-j4"], check=True)
-    model, data = os.path.join(G, "TF_3443483_local-v3.model"), os.path.join(G, "TF_3443483_local-v3.data")
-    out = str(tmp_path) + "/"
-    s = Setup(CFG).load(model, data, 0)
-    s.set("MALA", "Nchains", 2)
-    for k, v in (("output_dir", out), ("restore_dir", out), ("output_root_name", "TF_A_"), ("Nbuffer", 50), ("file_format", "binary")):
-        s.set("Outputs", k, v)
-    s.set("MALA", "Nt_learn", "10, 30, 100000")
-    s.apply_phase("Burn-in", 50, 1.8)
-    orc = pyorc()
-
-    def ev(P, T):
-        return orc.generate_batch(s.model_case, s.plength, s.x, s.y, P, T, likelihood_p=s.likelihood_p)[:2]
-    smp = S.Sampler(s.sampler_cfg(seed=5), ev, s.plength, s.inputs, s.relax, s.err, s.priors_names_switch, s.priors, s.extra_priors)
-    O.run_phase(s, smp)
-    root = out + "TF_A_params"
-    v, h = O.read_params_bin(root, 0)
+    s, root, v, rows, common, sel = stored_chain(tmp_path)
     assert v.shape == (50, s.Nvars)
     table = str(tmp_path / "summary.txt")
-    r = subprocess.run([exe, CFG, model, data, root, table, "--thin", "2", "--first", "4", "--block", "7"],
-                       capture_output=True, text=True, timeout=120)
+    r = subprocess.run(common + [table] + sel, capture_output=True, text=True, timeout=120)
     assert r.returncode == 0, r.stdout + r.stderr
-    rows = np.tile(s.inputs, (23, 1))
-    rows[:, s.index_to_relax] = v[4::2]                       # update_params_with_vars, model_def.cpp:370-378
     with accel_mod.Accel(s.model_case, s.plength, s.x, s.y, sigma_y=s.sigma_y, likelihood_case=s.likelihood_case,
                          likelihood_p=s.likelihood_p) as acc:
         res, _, st = summarize(acc, [rows])
     assert np.all(st == 0)
-    f12 = lambda a: np.array([float("%.12g" % t) for t in np.atleast_1d(a)])       # noqa: E731
     t = np.loadtxt(table)
     assert t.shape == (s.Nx, 8)
     cols = [s.x, s.y, res["mean_M"], np.sqrt(res["var_M"]), res["min_M"], res["max_M"], res["lppd"], res["var_l"]]
     for k, c in enumerate(cols):
         assert np.array_equal(t[:, k], f12(c)), k
-    head = {}
-    for line in open(table):
-        if line.startswith("#"):
-            tok = line[1:].split()
-            head.update({a[:-1]: b for a, b in zip(tok, tok[1:]) if a.endswith("=")})
+    head = header_values(line for line in open(table) if line.startswith("#"))
     assert (int(head["n_used"]), int(head["n_rejected"]), int(head["first"]), int(head["last"]), int(head["thin"])) == (23, 0, 4, 48, 2)
     for k in ("lppd_total", "p_waic", "waic"):
         assert head[k] == "%.12g" % res[k], k
@@ -387,5 +229,5 @@ def test_command_line(accel_mod, tmp_path):
     hdr = open(root + ".hdr").read()
     assert f"! Nvars= {s.Nvars}\n" in hdr
     open(root + ".hdr", "w").write(hdr.replace(f"! Nvars= {s.Nvars}\n", f"! Nvars= {s.Nvars + 1}\n"))
-    r = subprocess.run([exe, CFG, model, data, root, table], capture_output=True, text=True, timeout=120)
+    r = subprocess.run(common + [table], capture_output=True, text=True, timeout=120)
     assert r.returncode != 0 and f"but the setup has {s.Nvars} variables" in r.stderr

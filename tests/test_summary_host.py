@@ -1,37 +1,16 @@
 """Posterior summaries (tamcmc_summary_*, include/tamcmc_accel.h), the part that needs no GPU: the symbols exist with the
 declared signatures, bad arguments are refused before any device is touched, and the command-line tool answers."""
 import ctypes as C
-import os
 import re
 import subprocess
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from summary_support import prototypes
+from support import tool
+
 NAMES = ["tamcmc_summary_create", "tamcmc_summary_push", "tamcmc_summary_push_device", "tamcmc_summary_result",
          "tamcmc_summary_reset", "tamcmc_summary_destroy"]
-
-
-def tool():
-    exe = os.path.join(ROOT, "bin", "chainsummary_hip")
-    if not os.path.exists(exe):        # tests/conftest.py builds only when one of the two older tools is missing
-        subprocess.run(["make", "-C", os.path.join(ROOT, "tamcmc-c-_amd", "csrc"), "-j4"], check=True)
-    return exe
-
-
-def prototypes():
-    """name -> list of parameter types as the header spells them (comments and names stripped)."""
-    txt = open(os.path.join(ROOT, "include", "tamcmc_accel.h")).read()
-    txt = re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
-    out = {}
-    for name, args in re.findall(r"\bint\s+(tamcmc_summary_[a-z_]+)\s*\(([^)]*)\)\s*;", txt):
-        types = []
-        for a in args.split(","):
-            a = " ".join(a.split())
-            a = re.sub(r"\s*\b[A-Za-z_]\w*$", "", a) if not a.endswith("*") else a      # drop the parameter's name
-            types.append(a.replace(" *", "*"))
-        out[name] = types
-    return out, txt
 
 
 def test_symbols_and_signatures(accel_mod):

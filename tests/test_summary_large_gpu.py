@@ -9,7 +9,7 @@ positive.  A block of B samples is one launch over B chains, so blocks of 65 535
 launch at those chain counts.
 
 Bounds (none is new):
-  a. the fold against the oracle: reference() / check() of tests/test_summary_gpu.py as they are, E = EPS + n 2^-52 with
+  a. the fold against the oracle: reference() / check() of tests/summary_support.py as they are, E = EPS + n 2^-52 with
      n 2^-52 = 1.6e-11 now the larger term.
   b. accumulation alone: the GPU's own model rows reduced in long double by the same formulas, EPS replaced by 0, so that
      only the n 2^-52 terms remain: |d mean_M| <= acc mean|M|, |d var_M| <= 4 acc mean(M^2), min_M / max_M bit-equal,
@@ -37,9 +37,10 @@ import numpy as np
 import pytest
 
 import workloads as W
+from summary_support import (Q8, check, gpu_rows, ranks_of, reference, same, same_traj, select, sigma_of, spectrum_for, summarize,
+                             truth_of, unresolved_bits)
+from support import LD, bits
 from tamcmc_amd import capi, synth
-from test_summary_gpu import LD, bits, check, reference, same, spectrum_for
-from test_summary_quantiles_gpu import Q8, gpu_rows, ranks_of, same_traj, select, truth_of, unresolved_bits
 
 pytestmark = pytest.mark.gpu
 
@@ -56,10 +57,6 @@ def rows_around(w, n, seed=20261, scale=0.5):
     P = np.tile(w["params_true"], (n, 1))
     P[1:, idx] += scale * w["err"][None, :] * rng.standard_normal((n - 1, idx.size))
     return P
-
-
-def sigma_of(n):
-    return 0.05 + 0.2 * np.abs(np.sin(np.arange(n)))    # tests/test_summary_gpu.py, the chi_square cases
 
 
 @functools.lru_cache(maxsize=None)
@@ -97,12 +94,6 @@ def rows_of_case(acc, like):
     return _ROWS[like]
 
 
-def summarize(acc, pushes, block_chains=0):
-    with capi.Summary(acc, block_chains) as s:
-        out = [s.push(P) for P in pushes]
-        return s.result(), np.concatenate([o[0] for o in out]), np.concatenate([o[1] for o in out])
-
-
 @pytest.mark.parametrize("like", [0, 1], ids=["chi22p", "chi-square"])
 def test_fold_against_the_oracle(accel_mod, like):
     """1094 launches of the default block of 64; reference() and check() as they are."""
@@ -117,7 +108,7 @@ def test_fold_against_the_oracle(accel_mod, like):
 
 
 def accumulation_reference(M, y, sigma, like, p=1.0):
-    """reference() of tests/test_summary_gpu.py on given rows with EPS = 0, plus the rounding of l (module docstring)."""
+    """reference() of tests/summary_support.py on given rows with EPS = 0, plus the rounding of l (module docstring)."""
     n = len(M)
     Mq, yq = M.astype(LD), y.astype(LD)
     if like == 0:
@@ -170,7 +161,7 @@ def test_block_size_cannot_change_a_bit(accel_mod):
 
 
 def steps(s, q, nbits, push_pass, truth, limit):
-    """select() of tests/test_summary_quantiles_gpu.py, ended after `limit` steps: the trajectory so far."""
+    """select() of tests/summary_support.py, ended after `limit` steps: the trajectory so far."""
     s.quantiles_begin(q, nbits)
     r = s.quantiles_result()
     traj = [(r["lo"], r["hi"])]

@@ -23,18 +23,17 @@ Worst ratios observed on an MI355X over all cases below: on the GPU's own rows e
 70 001-sample one among them), k-hat 0.070 (likelihood_p = 2); on the oracle's rows elpd_loo 1.5e-4 (triples), k-hat
 2.3e-5 (700 bins, 200 samples, scale 3).
 """
-import functools
 import math
-import os
 import subprocess
-import sys
 
 import numpy as np
 import pytest
 
 import workloads as W
+from summary_support import (c2_case, c2_chain, f12, gpu_rows, header_values, other_cases, row_groups, same, spectrum_for,
+                             stored_chain)
+from support import LD, bits, in_torch_process, pyorc
 from tamcmc_amd import capi, synth
-from test_summary_gpu import CFG, G, LD, ROOT, bits, c2_case, other_cases, pyorc, same, spectrum_for
 
 pytestmark = pytest.mark.gpu
 
@@ -103,12 +102,6 @@ def x_of(rows, y, like=0, p=1.0, sigma=None, dtype=LD):
     return ((yq - Mq) ** 2) / np.asarray(sigma).astype(dtype) ** 2          # the reference's convention: no factor 1/2
 
 
-def row_groups(P):
-    """Index of each row's first identical row: duplicated parameter rows share their perturbation."""
-    _, inv = np.unique(np.ascontiguousarray(P), axis=0, return_inverse=True)
-    return np.asarray(inv).reshape(-1)
-
-
 def perturbed(x, rel, seed, groups):
     """x (1 + rel s), s = +-1, one sign per distinct row and bin."""
     rng = np.random.default_rng(seed)
@@ -158,10 +151,6 @@ def check_reference(tag, res, x_ld, groups, rel, seeds, x64=None, totals=True):
     return ref
 
 
-def gpu_rows(acc, P):
-    return acc.eval_batch(P, np.ones(len(P)), model_rows=np.arange(len(P)))
-
-
 def run_loo(acc, pushes, block=0):
     """Fold pass and LOO pass over the same pushes.  Returns (loo result, fold result, logL, status of the LOO pass)."""
     with capi.Summary(acc, block) as s:
@@ -207,16 +196,6 @@ def exact_structure(tag, res, l):
     z = xs - xs[-1]
     c = np.maximum(z[n - M - 1], np.log(np.finfo(np.float64).tiny))
     assert np.array_equal(res["tail_len"], (z > c).sum(axis=0)), (tag, "tail_len")
-
-
-@functools.lru_cache(maxsize=None)
-def c2_chain(Nx, S, scale=0.5):
-    w = synth.workload_c2(Nx=Nx)
-    y = spectrum_for(w)
-    P = synth.chain_params(w, S, scale=scale)
-    for a in (y, P):
-        a.setflags(write=False)
-    return w, y, P
 
 
 @pytest.mark.parametrize("Nx", [2, 63, 64, 65, 257, 700])
@@ -499,48 +478,20 @@ def _device_check():
 
 
 def test_device_pointers():
-    here = os.path.dirname(os.path.abspath(__file__))
-    code = ("import torch, sys; sys.path[:0] = [%r, %r]; import test_summary_loo_gpu as t; t._device_check()"
-            % (os.path.dirname(here), here))
-    r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0 and "loo device path ok" in r.stdout, (r.stdout[-2000:], r.stderr[-3000:])
+    in_torch_process("test_summary_loo_gpu", "_device_check", "loo device path ok")
 
 
 def test_command_line(accel_mod, tmp_path):
-    """The 23-sample chain of tests/test_summary_gpu.py::test_command_line on the golden local-model inputs with --loo: one
-    more header line and two last columns, the numbers Summary.loo gives to the 12 printed digits; everything else is, byte
-    for byte, what the same binary writes without the flag."""
-    from tamcmc_amd import outputs as O
-    from tamcmc_amd import sampler as S
-    from tamcmc_amd.setup_io import Setup
-    exe = os.path.join(ROOT, "bin", "chainsummary_hip")
-    model, data = os.path.join(G, "TF_3443483_local-v3.model"), os.path.join(G, "TF_3443483_local-v3.data")
-    out = str(tmp_path) + "/"
-    s = Setup(CFG).load(model, data, 0)
-    s.set("MALA", "Nchains", 2)
-    for k, v in (("output_dir", out), ("restore_dir", out), ("output_root_name", "TF_A_"), ("Nbuffer", 50), ("file_format", "binary")):
-        s.set("Outputs", k, v)
-    s.set("MALA", "Nt_learn", "10, 30, 100000")
-    s.apply_phase("Burn-in", 50, 1.8)
-    orc = pyorc()
-
-    def ev(P, T):
-        return orc.generate_batch(s.model_case, s.plength, s.x, s.y, P, T, likelihood_p=s.likelihood_p)[:2]
-    smp = S.Sampler(s.sampler_cfg(seed=5), ev, s.plength, s.inputs, s.relax, s.err, s.priors_names_switch, s.priors, s.extra_priors)
-    O.run_phase(s, smp)
-    root = out + "TF_A_params"
-    v, _ = O.read_params_bin(root, 0)
-    common = [exe, CFG, model, data, root]
-    sel = ["--thin", "2", "--first", "4", "--block", "7"]
-    rows = np.tile(s.inputs, (23, 1))
-    rows[:, s.index_to_relax] = v[4::2]
+    """The 23-sample chain of summary_support.stored_chain on the golden local-model inputs with --loo: one more header line
+    and two last columns, the numbers Summary.loo gives to the 12 printed digits; everything else is, byte for byte, what the
+    same binary writes without the flag."""
+    s, root, v, rows, common, sel = stored_chain(tmp_path)
     with accel_mod.Accel(s.model_case, s.plength, s.x, s.y, sigma_y=s.sigma_y, likelihood_case=s.likelihood_case,
                          likelihood_p=s.likelihood_p) as acc:
         with capi.Summary(acc) as sm:
             _, st = sm.push(rows)
             d = sm.loo(rows)
     assert np.all(st == 0) and d["n_used"] == 23
-    f12 = lambda a: np.array([float("%.12g" % t) for t in np.atleast_1d(a)])       # noqa: E731
     for extra, ncol in (([], 8), (["--quantiles", "0.16,0.5,0.84"], 11)):
         plain, table = str(tmp_path / f"plain{ncol}.txt"), str(tmp_path / f"loo{ncol}.txt")
         for path, flag in ((plain, []), (table, ["--loo"])):
@@ -552,8 +503,7 @@ def test_command_line(accel_mod, tmp_path):
         lines0, lines = open(plain).read().split("\n"), open(table).read().split("\n")
         added = [k for k, line in enumerate(lines) if line.startswith("# elpd_loo=")]
         assert len(added) == 1 and lines[added[0] - 1].startswith("# quantiles=" if extra else "# lppd_total=")
-        tok = lines[added[0]][1:].split()
-        head = {a[:-1]: b for a, b in zip(tok, tok[1:]) if a.endswith("=")}
+        head = header_values([lines[added[0]]])
         for k, key in (("elpd_loo", "elpd_loo_total"), ("p_loo", "p_loo"), ("looic", "looic"), ("k_max", "k_max")):
             assert head[k] == "%.12g" % d[key], k
         assert int(head["n_k_high"]) == d["n_k_high"] and int(head["n_k_inf"]) == d["n_k_inf"]

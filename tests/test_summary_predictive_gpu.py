@@ -30,95 +30,35 @@ p = 64.  With plain (uncompensated) sums the 2-bin case misses its log_cdf bound
 4e-16 on a value of -1e-9.
 """
 import functools
-import os
 
 import numpy as np
 import pytest
 
 import workloads as W
-from predictive_reference import LD, predictive_reference, totals_from_pit
+from predictive_reference import predictive_reference, totals_from_pit
+from summary_support import (c2_case, c2_chain, check_pit, check_tails_reference, diff, edited, gpu_rows, perturbed_rows, row_groups,
+                             same, same_pred, sigma_of, spectrum_for, true_model)
+from support import bits, pyorc
 from tamcmc_amd import capi, synth
-from test_summary_gpu import bits, c2_case, pyorc, same, spectrum_for
-from test_summary_loo_gpu import gpu_rows, row_groups
 
 pytestmark = pytest.mark.gpu
 
 KEYS = capi.Summary.PREDICTIVE_ARRAYS
-TOTALS = capi.Summary.PREDICTIVE_TOTALS
-EPS = 2.0 ** -52
-
-
-def same_pred(r1, r2):
-    return all(np.array_equal(bits(r1[k]), bits(r2[k])) for k in KEYS) and np.array_equal(r1["pit_hist"], r2["pit_hist"]) and \
-        all(np.array_equal(bits(float(r1[k])), bits(float(r2[k]))) for k in TOTALS)
-
-
-def diff(key, a, b):
-    """max over the bins of the difference of two results of `key`: relative to max(1, |b|), absolute for pit; where a
-    value is infinite both must be the same infinity (else inf)."""
-    a, b = np.asarray(a).astype(LD), np.asarray(b).astype(LD)
-    fin = np.isfinite(a) & np.isfinite(b)
-    if not np.array_equal(a[~fin], b[~fin]):
-        return np.inf
-    if not fin.any():
-        return 0.0
-    d = np.abs(a[fin] - b[fin])
-    if key != "pit":
-        d = d / np.maximum(1, np.abs(b[fin]))
-    return float(np.max(d))
-
-
-def perturbed_rows(rows, rel, seed, groups):
-    """rows (1 + rel s), s = +-1, one sign per distinct parameter row and bin."""
-    rng = np.random.default_rng(seed)
-    s = rng.integers(0, 2, size=(int(groups.max()) + 1, rows.shape[1])) * 2 - 1
-    r = np.asarray(rows).astype(LD)
-    return r * (1 + LD(rel) * s[groups].astype(LD))
 
 
 def check_reference(tag, res, rows, y, groups, rel, seeds, with_f64, like=0, p=1, sigma=None):
     """res against predictive_reference(rows) with the bounds of the module docstring; then the self-check and the
     totals.  Returns the reference."""
-    kw = dict(like=like, p=p, sigma=sigma)
-    n = len(rows)
-    ref = predictive_reference(rows, y, **kw)
-    d = {k: 0.0 for k in KEYS}
-    for seed in seeds:
-        pert = predictive_reference(perturbed_rows(rows, rel, seed, groups), y, **kw)
-        for k in KEYS:
-            d[k] = max(d[k], diff(k, pert[k], ref[k]))
-    b64 = {k: 0.0 for k in KEYS}
-    if with_f64:
-        r64 = predictive_reference(rows, y, dtype=np.float64, **kw)
-        for k in KEYS:
-            b64[k] = diff(k, r64[k], ref[k])
-            d[k] = max(d[k], b64[k])
-    for k, dk in d.items():
-        assert np.isfinite(dk), (tag, k, "the reference runs disagree on where the value is finite: the case has no bound")
-    ratios = {}
-    for k, dk in d.items():
-        err = diff(k, res[k], ref[k])
-        ratios[k] = err / (10.0 * dk) if dk > 0 else (0.0 if err == 0 else np.inf)
-    print(f"RATIO predictive {tag}: " + " ".join(f"{k}={v:.3g} (bound {10.0 * d[k]:.3g})" for k, v in ratios.items()))
-    for k, v in ratios.items():
-        assert v <= 1.0, (tag, k, v)
-    # self-check: the two tails of a bin sum to 1
-    lc, ls = np.asarray(res["log_cdf"]), np.asarray(res["log_sf"])
-    one = np.abs(np.exp(lc) + np.exp(ls) - 1.0)
-    slack = (n + 2) * EPS + (10.0 * max(b64["log_cdf"], b64["log_sf"]) if like == 0 and p > 1 else 0.0)
-    print(f"SELF predictive {tag}: |P + Q - 1| = {float(one.max()):.3g} (bound {slack:.3g})")
-    assert np.all(one <= slack), (tag, float(one.max()), slack)
-    check_totals(tag, res, n)
+    reference = functools.partial(predictive_reference, like=like, p=p, sigma=sigma)
+    ref = check_tails_reference(reference, "predictive", KEYS, tag, res, rows, y, groups, rel, seeds, with_f64, like, p, f64_always=False)
+    check_totals(tag, res, len(rows))
     return ref
 
 
 def check_totals(tag, res, n, n_rejected=0):
     """pit from the smaller tail, within 2 ulp; every total recomputed from the library's own arrays: exact."""
-    lc, ls, pit = np.asarray(res["log_cdf"]), np.asarray(res["log_sf"]), np.asarray(res["pit"])
     assert res["n_used"] == n and res["n_rejected"] == n_rejected, tag
-    want = np.where(lc < ls, np.exp(lc), -np.expm1(ls))      # (the host's exp / expm1 and numpy's: each within an ulp of the truth)
-    assert np.all(np.abs(pit - want) <= 2.0 * np.spacing(want)), (tag, "pit")
-    assert np.all((pit >= 0) & (pit <= 1)) and np.all(lc <= 0) and np.all(ls <= 0), tag
+    lc, ls, pit = check_pit(tag, res)
     D, hist = totals_from_pit(pit)
     assert res["ks_D"] == D, (tag, res["ks_D"], D)
     assert np.array_equal(res["pit_hist"], hist) and int(res["pit_hist"].sum()) == pit.size, (tag, res["pit_hist"], hist)
@@ -132,29 +72,6 @@ def run(acc, pushes, block=0):
         for P in pushes:
             s.push(P)
         return s.predictive_result(), s.result()
-
-
-def edited(y, like=0, M0=None, sigma=None):
-    """The data edits of a case, on a copy: (y, dict name -> bin).  chi(2,2p): one y times 2000 (the largest datum, so that
-    y / M is not small to begin with), one 0, one 1e-300, one negative; chi_square: y at M0 + 40 sigma and at M0 - 40 sigma,
-    M0 the model at the chain's centre."""
-    y = np.array(y)
-    nx = y.size
-    where = {}
-    if like == 0:
-        if nx < 8:
-            where = dict(zero=nx - 1)
-        else:
-            top = int(np.argmax(y))
-            free = [k for k in range(3, nx, 14) if k != top]
-            where = dict(x2000=top, zero=free[0], tiny=free[1], negative=free[2])
-        for name, k in where.items():
-            y[k] = dict(x2000=2000.0 * y[k], zero=0.0, tiny=1e-300, negative=-abs(y[k]) - 1.0)[name]
-    elif nx >= 8:
-        where = dict(plus40=5, minus40=nx - 3)
-        y[5] = M0[5] + 40.0 * sigma[5]
-        y[nx - 3] = M0[nx - 3] - 40.0 * sigma[nx - 3]
-    return y, where
 
 
 def check_edits(tag, res, where, y):
@@ -172,26 +89,6 @@ def check_edits(tag, res, where, y):
             assert np.isfinite(ls) and ls < -1000.0 and pit == 1.0, (tag, name, ls, pit)
         elif name == "minus40":
             assert np.isfinite(lc) and lc < -1000.0 and 0.0 <= pit < 1e-300, (tag, name, lc, pit)
-
-
-@functools.lru_cache(maxsize=None)
-def c2_chain(Nx, S):
-    w = synth.workload_c2(Nx=Nx)
-    y0 = spectrum_for(w)
-    P = synth.chain_params(w, S)
-    for a in (y0, P):
-        a.setflags(write=False)
-    return w, y0, P
-
-
-def sigma_of(n):
-    return 0.05 + 0.2 * np.abs(np.sin(np.arange(n)))        # (tests/test_parity_gpu.py::test_chi_square_likelihood)
-
-
-def true_model(w):
-    m, st = pyorc().model(w["model_case"], w["params_true"], w["plength"], w["x"])
-    assert st == 0
-    return m
 
 
 @pytest.mark.parametrize("Nx", [2, 63, 64, 65, 129, 700])

@@ -11,78 +11,20 @@ Against the oracle (pyoracle.generate_batch(..., want_models=True), sorted per b
 |value - ref| <= EPS max_s |M_is|.  The worst ratio is printed before it is asserted (pytest -s).
 Worst ratios observed on an MI355X: 8.6e-4 (id 2, 700 bins), 3.3e-3 (id 3, asymmetry 10).
 """
-import math
-import os
 import subprocess
-import sys
 
 import numpy as np
 import pytest
 
 import workloads as W
+from summary_support import (EPS, Q8, c2_case, f12, gpu_rows, header_values, other_cases, ranks_of, same, same_traj, select,
+                             spectrum_for, stored_chain, truth_of, unresolved_bits)
+from support import LD, bits, in_torch_process, pyorc
 from tamcmc_amd import capi, synth
-from test_summary_gpu import CFG, EPS, G, LD, ROOT, bits, c2_case, other_cases, pyorc, same, spectrum_for
 
 pytestmark = pytest.mark.gpu
 
-Q8 = (0.0, 0.025, 0.16, 0.5, 0.84, 0.975, 1.0, 0.5)        # the last one is a duplicate
 Q3 = (0.16, 0.5, 0.84)
-ONE = np.uint64(1)
-
-
-def ranks_of(q, n):
-    return np.array([min(max(int(math.ceil(t * float(n))) - 1, 0), n - 1) for t in q])
-
-
-def truth_of(rows, q):
-    """(Nq, Nx): the order statistics of the accepted rows."""
-    return np.sort(rows, axis=0)[ranks_of(q, len(rows))]
-
-
-def keys(a):
-    u = (np.asarray(a, dtype=np.float64) + 0.0).view(np.uint64)
-    return np.where((u >> np.uint64(63)) != 0, ~u, u | (ONE << np.uint64(63)))
-
-
-def unresolved_bits(rows):
-    """max over the bins of bit_length(key(max) - key(min))."""
-    k = keys(rows)
-    return max(int(r).bit_length() for r in (k.max(axis=0) - k.min(axis=0)))
-
-
-def gpu_rows(acc, P):
-    L, st, rows = acc.eval_batch(P, np.ones(len(P)), model_rows=np.arange(len(P)))
-    return L, st, rows
-
-
-def select(s, q, nbits, push_pass, truth=None, u0=None):
-    """begin, then passes of push_pass(pass number) + step until 0 bits are left.  Returns the brackets after begin and after
-    every step.  With `truth`: containment and monotony after every step; with `u0`: bits_left after every step."""
-    b = nbits if nbits else 6
-    s.quantiles_begin(q, nbits)
-    r = s.quantiles_result()
-    traj = [(r["lo"], r["hi"])]
-    left, steps = None, 0
-    while left != 0:
-        push_pass(steps)
-        left = s.quantiles_step()
-        steps += 1
-        assert steps <= -(-64 // b), "more steps than ceil(64 / bits)"
-        r = s.quantiles_result()
-        if u0 is not None:
-            assert left == max(u0 - steps * b, 0), (steps, left, u0)
-        elif len(traj) > 1:
-            assert left == max(prev_left - b, 0)
-        prev_left = left
-        if truth is not None:
-            assert np.all(r["lo"] <= truth) and np.all(truth <= r["hi"]), f"step {steps}: the bracket lost the truth"
-        assert np.all(r["lo"] >= traj[-1][0]) and np.all(r["hi"] <= traj[-1][1]), f"step {steps}: a bracket grew"
-        traj.append((r["lo"], r["hi"]))
-    return traj, r["ranks"]
-
-
-def same_traj(t1, t2):
-    return len(t1) == len(t2) and all(np.array_equal(bits(a[0]), bits(b[0])) and np.array_equal(bits(a[1]), bits(b[1])) for a, b in zip(t1, t2))
 
 
 @pytest.mark.parametrize("nbits", [1, 4, 6, 0])
@@ -458,52 +400,24 @@ def _device_check():
 
 
 def test_device_pointers():
-    here = os.path.dirname(os.path.abspath(__file__))
-    code = ("import torch, sys; sys.path[:0] = [%r, %r]; import test_summary_quantiles_gpu as t; t._device_check()"
-            % (os.path.dirname(here), here))
-    r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0 and "quantile device path ok" in r.stdout, (r.stdout[-2000:], r.stderr[-3000:])
+    in_torch_process("test_summary_quantiles_gpu", "_device_check", "quantile device path ok")
 
 
 def test_command_line(accel_mod, tmp_path):
-    """The 23-sample chain of tests/test_summary_gpu.py::test_command_line with --quantiles: three more columns, the first
-    eight unchanged, the header says which quantiles and how many passes."""
-    from tamcmc_amd import outputs as O
-    from tamcmc_amd import sampler as S
-    from tamcmc_amd.setup_io import Setup
-    exe = os.path.join(ROOT, "bin", "chainsummary_hip")
-    model, data = os.path.join(G, "TF_3443483_local-v3.model"), os.path.join(G, "TF_3443483_local-v3.data")
-    out = str(tmp_path) + "/"
-    s = Setup(CFG).load(model, data, 0)
-    s.set("MALA", "Nchains", 2)
-    for k, v in (("output_dir", out), ("restore_dir", out), ("output_root_name", "TF_A_"), ("Nbuffer", 50), ("file_format", "binary")):
-        s.set("Outputs", k, v)
-    s.set("MALA", "Nt_learn", "10, 30, 100000")
-    s.apply_phase("Burn-in", 50, 1.8)
-    orc = pyorc()
-
-    def ev(P, T):
-        return orc.generate_batch(s.model_case, s.plength, s.x, s.y, P, T, likelihood_p=s.likelihood_p)[:2]
-    smp = S.Sampler(s.sampler_cfg(seed=5), ev, s.plength, s.inputs, s.relax, s.err, s.priors_names_switch, s.priors, s.extra_priors)
-    O.run_phase(s, smp)
-    root = out + "TF_A_params"
-    v, _ = O.read_params_bin(root, 0)
+    """The 23-sample chain of summary_support.stored_chain with --quantiles: three more columns, the first eight unchanged,
+    the header says which quantiles and how many passes."""
+    s, root, v, rows, common, sel = stored_chain(tmp_path)
     plain, table = str(tmp_path / "plain.txt"), str(tmp_path / "bands.txt")
-    common = [exe, CFG, model, data, root]
-    sel = ["--thin", "2", "--first", "4", "--block", "7"]
     r = subprocess.run(common + [plain] + sel, capture_output=True, text=True, timeout=120)
     assert r.returncode == 0, r.stdout + r.stderr
     r = subprocess.run(common + [table] + sel + ["--quantiles", "0.16,0.5,0.84"], capture_output=True, text=True, timeout=120)
     assert r.returncode == 0, r.stdout + r.stderr
-    rows = np.tile(s.inputs, (23, 1))
-    rows[:, s.index_to_relax] = v[4::2]
     with accel_mod.Accel(s.model_case, s.plength, s.x, s.y, sigma_y=s.sigma_y, likelihood_case=s.likelihood_case,
                          likelihood_p=s.likelihood_p) as acc:
         with capi.Summary(acc) as sm:
             _, st = sm.push(rows)
             q = sm.quantiles(rows, Q3)
     assert np.all(st == 0) and q["bits_left"] == 0
-    f12 = lambda a: np.array([float("%.12g" % t) for t in np.atleast_1d(a)])       # noqa: E731
     t0, t = np.loadtxt(plain), np.loadtxt(table)
     assert t0.shape == (s.Nx, 8) and t.shape == (s.Nx, 11)
     assert np.array_equal(t[:, :8], t0)
@@ -512,10 +426,7 @@ def test_command_line(accel_mod, tmp_path):
     assert np.all(t[:, 4] <= t[:, 8]) and np.all(t[:, 8] <= t[:, 9]) and np.all(t[:, 9] <= t[:, 10]) and np.all(t[:, 10] <= t[:, 5])
     lines0 = [l for l in open(plain) if l.startswith("#")]
     lines = [l for l in open(table) if l.startswith("#")]
-    head = {}
-    for line in lines:
-        tok = line[1:].split()
-        head.update({a[:-1]: b for a, b in zip(tok, tok[1:]) if a.endswith("=")})
+    head = header_values(lines)
     assert head["quantiles"] == "0.16,0.5,0.84" and int(head["passes"]) == q["passes"] and int(head["n_used"]) == 23
     assert lines[-1].split() == "# x y mean_M sd_M min_M max_M lppd var_l q0.16 q0.5 q0.84".split()
     assert not any("quantiles=" in l for l in lines0) and lines0[-1].split() == "# x y mean_M sd_M min_M max_M lppd var_l".split()

@@ -11,8 +11,8 @@ order in which the three checks were enabled; the fold, per-bin and windowed res
 and off; the scan's results untouched by a quantile, a LOO and an ESS pass and the same after a reset and a second pass;
 totals and regions recomputed from the library's own arrays.
 
-Against the reference (tests/scan_reference.py, long double) the rule and the bounds are those of check_reference in
-tests/test_summary_window_gpu.py, unchanged: on the GPU's own rows 10 x the larger of (a) the reference's change under a
+Against the reference (tests/scan_reference.py, long double) the rule and the bounds are those of the windowed check
+(check_tails_reference in tests/summary_support.py, called as tests/test_summary_window_gpu.py calls it): on the GPU's own rows 10 x the larger of (a) the reference's change under a
 2^-50 relative perturbation of the rows and (b) its float64-minus-long-double difference; on the oracle's rows 10 x the
 change under a 1e-12 perturbation, the maximum over five seeds; |P + Q - 1| as there.  Every worst ratio is printed before
 it is asserted (pytest -s).  At 70 001 samples the reference is evaluated at every sixth position and at both ends -- its
@@ -25,6 +25,7 @@ oracle's rows 2.7e-4, 2.5e-4, 2.3e-4 and 6.1e-4.  |P + Q - 1| was 1.1e-14 or les
 best log_sf -4.446 (window 18), the best single bin -5.348 (bin 109), the line -8.161, the scan -8.63863 at position 350,
 one region, positions 350 ... 351."""
 
+import functools
 import itertools
 
 import numpy as np
@@ -32,30 +33,18 @@ import pytest
 
 from predictive_reference import predictive_reference
 from scan_reference import default_line, regions, scan_reference, scan_totals
+from summary_support import (accepted, c2_case, c2_chain, check_pit, check_tails_reference, collect, data_of, edited, edited_chi, open_case,
+                             row_groups, same, same_pred, same_scan, same_scans, same_win, sigma_of, spectrum_for, true_model,
+                             with_rejected)
+from support import bits, pyorc
 from tamcmc_amd import capi, synth
-from test_summary_gpu import bits, c2_case, pyorc, same, spectrum_for
-from test_summary_loo_gpu import row_groups
-from test_summary_predictive_gpu import c2_chain, diff, edited, perturbed_rows, same_pred, sigma_of, true_model
-from test_summary_window_gpu import accepted, data_of, edited_chi, open_case, same_win, with_rejected
 from window_reference import window_reference
 
 pytestmark = pytest.mark.gpu
 
 KEYS = capi.Summary.SCAN_ARRAYS
-TOTALS = capi.Summary.SCAN_TOTALS
-EPS = 2.0 ** -52
 TILE = 2048                                                  # TM_SCAN_TILE: positions per workgroup of the sums kernel
 WORST = {}                                                   # tag of the test -> key -> worst ratio seen (printed per case as well)
-
-
-def same_scan(r1, r2):
-    return all(np.array_equal(bits(r1[k]), bits(r2[k])) for k in KEYS) and \
-        all(np.array_equal(bits(float(r1[k])), bits(float(r2[k]))) for k in TOTALS) and \
-        np.array_equal(r1["first_bin"], r2["first_bin"]) and np.array_equal(r1["last_bin"], r2["last_bin"])
-
-
-def same_scans(a, b):
-    return len(a) == len(b) and all(same_scan(x, y) for x, y in zip(a, b))
 
 
 def widths_for(Nx, like, p, want):
@@ -87,10 +76,7 @@ def check_totals(tag, res, n, n_rejected, Nx, W):
     assert res["n_used"] == n and res["n_rejected"] == n_rejected, (tag, res["n_used"], res["n_rejected"])
     assert res["W"] == W and res["n_positions"] == n_pos == len(res["pit"]), tag
     assert np.array_equal(res["first_bin"], np.arange(n_pos)) and np.array_equal(res["last_bin"], np.arange(n_pos) + W - 1), tag
-    lc, ls, pit = np.asarray(res["log_cdf"]), np.asarray(res["log_sf"]), np.asarray(res["pit"])
-    want = np.where(lc < ls, np.exp(lc), -np.expm1(ls))
-    assert np.all(np.abs(pit - want) <= 2.0 * np.spacing(want)), (tag, "pit")
-    assert np.all((pit >= 0) & (pit <= 1)) and np.all(lc <= 0) and np.all(ls <= 0), tag
+    lc, ls, _ = check_pit(tag, res)
     t = scan_totals(lc, ls)
     for k in ("min_log_sf", "min_log_cdf", "pos_min_log_sf", "pos_min_log_cdf"):
         assert res[k] == t[k], (tag, k, res[k], t[k])
@@ -111,46 +97,10 @@ def check_regions(tag, s, k, res, Nx):
 
 def check_reference(tag, res, rows, y, groups, rel, seeds, with_f64, W, like=0, p=1, sigma=None, n_rejected=0, positions=None):
     """res against scan_reference(rows) with the bounds of the module docstring; then the self-check and the totals."""
-    kw = dict(W=W, like=like, p=p, sigma=sigma, positions=positions)
-    n = len(rows)
-    sel = slice(None) if positions is None else np.asarray(positions)
-    ref = scan_reference(rows, y, **kw)
-    d = {k: 0.0 for k in KEYS}
-    for seed in seeds:
-        pert = scan_reference(perturbed_rows(rows, rel, seed, groups), y, **kw)
-        for k in KEYS:
-            d[k] = max(d[k], diff(k, pert[k], ref[k]))
-    r64 = scan_reference(rows, y, dtype=np.float64, **kw)
-    b64 = {k: diff(k, r64[k], ref[k]) for k in KEYS}             # bound (b)
-    if with_f64:
-        for k in KEYS:
-            d[k] = max(d[k], b64[k])
-    for k, dk in d.items():
-        assert np.isfinite(dk), (tag, k, "the reference runs disagree on where the value is finite: the case has no bound")
-    ratios = {}
-    for k, dk in d.items():
-        err = diff(k, np.asarray(res[k])[sel], ref[k])
-        ratios[k] = err / (10.0 * dk) if dk > 0 else (0.0 if err == 0 else np.inf)
-    print(f"RATIO scan {tag}: " + " ".join(f"{k}={v:.3g} (bound {10.0 * d[k]:.3g})" for k, v in ratios.items()))
-    worst = WORST.setdefault(tag.split(" ")[0], {k: 0.0 for k in KEYS})
-    for k, v in ratios.items():
-        worst[k] = max(worst[k], v)
-        assert v <= 1.0, (tag, k, v)
-    lc, ls = np.asarray(res["log_cdf"]), np.asarray(res["log_sf"])
-    one = np.abs(np.exp(lc) + np.exp(ls) - 1.0)[sel]
-    slack = (n + 2) * EPS + (10.0 * max(b64["log_cdf"], b64["log_sf"]) if like == 0 and p * W > 1 else 0.0)
-    print(f"SELF scan {tag}: |P + Q - 1| = {float(one.max()):.3g} (bound {slack:.3g})")
-    assert np.all(one <= slack), (tag, float(one.max()), slack)
-    check_totals(tag, res, n, n_rejected, len(y), W)
-
-
-def collect(misses, tag, *a, **k):
-    """check_reference with a miss recorded, not raised: every combination of a case is checked and printed before the case
-    fails on `assert not misses`."""
-    try:
-        check_reference(tag, *a, **k)
-    except AssertionError as e:
-        misses.append(str(e).split("\n")[0])
+    reference = functools.partial(scan_reference, W=W, like=like, p=p, sigma=sigma, positions=positions)
+    check_tails_reference(reference, "scan", KEYS, tag, res, rows, y, groups, rel, seeds, with_f64, like, p * W, f64_always=True,
+                          positions=positions, worst=WORST)
+    check_totals(tag, res, len(rows), n_rejected, len(y), W)
 
 
 def first_for(b, W):
@@ -385,7 +335,7 @@ def test_against_the_reference(accel_mod, Nx, S, cfg):
             for k, W in enumerate(widths):
                 res = s.scan_result(k)
                 tag = f"gpu-rows Nx={Nx} S={S} {cfg} W={W}"
-                collect(misses, tag, res, rows, y, np.arange(S), 2.0 ** -50, (1,), True, W, like, p, sigma, n_rejected=n_bad)
+                collect(check_reference, misses, tag, res, rows, y, np.arange(S), 2.0 ** -50, (1,), True, W, like, p, sigma, n_rejected=n_bad)
                 check_regions(tag, s, k, res, Nx)
     print("WORST gpu-rows", WORST.get("gpu-rows"))
     assert not misses, misses
@@ -400,7 +350,7 @@ def test_the_largest_shape(accel_mod, name, p, W):
     with accel_mod.Accel(2, w["plength"], w["x"], y, likelihood_p=float(p)) as acc:
         rows = accepted(acc, P, 0)
         res = run(acc, [P], 16, scan=W)[0][0]
-        collect(misses, f"shape-512 {name}", res, rows, y, np.arange(37), 2.0 ** -50, (1,), True, W, 0, p)
+        collect(check_reference, misses, f"shape-512 {name}", res, rows, y, np.arange(37), 2.0 ** -50, (1,), True, W, 0, p)
     print("WORST shape-512", WORST.get("shape-512"))
     assert not misses, misses
 
@@ -425,7 +375,7 @@ def test_against_the_oracle(accel_mod, name):
     with accel_mod.Accel(2, w["plength"], w["x"], y, sigma_y=sigma, likelihood_case=like, likelihood_p=float(p)) as acc:
         res = run(acc, [P], scan=(7, 64, 100))[0]
         for k, W in enumerate((7, 64, 100)):
-            collect(misses, f"oracle {name} W={W}", res[k], M, y, row_groups(P), 1e-12, (1, 2, 3, 4, 5), False, W, like, p, sigma)
+            collect(check_reference, misses, f"oracle {name} W={W}", res[k], M, y, row_groups(P), 1e-12, (1, 2, 3, 4, 5), False, W, like, p, sigma)
     print("WORST oracle", WORST.get("oracle"))
     assert not misses, misses
 

@@ -11,7 +11,8 @@ import subprocess
 
 import numpy as np
 
-from test_summary_host import prototypes, tool
+from summary_support import prototypes
+from support import tool
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NAMES = ["tamcmc_summary_scan_enable", "tamcmc_summary_scan_result", "tamcmc_summary_scan_regions", "tamcmc_summary_scan_kernel_time"]

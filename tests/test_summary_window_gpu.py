@@ -33,28 +33,22 @@ With tmp_chi_p at every shape -- the first build -- [65-200-p3] at W = 7, first 
 pit at 2.07, from the device's log times the shape (tamcmc_window.h, tmw_chi_a); it is at 0.24 and 0.11 now.
 """
 
+import functools
+
 import numpy as np
 import pytest
 
 from predictive_reference import predictive_reference
+from summary_support import (accepted, c2_case, c2_chain, check_pit, check_tails_reference, collect, data_of, edited, edited_chi, open_case,
+                             row_groups, same, same_pred, same_win, sigma_of, spectrum_for, true_model, with_rejected)
+from support import bits, pyorc
 from tamcmc_amd import capi, synth
-from test_summary_gpu import bits, c2_case, pyorc, same, spectrum_for
-from test_summary_loo_gpu import gpu_rows, row_groups
-from test_summary_predictive_gpu import c2_chain, diff, edited, perturbed_rows, same_pred, sigma_of, true_model
 from window_reference import partition, window_reference, window_totals
 
 pytestmark = pytest.mark.gpu
 
 KEYS = capi.Summary.WINDOW_ARRAYS
-TOTALS = capi.Summary.WINDOW_TOTALS
-EPS = 2.0 ** -52
 WORST = {}                                                   # tag of the test -> key -> worst ratio seen (printed per case as well)
-
-
-def same_win(r1, r2):
-    return all(np.array_equal(bits(r1[k]), bits(r2[k])) for k in KEYS) and np.array_equal(r1["pit_hist"], r2["pit_hist"]) and \
-        all(np.array_equal(bits(float(r1[k])), bits(float(r2[k]))) for k in TOTALS) and \
-        np.array_equal(r1["first_bin"], r2["first_bin"]) and np.array_equal(r1["last_bin"], r2["last_bin"])
 
 
 def check_totals(tag, res, n, n_rejected, Nx, W, first):
@@ -64,10 +58,7 @@ def check_totals(tag, res, n, n_rejected, Nx, W, first):
     assert res["n_used"] == n and res["n_rejected"] == n_rejected, (tag, res["n_used"], res["n_rejected"])
     assert res["n_windows"] == len(begin) == len(res["pit"]) and res["W"] == W and res["first"] == f, tag
     assert np.array_equal(res["first_bin"], begin) and np.array_equal(res["last_bin"], end - 1), tag
-    lc, ls, pit = np.asarray(res["log_cdf"]), np.asarray(res["log_sf"]), np.asarray(res["pit"])
-    want = np.where(lc < ls, np.exp(lc), -np.expm1(ls))
-    assert np.all(np.abs(pit - want) <= 2.0 * np.spacing(want)), (tag, "pit")
-    assert np.all((pit >= 0) & (pit <= 1)) and np.all(lc <= 0) and np.all(ls <= 0), tag
+    lc, ls, pit = check_pit(tag, res)
     t = window_totals(pit, lc, ls)
     assert res["ks_D"] == t["ks_D"], (tag, res["ks_D"], t["ks_D"])
     assert np.array_equal(res["pit_hist"], t["pit_hist"]) and int(res["pit_hist"].sum()) == pit.size, (tag, res["pit_hist"])
@@ -78,46 +69,11 @@ def check_totals(tag, res, n, n_rejected, Nx, W, first):
 def check_reference(tag, res, rows, y, groups, rel, seeds, with_f64, W, first=0, like=0, p=1, sigma=None, n_rejected=0):
     """res against window_reference(rows) with the bounds of the module docstring; then the self-check and the totals.
     Returns the reference."""
-    kw = dict(W=W, first=first, like=like, p=p, sigma=sigma)
-    n = len(rows)
-    ref = window_reference(rows, y, **kw)
-    d = {k: 0.0 for k in KEYS}
-    for seed in seeds:
-        pert = window_reference(perturbed_rows(rows, rel, seed, groups), y, **kw)
-        for k in KEYS:
-            d[k] = max(d[k], diff(k, pert[k], ref[k]))
-    r64 = window_reference(rows, y, dtype=np.float64, **kw)
-    b64 = {k: diff(k, r64[k], ref[k]) for k in KEYS}             # bound (b): part of the bound on the GPU's own rows, and of the self-check's slack
-    if with_f64:
-        for k in KEYS:
-            d[k] = max(d[k], b64[k])
-    for k, dk in d.items():
-        assert np.isfinite(dk), (tag, k, "the reference runs disagree on where the value is finite: the case has no bound")
-    ratios = {}
-    for k, dk in d.items():
-        err = diff(k, res[k], ref[k])
-        ratios[k] = err / (10.0 * dk) if dk > 0 else (0.0 if err == 0 else np.inf)
-    print(f"RATIO window {tag}: " + " ".join(f"{k}={v:.3g} (bound {10.0 * d[k]:.3g})" for k, v in ratios.items()))
-    worst = WORST.setdefault(tag.split(" ")[0], {k: 0.0 for k in KEYS})
-    for k, v in ratios.items():
-        worst[k] = max(worst[k], v)
-        assert v <= 1.0, (tag, k, v)
-    lc, ls = np.asarray(res["log_cdf"]), np.asarray(res["log_sf"])
-    one = np.abs(np.exp(lc) + np.exp(ls) - 1.0)
-    slack = (n + 2) * EPS + (10.0 * max(b64["log_cdf"], b64["log_sf"]) if like == 0 and p * W > 1 else 0.0)
-    print(f"SELF window {tag}: |P + Q - 1| = {float(one.max()):.3g} (bound {slack:.3g})")
-    assert np.all(one <= slack), (tag, float(one.max()), slack)
-    check_totals(tag, res, n, n_rejected, len(y), W, first)
+    reference = functools.partial(window_reference, W=W, first=first, like=like, p=p, sigma=sigma)
+    ref = check_tails_reference(reference, "window", KEYS, tag, res, rows, y, groups, rel, seeds, with_f64, like, p * W, f64_always=True,
+                                worst=WORST)
+    check_totals(tag, res, len(rows), n_rejected, len(y), W, first)
     return ref
-
-
-def collect(misses, tag, *a, **k):
-    """check_reference with a miss recorded, not raised: every combination of a case is checked and printed before the case
-    fails on `assert not misses`."""
-    try:
-        check_reference(tag, *a, **k)
-    except AssertionError as e:
-        misses.append(str(e).split("\n")[0])
 
 
 def run(acc, pushes, block=0, window=7, predictive=False):
@@ -129,49 +85,8 @@ def run(acc, pushes, block=0, window=7, predictive=False):
         return out + (s.predictive_result(),) if predictive else out
 
 
-def edited_chi(y):
-    """The chi(2,2p) data edits, on a copy: three neighbouring bins -- inside one window wherever W >= 7 -- hold a datum
-    times 2000, a 0 and a negative one; a grid shorter than 7 bins gets the 0 alone."""
-    y = np.array(y)
-    if y.size < 7:
-        y[-1] = 0.0
-    else:
-        y[4] *= 2000.0
-        y[5] = 0.0
-        y[6] = -abs(y[6]) - 1.0
-    return y
-
-
-def with_rejected(w, P, at):
-    """P with a row whose first relaxed parameter is NaN inserted before each position of `at`."""
-    bad = np.array(P[0])
-    bad[w["index_to_relax"][0]] = np.nan
-    return np.insert(np.array(P), at, bad, axis=0)
-
-
-def accepted(acc, P, n_bad):
-    _, st, rows = gpu_rows(acc, P)
-    assert int((st != 0).sum()) == n_bad
-    return rows[st == 0]
-
-
 def firsts(W):
     return sorted({0, 1, min(3, W), W - 1} - ({W - 1} if W == 1 else set()))
-
-
-def open_case(accel_mod, w, y, cfg):
-    if cfg == "chi-square":
-        return accel_mod.Accel(2, w["plength"], w["x"], y, sigma_y=sigma_of(len(y)), likelihood_case=1)
-    return accel_mod.Accel(2, w["plength"], w["x"], y, likelihood_p=float(cfg[1:]) + 0.5)      # truncated as everywhere
-
-
-def data_of(w, y0, cfg):
-    """(y, like, p, sigma) of a likelihood configuration "p1", "p3", ... or "chi-square"."""
-    if cfg == "chi-square":
-        sigma = sigma_of(len(y0))
-        y = edited(y0, 1, true_model(w), sigma)[0]
-        return y, 1, 1, sigma
-    return edited_chi(y0), 0, int(cfg[1:]), None
 
 
 # ---- 1. W = 1 is the per-bin check ----
@@ -225,7 +140,7 @@ def test_against_the_reference(accel_mod, Nx, S, cfg):
                 continue
             for first in (firsts(W) if Nx < 5000 or W == 100 else [3 if W > 3 else 1]):
                 res, _ = run(acc, [P], 16, window=(W, first))
-                collect(misses, f"gpu-rows Nx={Nx} S={S} {cfg} W={W} first={first}", res, rows, y, np.arange(S), 2.0 ** -50, (1,), True,
+                collect(check_reference, misses, f"gpu-rows Nx={Nx} S={S} {cfg} W={W} first={first}", res, rows, y, np.arange(S), 2.0 ** -50, (1,), True,
                         W, first, like, p, sigma, n_rejected=n_bad)
     print("WORST gpu-rows", WORST.get("gpu-rows"))
     assert not misses, misses
@@ -242,7 +157,7 @@ def test_the_largest_shape(accel_mod, name, p, W):
             rows = accepted(acc, P, 0)
             for first in (0, 3):
                 res, _ = run(acc, [P], 16, window=(W, first))
-                collect(misses, f"shape-512 {name} Nx={Nx} first={first}", res, rows, y, np.arange(37), 2.0 ** -50, (1,), True, W, first, 0, p)
+                collect(check_reference, misses, f"shape-512 {name} Nx={Nx} first={first}", res, rows, y, np.arange(37), 2.0 ** -50, (1,), True, W, first, 0, p)
     print("WORST shape-512", WORST.get("shape-512"))
     assert not misses, misses
 
@@ -267,7 +182,7 @@ def test_against_the_oracle(accel_mod, name):
     with accel_mod.Accel(2, w["plength"], w["x"], y, sigma_y=sigma, likelihood_case=like, likelihood_p=float(p)) as acc:
         for W, first in ((7, 3), (64, 0), (100, 99)):
             res, _ = run(acc, [P], window=(W, first))
-            collect(misses, f"oracle {name} W={W} first={first}", res, M, y, row_groups(P), 1e-12, (1, 2, 3, 4, 5), False, W, first, like, p, sigma)
+            collect(check_reference, misses, f"oracle {name} W={W} first={first}", res, M, y, row_groups(P), 1e-12, (1, 2, 3, 4, 5), False, W, first, like, p, sigma)
     print("WORST oracle", WORST.get("oracle"))
     assert not misses, misses
 

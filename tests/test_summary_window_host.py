@@ -12,7 +12,8 @@ import subprocess
 import numpy as np
 import pytest
 
-from test_summary_host import prototypes, tool
+from summary_support import prototypes
+from support import tool
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NAMES = ["tamcmc_summary_window_enable", "tamcmc_summary_window_result", "tamcmc_summary_window_kernel_time"]
