@@ -99,7 +99,11 @@ int tamcmc_ctx_create(tamcmc_ctx **out, int device_id, int model_case, int likel
  * TAMCMC_E_NOGRAD (nothing changed) when the gradient tables of the layout with these variables exceed the backward
  * kernel's LDS (504 bytes per multiplet + 72 per variable + 12 per parameter > 150 KB: with every entry a variable
  * from some 210 (id 13) to 235 (id 2) multiplets on; 256 multiplets take up to 262 variables); likelihood batches are
- * not affected. */
+ * not affected.
+ * TAMCMC_E_INVALID (nothing changed, the earlier variables stay) for an index outside 0 ... Nparams - 1, for an index that
+ * occurs twice (hence for Nvars > Nparams: every variable is one column, in the order of the list, which need not be
+ * ascending), and while a batch is in flight or armed.  Nvars = 0 takes the variables away: a gradient request then
+ * returns TAMCMC_E_NOVARS. */
 int tamcmc_ctx_set_vars(tamcmc_ctx *ctx, int32_t Nvars, const int32_t *index_to_relax);
 
 /* Extension (no counterpart in the reference, which fits one spectrum per process): several spectra ON THE SAME GRID

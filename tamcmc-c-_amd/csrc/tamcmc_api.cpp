@@ -311,9 +311,19 @@ extern "C" int tamcmc_ctx_destroy(tamcmc_ctx *c)
 
 extern "C" int tamcmc_ctx_set_vars(tamcmc_ctx *c, int32_t Nvars, const int32_t *index_to_relax)
 {
-    if (!ctx_usable(c) || Nvars < 0 || (Nvars > 0 && !index_to_relax)) return TAMCMC_E_INVALID;
-    for (int i = 0; i < Nvars; i++)
-        if (index_to_relax[i] < 0 || index_to_relax[i] >= c->L.Nparams) return TAMCMC_E_INVALID;
+    if (!ctx_usable(c) || c->in_flight || Nvars < 0 || (Nvars > 0 && !index_to_relax)) return TAMCMC_E_INVALID;
+    // Every index in range and none twice (so Nvars <= Nparams): the backward kernel routes a pair to its variable through
+    // the inverse of this list, and a parameter listed twice would have two columns of which an undefined one gets the
+    // gradient and the other 0.  The reference's list comes from flags and cannot repeat (model_def.cpp:81-88).  Checked
+    // before anything is freed or waited for: a refusal leaves the context as it was.
+    {
+        std::vector<char> seen((size_t)c->L.Nparams, 0);
+        for (int i = 0; i < Nvars; i++) {
+            const int32_t r = index_to_relax[i];
+            if (r < 0 || r >= c->L.Nparams || seen[(size_t)r]) return TAMCMC_E_INVALID;
+            seen[(size_t)r] = 1;
+        }
+    }
     // a layout whose gradient tables outgrow the backward kernel's LDS (every entry a variable: from some 210 to 235 multiplets on)
     // is refused here, the context left as it was -- not at the first gradient batch, after two of its three launches
     if (Nvars > 0 && !tm_backward_fits(c->L, c->tiles_g, Nvars)) return TAMCMC_E_NOGRAD;

@@ -48,3 +48,30 @@ def check_against_oracle(acc, orc, mid, w, y, P, T, sigma=None, like=0, likeliho
     assert np.any(ok), tag
     assert_grad_entrywise(np.asarray(g)[ok], ref[ok], ref_abs[ok], tag)
     return g
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# The oracle's analytic gradient against finite differences of the oracle's own log-likelihood (the checker being checked:
+# tests/test_oracle_grad.py has the reasoning, tests/test_grad_vars_host.py uses the same rule over whole rows).
+# Per entry k:   |g_k - fd_k| <= 1e-6 * (|g_k| + 1e-9 * max_j |g_j|)   at one of four relative steps.
+STEPS = (1e-6, 1e-5, 1e-4, 1e-3)
+RTOL, FLOOR = 1e-6, 1e-9
+
+
+def entrywise_error(orc, mid, w, y, P, T, idx, sigma=None, like=0, steps=STEPS):
+    g, gabs, L, st = orc.grad_analytic(mid, w["plength"], w["x"], y, P, T, idx, sigma_y=sigma, likelihood_case=like)
+    assert np.all(st == 0) and np.all(np.isfinite(g)) and np.all(gabs >= np.abs(g) * (1 - 1e-12))
+    rL, _ = orc.generate_batch(mid, w["plength"], w["x"], y, P, T, sigma_y=sigma, likelihood_case=like)
+    assert np.array_equal(L, rL)                      # the gradient is taken at the oracle's own model evaluation
+    worst = 0.0
+    for k in range(P.shape[0]):
+        best = np.full(idx.size, np.inf)
+        for rs in steps:
+            fd, st2 = orc.grad_fd_wide(mid, w["plength"], w["x"], y, P[k], T[k], idx, rel_step=rs, sigma_y=sigma,
+                                       likelihood_case=like)
+            assert st2 == 0
+            best = np.minimum(best, np.abs(g[k] - fd) / (np.abs(g[k]) + FLOOR * np.max(np.abs(g[k]))))
+        j = int(np.argmax(best))
+        assert best[j] <= RTOL, (mid, k, j, int(idx[j]), g[k][j], best[j])
+        worst = max(worst, best[j])
+    return worst

@@ -7,7 +7,7 @@ import pytest
 
 import datacases as D
 import workloads as W
-from test_oracle_grad import entrywise_error
+from gradcheck import entrywise_error
 
 EPS = np.finfo(np.float64).eps
 

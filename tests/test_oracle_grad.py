@@ -13,10 +13,8 @@ import numpy as np
 import pytest
 
 import workloads as W
+from gradcheck import entrywise_error
 from tamcmc_amd import synth
-
-STEPS = (1e-6, 1e-5, 1e-4, 1e-3)
-RTOL, FLOOR = 1e-6, 1e-9
 
 
 def with_shape_variables(w):
@@ -28,25 +26,6 @@ def with_shape_variables(w):
     w["relax"] = relax
     w["index_to_relax"] = np.flatnonzero(relax).astype(np.int32)
     return w
-
-
-def entrywise_error(orc, mid, w, y, P, T, idx, sigma=None, like=0, steps=STEPS):
-    g, gabs, L, st = orc.grad_analytic(mid, w["plength"], w["x"], y, P, T, idx, sigma_y=sigma, likelihood_case=like)
-    assert np.all(st == 0) and np.all(np.isfinite(g)) and np.all(gabs >= np.abs(g) * (1 - 1e-12))
-    rL, _ = orc.generate_batch(mid, w["plength"], w["x"], y, P, T, sigma_y=sigma, likelihood_case=like)
-    assert np.array_equal(L, rL)                      # the gradient is taken at the oracle's own model evaluation
-    worst = 0.0
-    for k in range(P.shape[0]):
-        best = np.full(idx.size, np.inf)
-        for rs in steps:
-            fd, st2 = orc.grad_fd_wide(mid, w["plength"], w["x"], y, P[k], T[k], idx, rel_step=rs, sigma_y=sigma,
-                                       likelihood_case=like)
-            assert st2 == 0
-            best = np.minimum(best, np.abs(g[k] - fd) / (np.abs(g[k]) + FLOOR * np.max(np.abs(g[k]))))
-        j = int(np.argmax(best))
-        assert best[j] <= RTOL, (mid, k, j, int(idx[j]), g[k][j], best[j])
-        worst = max(worst, best[j])
-    return worst
 
 
 @pytest.mark.parametrize("mid", [2, 3, 6, 7, 8, 9, 10, 11, 12, 13, 14])
