@@ -30,6 +30,9 @@
 //   reference's H V_m / (1 + 4 (x-nu_m)^2/Gamma^2) and differs from it only in rounding (<~1e-15 relative per bin).
 //   Harvey profiles: per 4096-bin cell the whole background is one degree-8 polynomial in (log x - log x_c) built by
 //   the setup kernel (truncation error < 1e-16 relative, checked there; wider cells in log x fall back to exp per bin).
+//   The kind of a cell's background -- polynomial, exp fallback, no profile -- is chosen where the walk over the tile
+//   enters the cell, and the common-case kernels (GEN = false) hold the group loops once per kind: the loops of the
+//   polynomial cells contain neither the fallback nor a branch on the kind (tamcmc_eval_body.h, TmCellKind).
 //   Sum of log M: mantissas are multiplied and exponents added per bin (v_frexp_*), one log per thread and tile
 //   instead of one per bin.
 //   Reductions: likelihood: wave exchanges (v_permlane*_swap, DPP) -> one LDS slot per wave -> one partial per (chain,

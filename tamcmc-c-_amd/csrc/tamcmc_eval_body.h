@@ -393,8 +393,19 @@ __device__ unsigned long long *g_tm_trace = nullptr;
 #define TM_STAMP(slot) do { } while (0)
 #endif
 
+// a + b as one rounded addition, whatever produced b: kept out of FMA contraction, so that the sum of the weights is the
+// same number in every copy of the group (beside a product in the same block the compiler would fuse the two)
+#pragma clang fp contract(off)
+__device__ __forceinline__ double tm_add_plain(double a, double b) { return a + b; }
+#pragma clang fp contract(fast)
+
 template <int N> struct TmInt { static constexpr int value = N; };
 template <bool B> struct TmBool { static constexpr bool value = B; };
+
+// What the background of a cell is made of (pass 1 of tm_eval_body): the cell's polynomial (the common case), exp per
+// Harvey profile and bin where the polynomial is not valid (TmCellRec::npoly == 0), or white noise alone (nh == 0).
+// TM_CK_ANY: not a kind -- the group decides at run time (generic kernels).
+enum TmCellKind { TM_CK_POLY = 0, TM_CK_EXP = 1, TM_CK_NONE = 2, TM_CK_ANY = 3 };
 
 // The workgroup's work for (chain, tile): pass 1 (model, likelihood partials, weights), in-launch finalize or pass 2.
 // s_w: dynamic LDS for the weights, [TM_TILE_MAXU * TM_UNIT_BINS] doubles (GRAD only).  Called by tamcmc_eval_kernel
@@ -406,8 +417,12 @@ template <bool B> struct TmBool { static constexpr bool value = B; };
 // inside the grid takes the FULL path: no index clamps, no per-bin validity tests, loads at constant offsets from one
 // per-thread pointer; within it a multiplet whose window covers the whole group takes the no-test form of
 // tm_accum_mult.  Only the grid's last, partial unit takes the guarded path.
+// A group is compiled for ONE kind of cell background (TmCellKind: polynomial, exp fallback, no Harvey profile); the walk
+// picks the kind where it enters a cell (a gradient tile meets at most two cells), so the loops of the polynomial cells
+// hold that variant alone -- see the walk below for the loops each kind gets.
 // GEN = false: the common case compiled on its own -- chi(2,2p) likelihood, no Gaussian term (ids 0, 1), no model rows
 // requested; the launcher picks it from the context (TmEvalArgs::generic).  Same arithmetic, fewer live scalars.
+// GEN = true keeps the kind of the cell a run-time branch inside the group (TM_CK_ANY): see the walk.
 template <bool GRAD, bool GEN = true>
 __device__ __forceinline__ void tm_eval_body(const TmEvalArgs &a, const int chain, const int tile, double *s_w)
 {
@@ -460,11 +475,22 @@ __device__ __forceinline__ void tm_eval_body(const TmEvalArgs &a, const int chai
     for (int s_ = 0; s_ < (GRAD ? TM_GSLOTS : 1); s_++) gn_[s_] = 0.0;
     const double wscale = GRAD ? a.wt[2 * chain + 1] : 0.0;
 
-    // one group of KG / 2 units starting at unit u, inside cell `tr`
-    auto group = [&](auto kg_c, auto full_c, const int u, TmCellRecK tr) __attribute__((always_inline)) {
+    // one group of KG / 2 units starting at unit u, inside cell `tr`, whose background is of kind CK (TmCellKind): a
+    // compile-time choice, so that a group holds ONE variant of the background code and of the noise sums (TM_CK_ANY:
+    // both behind run-time branches, as the generic kernels keep them).  Bit 3 of kind_c marks a cold copy: no early loads.
+    auto group = [&](auto kg_c, auto full_c, auto kind_c, const int u, TmCellRecK tr) __attribute__((always_inline)) {
         constexpr int KG = decltype(kg_c)::value;
         constexpr bool FULL = decltype(full_c)::value;
+        constexpr int CK = decltype(kind_c)::value & 7;
+        constexpr bool COLD = (decltype(kind_c)::value & 8) != 0;
+        constexpr bool RT = CK == TM_CK_ANY;
+        const bool HARVEY = RT ? nh > 0 : CK != TM_CK_NONE;     // the chain has Harvey profiles (nh > 0)
+        const bool NPOLY = RT ? (nh > 0 && tr->npoly != 0) : CK == TM_CK_POLY;      // ... and this cell's polynomial is valid (TmCellRec::npoly)
         const int lo = u << TM_UNIT_SHIFT, hi = lo + KG * TM_THREADS;
+        // cold copies: the profile count behind an empty asm, so that the `h < nh` masks of the fallback are made where
+        // they are used instead of being hoisted in front of the cold loop and spilled across it
+        int nhx = nh;
+        if constexpr (COLD) asm volatile("" : "+s"(nhx));
         double x2[KG], acc[KG];
         int bi[KG];
 #pragma unroll
@@ -482,11 +508,11 @@ __device__ __forceinline__ void tm_eval_body(const TmEvalArgs &a, const int chai
         }
         // likelihood-only kernel (registers to spare): log x and y are requested now, so that their latency passes
         // behind the multiplet loop instead of in front of the background / likelihood arithmetic
-        constexpr bool EARLY = FULL && !GRAD;
+        constexpr bool EARLY = FULL && !GRAD && !COLD;
         double lxe[EARLY ? KG : 1], ye[EARLY ? KG : 1];
         if constexpr (EARLY) {
 #pragma unroll
-            for (int k = 0; k < KG; k++) { lxe[k] = (nh > 0) ? lb[(unsigned)bi[k]] : 0.0; ye[k] = yp[(unsigned)bi[k]]; }
+            for (int k = 0; k < KG; k++) { lxe[k] = HARVEY ? lb[(unsigned)bi[k]] : 0.0; ye[k] = yp[(unsigned)bi[k]]; }
         }
         if constexpr (GRAD) {
             for (int jj = 0; jj < nact; jj++) {
@@ -514,12 +540,11 @@ __device__ __forceinline__ void tm_eval_body(const TmEvalArgs &a, const int chai
         // three accumulators per component in pass 2 and sixteen noise sums here, so it takes the four bins of a group
         // in two halves (fewer values live at once: 4 waves per SIMD instead of 3)
         constexpr int KH = GRAD ? 2 : KG;
-        const bool npoly = tr->npoly != 0;
 #pragma unroll
         for (int h0 = 0; h0 < KG; h0 += KH) {
         double hu[TM_MAXH][GRAD ? KH : 1], harg[GRAD ? KH : 1];   // GRAD: u = 1/(1+t) per Harvey and bin (t u = 1 - u), log x per bin
-        bool n0_done = false;
-        if (nh > 0) {
+        const bool n0_done = NPOLY;                           // the polynomial's constant term holds N0
+        if (HARVEY) {
             double dl[KH];
 #pragma unroll
             for (int k = 0; k < KH; k++) {
@@ -530,18 +555,17 @@ __device__ __forceinline__ void tm_eval_body(const TmEvalArgs &a, const int chai
 #endif
                 if constexpr (GRAD) harg[k] = dl[k];
             }
-            if (npoly) {
+            if (NPOLY) {
                 const double lxc = tr->lxc;
                 // whole background (all profiles + white noise) as ONE polynomial: 8 FMAs per bin.  The gradient path
                 // accumulates the moments sum w dl^j instead of per-profile sums (below); the backward kernel turns
                 // them into the per-profile sums with each profile's own series coefficients.
 #pragma unroll
                 for (int k = 0; k < KH; k++) { dl[k] -= lxc; acc[h0 + k] += tm_poly(tr, dl[k]); if constexpr (GRAD) harg[k] = dl[k]; }
-                n0_done = true;
             } else {
 #pragma unroll
                 for (int h = 0; h < TM_MAXH; h++) {
-                    if (h < nh) {
+                    if (h < nhx) {
                         const double Hh = sn->H[h], ph = sn->p[h], lth = sn->lt[h];
 #pragma unroll
                         for (int k = 0; k < KH; k++) {
@@ -621,24 +645,25 @@ __device__ __forceinline__ void tm_eval_body(const TmEvalArgs &a, const int chai
             for (int k = 0; k < KH; k++) {
                 const double wk = wreg[k];
                 s_w[((u - u0) * 2 + h0 + k) * TM_THREADS + tid] = wk;
-                gn_[3 * TM_MAXH] += wk;
+                gn_[3 * TM_MAXH] = tm_add_plain(gn_[3 * TM_MAXH], wk);
 #if defined(TM_ABLATE) && (TM_ABLATE & 512)   // timing-only build: no weight moments
                 if (false) {
 #else
-                if (nh > 0 && npoly) {
+                if (NPOLY) {
 #endif
                     // moments of the weights about the cell centre: slot j-1 <- sum w dl^j, j = 1..TM_HSER-1
+                    // (each power is rounded for the next one, and added fused: w dl^j = fma(dl, w dl^(j-1), sum))
                     double q = wk;
 #pragma unroll
-                    for (int j = 0; j < TM_HSER - 1; j++) { q *= harg[k]; gn_[j] += q; }
-                } else if (nh > 0) {
+                    for (int j = 0; j < TM_HSER - 1; j++) { gn_[j] = __builtin_fma(harg[k], q, gn_[j]); q *= harg[k]; }
+                } else if (HARVEY) {
 #pragma unroll
                     for (int h = 0; h < TM_MAXH; h++) {
-                        if (h < nh) {
+                        if (h < nhx) {
                             const double wu = wk * hu[h][k];
                             const double tu2 = wu * (1.0 - hu[h][k]);   // t u = 1 - u
-                            gn_[3 * h] += wu;
-                            gn_[3 * h + 1] += tu2;
+                            gn_[3 * h] = __builtin_fma(wk, hu[h][k], gn_[3 * h]);
+                            gn_[3 * h + 1] = __builtin_fma(wu, 1.0 - hu[h][k], gn_[3 * h + 1]);
                             gn_[3 * h + 2] = __builtin_fma(tu2, sn->lt[h] + harg[k], gn_[3 * h + 2]);
                         }
                     }
@@ -658,20 +683,24 @@ __device__ __forceinline__ void tm_eval_body(const TmEvalArgs &a, const int chai
     };
 
     // GRAD: the noise partial sums of the cell just finished -> gnoise[chain][tile][part]
-    auto flush_noise = [&](const int part) __attribute__((always_inline)) {
+    auto flush_noise = [&](const int part, auto cold_c) __attribute__((always_inline)) {
         if constexpr (GRAD) {
+            // the cold loop's copy: lane and thread index behind an empty asm, so that its lane masks are made here, once
+            // per flush, instead of being hoisted in front of that loop and spilled across it (8 SGPRs)
+            int ln = lane, td = tid;
+            if constexpr (decltype(cold_c)::value) asm volatile("" : "+v"(ln), "+v"(td));
             static_assert(TM_NSLOTS == 16, "butterfly below assumes 16 noise slots");
-            TmBfly<TM_NSLOTS, 32>::run(gn_, lane);
+            TmBfly<TM_NSLOTS, 32>::run(gn_, ln);
             bool valid = true;
-            const int slot = TmBfly<TM_NSLOTS, 32>::slot_of(lane, valid);
+            const int slot = TmBfly<TM_NSLOTS, 32>::slot_of(ln, valid);
             double *red = s_red[1][wave];
-            if ((lane & 3) == 0) red[slot] = gn_[0];
+            if ((ln & 3) == 0) red[slot] = gn_[0];
             __syncthreads();
-            if (tid < TM_NSLOTS) {
+            if (td < TM_NSLOTS) {
                 double t = 0.0;
 #pragma unroll
-                for (int wv = 0; wv < TM_WAVES; wv++) t += s_red[1][wv][tid];
-                a.gnoise[(((size_t)chain * a.tiles + tile) * 2 + part) * TM_NSLOTS + tid] = t;
+                for (int wv = 0; wv < TM_WAVES; wv++) t += s_red[1][wv][td];
+                a.gnoise[(((size_t)chain * a.tiles + tile) * 2 + part) * TM_NSLOTS + td] = t;
             }
             __syncthreads();
 #pragma unroll
@@ -680,32 +709,89 @@ __device__ __forceinline__ void tm_eval_body(const TmEvalArgs &a, const int chai
     };
 
     {
-        // The walk over the tile's units.  The hot loop is the run of PAIRS (two units: four bins per thread), aligned
-        // to even units so that a pair never straddles two cells; it holds the only copy of the pair code, and nothing
-        // else updates the accumulators inside it (a second variant behind a branch in the same loop costs ~40
-        // registers in copies where the two meet).  An odd first unit is taken alone before the loop; what is left after
-        // it -- an odd last unit, and at the end of the grid the partial unit -- alone after it.
-        const int cell0 = u0 >> TM_CELL_SHIFT;
-        int cur_cell = cell0;
-        auto cell_of = [&](const int uu) __attribute__((always_inline)) {
-            const int ce = uu >> TM_CELL_SHIFT;
-            if (GRAD && ce != cur_cell) { flush_noise(0); cur_cell = ce; }   // at most once per tile (TM_TILE_MAXU <= TM_CELL_UNITS)
-            return cells + ce;
+        // The walk over the tile's units, cell by cell: the part [u, ue) of the tile that lies in one cell has one kind of
+        // background (TmCellKind), chosen where the walk enters the cell.  Within it the hot loop is the run of PAIRS (two
+        // units: four bins per thread), aligned to even units; cells begin on even units, so a pair never straddles two
+        // cells and the groups are those of one walk over the whole tile.  An odd first unit is taken alone before the
+        // pair loop; what is left after it -- an odd last unit, and at the end of the grid the partial unit -- alone
+        // after it.  A loop holds ONE variant of the group: a second one behind a branch in the same loop costs registers
+        // in copies where the two meet (~40 for the pair code; 9 copies of noise sums per bin for the two backgrounds).
+        auto walk = [&](auto kind_c, int u, const int ue, TmCellRecK tr) __attribute__((always_inline)) {
+            if ((u & 1) && u < ue && ((u + 1) << TM_UNIT_SHIFT) <= a.Nx) { group(TmInt<2>(), TmBool<true>(), kind_c, u, tr); u += 1; }
+#pragma unroll 1
+            for (; u + 2 <= ue && ((u + 2) << TM_UNIT_SHIFT) <= a.Nx; u += 2) group(TmInt<4>(), TmBool<true>(), kind_c, u, tr);
+#pragma unroll 1
+            for (; u < ue; u += 1) {
+                if (((u + 1) << TM_UNIT_SHIFT) <= a.Nx) group(TmInt<2>(), TmBool<true>(), kind_c, u, tr);
+                else                                    group(TmInt<2>(), TmBool<false>(), kind_c, u, tr);
+            }
         };
+        // the same units one at a time (cold cells): a pair is its two units in turn -- the same sums in the same order,
+        // the mantissa product rescaled (exactly: by powers of two) twice as often
+        auto walk_single = [&](auto kind_c, int u, const int ue, TmCellRecK tr) __attribute__((always_inline)) {
+#pragma unroll 1
+            for (; u < ue; u += 1) {
+                if (((u + 1) << TM_UNIT_SHIFT) <= a.Nx) group(TmInt<2>(), TmBool<true>(), kind_c, u, tr);
+                else                                    group(TmInt<2>(), TmBool<false>(), kind_c, u, tr);
+            }
+        };
+        const int cell0 = u0 >> TM_CELL_SHIFT;
+        int ce = cell0;
         int u = u0;
 #if defined(TM_ABLATE) && (TM_ABLATE & 256)   // timing-only build: no pass 1
         u = u1;
 #endif
-        if ((u & 1) && u < u1 && ((u + 1) << TM_UNIT_SHIFT) <= a.Nx) { TmCellRecK tr = cell_of(u); group(TmInt<2>(), TmBool<true>(), u, tr); u += 1; }
+        if constexpr (GEN) {
+            // The generic kernels sit at their register budgets (128 / 72 VGPRs) with one copy of the three loops and have
+            // no room for a second, nor for a loop over the cells around them: they walk the tile in one go and keep the
+            // kind a run-time branch inside the group (TM_CK_ANY).
+            int cur_cell = cell0;
+            auto cell_of = [&](const int uu) __attribute__((always_inline)) {
+                const int c = uu >> TM_CELL_SHIFT;
+                if (GRAD && c != cur_cell) { flush_noise(0, TmBool<false>()); cur_cell = c; }   // at most once per tile (TM_TILE_MAXU <= TM_CELL_UNITS)
+                return cells + c;
+            };
+            if ((u & 1) && u < u1 && ((u + 1) << TM_UNIT_SHIFT) <= a.Nx) { TmCellRecK tr = cell_of(u); group(TmInt<2>(), TmBool<true>(), TmInt<TM_CK_ANY>(), u, tr); u += 1; }
 #pragma unroll 1
-        for (; u + 2 <= u1 && ((u + 2) << TM_UNIT_SHIFT) <= a.Nx; u += 2) { TmCellRecK tr = cell_of(u); group(TmInt<4>(), TmBool<true>(), u, tr); }
+            for (; u + 2 <= u1 && ((u + 2) << TM_UNIT_SHIFT) <= a.Nx; u += 2) { TmCellRecK tr = cell_of(u); group(TmInt<4>(), TmBool<true>(), TmInt<TM_CK_ANY>(), u, tr); }
 #pragma unroll 1
-        for (; u < u1; u += 1) {
-            TmCellRecK tr = cell_of(u);
-            if (((u + 1) << TM_UNIT_SHIFT) <= a.Nx) group(TmInt<2>(), TmBool<true>(), u, tr);
-            else                                    group(TmInt<2>(), TmBool<false>(), u, tr);
+            for (; u < u1; u += 1) {
+                TmCellRecK tr = cell_of(u);
+                if (((u + 1) << TM_UNIT_SHIFT) <= a.Nx) group(TmInt<2>(), TmBool<true>(), TmInt<TM_CK_ANY>(), u, tr);
+                else                                    group(TmInt<2>(), TmBool<false>(), TmInt<TM_CK_ANY>(), u, tr);
+            }
+            ce = cur_cell + 1;
+        } else {
+            // The polynomial cells at the head of the tile -- in the common case all of it -- in a loop of their own,
+            // with the three loops of `walk`: neither the exp fallback nor a branch on the kind is in it, none of the
+            // fallback's scalars (sn->H/p/lt, the constants of exp) is live in it, and acc[] and the noise sums are
+            // updated in place.
+#pragma unroll 1
+            for (; u < u1; ce++) {
+                TmCellRecK tr = cells + ce;
+                if (nh <= 0 || tr->npoly == 0) break;
+                if (GRAD && ce != cell0) flush_noise(0, TmBool<false>());
+                const int cend = (ce + 1) << TM_CELL_SHIFT;
+                const int ue = cend < u1 ? cend : u1;
+                walk(TmInt<TM_CK_POLY>(), u, ue, tr);
+                u = ue;
+            }
+            // From the first cell of another kind to the end of the tile (cold): every kind, each with its own loop, one
+            // unit at a time and without the early loads.  With pair loops as well these copies took the gradient
+            // kernel to 128 VGPRs plus 2 spilled and the likelihood kernel to 75.
+#pragma unroll 1
+            for (; u < u1; ce++) {
+                TmCellRecK tr = cells + ce;
+                if (GRAD && ce != cell0) flush_noise(0, TmBool<true>());
+                const int cend = (ce + 1) << TM_CELL_SHIFT;
+                const int ue = cend < u1 ? cend : u1;
+                if (nh <= 0)             walk_single(TmInt<8 + TM_CK_NONE>(), u, ue, tr);
+                else if (tr->npoly != 0) walk_single(TmInt<8 + TM_CK_POLY>(), u, ue, tr);
+                else                     walk_single(TmInt<8 + TM_CK_EXP>(), u, ue, tr);
+                u = ue;
+            }
         }
-        if (GRAD) flush_noise(cur_cell - cell0);
+        if (GRAD) flush_noise(ce > cell0 + 1 ? 1 : 0, TmBool<false>());   // the part of the tile's last cell
     }
     TM_STAMP(1);
     // tile partials: S1 = sum y/M (or the chi-square sum), and sum log M as (mantissa product, exponent sum)
