@@ -471,7 +471,58 @@ int tamcmc_group_members(const tamcmc_group *g, int32_t *n_members, int32_t *Npa
  *                pushes fold as before.  tamcmc_summary_reset also leaves the mode; tamcmc_summary_destroy works in any.
  *                _result, _acov and _end outside the mode return TAMCMC_E_INVALID.
  *   profile / kernel_time in ESS mode: the centre and lag kernels of every block together (one event pair per block), and
- *   the finish kernel of every ess_result. */
+ *   the finish kernel of every ess_result.
+ *
+ * ESS AND MCSE OF THE CREDIBLE-BAND EDGES (band ESS mode): the quantiles above are Monte-Carlo estimates too, and the ESS of
+ * mean_M does not say how well they are determined: a chain worth 2000 independent draws for the mean can be worth 150 for
+ * its 2.5 % edge.  Following Vehtari et al. (2021), the ESS of a quantile estimate is the ESS of the indicator series
+ * I(M_t <= q) at the quantile's value (their tail-ESS is the smaller of the two at the 5 % and 95 % values).  A fifth mode
+ * beside fold, quantile, LOO and ESS mode: after the fold pass the caller pushes the SAME samples once more, in the same order.
+ * The thresholds are whatever the caller hands in -- normally the resolved lo == hi of the quantile selection -- and the mode
+ * does not depend on quantile mode.  An indicator is 0 or 1, so everything on the device up to one conversion is exact
+ * integer arithmetic.
+ *   Definition, per threshold j (K arrays of Nx doubles, 1 <= K <= TAMCMC_SUMMARY_MAX_QUANTILES) and bin i, with n = n_used and
+ *   t = 0 ... n - 1 counting the accepted samples in push order (a rejected sample is skipped and counted and does not advance t):
+ *     1. Series: b_t = (M_it <= thr_ji), the IEEE comparison of doubles: -0 = +0, and a NaN threshold gives 0 throughout.
+ *     2. Lag limit: L as in ESS mode, from max_lag and n.
+ *     3. Counts, exact integers: N = sum b_t; C_k = sum_{t=k}^{n-1} b_t b_{t-k}, k = 0 ... L; H_k = sum_{t<k} b_t (the first k
+ *        samples); T_k = sum_{t>=n-k} b_t (the last k).
+ *     4. Centred lag products times n^2, still exact: E_k = n^2 C_k - n N (2N - H_k - T_k) + (n - k) N^2
+ *        = n^2 sum_{t=k}^{n-1} (b_t - N/n)(b_{t-k} - N/n), held in int64_t (|E_k| < 2^62 for n < 2^20); E_0 = n N (n - N).
+ *     5. Finish: A_k = (double)E_k, one rounding, then step 4 of ESS mode on A_0 ... A_L as it stands: the same rule, the same
+ *        1 / log10(n) from the host, the same meaning of cut.  A constant series (N = 0 or N = n) has A_0 = 0: tau = ess = NaN,
+ *        cut = 0.
+ *     6. Per (j, bin), at [j * Nx + i]: count_le = N; ess, tau, cut; p_hat = (double)N / (double)n;
+ *        mcse_p = sqrt(p_hat * (1.0 - p_hat) / ess), on the host in that order, without contraction.
+ *     7. Totals, per threshold, on the host in bin order, the first bin winning a tie and a NaN skipped (a bin of -1: every
+ *        value was NaN): n_used, n_rejected, lag = L, n_thresholds = K; min_ess[j] with bin_min_ess[j]; n_truncated[j] = bins
+ *        with cut = L + 1; n_constant[j] = bins with N = 0 or N = n.  Entries j >= K: NaN, -1, 0, 0.
+ *   bandess_begin   freezes the fold state as ess_begin does, copies the thresholds (thr[j * Nx + i]), resolves L (*lag_used, may
+ *                be NULL) and allocates on the device: the series as ONE BIT per sample -- per threshold and bin a ring of
+ *                ceil(L / 64) + 2 64-bit words (the chunk under way and the L bits before it) and the first ceil(L / 64) words
+ *                for H_k --, (L + 1) 32-bit counters per threshold and bin, one column of L + 1 doubles per bin that the
+ *                thresholds share at the finish, and 28 K bytes per bin of thresholds and results:
+ *                ((4 K + 8) (L + 1) + 16 K (ceil(L / 64) + 1) + 28 K) Nx + 32 bytes in all -- 0.54 GB for Nx = 1e5 at L = 255 and
+ *                K = 3.  TAMCMC_E_NOMEM when that fails, and the object stays as it was.  Refused with TAMCMC_E_INVALID: what
+ *                ess_begin refuses (n_used < 4, max_lag outside 0 ... TAMCMC_SUMMARY_ESS_MAX_LAG, any mode already on, a batch in
+ *                flight or armed), K outside 1 ... 8, NULL thr, n_used >= 2^20 (thin the chain).  While the mode is on,
+ *                quantiles_begin, loo_begin, ess_begin, predictive_enable, window_enable and scan_enable are refused.
+ *   While the mode is on, push and push_device evaluate the rows as before and hand out the same logL and status bits, but
+ *   feed the band kernels (tamcmc_bandess.hip) instead of the fold kernel; tamcmc_summary_result keeps returning the frozen fold
+ *   results, and the predictive, window and scan states are not touched.  Integer sums do not depend on the order of their
+ *   terms: every result is bit for bit independent of block_chains and of how the pass is split over pushes.
+ *   bandess_result  totals and six arrays of K x Nx on the host, any of them may be NULL.  If the pass did not see exactly the
+ *                fold pass's accepted and rejected counts: TAMCMC_E_INVALID, the pass is discarded and may be repeated.  May
+ *                be called again without another pass.
+ *   bandess_counts  of a complete pass and threshold j: C_k (they fit int32_t) and E_k, each (L + 1) x Nx on the host, lag k of
+ *                bin i at [k * Nx + i]; either may be NULL.  TAMCMC_E_INVALID for an incomplete pass (which it leaves alone)
+ *                and for j outside 0 ... K - 1.
+ *   bandess_end     frees the mode's memory and goes back to fold mode.  tamcmc_summary_reset also leaves the mode;
+ *                tamcmc_summary_destroy works in any.  _result, _counts and _end outside the mode return TAMCMC_E_INVALID.
+ *   profile / kernel_time in the mode: the pack and lag kernels of every block together (one event pair per block), and the
+ *   finish kernel of every bandess_result (one launch per threshold).
+ *   Not here: the MCSE of a quantile on the value scale, which needs order statistics at ranks that differ from bin to bin, and
+ *   rank-normalised bulk ESS, which needs per-bin ranks of every sample. */
 typedef struct tamcmc_summary tamcmc_summary;
 typedef struct {
     int64_t n_used, n_rejected;
@@ -557,6 +608,19 @@ int tamcmc_summary_ess_result(tamcmc_summary *s, tamcmc_summary_ess_totals *tota
                               double *ess_l, double *r_eff, int32_t *cut_l);
 int tamcmc_summary_ess_acov(tamcmc_summary *s, int32_t which, double *acov);
 int tamcmc_summary_ess_end(tamcmc_summary *s);
+typedef struct {
+    int64_t n_used, n_rejected, lag, n_thresholds;
+    double  min_ess[TAMCMC_SUMMARY_MAX_QUANTILES];
+    int64_t bin_min_ess[TAMCMC_SUMMARY_MAX_QUANTILES],
+            n_truncated[TAMCMC_SUMMARY_MAX_QUANTILES],
+            n_constant[TAMCMC_SUMMARY_MAX_QUANTILES];
+} tamcmc_summary_bandess_totals;
+int tamcmc_summary_bandess_begin(tamcmc_summary *s, int32_t K, const double *thr, int32_t max_lag, int32_t *lag_used);
+int tamcmc_summary_bandess_result(tamcmc_summary *s, tamcmc_summary_bandess_totals *totals,
+                                  int32_t *count_le, double *p_hat, double *ess, double *tau,
+                                  double *mcse_p, int32_t *cut);
+int tamcmc_summary_bandess_counts(tamcmc_summary *s, int32_t j, int32_t *C, int64_t *E);
+int tamcmc_summary_bandess_end(tamcmc_summary *s);
 
 /* MONTE-CARLO NULL OF THE SCAN: the law of the sliding-window scan's extremes under a correctly specified model, and the
  * lines and p-values that follow from it.  The scan's default line log(0.01 W / Nx) is Bonferroni over Nx / W independent

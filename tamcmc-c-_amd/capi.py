@@ -37,6 +37,7 @@ EXPORTS = [
     "tamcmc_summary_window_enable", "tamcmc_summary_window_result", "tamcmc_summary_window_kernel_time",
     "tamcmc_summary_scan_enable", "tamcmc_summary_scan_result", "tamcmc_summary_scan_regions", "tamcmc_summary_scan_kernel_time",
     "tamcmc_summary_ess_begin", "tamcmc_summary_ess_result", "tamcmc_summary_ess_acov", "tamcmc_summary_ess_end",
+    "tamcmc_summary_bandess_begin", "tamcmc_summary_bandess_result", "tamcmc_summary_bandess_counts", "tamcmc_summary_bandess_end",
     "tamcmc_scan_null_create", "tamcmc_scan_null_run", "tamcmc_scan_null_replicates", "tamcmc_scan_null_result",
     "tamcmc_scan_null_line", "tamcmc_scan_null_pvalue", "tamcmc_scan_null_variates", "tamcmc_scan_null_profile",
     "tamcmc_scan_null_kernel_time", "tamcmc_scan_null_destroy",
@@ -90,6 +91,16 @@ class SummaryEssTotals(C.Structure):
                 ("min_ess_M", C.c_double), ("min_ess_l", C.c_double), ("max_rhat", C.c_double),
                 ("bin_min_ess_M", C.c_int64), ("bin_min_ess_l", C.c_int64), ("bin_max_rhat", C.c_int64),
                 ("n_truncated_M", C.c_int64), ("n_truncated_l", C.c_int64), ("n_rhat_high", C.c_int64)]
+
+
+MAX_QUANTILES = 8       # TAMCMC_SUMMARY_MAX_QUANTILES
+
+
+class SummaryBandEssTotals(C.Structure):
+    """tamcmc_summary_bandess_totals"""
+    _fields_ = [("n_used", C.c_int64), ("n_rejected", C.c_int64), ("lag", C.c_int64), ("n_thresholds", C.c_int64),
+                ("min_ess", C.c_double * MAX_QUANTILES), ("bin_min_ess", C.c_int64 * MAX_QUANTILES),
+                ("n_truncated", C.c_int64 * MAX_QUANTILES), ("n_constant", C.c_int64 * MAX_QUANTILES)]
 
 
 class AccelError(RuntimeError):
@@ -173,6 +184,10 @@ def load_library():
     lib.tamcmc_summary_ess_result.argtypes = [vp, C.POINTER(SummaryEssTotals), dp, dp, dp, dp, ip, dp, dp, ip]
     lib.tamcmc_summary_ess_acov.argtypes = [vp, C.c_int32, dp]
     lib.tamcmc_summary_ess_end.argtypes = [vp]
+    lib.tamcmc_summary_bandess_begin.argtypes = [vp, C.c_int32, dp, C.c_int32, ip]
+    lib.tamcmc_summary_bandess_result.argtypes = [vp, C.POINTER(SummaryBandEssTotals), ip, dp, dp, dp, dp, ip]
+    lib.tamcmc_summary_bandess_counts.argtypes = [vp, C.c_int32, ip, C.POINTER(C.c_int64)]
+    lib.tamcmc_summary_bandess_end.argtypes = [vp]
     lp = C.POINTER(C.c_int64)
     lib.tamcmc_scan_null_create.argtypes = [C.POINTER(vp), C.c_int, C.c_int, C.c_double, C.c_int64, C.c_int32, ip, C.c_uint64, C.c_int64]
     lib.tamcmc_scan_null_run.argtypes = [vp, C.c_int64]
@@ -493,7 +508,8 @@ class Summary:
     bit for bit, on block_chains or on how the rows are split over pushes.  quantiles() gives the exact per-bin quantiles
     of the model (credible bands) by pushing the same rows again a few times; loo() gives PSIS-LOO (elpd_loo and the
     Pareto k-hat per bin) by pushing them once more, and ess() the effective sample size, Monte-Carlo standard error and
-    split R-hat per bin by pushing them once more in the same order.  With predictive=True every fold pass also accumulates the
+    split R-hat per bin by pushing them once more in the same order; band_ess() the quantiles together with the effective sample
+    size of each of them (of the indicator M <= quantile), by one more pass after the selection.  With predictive=True every fold pass also accumulates the
     posterior predictive check (predictive_result(): PIT and both log tail probabilities per bin), and with window=W or
     window=(W, first) the same check over disjoint windows of W bins (window_result()); with scan=W or scan=(W0, W1, ...) the
     windowed check at every start position for up to eight widths at once (scan_result(k), scan_regions(k)).  The Accel cannot be closed while
@@ -552,6 +568,7 @@ class Summary:
         self._nq = 0                                            # reset leaves quantile mode
         self._loo = False                                       # and LOO mode
         self._ess_lag = 0                                       # and ESS mode
+        self._band = None                                       # and band ESS mode
 
     def profile(self, enable=True):
         self._check(self._lib.tamcmc_summary_profile(self._s, int(enable)), "tamcmc_summary_profile")
@@ -824,6 +841,67 @@ class Summary:
         finally:
             if getattr(self, "_ess_lag", 0):
                 self.ess_end()
+
+    # ---- ESS and MCSE of the credible-band edges: the indicator M <= threshold, one more pass in the same order ----
+    BANDESS_ARRAYS = ("count_le", "p_hat", "ess", "tau", "mcse_p", "cut")
+    BANDESS_TOTALS = ("n_used", "n_rejected", "lag", "n_thresholds", "min_ess", "bin_min_ess", "n_truncated", "n_constant")
+
+    def bandess_begin(self, thr, max_lag=0):
+        """Enters band ESS mode for the thresholds thr, (K, Nx) or (Nx,) doubles, 1 <= K <= 8, with lags up to max_lag (0 = the
+        library's default, 255); returns the lag limit L in use.  From here on push / push_device feed the band kernels: push
+        the same rows again in the same order, then bandess_result()."""
+        thr = _c64(np.atleast_2d(thr))
+        if thr.ndim != 2 or thr.shape[1] != self.accel.Nx:
+            raise ValueError(f"thr must be (K, {self.accel.Nx})")
+        lag = C.c_int32(0)
+        self._check(self._lib.tamcmc_summary_bandess_begin(self._s, thr.shape[0], _dptr(thr), int(max_lag), C.byref(lag)),
+                    "tamcmc_summary_bandess_begin")
+        self._band = (int(thr.shape[0]), int(lag.value))
+        return int(lag.value)
+
+    def bandess_result(self):
+        """dict: count_le, cut (K x Nx int32), p_hat, ess, tau, mcse_p (K x Nx doubles) and the totals n_used, n_rejected, lag,
+        n_thresholds, and per threshold (K values each) min_ess, bin_min_ess, n_truncated, n_constant."""
+        K = (getattr(self, "_band", None) or (MAX_QUANTILES, 0))[0]       # (outside the mode the library refuses before it writes)
+        out = {k: np.empty((K, self.accel.Nx), dtype=np.int32 if k in ("count_le", "cut") else np.float64) for k in self.BANDESS_ARRAYS}
+        t = SummaryBandEssTotals()
+        args = [(_iptr if k in ("count_le", "cut") else _dptr)(out[k]) for k in self.BANDESS_ARRAYS]
+        self._check(self._lib.tamcmc_summary_bandess_result(self._s, C.byref(t), *args), "tamcmc_summary_bandess_result")
+        out.update(n_used=int(t.n_used), n_rejected=int(t.n_rejected), lag=int(t.lag), n_thresholds=int(t.n_thresholds),
+                   min_ess=np.array(list(t.min_ess)[:K]), bin_min_ess=np.array(list(t.bin_min_ess)[:K], dtype=np.int64),
+                   n_truncated=np.array(list(t.n_truncated)[:K], dtype=np.int64), n_constant=np.array(list(t.n_constant)[:K], dtype=np.int64))
+        return out
+
+    def bandess_counts(self, j):
+        """(C, E) of threshold j after a complete pass: the lag counts C_k (int32) and the centred lag products times n^2, E_k
+        (int64), each (L + 1, Nx)."""
+        L = (getattr(self, "_band", None) or (0, 0))[1]
+        Ck = np.empty((L + 1, self.accel.Nx), dtype=np.int32)
+        Ek = np.empty((L + 1, self.accel.Nx), dtype=np.int64)
+        self._check(self._lib.tamcmc_summary_bandess_counts(self._s, int(j), _iptr(Ck), Ek.ctypes.data_as(C.POINTER(C.c_int64))),
+                    "tamcmc_summary_bandess_counts")
+        return Ck, Ek
+
+    def bandess_end(self):
+        self._check(self._lib.tamcmc_summary_bandess_end(self._s), "tamcmc_summary_bandess_end")
+        self._band = None
+
+    def band_ess(self, params, q, max_lag=0, bits_per_pass=0):
+        """The exact quantiles q of the model over the rows already pushed (`params` being those rows in the same order) and
+        how well each is determined: quantiles() to exactness, then one band ESS pass at the values found.  Returns the
+        dicts of quantiles() and bandess_result() merged, plus tail_ess (Nx): per bin the smaller of the ESS at the lowest and
+        at the highest of q, NaN if either is.  Always leaves the mode."""
+        r = self.quantiles(params, q, bits_per_pass)
+        self.bandess_begin(r["lo"], max_lag)
+        try:
+            self.push(params)
+            r.update(self.bandess_result())
+        finally:
+            if getattr(self, "_band", None):
+                self.bandess_end()
+        lo, hi = int(np.argmin(r["q"])), int(np.argmax(r["q"]))
+        r["tail_ess"] = np.minimum(r["ess"][lo], r["ess"][hi])              # (np.minimum propagates NaN)
+        return r
 
     def close(self):
         if getattr(self, "_s", None) is not None and self._s.value:

@@ -10,11 +10,12 @@
 // With the sliding-window scan enabled (tamcmc_summary_scan_*, tamcmc_scan.h) a stage 5 follows: the sums, tails and fold
 // kernels of tamcmc_scan.hip per chunk of the block, on the same rows.
 // In ESS mode (tamcmc_summary_ess_*, tamcmc_ess.h) stage 2 is the centre and lag kernels of tamcmc_ess.hip, once per chunk of
-// the block.
+// the block; in band ESS mode (tamcmc_summary_bandess_*, tamcmc_bandess.h) the pack and lag kernels of tamcmc_bandess.hip, likewise.
 #include <algorithm>
 #include <cmath>
 #include <new>
 
+#include "tamcmc_bandess.h"
 #include "tamcmc_ess.h"
 #include "tamcmc_host.h"
 #include "tamcmc_loo.h"
@@ -75,6 +76,19 @@ struct TmEssMode : TmMode {
     int32_t *cut = nullptr;
 };
 
+// Band ESS mode: the thresholds, the bit-packed series (ring and head), the integer lag counts and the results of the pass
+// on the device, and what the host remembers of the fold pass.
+struct TmBandMode : TmMode {
+    int K = 0, L = 0, RW = 0, HW = 0;
+    uint32_t *d_C = nullptr;             // [K][L + 1][Nx]
+    uint64_t *d_bits = nullptr;          // one allocation: ring[K][RW][Nx] | head[K][HW][Nx]
+    uint64_t *head = nullptr;
+    void *d_work = nullptr;              // [L + 1][Nx] of 8 bytes: the finish kernel's A_k or E_k of one threshold
+    char *d_state = nullptr;             // one allocation: thr[K][Nx] | tau[K][Nx] | ess[K][Nx] | cnt[2][2] | cut[K][Nx]
+    double *thr = nullptr, *tau = nullptr, *ess = nullptr;
+    int32_t *cut = nullptr;
+};
+
 // The predictive check: a setting of the object (on from _enable until destroy), not a mode.
 struct TmPredictive {
     bool on = false;
@@ -128,6 +142,7 @@ struct tamcmc_summary {
     TmQuantMode q;
     TmLooMode loo;
     TmEssMode ess;
+    TmBandMode band;
     TmPredictive pred;
     TmWindow win;
     TmScan scan;
@@ -161,7 +176,8 @@ static const TmMode *active_mode(const tamcmc_summary *s)
 {
     if (s->q.on) return &s->q;
     if (s->loo.on) return &s->loo;
-    return s->ess.on ? &s->ess : nullptr;
+    if (s->ess.on) return &s->ess;
+    return s->band.on ? &s->band : nullptr;
 }
 
 // the pass under way saw exactly the fold pass's samples (the stream must be idle)
@@ -304,6 +320,54 @@ static void ess_free(tamcmc_summary *s)
     s->ess = TmEssMode();
 }
 
+static TmBandArgs band_args(const tamcmc_summary *s)
+{
+    const TmBandMode &m = s->band;
+    TmBandArgs a{};
+    a.thr = m.thr; a.ring = m.d_bits; a.head = m.head; a.C = m.d_C; a.work = m.d_work; a.tau = m.tau; a.ess = m.ess; a.cut = m.cut;
+    a.cnt_in = m.cnt.in(); a.cnt_out = m.cnt.out();
+    a.n = m.n_used;
+    a.Nx = s->c->L.Nx; a.L = m.L; a.RW = m.RW; a.HW = m.HW; a.K = m.K;
+    a.tau_floor = 1.0 / std::log10((double)m.n_used);
+    return a;
+}
+
+// stage 2 of a block in band ESS mode: per chunk of the block the pack kernel and the lag kernel in the fold kernel's place
+static int band_block(tamcmc_summary *s, int n, const int32_t *d_status)
+{
+    tamcmc_ctx *c = s->c;
+    return timed_launch(s, s->timer, "summary bandess chunk", [&] {
+        int hr = 0;
+        for (int k = 0; k < n && hr == 0; k += TM_ESS_CHUNK) {
+            TmBandArgs a = band_args(s);
+            a.rows = s->d_model + (size_t)k * (size_t)c->L.Nx; a.status = d_status + k;
+            a.B = n - k < TM_ESS_CHUNK ? n - k : TM_ESS_CHUNK;
+            hr = tm_launch_bandess_chunk(a, c->stream);
+            if (hr == 0) s->band.cnt.flip();                // per chunk, as ess_block
+        }
+        return hr;
+    });
+}
+
+static size_t band_bits_bytes(const TmBandMode &m, size_t nx) { return (size_t)m.K * (size_t)(m.RW + m.HW) * nx * sizeof(uint64_t); }
+
+// a pass starts from empty counts and lag counts; the bits are cleared too, so that no launch reads a word never written
+static int band_pass_clear(tamcmc_summary *s)
+{
+    TmBandMode &m = s->band;
+    const size_t nx = (size_t)s->c->L.Nx;
+    TM_HIP(hipMemsetAsync(m.d_C, 0, (size_t)m.K * (size_t)(m.L + 1) * nx * sizeof(uint32_t), s->c->stream));
+    TM_HIP(hipMemsetAsync(m.d_bits, 0, band_bits_bytes(m, nx), s->c->stream));
+    return m.cnt.clear(s->c->stream);
+}
+
+// the stream must be idle
+static void band_free(tamcmc_summary *s)
+{
+    (void)hipFree(s->band.d_state); (void)hipFree(s->band.d_C); (void)hipFree(s->band.d_bits); (void)hipFree(s->band.d_work);
+    s->band = TmBandMode();
+}
+
 // stage 3 of a fold-mode block: the predictive kernel on the same rows, counting on from the pair the fold launch read
 static int predictive_block(tamcmc_summary *s, int n, const int32_t *d_status, const long long *cnt_in)
 {
@@ -357,6 +421,7 @@ static int summary_block(tamcmc_summary *s, int n, const double *d_params, doubl
     if (s->q.on) return quantile_block(s, n, d_status);
     if (s->loo.on) return loo_block(s, n, d_status);
     if (s->ess.on) return ess_block(s, n, d_status);
+    if (s->band.on) return band_block(s, n, d_status);
     TmSummaryArgs a{};
     a.rows = s->d_model; a.status = d_status; a.y = c->d_y; a.isig2 = c->d_isig2; a.state = s->d_state;
     a.cnt_in = s->cnt.in(); a.cnt_out = s->cnt.out();
@@ -429,6 +494,7 @@ extern "C" int tamcmc_summary_destroy(tamcmc_summary *s)
     quantile_free(s);
     loo_free(s);
     ess_free(s);
+    band_free(s);
     (void)hipFree(s->d_model); (void)hipFree(s->d_state); (void)hipFree(s->cnt.d); (void)hipFree(s->d_rows);
     (void)hipFree(s->d_T); (void)hipFree(s->d_logL); (void)hipFree(s->d_status); (void)hipFree(s->pred.d_state);
     (void)hipFree(s->win.d_state); (void)hipFree(s->win.d_scratch);
@@ -450,11 +516,12 @@ extern "C" int tamcmc_summary_reset(tamcmc_summary *s)
     if (!s || s->c->in_flight || s->c->armed) return TAMCMC_E_INVALID;
     tamcmc_ctx *c = s->c;
     TM_HIP(hipSetDevice(c->device));
-    if (active_mode(s)) {                           // reset leaves quantile mode, LOO mode and ESS mode
+    if (active_mode(s)) {                           // reset leaves quantile mode, LOO mode, ESS mode and band ESS mode
         TM_HIP(tm_ctx_stream_sync(c));
         quantile_free(s);
         loo_free(s);
         ess_free(s);
+        band_free(s);
     }
     TM_HIP(tm_ctx_settle(c));
     c->enq_seq++;
@@ -1238,5 +1305,141 @@ extern "C" int tamcmc_summary_ess_end(tamcmc_summary *s)
     if (!s || !s->ess.on) return TAMCMC_E_INVALID;
     const int rc = summary_enter(s);
     if (rc == TAMCMC_OK) ess_free(s);
+    return rc;
+}
+
+// ---- ESS and MCSE of the credible-band edges (tamcmc_bandess.h) ----
+
+extern "C" int tamcmc_summary_bandess_begin(tamcmc_summary *s, int32_t K, const double *thr, int32_t max_lag, int32_t *lag_used)
+{
+    if (!s || K < 1 || K > TAMCMC_SUMMARY_MAX_QUANTILES || !thr || max_lag < 0 || max_lag > TAMCMC_SUMMARY_ESS_MAX_LAG) return TAMCMC_E_INVALID;
+    tamcmc_ctx *c = s->c;
+    if (active_mode(s)) return TAMCMC_E_INVALID;
+    long long cnt[2] = {0, 0};
+    const int rc = summary_enter(s, cnt);
+    if (rc != TAMCMC_OK) return rc;
+    if (cnt[0] < 4 || cnt[0] >= TM_BANDESS_MAX_N) return TAMCMC_E_INVALID;      // (2^20 samples and more: thin the chain)
+    const size_t nx = (size_t)c->L.Nx, k = (size_t)K;
+    TmBandMode m;
+    m.K = K;
+    m.L = tme_lag_limit(max_lag, cnt[0]);
+    m.RW = tmb_ring_words(m.L);
+    m.HW = tmb_head_words(m.L);
+    m.n_used = cnt[0]; m.n_rejected = cnt[1];
+    const size_t state_bytes = 3 * k * nx * sizeof(double) + 4 * sizeof(long long) + k * nx * sizeof(int32_t);
+    if (hipMalloc(&m.d_state, state_bytes) != hipSuccess) { (void)hipGetLastError(); return TAMCMC_E_NOMEM; }
+    if (hipMalloc(&m.d_C, k * (size_t)(m.L + 1) * nx * sizeof(uint32_t)) != hipSuccess) { (void)hipGetLastError(); (void)hipFree(m.d_state); return TAMCMC_E_NOMEM; }
+    if (hipMalloc(&m.d_bits, band_bits_bytes(m, nx)) != hipSuccess) {
+        (void)hipGetLastError(); (void)hipFree(m.d_state); (void)hipFree(m.d_C);
+        return TAMCMC_E_NOMEM;
+    }
+    if (hipMalloc(&m.d_work, (size_t)(m.L + 1) * nx * sizeof(double)) != hipSuccess) {
+        (void)hipGetLastError(); (void)hipFree(m.d_state); (void)hipFree(m.d_C); (void)hipFree(m.d_bits);
+        return TAMCMC_E_NOMEM;
+    }
+    m.head = m.d_bits + k * (size_t)m.RW * nx;
+    m.thr = reinterpret_cast<double *>(m.d_state);
+    m.tau = m.thr + k * nx;
+    m.ess = m.tau + k * nx;
+    m.cnt.d = reinterpret_cast<long long *>(m.ess + k * nx);
+    m.cut = reinterpret_cast<int32_t *>(m.cnt.d + 4);
+    m.on = true;
+    s->band = m;
+    c->enq_seq++;
+    if (hipMemcpy(m.thr, thr, k * nx * sizeof(double), hipMemcpyHostToDevice) != hipSuccess || band_pass_clear(s) != TAMCMC_OK) {
+        (void)hipStreamSynchronize(c->stream);
+        band_free(s);
+        return TAMCMC_E_HIP;
+    }
+    if (lag_used) *lag_used = m.L;
+    return TAMCMC_OK;
+}
+
+extern "C" int tamcmc_summary_bandess_result(tamcmc_summary *s, tamcmc_summary_bandess_totals *totals,
+                                             int32_t *count_le, double *p_hat, double *ess, double *tau, double *mcse_p, int32_t *cut)
+{
+    if (!s || !s->band.on) return TAMCMC_E_INVALID;
+    int rc = summary_enter(s);
+    if (rc != TAMCMC_OK) return rc;
+    tamcmc_ctx *c = s->c;
+    TmBandMode &m = s->band;
+    c->enq_seq++;
+    bool complete = false;
+    rc = pass_complete(m, &complete);
+    if (rc != TAMCMC_OK) return rc;
+    if (!complete) {                                                    // not the fold pass's samples: the pass is discarded
+        rc = band_pass_clear(s);
+        return rc != TAMCMC_OK ? rc : TAMCMC_E_INVALID;
+    }
+    const size_t nx = (size_t)c->L.Nx, K = (size_t)m.K;
+    std::vector<double> out;
+    std::vector<int32_t> cutv;
+    std::vector<uint32_t> N;
+    try { out.resize(2 * K * nx); cutv.resize(K * nx); N.resize(K * nx); } catch (const std::bad_alloc &) { return TAMCMC_E_NOMEM; }
+    for (size_t j = 0; j < K; j++) {                                    // one threshold at a time: they share the work column
+        TmBandArgs a = band_args(s);
+        a.j = (int32_t)j;
+        rc = timed_launch(s, s->timer, "summary bandess finish", [&] { return tm_launch_bandess_finish(a, c->stream); });
+        if (rc != TAMCMC_OK) return rc;
+        TM_HIP(hipMemcpyAsync(N.data() + j * nx, m.d_C + j * (size_t)(m.L + 1) * nx, nx * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));   // N = C_0
+    }
+    TM_HIP(hipMemcpyAsync(out.data(), m.tau, 2 * K * nx * sizeof(double), hipMemcpyDeviceToHost, c->stream));     // tau[K] | ess[K]
+    TM_HIP(hipMemcpyAsync(cutv.data(), m.cut, K * nx * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    TM_HIP(hipStreamSynchronize(c->stream));
+    const double dn = (double)m.n_used, nan = std::nan("");
+    const double *tauv = out.data(), *essv = out.data() + K * nx;
+    tamcmc_summary_bandess_totals t{};
+    t.n_used = m.n_used; t.n_rejected = m.n_rejected; t.lag = m.L; t.n_thresholds = m.K;
+    for (size_t j = 0; j < TAMCMC_SUMMARY_MAX_QUANTILES; j++) { t.min_ess[j] = nan; t.bin_min_ess[j] = -1; }
+    for (size_t j = 0; j < K; j++)
+        for (size_t i = 0; i < nx; i++) {
+            const size_t at = j * nx + i;
+            const double e = essv[at];
+            const double p = (double)N[at] / dn;
+            const double q = 1.0 - p, pq = p * q;                       // (spelled out: no contraction whatever the flags)
+            if (count_le) count_le[at] = (int32_t)N[at];
+            if (p_hat) p_hat[at] = p;
+            if (ess) ess[at] = e;
+            if (tau) tau[at] = tauv[at];
+            if (mcse_p) mcse_p[at] = std::sqrt(pq / e);
+            if (cut) cut[at] = cutv[at];
+            // the first bin wins a tie, a NaN is skipped
+            if (t.bin_min_ess[j] < 0 ? !std::isnan(e) : e < t.min_ess[j]) { t.min_ess[j] = e; t.bin_min_ess[j] = (int64_t)i; }
+            if (cutv[at] == m.L + 1) t.n_truncated[j]++;
+            if (N[at] == 0 || (long long)N[at] == m.n_used) t.n_constant[j]++;
+        }
+    if (totals) *totals = t;
+    return TAMCMC_OK;
+}
+
+extern "C" int tamcmc_summary_bandess_counts(tamcmc_summary *s, int32_t j, int32_t *C, int64_t *E)
+{
+    if (!s || !s->band.on || j < 0 || j >= s->band.K) return TAMCMC_E_INVALID;
+    bool complete = false;
+    int rc = summary_enter(s);
+    if (rc == TAMCMC_OK) rc = pass_complete(s->band, &complete);
+    if (rc != TAMCMC_OK) return rc;
+    tamcmc_ctx *c = s->c;
+    if (!complete) return TAMCMC_E_INVALID;                             // (the pass stays: tamcmc_summary_bandess_result discards it)
+    const TmBandMode &m = s->band;
+    const size_t len = (size_t)(m.L + 1) * (size_t)c->L.Nx;
+    if (C) TM_HIP(hipMemcpy(C, m.d_C + (size_t)j * len, len * sizeof(uint32_t), hipMemcpyDeviceToHost));     // (every count is <= n < 2^20)
+    if (E) {
+        TmBandArgs a = band_args(s);
+        a.j = j; a.want_E = 1;
+        c->enq_seq++;
+        const int hr = tm_launch_bandess_finish(a, c->stream);
+        if (hr != 0) return tm_launch_failed("summary bandess counts", hr);
+        TM_HIP(hipMemcpyAsync(E, m.d_work, len * sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
+        TM_HIP(hipStreamSynchronize(c->stream));
+    }
+    return TAMCMC_OK;
+}
+
+extern "C" int tamcmc_summary_bandess_end(tamcmc_summary *s)
+{
+    if (!s || !s->band.on) return TAMCMC_E_INVALID;
+    const int rc = summary_enter(s);
+    if (rc == TAMCMC_OK) band_free(s);
     return rc;
 }

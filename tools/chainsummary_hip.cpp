@@ -4,7 +4,7 @@
 //   chainsummary_hip <config dir> <model file> <data file> <params root> <output file>
 //                    [--chain m] [--slice s] [--first i] [--last j] [--thin k] [--block B]
 //                    [--quantiles q1,q2,...] [--qbits b] [--loo] [--predictive] [--window W[,first]] [--ess [L]]
-//                    [--scan W0[,W1,...]] [--scan-below T] [--scan-null R[,seed]]
+//                    [--scan W0[,W1,...]] [--scan-below T] [--scan-null R[,seed]] [--band-ess [L]]
 //
 // <config dir> is the reference's Config/default; model id, likelihood, p, plength, the inputs row and the relax mask
 // come from the setup it describes (tamcmc_setup_create / tamcmc_setup_load, slice s counted from 0).  The samples are
@@ -54,6 +54,12 @@
 // lag= ...`, `# min_ess_M= ...  bin_min_ess_M= ...  min_ess_l= ...  bin_min_ess_l= ...`, `# max_rhat= ...  bin_max_rhat= ...
 // n_rhat_high= ...`, `# n_truncated_M= ...  n_truncated_l= ...` -- then one row per bin:
 //   x  ess_M  tau_M  mcse_M  rhat_M  cut_M  ess_l  r_eff  cut_l
+// With --band-ess [L] (needs --quantiles) the selected samples are read once more after the selection is exact, for the
+// effective sample size of every quantile: that of the indicator `model <= quantile` (tamcmc_summary_bandess_*; lags up to L as
+// for --ess).  The output file keeps every byte; the results go to <output file>.bandess: `#` header lines -- the version,
+// `# quantiles= q1,q2,...`, `# n_used= ...  n_rejected= ...  lag= ...`, per quantile `# q= ...  min_ess= ...  bin_min_ess= ...
+// n_truncated= ...  n_constant= ...` -- then one row per bin, x and per quantile seven columns:
+//   value  count_le  p_hat  ess  tau  mcse_p  cut
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -70,7 +76,7 @@ static int usage()
     fprintf(stderr, " Usage: chainsummary_hip <config dir> <model file> <data file> <params root> <output file>\n"
                     "                         [--chain m] [--slice s] [--first i] [--last j] [--thin k] [--block B]\n"
                     "                         [--quantiles q1,q2,...] [--qbits b] [--loo] [--predictive] [--window W[,first]] [--ess [L]]\n"
-                    "                         [--scan W0[,W1,...]] [--scan-below T] [--scan-null R[,seed]]\n"
+                    "                         [--scan W0[,W1,...]] [--scan-below T] [--scan-null R[,seed]] [--band-ess [L]]\n"
                     "     [1] The directory of config_default.cfg, errors_default.cfg and the *_ctrl.list files (Config/default)\n"
                     "     [2] The .model file and [3] the .data file of the fit\n"
                     "     [4] The root of the parameter files: <root>_chain-<m>.bin and <root>.hdr\n"
@@ -100,6 +106,10 @@ static int usage()
                     "     --ess [L]   effective sample size, Monte-Carlo standard error and split R-hat per bin from the autocorrelation up\n"
                     "             to lag L (0 ... 1023, default 0: the library's 255): written to <output file>.ess, one row per bin,\n"
                     "             x ess_M tau_M mcse_M rhat_M cut_M ess_l r_eff cut_l (the samples are read once more; [5] is unchanged)\n"
+                    "     --band-ess [L]   needs --quantiles: the effective sample size of every quantile, that of the indicator model <= quantile,\n"
+                    "             from its autocorrelation up to lag L (0 ... 1023, default 0: the library's 255): written to <output file>.bandess,\n"
+                    "             one row per bin, x and per quantile value count_le p_hat ess tau mcse_p cut (the samples are read once more\n"
+                    "             after the selection; [5] is unchanged)\n"
                     " chainsummary_hip version   prints the library version\n");
     return EXIT_FAILURE;
 }
@@ -138,6 +148,7 @@ int main(int argc, char *argv[])
     std::string quant_text;
     bool loo = false, predictive = false;
     long win_W = 0, win_first = 0, ess_lag = -1;            // ess_lag < 0: no --ess
+    long band_lag = -1;                                     // < 0: no --band-ess
     std::vector<int32_t> scan_W;
     std::string scan_text;
     double scan_below = std::nan("");                       // NaN: the library's default line per width
@@ -156,6 +167,16 @@ int main(int argc, char *argv[])
                 char *end = nullptr;
                 ess_lag = strtol(argv[++i], &end, 10);
                 if (*end != '\0' || ess_lag > TAMCMC_SUMMARY_ESS_MAX_LAG) return usage();
+            }
+            continue;
+        }
+        if (a == "--band-ess") {                    // alone, or followed by the lag limit
+            if (band_lag >= 0) return usage();
+            band_lag = 0;
+            if (i + 1 < argc && argv[i + 1][0] >= '0' && argv[i + 1][0] <= '9') {
+                char *end = nullptr;
+                band_lag = strtol(argv[++i], &end, 10);
+                if (*end != '\0' || band_lag > TAMCMC_SUMMARY_ESS_MAX_LAG) return usage();
             }
             continue;
         }
@@ -237,6 +258,7 @@ int main(int argc, char *argv[])
     }
     if (chain < 0 || slice < 0 || first < 0 || thin < 1 || block < 0 || block > 0x7FFFFFFF || qbits < 0 || qbits > 6) return usage();
     if ((have_below || null_R) && scan_W.empty()) return usage();
+    if (band_lag >= 0 && quant.empty()) { fprintf(stderr, "chainsummary_hip: --band-ess needs --quantiles\n"); return usage(); }
 
     tamcmc_setup *S = nullptr;
     if (tamcmc_setup_create(&S, cfg_dir.c_str()) != TAMCMC_IO_OK) return fail("cannot read the default configuration in " + cfg_dir);
@@ -385,6 +407,20 @@ int main(int argc, char *argv[])
         if (rc != TAMCMC_OK) return qfail("tamcmc_summary_quantiles_result");
         tamcmc_summary_quantiles_end(sum);
     }
+    // band ESS: the same samples once more, in the same order, against the exact quantiles
+    tamcmc_summary_bandess_totals bt{};
+    const size_t Nb = band_lag >= 0 ? Nq * (size_t)Nx : 0;
+    std::vector<double> b_p(Nb), b_ess(Nb), b_tau(Nb), b_mcse(Nb);
+    std::vector<int32_t> b_count(Nb), b_cut(Nb);
+    if (band_lag >= 0) {
+        auto bfail = [&](const char *what) { return fail(std::string(what) + ": " + tamcmc_strerror(rc) + " " + tamcmc_last_hip_error()); };
+        rc = tamcmc_summary_bandess_begin(sum, (int32_t)Nq, qlo.data(), (int32_t)band_lag, nullptr);
+        if (rc != TAMCMC_OK) return bfail("tamcmc_summary_bandess_begin");
+        if (push_selected() != 0) return EXIT_FAILURE;
+        rc = tamcmc_summary_bandess_result(sum, &bt, b_count.data(), b_p.data(), b_ess.data(), b_tau.data(), b_mcse.data(), b_cut.data());
+        if (rc != TAMCMC_OK) return bfail("tamcmc_summary_bandess_result");
+        tamcmc_summary_bandess_end(sum);
+    }
     // PSIS-LOO: the same samples once more
     tamcmc_summary_loo_totals lt{};
     std::vector<double> elpd(loo ? (size_t)Nx : 0), khat(loo ? (size_t)Nx : 0);
@@ -528,6 +564,33 @@ int main(int argc, char *argv[])
             fprintf(oe, "%.12g %.12g %.12g %.12g %.12g %d %.12g %.12g %d\n", x[(size_t)i], ess_M[(size_t)i], tau_M[(size_t)i], mcse_M[(size_t)i],
                     rhat_M[(size_t)i], (int)cut_M[(size_t)i], ess_l[(size_t)i], r_eff[(size_t)i], (int)cut_l[(size_t)i]);
         fclose(oe);
+    }
+    if (band_lag >= 0) {
+        const std::string band_file = out_file + ".bandess";
+        FILE *ob = fopen(band_file.c_str(), "w");
+        if (!ob) return fail("unable to open the output file " + band_file);
+        fprintf(ob, "# chainsummary_hip (%s)\n", tamcmc_version());
+        fprintf(ob, "# quantiles= %s\n", quant_text.c_str());
+        fprintf(ob, "# n_used= %lld  n_rejected= %lld  lag= %lld\n", (long long)bt.n_used, (long long)bt.n_rejected, (long long)bt.lag);
+        for (size_t j = 0; j < Nq; j++)
+            fprintf(ob, "# q= %.6g  min_ess= %.12g  bin_min_ess= %lld  n_truncated= %lld  n_constant= %lld\n", quant[j], bt.min_ess[j],
+                    (long long)bt.bin_min_ess[j], (long long)bt.n_truncated[j], (long long)bt.n_constant[j]);
+        fprintf(ob, "# x");
+        for (size_t j = 0; j < Nq; j++) {
+            char q[32];
+            snprintf(q, sizeof q, "%.6g", quant[j]);
+            fprintf(ob, " q%s count_le_%s p_hat_%s ess_%s tau_%s mcse_p_%s cut_%s", q, q, q, q, q, q, q);
+        }
+        fprintf(ob, "\n");
+        for (int64_t i = 0; i < Nx; i++) {
+            fprintf(ob, "%.12g", x[(size_t)i]);
+            for (size_t j = 0; j < Nq; j++) {
+                const size_t at = j * (size_t)Nx + (size_t)i;
+                fprintf(ob, " %.12g %d %.12g %.12g %.12g %.12g %d", qlo[at], (int)b_count[at], b_p[at], b_ess[at], b_tau[at], b_mcse[at], (int)b_cut[at]);
+            }
+            fprintf(ob, "\n");
+        }
+        fclose(ob);
     }
     printf("Summary of %lld samples (%lld rejected) written to %s\n", (long long)t.n_used, (long long)t.n_rejected, out_file.c_str());
     return 0;

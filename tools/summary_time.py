@@ -39,6 +39,12 @@ Prints one JSON line:
                             runs appended to one object -- wall seconds per replicate through ScanNull.run (the copy back and the
                             host's tail functions included) and the two kernels alone from HIP events around every chunk; the
                             joint and the per-width 1 % line of the excess side beside the default line.  Only this leg runs.
+  k_bandess_*               with --band-ess L (0: the library's default lag limit; --quantiles K thresholds, default 3): after a fold
+                            pass and the exact selection of K quantiles, the band ESS pass of the same rows through Summary.push
+                            beside the fold pass, alternating in one run (seconds per 1000 samples), and from profiled passes the
+                            fold kernel alone beside the band kernels alone (pack and lag kernels of every block,
+                            Summary.kernel_time in the mode) and the eval launches, the finish kernels (one per threshold),
+                            bandess_result on the host clock, and the device memory the mode allocates.  Only this leg runs.
 Every timed shape is warmed up first (--warmup pushes); host clocks stop after calls that end in a device synchronise.
 """
 import argparse
@@ -284,6 +290,70 @@ def ess_leg(a, w, y, P):
     return out
 
 
+def bandess_leg(a, w, y, P):
+    """(k) the fold pass beside the band ESS pass of the same rows, and the kernels' own times."""
+    out = {}
+    q = [0.025, 0.5, 0.975, 0.16, 0.84, 0.0, 1.0, 0.25][:a.quantiles]
+    with tamcmc_amd.Accel(2, w["plength"], w["x"], y) as acc:
+        with tamcmc_amd.Summary(acc, a.block) as s:
+            s.push(P)
+            thr = s.quantiles(P, q, a.qbits)["lo"]          # the exact quantiles: the thresholds of every pass below
+            times = {"fold": [], "bandess": []}
+            for k in range(a.warmup + a.steps):
+                s.reset()
+                acc.synchronize()
+                t0 = time.perf_counter()
+                s.push(P)                                   # synchronous: results are on the host on return
+                t1 = time.perf_counter()
+                L = s.bandess_begin(thr, a.band_ess)
+                acc.synchronize()
+                t2 = time.perf_counter()
+                s.push(P)
+                t3 = time.perf_counter()
+                if k >= a.warmup:
+                    times["fold"].append(t1 - t0)
+                    times["bandess"].append(t3 - t2)
+                if k + 1 < a.warmup + a.steps:
+                    s.bandess_end()
+            for key, v in times.items():
+                out[f"k_bandess_{key}_pass_s_per_1000"] = float(np.median(v)) * 1000.0 / a.samples
+                out[f"k_bandess_{key}_pass_spread"] = [float(min(v)) * 1000.0 / a.samples, float(max(v)) * 1000.0 / a.samples]
+            acc.synchronize()
+            t0 = time.perf_counter()
+            r = s.bandess_result()
+            t_result = time.perf_counter() - t0
+            s.profile(True)                                 # the finish kernels alone: a second result without another pass
+            s.bandess_result()
+            fin_ms, fin_launches = s.kernel_time()
+            s.profile(False)
+            s.bandess_end()
+            s.reset()                                       # the kernels alone: a profiled fold pass, then a profiled band pass
+            s.profile(True)
+            acc.profile(True)
+            s.push(P)
+            fold_ms, fold_launches = s.kernel_time()
+            eval_ms, eval_launches = acc.kernel_time()
+            acc.profile(False)
+            s.profile(False)
+            s.bandess_begin(thr, a.band_ess)
+            s.profile(True)
+            s.push(P)
+            band_ms, band_blocks = s.kernel_time()
+            s.profile(False)
+            s.bandess_end()
+            K = len(q)
+            out.update(k_bandess_lag=L, k_bandess_K=K, k_bandess_blocks=band_blocks, k_bandess_us_per_block=band_ms * 1e3 / band_blocks,
+                       k_bandess_kernels_s_per_1000=band_ms * 1e-3 * 1000.0 / a.samples,
+                       k_fold_kernel_s_per_1000=fold_ms * 1e-3 * 1000.0 / a.samples,
+                       k_eval_kernel_s_per_1000=eval_ms * 1e-3 * 1000.0 / a.samples,
+                       k_bandess_counter_bytes_per_s=2.0 * 4 * K * (L + 1) * a.nx * band_blocks / (band_ms * 1e-3),
+                       k_bandess_result_s=t_result, k_bandess_finish_ms_per_threshold=fin_ms / max(fin_launches, 1),
+                       k_bandess_bytes=((4 * K + 8) * (L + 1) + 16 * K * (-(-L // 64) + 1) + 28 * K) * a.nx + 32,
+                       k_bandess_min_ess=[float(v) for v in r["min_ess"]], k_bandess_n_truncated=[int(v) for v in r["n_truncated"]],
+                       k_bandess_n_constant=[int(v) for v in r["n_constant"]], n_used=r["n_used"])
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--samples", type=int, default=4096)
@@ -299,6 +369,7 @@ def main():
     ap.add_argument("--window", type=int, default=0)
     ap.add_argument("--scan", default="", help="W0[,W1,...]: strictly ascending widths of the sliding-window scan")
     ap.add_argument("--ess", type=int, default=-1)
+    ap.add_argument("--band-ess", type=int, default=-1, help="L: the band ESS pass at --quantiles thresholds (0: the library's lag limit)")
     ap.add_argument("--scan-null", type=int, default=0, help="R: replicates per run of the scan's Monte-Carlo null (widths of --scan)")
     a = ap.parse_args()
     if a.steps < 1 or a.warmup < 0 or a.samples < 1 or a.samples_b < 2 or a.scan_null < 0:
@@ -315,8 +386,8 @@ def main():
     assert st == 0
     y = synth.make_spectrum(m_true)
     out = dict(tool="summary_time", Nx=a.nx, samples=a.samples, steps=a.steps, warmup=a.warmup, version=tamcmc_amd.capi.version())
-    if a.predictive or a.window or a.scan or a.ess >= 0:
-        out.update(ess_leg(a, w, y, P) if a.ess >= 0 else scan_leg(a, w, y, P) if a.scan else window_leg(a, w, y, P) if a.window
+    if a.predictive or a.window or a.scan or a.ess >= 0 or a.band_ess >= 0:
+        out.update(bandess_leg(a, w, y, P) if a.band_ess >= 0 else ess_leg(a, w, y, P) if a.ess >= 0 else scan_leg(a, w, y, P) if a.scan else window_leg(a, w, y, P) if a.window
                    else predictive_leg(a, w, y, P))
         print(json.dumps(out))
         return
