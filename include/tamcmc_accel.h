@@ -89,7 +89,11 @@ typedef struct tamcmc_ctx tamcmc_ctx;
  *                    x[0] == 0 is supported (likelihood and gradient) with every active Harvey exponent |p| >= 1e-297;
  *                    a Harvey exponent of 0 on such a grid, and negative frequencies, are not.
  *   Nx               2 <= Nx <= 2^28 (TAMCMC_E_INVALID outside): the kernels address the grid with 32-bit byte
- *                    offsets; the reference itself reads at most 1e6 rows (config.cpp:531). */
+ *                    offsets; the reference itself reads at most 1e6 rows (config.cpp:531).  All launches are tested
+ *                    against the oracle up to Nx = 4 194 779 (8193 units of 512 bins, 1025 / 1178 tiles per chain;
+ *                    tests/test_long_grids_gpu.py); what changes between there and 2^28 -- the chain-major launch
+ *                    above 65 535 tiles, the backward kernel's LDS growing with the tile count (tamcmc_ctx_set_vars) --
+ *                    is tested on a short grid with tile counts given by hand, not at those lengths. */
 int tamcmc_ctx_create(tamcmc_ctx **out, int device_id, int model_case, int likelihood_case,
                       double likelihood_p, const int32_t plength[11], int64_t Nx,
                       const double *x, const double *y, const double *sigma_y);
@@ -97,9 +101,13 @@ int tamcmc_ctx_create(tamcmc_ctx **out, int device_id, int model_case, int likel
 /* Replaces: Model_def::index_to_relax (model_def.cpp:81-88).  Declares which params columns are
  * the free variables; needed only for gradients.  grad column k = d(logL/T)/d params[index_to_relax[k]].
  * TAMCMC_E_NOGRAD (nothing changed) when the gradient tables of the layout with these variables exceed the backward
- * kernel's LDS (504 bytes per multiplet + 72 per variable + 12 per parameter > 150 KB: with every entry a variable
- * from some 210 (id 13) to 235 (id 2) multiplets on; 256 multiplets take up to 262 variables); likelihood batches are
- * not affected.
+ * kernel's LDS (504 bytes per multiplet + 72 per variable + 12 per parameter + 4 per gradient tile > 150 KB: with every
+ * entry a variable from some 210 (id 13) to 235 (id 2) multiplets on; 256 multiplets take up to 262 variables);
+ * likelihood batches are not affected.  The tile term is what a long grid adds: the gradient launch has about
+ * 0.144 tiles per unit of 512 bins (tamcmc_ctx_geometry_grad), i.e. 28 tiles per 1e5 bins.  For a typical layout
+ * -- 21 multiplets, 56 parameters, 44 variables: 15 224 bytes + 4 per tile -- the largest accepted count is 34 593 tiles
+ * (tested, through TAMCMC_TILES_GRAD on a short grid), which the default geometry exceeds from Nx = 123 211 777 on
+ * (240 649 units; computed from the tile rule, not run): from there on such a star has a likelihood and no gradient.
  * TAMCMC_E_INVALID (nothing changed, the earlier variables stay) for an index outside 0 ... Nparams - 1, for an index that
  * occurs twice (hence for Nvars > Nparams: every variable is one column, in the order of the list, which need not be
  * ascending), and while a batch is in flight or armed.  Nvars = 0 takes the variables away: a gradient request then
@@ -774,6 +782,9 @@ int tamcmc_ctx_clock_probe_end(tamcmc_ctx *ctx, double *core_GHz, double *second
  * launch), tiles = tiles per chain of the most recent likelihood-only call. */
 int tamcmc_ctx_geometry(tamcmc_ctx *ctx, int32_t *bins_per_tile, int32_t *tiles, int32_t *threads_per_block,
                         int32_t *n_multiplets);
+/* The same for the gradient launch: tiles = tiles per chain of a gradient batch (fixed at create time: the tail rule on
+ * long grids, or TAMCMC_TILES_GRAD), bins_per_tile = its largest tile (8 units of 512 bins).  Either pointer may be NULL. */
+int tamcmc_ctx_geometry_grad(tamcmc_ctx *ctx, int32_t *tiles, int32_t *bins_per_tile);
 
 /* TAMCMC_E_INVALID (and nothing happens) while the context is a member of a fit group or has a summary object. */
 int tamcmc_ctx_destroy(tamcmc_ctx *ctx);

@@ -23,7 +23,7 @@ EXPORTS = [
     "tamcmc_ctx_reserve",
     "tamcmc_eval_batch_arm", "tamcmc_eval_batch_fire", "tamcmc_eval_batch_disarm", "tamcmc_eval_batch_poll",
     "tamcmc_model_explicit", "tamcmc_ctx_set_stream", "tamcmc_ctx_synchronize", "tamcmc_ctx_profile",
-    "tamcmc_ctx_kernel_time", "tamcmc_ctx_clock_probe_begin", "tamcmc_ctx_clock_probe_end", "tamcmc_ctx_geometry", "tamcmc_ctx_destroy", "tamcmc_device_count",
+    "tamcmc_ctx_kernel_time", "tamcmc_ctx_clock_probe_begin", "tamcmc_ctx_clock_probe_end", "tamcmc_ctx_geometry", "tamcmc_ctx_geometry_grad", "tamcmc_ctx_destroy", "tamcmc_device_count",
     "tamcmc_strerror", "tamcmc_last_hip_error", "tamcmc_version",
     "tamcmc_group_create", "tamcmc_group_eval", "tamcmc_group_eval_device", "tamcmc_group_set_stream",
     "tamcmc_group_synchronize", "tamcmc_group_destroy",
@@ -139,6 +139,7 @@ def load_library():
     lib.tamcmc_ctx_clock_probe_begin.argtypes = [vp, C.c_double]
     lib.tamcmc_ctx_clock_probe_end.argtypes = [vp, dp, dp]
     lib.tamcmc_ctx_geometry.argtypes = [vp, ip, ip, ip, ip]
+    lib.tamcmc_ctx_geometry_grad.argtypes = [vp, ip, ip]
     lib.tamcmc_ctx_destroy.argtypes = [vp]
     lib.tamcmc_device_count.argtypes = []
     lib.tamcmc_strerror.argtypes = [C.c_int]
@@ -398,7 +399,10 @@ class Accel:
     def geometry(self):
         v = [C.c_int32(0) for _ in range(4)]
         self._check(self._lib.tamcmc_ctx_geometry(self._ctx, *[C.byref(e) for e in v]), "tamcmc_ctx_geometry")
-        return dict(bins_per_tile=v[0].value, tiles=v[1].value, threads_per_block=v[2].value, n_multiplets=v[3].value)
+        g = [C.c_int32(0) for _ in range(2)]
+        self._check(self._lib.tamcmc_ctx_geometry_grad(self._ctx, *[C.byref(e) for e in g]), "tamcmc_ctx_geometry_grad")
+        return dict(bins_per_tile=v[0].value, tiles=v[1].value, threads_per_block=v[2].value, n_multiplets=v[3].value,
+                    tiles_grad=g[0].value, bins_per_tile_grad=g[1].value)
 
 
 class Group:

@@ -473,6 +473,14 @@ extern "C" int tamcmc_ctx_geometry(tamcmc_ctx *c, int32_t *bins_per_tile, int32_
     return TAMCMC_OK;
 }
 
+extern "C" int tamcmc_ctx_geometry_grad(tamcmc_ctx *c, int32_t *tiles, int32_t *bins_per_tile)
+{
+    if (!c) return TAMCMC_E_INVALID;
+    if (tiles) *tiles = tm_ctx_tiles(c, true);
+    if (bins_per_tile) *bins_per_tile = TM_UNIT_BINS * TM_TILE_MAXU;
+    return TAMCMC_OK;
+}
+
 // Arguments of the eval launch of a batch on the context (solo launches and fit groups alike).
 TmEvalArgs tm_eval_args(const tamcmc_ctx *c, int tiles, bool grad, double *d_logL, int32_t *d_status, const int32_t *d_rows,
                         double *d_model)

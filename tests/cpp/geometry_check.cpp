@@ -10,10 +10,16 @@ static unsigned next_u32() { rng ^= rng << 13; rng ^= rng >> 7; rng ^= rng << 17
 
 int main() {
     long checked = 0;
-    for (int units = 1; units <= TM_EQ_MAXU; units = units < 700 ? units + 1 : units + 97) {
+    // every unit count up to 700, then steps of 97, then TM_EQ_MAXU - 1 and TM_EQ_MAXU themselves (one unit of slack, none)
+    for (int units = 1; units <= TM_EQ_MAXU; units = units < 700 ? units + 1 : (units < TM_EQ_MAXU - 1 && units + 97 > TM_EQ_MAXU - 1) ? TM_EQ_MAXU - 1 : (units == TM_EQ_MAXU - 1) ? TM_EQ_MAXU : units + 97) {
         for (int grad = 0; grad < 2; grad++) {
             const int T = tm_tiles(units, grad);
             if (T < 1 || (long long)T * TM_TILE_MAXU < units) { printf("bad tile count: units %d -> %d\n", units, T); return 1; }
+            // the balancer's predicate is the one this check skips by: slack, more than one tile, ranks in LDS
+            if (tm_setup_balances(units, T, 1, TM_TILE_MAXU) != ((T > 1 && T <= TM_ORDER_MAX && (long long)T * TM_TILE_MAXU > units) ? 1 : 0) ||
+                tm_setup_balances(units, T, 0, TM_TILE_MAXU) != 0 || tm_setup_balances(units, T, 1, TM_TILE_MAXU_L) != 0) {
+                printf("bad balancer predicate: units %d T %d\n", units, T); return 1;
+            }
             if (T == 1 || (long long)T * TM_TILE_MAXU <= units) continue;      // the balancer needs slack; such grids get equal-length tiles
             for (int pattern = 0; pattern < 6; pattern++) {
                 std::vector<int> cost(units), pre(units);
@@ -44,6 +50,13 @@ int main() {
                 checked++;
             }
         }
+    }
+    // the unit bound: TM_EQ_MAXU - 1 units are balanced with one unit of slack, TM_EQ_MAXU have none, one more is too long
+    // for the LDS prefix whatever the slack
+    if (tm_tiles(TM_EQ_MAXU - 1, 0) * TM_TILE_MAXU - (TM_EQ_MAXU - 1) != 1 || tm_setup_balances(TM_EQ_MAXU - 1, tm_tiles(TM_EQ_MAXU - 1, 0), 1, TM_TILE_MAXU) != 1 ||
+        tm_setup_balances(TM_EQ_MAXU, tm_tiles(TM_EQ_MAXU, 0), 1, TM_TILE_MAXU) != 0 || tm_setup_balances(TM_EQ_MAXU, tm_tiles(TM_EQ_MAXU, 0) + 1, 1, TM_TILE_MAXU) != 1 ||
+        tm_setup_balances(TM_EQ_MAXU + 1, tm_tiles(TM_EQ_MAXU + 1, 0), 1, TM_TILE_MAXU) != 0 || tm_setup_balances(TM_EQ_MAXU + 1, TM_ORDER_MAX, 1, TM_TILE_MAXU) != 0) {
+        printf("bad balancer predicate at TM_EQ_MAXU\n"); return 1;
     }
     printf("ok %ld geometries\n", checked);
     return 0;

@@ -9,6 +9,7 @@ import math
 
 import numpy as np
 
+import longgrids
 import workloads as W
 from tamcmc_amd import synth
 
@@ -342,10 +343,8 @@ def grad_tiles(Nx):
 def backward_lds_bytes(w, nvars):
     pl = w["plength"]
     assert w["model_case"] in (2, 3, 6, 7, 8, 10, 12, 13)
-    Np, nm, tiles = int(pl.sum()), int(pl[0]) * (int(pl[1]) + 1), grad_tiles(w["x"].size)
-    npairs = nm * 12 + 64
-    return ((Np + nvars) * 8 + npairs * 8 + nm * (20 + 24 + 1) * 8 + 16 + ((npairs + 7) & ~7) * 4 + ((tiles + 2) & ~1) * 4
-            + ((Np + 1) & ~1) * 4 + 8 * nvars * 8)
+    assert int(pl.sum()) == w["params_true"].size
+    return longgrids.backward_lds_bytes(w, nvars, grad_tiles(w["x"].size))     # (the sum itself: any tile count)
 
 
 def records_bytes(w):
