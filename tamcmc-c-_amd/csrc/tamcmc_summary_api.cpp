@@ -454,10 +454,7 @@ extern "C" int tamcmc_summary_create(tamcmc_summary **out, tamcmc_ctx *c, int32_
     s->c = c;
     const size_t nx = (size_t)c->L.Nx;
     int B = block_chains;
-    if (B == 0) {                                   // 64, lowered so that a block's rows take at most 64 MiB
-        const size_t fit = ((size_t)64 << 20) / (nx * sizeof(double));
-        B = fit >= 64 ? 64 : (fit >= 1 ? (int)fit : 1);
-    }
+    if (B == 0) B = tms_default_block((long long)nx);      // 64, lowered so that a block's rows take at most 64 MiB
     s->B = B;
     auto fail = [&](int code) { tamcmc_summary_destroy(s); return code; };
     if (hipSetDevice(c->device) != hipSuccess) return fail(TAMCMC_E_NODEVICE);

@@ -41,6 +41,16 @@ TMS_FN double tms_resid(const bool chi_square, const double y, const double M, c
 
 inline unsigned tms_blocks(const long long Nx, const int threads) { return (unsigned)((Nx + threads - 1) / threads); }   // one thread per bin
 
+// samples per block where the caller leaves it open (block_chains = 0): 64, lowered so that a block's rows -- B x Nx doubles --
+// take at most 64 MiB; a grid whose single row is longer than that still gets 1
+#define TMS_DEFAULT_BLOCK 64
+#define TMS_DEFAULT_BLOCK_BYTES ((size_t)64 << 20)
+inline int tms_default_block(const long long Nx)
+{
+    const size_t fit = TMS_DEFAULT_BLOCK_BYTES / ((size_t)Nx * sizeof(double));
+    return fit >= TMS_DEFAULT_BLOCK ? TMS_DEFAULT_BLOCK : (fit >= 1 ? (int)fit : 1);
+}
+
 #if defined(__HIPCC__)
 // What l of a bin needs besides M, from launch arguments with y, isig2 (NULL unless chi_square), likelihood_case, like_p
 struct TmsBinLike {

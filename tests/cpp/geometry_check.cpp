@@ -1,7 +1,11 @@
 // Host-side check of the tile geometry (tamcmc_dev.h): tile counts keep tiles * TM_TILE_MAXU > units, and the
 // equal-cost boundaries of tm_tile_bound -- the same function the setup kernel runs -- cover [0, units) in order with
-// tiles of at most TM_TILE_MAXU units, for adversarial and random unit costs.  Built and run by tests/test_capi_host.py.
+// tiles of at most TM_TILE_MAXU units, for adversarial and random unit costs.  Also the default block of a posterior
+// summary (tms_default_block, tamcmc_summary_walk.h) at every edge of its rule: 64 up to 2^17 bins, 63 one bin later, 2 / 1
+// either side of 2^22, still 1 past a row of 64 MiB, and B Nx 8 <= 64 MiB wherever B > 1.  Built and run by
+// tests/test_capi_host.py.
 #include "tamcmc_dev.h"
+#include "tamcmc_summary_walk.h"
 #include <cstdio>
 #include <vector>
 
@@ -57,6 +61,25 @@ int main() {
         tm_setup_balances(TM_EQ_MAXU, tm_tiles(TM_EQ_MAXU, 0), 1, TM_TILE_MAXU) != 0 || tm_setup_balances(TM_EQ_MAXU, tm_tiles(TM_EQ_MAXU, 0) + 1, 1, TM_TILE_MAXU) != 1 ||
         tm_setup_balances(TM_EQ_MAXU + 1, tm_tiles(TM_EQ_MAXU + 1, 0), 1, TM_TILE_MAXU) != 0 || tm_setup_balances(TM_EQ_MAXU + 1, TM_ORDER_MAX, 1, TM_TILE_MAXU) != 0) {
         printf("bad balancer predicate at TM_EQ_MAXU\n"); return 1;
+    }
+    // the default block: B = min(64, 64 MiB / (8 Nx)), at least 1
+    {
+        const long long MiB64 = (long long)64 << 20;
+        const struct { long long nx; int B; } edge[] = {
+            {1, 64}, {2, 64}, {100000, 64}, {131072, 64}, {131073, 63}, {133152, 63}, {133153, 62}, {2796202, 3}, {2796203, 2},
+            {4194304, 2}, {4194305, 1}, {8388608, 1}, {8388609, 1}, {(long long)1 << 31, 1}, {((long long)1 << 31) + 1, 1}};
+        for (const auto &e : edge)
+            if (tms_default_block(e.nx) != e.B) { printf("bad default block: Nx %lld -> %d, not %d\n", e.nx, tms_default_block(e.nx), e.B); return 1; }
+        int prev = 64;
+        for (long long nx = 1; nx <= 9000000; nx += (nx < 140000 || (nx > 4190000 && nx < 4200000) || (nx > 8380000 && nx < 8390000)) ? 1 : 997) {
+            const int B = tms_default_block(nx);
+            // within 64 MiB unless it is the one sample that every block has; the largest such B; never growing with Nx
+            if (B < 1 || B > 64 || B > prev || (B > 1 && B * nx * 8 > MiB64) || (B < 64 && (B + 1) * nx * 8 <= MiB64)) {
+                printf("bad default block: Nx %lld -> %d\n", nx, B); return 1;
+            }
+            prev = B;
+            checked++;
+        }
     }
     printf("ok %ld geometries\n", checked);
     return 0;

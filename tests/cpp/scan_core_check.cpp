@@ -87,6 +87,18 @@ int main()
         CHECK(tmsc_chunk(5, total) == 5);
         CHECK(tmsc_chunk(64, TM_SCAN_SCRATCH_BYTES) == 1);       // one sample alone is past the cap: still one
     }
+    // the edges of the memory term fit = 256 MiB / (24 total): the last total at which a block of 64 is one chunk, the
+    // first with fit = 1 and the first with fit = 0 (still one sample); the scratch [3][C][total] stays within the cap
+    // wherever C > 1
+    CHECK(tmsc_chunk(64, 174762) == 64 && tmsc_chunk(64, 174763) == 63 && tmsc_chunk(63, 174763) == 63 && tmsc_chunk(4096, 2730) == 4096 && tmsc_chunk(4096, 2731) == 4095);
+    CHECK(tmsc_chunk(64, 5592405) == 2 && tmsc_chunk(64, 5592406) == 1 && tmsc_chunk(1, 5592405) == 1);
+    CHECK(tmsc_chunk(64, 11184810) == 1 && tmsc_chunk(64, 11184811) == 1 && TM_SCAN_SCRATCH_BYTES / (24 * 11184810LL) == 1 && TM_SCAN_SCRATCH_BYTES / (24 * 11184811LL) == 0);
+    for (const long long B : {1LL, 2LL, 63LL, 64LL, 2600LL, 4096LL, 70001LL})
+        for (long long total = 1; total <= 12000000; total += total < 5000 ? 1 : 4999) {
+            const long long c = tmsc_chunk(B, total);
+            CHECK(c >= 1 && c <= B && c <= TM_SCAN_CHUNK_MAX && (c == 1 || 24 * total * c <= TM_SCAN_SCRATCH_BYTES));
+            CHECK(c == B || c == TM_SCAN_CHUNK_MAX || c == 1 || 24 * total * (c + 1) > TM_SCAN_SCRATCH_BYTES);
+        }
 
     // the default line
     CHECK(tmsc_default_line(20, 700) == std::log(0.01 * 20.0 / 700.0) && std::fabs(tmsc_default_line(20, 700) - (-8.1605)) < 1e-4);

@@ -165,6 +165,18 @@ int main()
             CHECK(c >= 1 && (c == 1 || (c * tiles * K * 32 <= TM_NULL_PARTIAL_BYTES && c * tiles * TM_NULL_THREADS <= (1LL << 30))));
         }
 
+    // the memory term 64 MiB / (32 K tiles) = 2^21 / (K tiles) at its edge with the cap of 4096: K tiles = 512, 513, and 520
+    // (K = 8, 65 tiles: Nx = 131 073 with a narrowest width of 1)
+    CHECK(tmn_chunk(64, 8) == 4096 && tmn_chunk(512, 1) == 4096 && tmn_chunk(513, 1) == 4088 && tmn_chunk(171, 3) == 4088 && tmn_chunk(65, 8) == 4032);
+    CHECK(tmn_tiles(131072, 1) == 64 && tmn_tiles(131073, 1) == 65 && tmn_tiles(131073, 2) == 64);
+    for (int K = 1; K <= 8; K++)
+        for (long long tiles = 1; tiles <= 5000; tiles++) {
+            const long long c = tmn_chunk(tiles, K);
+            CHECK(c >= 1 && c <= TM_NULL_CHUNK_MAX && (c == TM_NULL_CHUNK_MAX) == (K * tiles <= 512));
+            CHECK(c == 1 || 2 * K * tiles * 16 * c <= TM_NULL_PARTIAL_BYTES);
+            CHECK(c == TM_NULL_CHUNK_MAX || 2 * K * tiles * 16 * (c + 1) > TM_NULL_PARTIAL_BYTES);        // (the 2^30-thread term is the larger one here)
+        }
+
     // 6. the calibration by hand: R = 4, K = 2
     {
         //            r:   0     1     2     3

@@ -1,6 +1,8 @@
 """What two or more of the posterior-summary suites use (tests/test_summary_*_gpu.py, tests/test_cli_*_gpu.py,
 tests/test_scan_null_gpu.py, tests/test_summary_*_host.py): the cases and their references, the bit-for-bit comparisons, the
-common body of the three tail checks, and the stored chain of the command-line tests.  Importing this module needs no GPU.
+common body of the three tail checks, the accumulation-alone reference of the fold, the PSIS-LOO reference with its check, the
+ESS and band-ESS passes with the checks of the lag products and the finish, and the stored chain of the command-line tests.
+Importing this module needs no GPU.
 
 Tolerances of reference() / check() are derived, not tuned: the project's per-bin model bar eps = 1e-12 (RTOL_MODEL,
 tests/test_parity_gpu.py) propagated through each statistic, plus n 2^-52 (relative) for the accumulation over n samples,
@@ -18,6 +20,7 @@ import re
 
 import numpy as np
 
+import ess_reference as R
 import workloads as W
 from support import CFG, DATA, LD, MODEL, ROOT, bits, pyorc, tool
 from tamcmc_amd import capi, synth
@@ -132,6 +135,15 @@ def c2_chain(Nx, S, scale=0.5):
     for a in (y, P):
         a.setflags(write=False)
     return w, y, P
+
+
+def rows_around(w, n, seed=20261, scale=0.5):
+    """As chains_around (tests/test_group_gpu.py): row 0 is the truth, the others the truth + scale err normal."""
+    rng = np.random.default_rng(seed)
+    idx = w["index_to_relax"]
+    P = np.tile(w["params_true"], (n, 1))
+    P[1:, idx] += scale * w["err"][None, :] * rng.standard_normal((n - 1, idx.size))
+    return P
 
 
 def other_cases():
@@ -327,6 +339,21 @@ def select(s, q, nbits, push_pass, truth=None, u0=None):
     return traj, r["ranks"]
 
 
+def steps(s, q, nbits, push_pass, truth, limit):
+    """select(), ended after `limit` steps: the trajectory so far."""
+    s.quantiles_begin(q, nbits)
+    r = s.quantiles_result()
+    traj = [(r["lo"], r["hi"])]
+    for k in range(limit):
+        push_pass(k)
+        s.quantiles_step()
+        r = s.quantiles_result()
+        assert np.all(r["lo"] <= truth) and np.all(truth <= r["hi"]), f"step {k + 1}: the bracket lost the truth"
+        traj.append((r["lo"], r["hi"]))
+    s.quantiles_end()
+    return traj
+
+
 def same_traj(t1, t2):
     return len(t1) == len(t2) and all(np.array_equal(bits(a[0]), bits(b[0])) and np.array_equal(bits(a[1]), bits(b[1])) for a, b in zip(t1, t2))
 
@@ -395,6 +422,259 @@ def collect(check, misses, tag, *a, **k):
         check(tag, *a, **k)
     except AssertionError as e:
         misses.append(str(e).split("\n")[0])
+
+
+# ---- the fold: accumulation alone (bound b of tests/test_summary_large_gpu.py) ----
+
+def accumulation_reference(M, y, sigma, like, p=1.0):
+    """reference() of tests/summary_support.py on given rows with EPS = 0, plus the rounding of l (module docstring)."""
+    n = len(M)
+    Mq, yq = M.astype(LD), y.astype(LD)
+    if like == 0:
+        l = -p * (yq / Mq + np.log(Mq))
+        dl = 2.0 * ULP * p * (yq / Mq + np.abs(np.log(Mq)))
+    else:
+        l = -((yq - Mq) ** 2) / sigma.astype(LD) ** 2
+        dl = 3.0 * ULP * np.abs(l)
+    acc = n * ULP
+    mean_M, mean_l = Mq.mean(axis=0), l.mean(axis=0)
+    a = l.max(axis=0)
+    ref = dict(n_used=n, n_rejected=0, mean_M=mean_M, min_M=Mq.min(axis=0), max_M=Mq.max(axis=0), mean_l=mean_l,
+               lppd=a + np.log(np.exp(l - a).sum(axis=0) / n))
+    delta = dl.max(axis=0) + acc * np.abs(l).max(axis=0)
+    ref["var_M"] = ((Mq - mean_M) ** 2).sum(axis=0) / (n - 1)
+    ref["var_l"] = ((l - mean_l) ** 2).sum(axis=0) / (n - 1)
+    bound = dict(mean_M=acc * np.abs(Mq).mean(axis=0), mean_l=delta, lppd=delta, var_M=4.0 * acc * (Mq ** 2).mean(axis=0),
+                 var_l=2.0 * delta * np.sqrt(ref["var_l"]) + delta ** 2)
+    ref["lppd_total"], bound["lppd_total"] = ref["lppd"].sum(), delta.sum()
+    ref["p_waic"], bound["p_waic"] = ref["var_l"].sum(), bound["var_l"].sum()
+    ref["waic"], bound["waic"] = -2.0 * (ref["lppd_total"] - ref["p_waic"]), 2.0 * (bound["lppd_total"] + bound["p_waic"])
+    return ref, bound
+
+
+# ---- PSIS-LOO: the reference and its bounds (tests/test_summary_loo_gpu.py has the rule) ----
+
+def tail_M(n):
+    return int(math.ceil(min(n / 5.0, 3.0 * math.sqrt(float(n)))))
+
+
+def psis_reference(x, dtype=LD):
+    """The definition, per bin.  x: (n, Nx) values of -l.  Returns elpd_loo, pareto_k, cutoff (dtype) and tail_len."""
+    x = np.asarray(x, dtype=dtype)
+    n, nx = x.shape
+    M = tail_M(n)
+    log_min = np.log(dtype(np.finfo(np.float64).tiny))
+    eps10 = dtype(10.0 * 2.0 ** -52)
+    elpd, khat, cutoff = np.empty(nx, dtype=dtype), np.full(nx, np.inf, dtype=dtype), np.full(nx, np.nan, dtype=dtype)
+    tail_len = np.zeros(nx, dtype=np.int32)
+    for i in range(nx):
+        xs = np.sort(x[:, i])
+        xmax = xs[-1]
+        z = xs - xmax
+        if n > M:
+            cutoff[i] = xs[n - M - 1]
+            c = max(z[n - M - 1], log_min)
+            in_tail = z > c
+        else:
+            c = dtype(np.inf)
+            in_tail = np.zeros(n, dtype=bool)
+        tail, body = z[in_tail], z[~in_tail]
+        L = tail.size
+        tail_len[i] = L
+        zt = tail.copy()
+        if L >= 5:
+            ec = np.exp(c)
+            t = np.exp(tail) - ec
+            m = 30 + int(math.floor(math.sqrt(L)))
+            q = int(math.floor(L / 4.0 + 0.5))
+            j = np.arange(1, m + 1).astype(dtype)
+            theta = (1 - np.sqrt(dtype(m) / (j - dtype(0.5)))) / (3 * t[q - 1]) + 1 / t[L - 1]
+            k = np.array([np.mean(np.log1p(-th * t)) for th in theta], dtype=dtype)
+            ell = L * (np.log(-theta / k) - k - 1)
+            w = np.array([1 / np.sum(np.exp(ell - lj)) for lj in ell], dtype=dtype)
+            w = np.where(w < eps10, dtype(0), w)
+            w = w / np.sum(w)
+            that = np.sum(w * theta)
+            kk = np.mean(np.log1p(-that * t))
+            sigma = -kk / that
+            kh = (L * kk + 5) / (L + 10)
+            khat[i] = kh
+            if np.isfinite(kh):
+                lp = np.log1p(-(np.arange(1, L + 1).astype(dtype) - dtype(0.5)) / L)
+                inner = -sigma * lp if kh == 0 else sigma / kh * np.expm1(-kh * lp)
+                zt = np.minimum(np.log(inner + ec), dtype(0))
+        elpd[i] = np.log(dtype(body.size) + np.sum(np.exp(zt - tail))) - xmax - np.log(np.sum(np.exp(body)) + np.sum(np.exp(zt)))
+    return dict(elpd_loo=elpd, pareto_k=khat, cutoff=cutoff, tail_len=tail_len)
+
+
+def x_of(rows, y, like=0, p=1.0, sigma=None, dtype=LD):
+    """-l of every accepted sample and bin from model rows, in the reference's own arithmetic."""
+    Mq, yq = np.asarray(rows).astype(dtype), np.asarray(y).astype(dtype)
+    if like == 0:
+        return dtype(float(int(p))) * (yq / Mq + np.log(Mq))                 # `long p`, likelihoods.cpp:17
+    return ((yq - Mq) ** 2) / np.asarray(sigma).astype(dtype) ** 2          # the reference's convention: no factor 1/2
+
+
+def perturbed(x, rel, seed, groups):
+    """x (1 + rel s), s = +-1, one sign per distinct row and bin."""
+    rng = np.random.default_rng(seed)
+    s = rng.integers(0, 2, size=(int(groups.max()) + 1, x.shape[1])) * 2 - 1
+    return x * (1 + x.dtype.type(rel) * s[groups].astype(x.dtype))
+
+
+def change(a, b):
+    """max over the bins of |a - b| where both are finite; where either is not, both must agree."""
+    fa, fb = np.isfinite(a), np.isfinite(b)
+    if not np.array_equal(fa, fb):
+        return np.inf
+    return float(np.max(np.abs(a[fa].astype(LD) - b[fa].astype(LD)))) if fa.any() else 0.0
+
+
+def check_loo_reference(tag, res, x_ld, groups, rel, seeds, x64=None, totals=True):
+    """res against psis_reference(x_ld) with the bounds of the module docstring.  Returns the reference."""
+    ref = psis_reference(x_ld)
+    d = dict(elpd_loo=0.0, pareto_k=0.0)
+    for seed in seeds:
+        pert = psis_reference(perturbed(x_ld, rel, seed, groups))
+        for k in d:
+            d[k] = max(d[k], change(pert[k], ref[k]))
+    if x64 is not None:
+        r64 = psis_reference(x64, np.float64)
+        for k in d:
+            d[k] = max(d[k], change(r64[k], ref[k]))
+    for k, dk in d.items():                                                  # change() gives inf when two reference runs disagree
+        assert np.isfinite(dk), (tag, k, "the reference runs disagree on where the value is finite: the case has no bound")
+    assert np.array_equal(res["tail_len"], ref["tail_len"]), (tag, "tail_len")
+    assert np.array_equal(np.isinf(res["pareto_k"]), np.isinf(ref["pareto_k"])), (tag, "where k-hat is +inf")
+    ratios = {}
+    for k, dk in d.items():
+        err = change(np.asarray(res[k]), ref[k])
+        ratios[k] = err / (10.0 * dk) if dk > 0 else (0.0 if err == 0 else np.inf)
+    print(f"RATIO loo {tag}: " + " ".join(f"{k}={v:.3g} (bound {10.0 * d[k]:.3g})" for k, v in ratios.items()))
+    for k, v in ratios.items():
+        assert v <= 1.0, (tag, k, v)
+    if not totals:
+        return ref
+    # totals: the sums of what was just checked, in long double
+    e = np.asarray(res["elpd_loo"]).astype(LD).sum()
+    assert res["elpd_loo_total"] == float(e) and res["looic"] == float(-2 * e), tag
+    kh = np.asarray(res["pareto_k"])
+    assert res["n_k_high"] == int((kh > 0.7).sum()) and res["n_k_inf"] == int(np.isposinf(kh).sum()), tag
+    assert res["k_max"] == np.nanmax(kh), tag
+    return ref
+
+
+# ---- ESS and band ESS: the passes and the checks of the lag products and the finish ----
+
+def run_ess(acc, pushes, max_lag=0, block=0, ess_pushes=None, acov=True):
+    """Fold pass over `pushes`, ESS pass over `ess_pushes` (default: the same pushes).  Returns the dict of ess_result()
+    with acov_M, acov_l, the fold result under "fold" and the logL / status of both passes."""
+    with capi.Summary(acc, block) as s:
+        out0 = [s.push(P) for P in pushes]
+        fold = s.result()
+        lag = s.ess_begin(max_lag)
+        out1 = [s.push(P) for P in (pushes if ess_pushes is None else ess_pushes)]
+        r = s.ess_result()
+        assert r["lag"] == lag
+        if acov:
+            r["acov_M"], r["acov_l"] = s.ess_acov(0), s.ess_acov(1)
+        assert same(s.result(), fold), "the fold results changed in ESS mode"
+        s.ess_end()
+    r["fold"] = fold
+    for k, o in (("fold_out", out0), ("ess_out", out1)):
+        r[k] = (np.concatenate([a[0] for a in o]), np.concatenate([a[1] for a in o]))
+    return r
+
+
+def ulps(a, b):
+    """max |a - b| in ulps of b; NaN must meet NaN."""
+    a, b = np.asarray(a, dtype=np.float64), np.asarray(b, dtype=np.float64)
+    assert np.array_equal(np.isnan(a), np.isnan(b))
+    ok = ~np.isnan(b)
+    if not ok.any():
+        return 0.0
+    with np.errstate(invalid="ignore"):
+        d = np.where(a[ok] == b[ok], 0.0, np.abs(a[ok] - b[ok]) / np.spacing(np.abs(b[ok])))
+    return float(np.max(d))
+
+
+ESS_WORST = {}
+
+
+def check_acov(tag, res, rows, y, like=0, p=1.0, sigma=None, sel=None):
+    """Case 1: ess_acov against the long-double lag products of the GPU's own rows (on the bins `sel`)."""
+    sel = np.arange(rows.shape[1]) if sel is None else np.asarray(sel)
+    fold, L = res["fold"], res["lag"]
+    sg = None if sigma is None else sigma[sel]
+    a, u, e_a, e_u = R.series(rows[:, sel], y[sel], fold["mean_M"][sel], fold["lppd"][sel], like, p, sg)
+    ratios = {}
+    for name, d, e in (("acov_M", a, e_a), ("acov_l", u, e_u)):
+        A, bound = R.lag_products(d, e, L)
+        got = res[name][:, sel]
+        assert got.shape == A.shape and np.all(np.isfinite(got)), (tag, name)
+        err = np.abs(got.astype(LD) - A).astype(np.float64)
+        with np.errstate(invalid="ignore", divide="ignore"):
+            ratio = np.where(bound > 0, err / (10.0 * bound), np.where(err == 0, 0.0, np.inf))
+        ratios[name] = float(ratio.max())
+    print(f"RATIO ess {tag} L={L}: " + " ".join(f"{k}={v:.3g}" for k, v in ratios.items()))
+    for k, v in ratios.items():
+        ESS_WORST[k] = max(ESS_WORST.get(k, 0.0), v)
+        assert v <= 1.0, (tag, k, v)
+
+
+def check_finish(tag, res, rows=None):
+    """Case 2: the finish in numpy float64 on the library's own lag products, and the totals."""
+    fold, n, L = res["fold"], res["n_used"], res["lag"]
+    assert n == fold["n_used"] and res["n_rejected"] == fold["n_rejected"] and L == res["acov_M"].shape[0] - 1
+    tau_M, ess_M, cut_M = R.finish(res["acov_M"], n)
+    _, ess_l, cut_l = R.finish(res["acov_l"], n)
+    assert np.array_equal(res["cut_M"], cut_M) and np.array_equal(res["cut_l"], cut_l), tag
+    with np.errstate(invalid="ignore"):
+        want = dict(tau_M=tau_M, ess_M=ess_M, ess_l=ess_l, mcse_M=np.sqrt(fold["var_M"] / ess_M), r_eff=ess_l / np.float64(n))
+    worst = {k: ulps(res[k], v) for k, v in want.items()}
+    print(f"ULPS ess {tag} L={L}: " + " ".join(f"{k}={v:.3g}" for k, v in worst.items()))
+    for k, v in worst.items():
+        assert v <= 4.0, (tag, k, v)
+    if rows is not None:
+        ref = R.rhat(rows)
+        got = np.asarray(res["rhat_M"]).astype(LD)
+        assert np.array_equal(np.isnan(got), np.isnan(ref)), tag
+        ok = ~np.isnan(ref)
+        rel = float(np.max(np.abs(got[ok] - ref[ok]) / ref[ok])) if ok.any() else 0.0
+        print(f"RHAT ess {tag}: max relative difference {rel:.3g}")
+        assert rel <= 1e-12, (tag, rel)
+    # totals: the first bin wins a tie, a NaN is skipped
+
+    def first(v, fn):
+        v = np.asarray(v, dtype=np.float64)
+        if np.all(np.isnan(v)):
+            return np.nan, -1
+        k = int(fn(np.where(np.isnan(v), -np.inf if fn is np.argmax else np.inf, v)))
+        return v[k], k
+    for key, arr, fn in (("min_ess_M", res["ess_M"], np.argmin), ("min_ess_l", res["ess_l"], np.argmin), ("max_rhat", res["rhat_M"], np.argmax)):
+        v, k = first(arr, fn)
+        assert bits(res[key]) == bits(v) and res["bin_" + key] == k, (tag, key)
+    assert res["n_truncated_M"] == int((res["cut_M"] == L + 1).sum()) and res["n_truncated_l"] == int((res["cut_l"] == L + 1).sum()), tag
+    with np.errstate(invalid="ignore"):
+        assert res["n_rhat_high"] == int((res["rhat_M"] > 1.01).sum()), tag
+
+
+def band_pass(s, pushes, thr, max_lag=0, counts=True):
+    """One pass inside an open summary: begin, the pushes, result (and counts), end."""
+    lag = s.bandess_begin(thr, max_lag)
+    out = [s.push(P) for P in pushes]
+    r = s.bandess_result()
+    assert r["lag"] == lag
+    if counts:
+        ce = [s.bandess_counts(j) for j in range(r["n_thresholds"])]
+        r["C"], r["E"] = [a for a, _ in ce], [b for _, b in ce]
+    s.bandess_end()
+    r["band_out"] = (np.concatenate([a[0] for a in out]), np.concatenate([a[1] for a in out]))
+    return r
+
+
+def order_stats(rows, levels):
+    return np.sort(rows, axis=0)[ranks_of(levels, len(rows))]
 
 
 # ---- the command-line tool ----

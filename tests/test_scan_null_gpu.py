@@ -10,6 +10,8 @@ independent numpy restatement of tests/scan_null_reference.py.
                 the shape, relative to max(1, |value|).
 4. independence replicate r has the same bits in runs of 1, 7 and 50, across run calls split any way, whichever other widths
                 are in the list, and in an object created at first_replicate = r.
+4b. long grid   131 073 bins, eight widths: 65 tiles, and replicate chunks of 4032 set by the 64 MiB of partials, not by the cap of
+                4096; variates, extremes and split independence across that chunk edge.
 5. distribution Kolmogorov distance to the exact law below 1.63 / sqrt(R), R = 2000, seed 3, in three cases.
 6. calibration  line and pvalue equal the counting rule restated in numpy on the returned min_log, exactly; joint <= per-width
                 <= the library's default line at Nx = 5000, widths (10, 20, 40), p = 1, R = 1000, seed 3.
@@ -176,6 +178,52 @@ def test_a_replicate_depends_on_nothing_else(accel_mod, like, p):
     with accel_mod.ScanNull(like, p, Nx, widths, seed + 1) as other:
         other.run(1)
         assert not same_bits(other.result(0, 0)["ext_sum"], full[0][0]["ext_sum"][:1])
+
+
+# ---- 4b. a long grid: the chunk set by the memory of the partials ----
+
+LONG_NX, LONG_WIDTHS, LONG_R = 131073, (1, 10, 20, 40, 64, 128, 256, 512), 4100
+
+
+def long_chunk():
+    """tmn_chunk (tamcmc_scan_null.h) restated: 64 MiB of partials at 2 K tiles (value, position) pairs of 16 bytes a
+    replicate, at most 2^30 threads a launch of 256-thread workgroups, at most 4096."""
+    K, tiles = len(LONG_WIDTHS), -(-(LONG_NX - LONG_WIDTHS[0] + 1) // 2048)
+    return K * tiles, max(1, min((64 << 20) // (2 * K * tiles * 16), (1 << 30) // (tiles * 256), 4096))
+
+
+@pytest.mark.parametrize("like", [0, 1], ids=["chi22p", "chi-square"])
+def test_a_long_grid_in_chunks_set_by_memory(accel_mod, like):
+    """131 073 bins with a narrowest width of 1 are 65 tiles; with eight widths K tiles = 520 > 512, so the memory rule and
+    not the cap of 4096 sets the chunk: floor(2^21 / 520) = 4032 replicates.  One run of 4100 is a chunk of 4032 and one of 68.
+    The replicates on both sides of that edge (and of 4033, where the edge would be with one pair less in the rule) have the
+    reference's variates within the suite's bound and the extremes of the library's own variates bit for bit; the same seed
+    run as the two chunks by hand, and as 41 runs of 100, gives the same bits in every replicate."""
+    kt, C = long_chunk()
+    assert kt == 520 and C == 4032 and 0 < LONG_R - C < C
+    reps = sorted({0, C - 1, C, C + 1, 4033, LONG_R - 1})
+    with accel_mod.ScanNull(like, 1, LONG_NX, LONG_WIDTHS, 31) as null:
+        assert null.run(LONG_R) == LONG_R
+        full = null_results(null)
+        worst = 0.0
+        for r in reps:
+            q = null.variates(r)
+            want, sens = R.variates(like, 1, LONG_NX, 31, r)
+            assert np.all(np.isfinite(q)) and np.all(sens > 0)
+            ratio = float(np.max(np.abs(q.astype(R.LD) - want) / (10.0 * sens)))
+            worst = max(worst, ratio)
+            print(f"RATIO scan-null long grid variates like={like} replicate={r}: {ratio:.3g}")
+            for k, W in enumerate(LONG_WIDTHS):
+                smax, amax, smin, amin = R.extremes(q, W)
+                assert same_bits(full[k][0]["ext_sum"][r], smax) and full[k][0]["pos"][r] == amax, (W, r, "max")
+                assert same_bits(full[k][1]["ext_sum"][r], smin) and full[k][1]["pos"][r] == amin, (W, r, "min")
+        assert worst <= 1.0, (like, worst)
+    for runs in ([C, LONG_R - C], [100] * 41):
+        with accel_mod.ScanNull(like, 1, LONG_NX, LONG_WIDTHS, 31) as null:
+            for n in runs:
+                null.run(n)
+            assert null.replicates == LONG_R
+            assert same_results(full, null_results(null)), runs[:2]
 
 
 # ---- 5. distribution ----

@@ -26,7 +26,7 @@ import pytest
 
 import bandess_reference as B
 import ess_reference as R
-from summary_support import Q8, c2_chain, gpu_rows, ranks_of, same, same_scans, spectrum_for
+from summary_support import Q8, band_pass, c2_chain, gpu_rows, order_stats, ranks_of, same, same_scans, spectrum_for
 from support import bits, in_torch_process
 from tamcmc_amd import capi, synth
 
@@ -35,20 +35,6 @@ pytestmark = pytest.mark.gpu
 PRED_KEYS = capi.Summary.PREDICTIVE_ARRAYS + capi.Summary.PREDICTIVE_TOTALS + ("pit_hist",)
 WIN_KEYS = capi.Summary.WINDOW_ARRAYS + capi.Summary.WINDOW_TOTALS + ("pit_hist",)
 LEVELS = (0.5, 0.025, 0.975, 0.16, 0.84, 0.3, 1.0, 0.0)    # case 1's thresholds: order statistics of the rows, so `<=` meets equality
-
-
-def band_pass(s, pushes, thr, max_lag=0, counts=True):
-    """One pass inside an open summary: begin, the pushes, result (and counts), end."""
-    lag = s.bandess_begin(thr, max_lag)
-    out = [s.push(P) for P in pushes]
-    r = s.bandess_result()
-    assert r["lag"] == lag
-    if counts:
-        ce = [s.bandess_counts(j) for j in range(r["n_thresholds"])]
-        r["C"], r["E"] = [a for a, _ in ce], [b for _, b in ce]
-    s.bandess_end()
-    r["band_out"] = (np.concatenate([a[0] for a in out]), np.concatenate([a[1] for a in out]))
-    return r
 
 
 def run_band(acc, pushes, thr, max_lag=0, block=0, band_pushes=None, counts=True):
@@ -61,10 +47,6 @@ def run_band(acc, pushes, thr, max_lag=0, block=0, band_pushes=None, counts=True
     r["fold"] = fold
     r["fold_out"] = (np.concatenate([a[0] for a in out0]), np.concatenate([a[1] for a in out0]))
     return r
-
-
-def order_stats(rows, levels):
-    return np.sort(rows, axis=0)[ranks_of(levels, len(rows))]
 
 
 LAGS = (1, 3, 15, 63, 65, 127, 129, 255, 1023)

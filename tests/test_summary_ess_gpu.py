@@ -24,8 +24,8 @@ import numpy as np
 import pytest
 
 import ess_reference as R
-from summary_support import c2_chain, gpu_rows, same, spectrum_for
-from support import LD, bits, in_torch_process
+from summary_support import c2_chain, check_acov, check_finish, gpu_rows, run_ess, same, spectrum_for
+from support import bits, in_torch_process
 from tamcmc_amd import capi, synth
 
 pytestmark = pytest.mark.gpu
@@ -36,103 +36,10 @@ PRED_KEYS = capi.Summary.PREDICTIVE_ARRAYS + capi.Summary.PREDICTIVE_TOTALS + ("
 WIN_KEYS = capi.Summary.WINDOW_ARRAYS + capi.Summary.WINDOW_TOTALS + ("pit_hist",)
 
 
-def run_ess(acc, pushes, max_lag=0, block=0, ess_pushes=None, acov=True):
-    """Fold pass over `pushes`, ESS pass over `ess_pushes` (default: the same pushes).  Returns the dict of ess_result()
-    with acov_M, acov_l, the fold result under "fold" and the logL / status of both passes."""
-    with capi.Summary(acc, block) as s:
-        out0 = [s.push(P) for P in pushes]
-        fold = s.result()
-        lag = s.ess_begin(max_lag)
-        out1 = [s.push(P) for P in (pushes if ess_pushes is None else ess_pushes)]
-        r = s.ess_result()
-        assert r["lag"] == lag
-        if acov:
-            r["acov_M"], r["acov_l"] = s.ess_acov(0), s.ess_acov(1)
-        assert same(s.result(), fold), "the fold results changed in ESS mode"
-        s.ess_end()
-    r["fold"] = fold
-    for k, o in (("fold_out", out0), ("ess_out", out1)):
-        r[k] = (np.concatenate([a[0] for a in o]), np.concatenate([a[1] for a in o]))
-    return r
-
-
 def same_ess(r1, r2, skip=()):
     keys = [k for k in ESS_KEYS + ESS_TOTALS + ("acov_M", "acov_l") if k not in skip and k in r1 and k in r2]
     return all(np.array_equal(bits(np.asarray(r1[k], dtype=np.float64)), bits(np.asarray(r2[k], dtype=np.float64))) for k in keys) and \
         all(np.asarray(r1[k]).shape == np.asarray(r2[k]).shape for k in keys)
-
-
-def ulps(a, b):
-    """max |a - b| in ulps of b; NaN must meet NaN."""
-    a, b = np.asarray(a, dtype=np.float64), np.asarray(b, dtype=np.float64)
-    assert np.array_equal(np.isnan(a), np.isnan(b))
-    ok = ~np.isnan(b)
-    if not ok.any():
-        return 0.0
-    with np.errstate(invalid="ignore"):
-        d = np.where(a[ok] == b[ok], 0.0, np.abs(a[ok] - b[ok]) / np.spacing(np.abs(b[ok])))
-    return float(np.max(d))
-
-
-WORST = {}
-
-
-def check_acov(tag, res, rows, y, like=0, p=1.0, sigma=None, sel=None):
-    """Case 1: ess_acov against the long-double lag products of the GPU's own rows (on the bins `sel`)."""
-    sel = np.arange(rows.shape[1]) if sel is None else np.asarray(sel)
-    fold, L = res["fold"], res["lag"]
-    sg = None if sigma is None else sigma[sel]
-    a, u, e_a, e_u = R.series(rows[:, sel], y[sel], fold["mean_M"][sel], fold["lppd"][sel], like, p, sg)
-    ratios = {}
-    for name, d, e in (("acov_M", a, e_a), ("acov_l", u, e_u)):
-        A, bound = R.lag_products(d, e, L)
-        got = res[name][:, sel]
-        assert got.shape == A.shape and np.all(np.isfinite(got)), (tag, name)
-        err = np.abs(got.astype(LD) - A).astype(np.float64)
-        with np.errstate(invalid="ignore", divide="ignore"):
-            ratio = np.where(bound > 0, err / (10.0 * bound), np.where(err == 0, 0.0, np.inf))
-        ratios[name] = float(ratio.max())
-    print(f"RATIO ess {tag} L={L}: " + " ".join(f"{k}={v:.3g}" for k, v in ratios.items()))
-    for k, v in ratios.items():
-        WORST[k] = max(WORST.get(k, 0.0), v)
-        assert v <= 1.0, (tag, k, v)
-
-
-def check_finish(tag, res, rows=None):
-    """Case 2: the finish in numpy float64 on the library's own lag products, and the totals."""
-    fold, n, L = res["fold"], res["n_used"], res["lag"]
-    assert n == fold["n_used"] and res["n_rejected"] == fold["n_rejected"] and L == res["acov_M"].shape[0] - 1
-    tau_M, ess_M, cut_M = R.finish(res["acov_M"], n)
-    _, ess_l, cut_l = R.finish(res["acov_l"], n)
-    assert np.array_equal(res["cut_M"], cut_M) and np.array_equal(res["cut_l"], cut_l), tag
-    with np.errstate(invalid="ignore"):
-        want = dict(tau_M=tau_M, ess_M=ess_M, ess_l=ess_l, mcse_M=np.sqrt(fold["var_M"] / ess_M), r_eff=ess_l / np.float64(n))
-    worst = {k: ulps(res[k], v) for k, v in want.items()}
-    print(f"ULPS ess {tag} L={L}: " + " ".join(f"{k}={v:.3g}" for k, v in worst.items()))
-    for k, v in worst.items():
-        assert v <= 4.0, (tag, k, v)
-    if rows is not None:
-        ref = R.rhat(rows)
-        got = np.asarray(res["rhat_M"]).astype(LD)
-        assert np.array_equal(np.isnan(got), np.isnan(ref)), tag
-        ok = ~np.isnan(ref)
-        rel = float(np.max(np.abs(got[ok] - ref[ok]) / ref[ok])) if ok.any() else 0.0
-        print(f"RHAT ess {tag}: max relative difference {rel:.3g}")
-        assert rel <= 1e-12, (tag, rel)
-    # totals: the first bin wins a tie, a NaN is skipped
-
-    def first(v, fn):
-        v = np.asarray(v, dtype=np.float64)
-        if np.all(np.isnan(v)):
-            return np.nan, -1
-        k = int(fn(np.where(np.isnan(v), -np.inf if fn is np.argmax else np.inf, v)))
-        return v[k], k
-    for key, arr, fn in (("min_ess_M", res["ess_M"], np.argmin), ("min_ess_l", res["ess_l"], np.argmin), ("max_rhat", res["rhat_M"], np.argmax)):
-        v, k = first(arr, fn)
-        assert bits(res[key]) == bits(v) and res["bin_" + key] == k, (tag, key)
-    assert res["n_truncated_M"] == int((res["cut_M"] == L + 1).sum()) and res["n_truncated_l"] == int((res["cut_l"] == L + 1).sum()), tag
-    with np.errstate(invalid="ignore"):
-        assert res["n_rhat_high"] == int((res["rhat_M"] > 1.01).sum()), tag
 
 
 @pytest.mark.parametrize("n", [4, 5, 64, 1000])

@@ -37,9 +37,9 @@ import numpy as np
 import pytest
 
 import workloads as W
-from summary_support import (Q8, check, gpu_rows, ranks_of, reference, same, same_traj, select, sigma_of, spectrum_for, summarize,
-                             truth_of, unresolved_bits)
-from support import LD, bits
+from summary_support import (Q8, accumulation_reference, check, gpu_rows, ranks_of, reference, rows_around, same, same_traj, select, sigma_of, spectrum_for,
+                             steps, summarize, truth_of, unresolved_bits)
+from support import bits
 from tamcmc_amd import capi, synth
 
 pytestmark = pytest.mark.gpu
@@ -48,15 +48,6 @@ N = 70001
 RUN = 65535                                              # TM_Q_RUN, tamcmc_quantile.h
 Q5 = (0.0, 0.16, 0.5, 0.84, 1.0)
 ULP = 2.0 ** -52
-
-
-def rows_around(w, n, seed=20261, scale=0.5):
-    """As chains_around (tests/test_group_gpu.py): row 0 is the truth, the others the truth + scale err normal."""
-    rng = np.random.default_rng(seed)
-    idx = w["index_to_relax"]
-    P = np.tile(w["params_true"], (n, 1))
-    P[1:, idx] += scale * w["err"][None, :] * rng.standard_normal((n - 1, idx.size))
-    return P
 
 
 @functools.lru_cache(maxsize=None)
@@ -107,32 +98,6 @@ def test_fold_against_the_oracle(accel_mod, like):
     check(f"n={N} fold vs oracle like={like}", res, ref, bound)
 
 
-def accumulation_reference(M, y, sigma, like, p=1.0):
-    """reference() of tests/summary_support.py on given rows with EPS = 0, plus the rounding of l (module docstring)."""
-    n = len(M)
-    Mq, yq = M.astype(LD), y.astype(LD)
-    if like == 0:
-        l = -p * (yq / Mq + np.log(Mq))
-        dl = 2.0 * ULP * p * (yq / Mq + np.abs(np.log(Mq)))
-    else:
-        l = -((yq - Mq) ** 2) / sigma.astype(LD) ** 2
-        dl = 3.0 * ULP * np.abs(l)
-    acc = n * ULP
-    mean_M, mean_l = Mq.mean(axis=0), l.mean(axis=0)
-    a = l.max(axis=0)
-    ref = dict(n_used=n, n_rejected=0, mean_M=mean_M, min_M=Mq.min(axis=0), max_M=Mq.max(axis=0), mean_l=mean_l,
-               lppd=a + np.log(np.exp(l - a).sum(axis=0) / n))
-    delta = dl.max(axis=0) + acc * np.abs(l).max(axis=0)
-    ref["var_M"] = ((Mq - mean_M) ** 2).sum(axis=0) / (n - 1)
-    ref["var_l"] = ((l - mean_l) ** 2).sum(axis=0) / (n - 1)
-    bound = dict(mean_M=acc * np.abs(Mq).mean(axis=0), mean_l=delta, lppd=delta, var_M=4.0 * acc * (Mq ** 2).mean(axis=0),
-                 var_l=2.0 * delta * np.sqrt(ref["var_l"]) + delta ** 2)
-    ref["lppd_total"], bound["lppd_total"] = ref["lppd"].sum(), delta.sum()
-    ref["p_waic"], bound["p_waic"] = ref["var_l"].sum(), bound["var_l"].sum()
-    ref["waic"], bound["waic"] = -2.0 * (ref["lppd_total"] - ref["p_waic"]), 2.0 * (bound["lppd_total"] + bound["p_waic"])
-    return ref, bound
-
-
 @pytest.mark.parametrize("like", [0, 1], ids=["chi22p", "chi-square"])
 def test_accumulation_alone(accel_mod, like):
     _, y, P = case()
@@ -158,21 +123,6 @@ def test_block_size_cannot_change_a_bit(accel_mod):
                 res, logL, st = summarize(acc, pushes, B)
                 assert same(res, first), ("block_chains", B, len(pushes))
                 assert np.array_equal(bits(logL), bits(logL0)) and np.array_equal(st, st0), ("block_chains", B, len(pushes))
-
-
-def steps(s, q, nbits, push_pass, truth, limit):
-    """select() of tests/summary_support.py, ended after `limit` steps: the trajectory so far."""
-    s.quantiles_begin(q, nbits)
-    r = s.quantiles_result()
-    traj = [(r["lo"], r["hi"])]
-    for k in range(limit):
-        push_pass(k)
-        s.quantiles_step()
-        r = s.quantiles_result()
-        assert np.all(r["lo"] <= truth) and np.all(truth <= r["hi"]), f"step {k + 1}: the bracket lost the truth"
-        traj.append((r["lo"], r["hi"]))
-    s.quantiles_end()
-    return traj
 
 
 @pytest.mark.parametrize("nbits", [1, 6])

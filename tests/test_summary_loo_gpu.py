@@ -2,7 +2,7 @@
 leave-one-out log predictive density by Pareto-smoothed importance sampling and the Pareto shape k-hat, from one more pass
 over the samples of the fold pass.
 
-Reference: psis_reference() below, an independent numpy transcription of the definition in the header, run in long double.
+Reference: psis_reference() of tests/summary_support.py, an independent numpy transcription of the definition in the header, run in long double.
 
 Exact checks (no tolerance): the library's own l_is, bit for bit, is mean_l of a summary that folded that sample alone; the
 cutoff must be the (M+1)-th largest -l, bit for bit -- which also pins that the tail kernel's restated formulas for l agree
@@ -23,15 +23,15 @@ Worst ratios observed on an MI355X over all cases below: on the GPU's own rows e
 70 001-sample one among them), k-hat 0.070 (likelihood_p = 2); on the oracle's rows elpd_loo 1.5e-4 (triples), k-hat
 2.3e-5 (700 bins, 200 samples, scale 3).
 """
-import math
 import subprocess
 
 import numpy as np
 import pytest
 
 import workloads as W
-from summary_support import (c2_case, c2_chain, f12, gpu_rows, header_values, other_cases, row_groups, same, spectrum_for,
-                             stored_chain)
+from summary_support import (c2_case, c2_chain, f12, gpu_rows, header_values, other_cases, row_groups,
+                             same, spectrum_for, stored_chain, tail_M, x_of)
+from summary_support import check_loo_reference as check_reference
 from support import LD, bits, in_torch_process, pyorc
 from tamcmc_amd import capi, synth
 
@@ -39,116 +39,6 @@ pytestmark = pytest.mark.gpu
 
 LOO_KEYS = ("elpd_loo", "pareto_k", "cutoff", "tail_len")
 LOO_TOTALS = capi.Summary.LOO_TOTALS
-
-
-def tail_M(n):
-    return int(math.ceil(min(n / 5.0, 3.0 * math.sqrt(float(n)))))
-
-
-def psis_reference(x, dtype=LD):
-    """The definition, per bin.  x: (n, Nx) values of -l.  Returns elpd_loo, pareto_k, cutoff (dtype) and tail_len."""
-    x = np.asarray(x, dtype=dtype)
-    n, nx = x.shape
-    M = tail_M(n)
-    log_min = np.log(dtype(np.finfo(np.float64).tiny))
-    eps10 = dtype(10.0 * 2.0 ** -52)
-    elpd, khat, cutoff = np.empty(nx, dtype=dtype), np.full(nx, np.inf, dtype=dtype), np.full(nx, np.nan, dtype=dtype)
-    tail_len = np.zeros(nx, dtype=np.int32)
-    for i in range(nx):
-        xs = np.sort(x[:, i])
-        xmax = xs[-1]
-        z = xs - xmax
-        if n > M:
-            cutoff[i] = xs[n - M - 1]
-            c = max(z[n - M - 1], log_min)
-            in_tail = z > c
-        else:
-            c = dtype(np.inf)
-            in_tail = np.zeros(n, dtype=bool)
-        tail, body = z[in_tail], z[~in_tail]
-        L = tail.size
-        tail_len[i] = L
-        zt = tail.copy()
-        if L >= 5:
-            ec = np.exp(c)
-            t = np.exp(tail) - ec
-            m = 30 + int(math.floor(math.sqrt(L)))
-            q = int(math.floor(L / 4.0 + 0.5))
-            j = np.arange(1, m + 1).astype(dtype)
-            theta = (1 - np.sqrt(dtype(m) / (j - dtype(0.5)))) / (3 * t[q - 1]) + 1 / t[L - 1]
-            k = np.array([np.mean(np.log1p(-th * t)) for th in theta], dtype=dtype)
-            ell = L * (np.log(-theta / k) - k - 1)
-            w = np.array([1 / np.sum(np.exp(ell - lj)) for lj in ell], dtype=dtype)
-            w = np.where(w < eps10, dtype(0), w)
-            w = w / np.sum(w)
-            that = np.sum(w * theta)
-            kk = np.mean(np.log1p(-that * t))
-            sigma = -kk / that
-            kh = (L * kk + 5) / (L + 10)
-            khat[i] = kh
-            if np.isfinite(kh):
-                lp = np.log1p(-(np.arange(1, L + 1).astype(dtype) - dtype(0.5)) / L)
-                inner = -sigma * lp if kh == 0 else sigma / kh * np.expm1(-kh * lp)
-                zt = np.minimum(np.log(inner + ec), dtype(0))
-        elpd[i] = np.log(dtype(body.size) + np.sum(np.exp(zt - tail))) - xmax - np.log(np.sum(np.exp(body)) + np.sum(np.exp(zt)))
-    return dict(elpd_loo=elpd, pareto_k=khat, cutoff=cutoff, tail_len=tail_len)
-
-
-def x_of(rows, y, like=0, p=1.0, sigma=None, dtype=LD):
-    """-l of every accepted sample and bin from model rows, in the reference's own arithmetic."""
-    Mq, yq = np.asarray(rows).astype(dtype), np.asarray(y).astype(dtype)
-    if like == 0:
-        return dtype(float(int(p))) * (yq / Mq + np.log(Mq))                 # `long p`, likelihoods.cpp:17
-    return ((yq - Mq) ** 2) / np.asarray(sigma).astype(dtype) ** 2          # the reference's convention: no factor 1/2
-
-
-def perturbed(x, rel, seed, groups):
-    """x (1 + rel s), s = +-1, one sign per distinct row and bin."""
-    rng = np.random.default_rng(seed)
-    s = rng.integers(0, 2, size=(int(groups.max()) + 1, x.shape[1])) * 2 - 1
-    return x * (1 + x.dtype.type(rel) * s[groups].astype(x.dtype))
-
-
-def change(a, b):
-    """max over the bins of |a - b| where both are finite; where either is not, both must agree."""
-    fa, fb = np.isfinite(a), np.isfinite(b)
-    if not np.array_equal(fa, fb):
-        return np.inf
-    return float(np.max(np.abs(a[fa].astype(LD) - b[fa].astype(LD)))) if fa.any() else 0.0
-
-
-def check_reference(tag, res, x_ld, groups, rel, seeds, x64=None, totals=True):
-    """res against psis_reference(x_ld) with the bounds of the module docstring.  Returns the reference."""
-    ref = psis_reference(x_ld)
-    d = dict(elpd_loo=0.0, pareto_k=0.0)
-    for seed in seeds:
-        pert = psis_reference(perturbed(x_ld, rel, seed, groups))
-        for k in d:
-            d[k] = max(d[k], change(pert[k], ref[k]))
-    if x64 is not None:
-        r64 = psis_reference(x64, np.float64)
-        for k in d:
-            d[k] = max(d[k], change(r64[k], ref[k]))
-    for k, dk in d.items():                                                  # change() gives inf when two reference runs disagree
-        assert np.isfinite(dk), (tag, k, "the reference runs disagree on where the value is finite: the case has no bound")
-    assert np.array_equal(res["tail_len"], ref["tail_len"]), (tag, "tail_len")
-    assert np.array_equal(np.isinf(res["pareto_k"]), np.isinf(ref["pareto_k"])), (tag, "where k-hat is +inf")
-    ratios = {}
-    for k, dk in d.items():
-        err = change(np.asarray(res[k]), ref[k])
-        ratios[k] = err / (10.0 * dk) if dk > 0 else (0.0 if err == 0 else np.inf)
-    print(f"RATIO loo {tag}: " + " ".join(f"{k}={v:.3g} (bound {10.0 * d[k]:.3g})" for k, v in ratios.items()))
-    for k, v in ratios.items():
-        assert v <= 1.0, (tag, k, v)
-    if not totals:
-        return ref
-    # totals: the sums of what was just checked, in long double
-    e = np.asarray(res["elpd_loo"]).astype(LD).sum()
-    assert res["elpd_loo_total"] == float(e) and res["looic"] == float(-2 * e), tag
-    kh = np.asarray(res["pareto_k"])
-    assert res["n_k_high"] == int((kh > 0.7).sum()) and res["n_k_inf"] == int(np.isposinf(kh).sum()), tag
-    assert res["k_max"] == np.nanmax(kh), tag
-    return ref
 
 
 def run_loo(acc, pushes, block=0):
