@@ -287,6 +287,45 @@ int tamcmc_group_members(const tamcmc_group *g, int32_t *n_members, int32_t *Npa
  *                _result and _end outside the mode return TAMCMC_E_INVALID.
  *   profile / kernel_time in LOO mode: the tail kernel of every block, and the finalize kernel of every loo_result.
  *
+ * LOO-PIT: the leave-one-out probability integral transform (ArviZ's loo_pit).  The posterior predictive check below uses
+ * each datum twice -- bin i's PIT is averaged over a posterior that was fitted to bin i -- so a narrow Lorentzian parked on
+ * one noise spike looks calibrated there.  Here the same predictive tails are averaged with the Pareto-smoothed importance
+ * weights of PSIS-LOO, and the same pass gives Kish's effective sample size of those weights, the diagnostic the `loo`
+ * literature expects beside k-hat.  A sub-mode of LOO mode: after a complete LOO pass the caller pushes the SAME samples a
+ * third time.  A stored MCMC chain repeats a row at every rejected proposal, so exact ties in the tail are the normal case.
+ *   Definition, per bin i, with xmax, c, the tail T of length L, z_(j) ascending, k-hat and the smoothed zt_(j) of steps 1-3
+ *   above, unchanged (zt = z where there is no usable fit).  For every accepted sample s, in push order:
+ *     1. x = -l_is as the tail kernel forms it; z = x - xmax.
+ *     2. The log weight lw_s.  Body (!(z > c), or no tail rule): lw = z.  Tail: let a..b be the run of sorted tail slots
+ *        whose stored value equals x bit for bit; a run of length 1 gives lw = zt_(a), a longer one lw = log((sum_{j=a..b}
+ *        exp(zt_(j))) / (b - a + 1)), summed in ascending j: every member of a tie gets the mean weight of the ranks the tie
+ *        occupies, so the result does not depend on which of two equal samples came first.
+ *     3. logP_is, logQ_is: the predictive tails of the posterior predictive check below, unchanged.
+ *     4. Four running-maximum log-sum-exps by that check's recurrence (Kahan-compensated, terms of -inf skipped):
+ *        lW = lse(lw), lA = lse(lw + logP), lB = lse(lw + logQ), lW2 = lse(2 lw).
+ *     loo_log_cdf = lA - lW, loo_log_sf = lB - lW; loo_pit from the smaller tail on the host, as pit is; is_ess =
+ *     exp(2 lW - lW2), Kish's effective sample size of the smoothed weights, in 1 ... n; log_wsum = lW.  A bin whose xmax is
+ *     not finite gives NaN in all five.
+ *   Totals, on the host in bin order in long double: n_used, n_rejected; ks_D and pit_hist of loo_pit as in the posterior
+ *   predictive check; min_log_sf and min_log_cdf with their bins and min_is_ess with its bin, the first bin winning a tie
+ *   (-1 and NaN where every bin is NaN).
+ *   loo_pit_begin   allowed in LOO mode once the LOO pass has seen exactly the fold pass's counts.  Allocates M x Nx doubles
+ *                for the table of log weights plus 116 Nx + 36 bytes of state (TAMCMC_E_NOMEM when that fails, and the
+ *                object stays as it was), then runs the prepare kernel (tamcmc_loopit.hip): per bin the top set is
+ *                sorted in place -- a sorted array is a valid heap, and loo_result keeps returning the same bits -- and the
+ *                table is filled.  Refused with TAMCMC_E_INVALID: outside LOO mode; an incomplete LOO pass, which is left
+ *                untouched (only loo_result discards it); a second call; a chi(2,2p) context with p < 1 or p >
+ *                TAMCMC_SUMMARY_PREDICTIVE_MAX_P; a context with a batch armed or in flight.
+ *   From then on push and push_device feed the PIT kernel; the top sets are frozen.  Every result is bit for bit independent
+ *   of block_chains and of how the pass is split over pushes.
+ *   loo_pit_result  totals and five arrays of Nx doubles on the host, any of them may be NULL.  If the third pass did not
+ *                see exactly the fold pass's counts, or any tail sample was not found bit for bit among the stored values
+ *                (the caller pushed other rows): TAMCMC_E_INVALID, the PIT pass is cleared and may be repeated.  May be
+ *                called again without another pass.
+ *   loo_end, tamcmc_summary_reset and tamcmc_summary_destroy free the sub-mode's memory with the mode's.
+ *   loo_pit_kernel_time   as tamcmc_summary_predictive_kernel_time, for the PIT kernel alone; tamcmc_summary_kernel_time
+ *                reports the prepare kernel with the tail and finalize kernels.
+ *
  * POSTERIOR PREDICTIVE CHECK: is the residual spectrum distributed as the likelihood claims, and in which bins is it not?
  * Per bin the predictive CDF of the datum averaged over the chain -- its probability integral transform (PIT) -- and both
  * tail probabilities as logarithms, which stay meaningful far below 1e-300: a missed mode has y / M of a few thousand.
@@ -575,6 +614,16 @@ int tamcmc_summary_predictive_enable(tamcmc_summary *s);
 int tamcmc_summary_predictive_result(tamcmc_summary *s, tamcmc_summary_predictive_totals *totals,
                                      double *pit, double *log_cdf, double *log_sf, double *mean_resid);
 int tamcmc_summary_predictive_kernel_time(tamcmc_summary *s, double *total_ms, int64_t *launches);
+typedef struct {
+    int64_t n_used, n_rejected;
+    double ks_D, min_log_sf, min_log_cdf, min_is_ess;
+    int64_t bin_min_log_sf, bin_min_log_cdf, bin_min_is_ess;
+    int64_t pit_hist[TAMCMC_SUMMARY_PIT_CELLS];
+} tamcmc_summary_loo_pit_totals;
+int tamcmc_summary_loo_pit_begin(tamcmc_summary *s);
+int tamcmc_summary_loo_pit_result(tamcmc_summary *s, tamcmc_summary_loo_pit_totals *totals,
+                                  double *loo_pit, double *loo_log_cdf, double *loo_log_sf, double *is_ess, double *log_wsum);
+int tamcmc_summary_loo_pit_kernel_time(tamcmc_summary *s, double *total_ms, int64_t *launches);
 #define TAMCMC_SUMMARY_WINDOW_MAX_BINS 512
 #define TAMCMC_SUMMARY_WINDOW_MAX_SHAPE 512
 typedef struct {

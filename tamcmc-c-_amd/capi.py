@@ -33,6 +33,7 @@ EXPORTS = [
     "tamcmc_summary_quantiles_begin", "tamcmc_summary_quantiles_step", "tamcmc_summary_quantiles_result",
     "tamcmc_summary_quantiles_end",
     "tamcmc_summary_loo_begin", "tamcmc_summary_loo_result", "tamcmc_summary_loo_end",
+    "tamcmc_summary_loo_pit_begin", "tamcmc_summary_loo_pit_result", "tamcmc_summary_loo_pit_kernel_time",
     "tamcmc_summary_predictive_enable", "tamcmc_summary_predictive_result", "tamcmc_summary_predictive_kernel_time",
     "tamcmc_summary_window_enable", "tamcmc_summary_window_result", "tamcmc_summary_window_kernel_time",
     "tamcmc_summary_scan_enable", "tamcmc_summary_scan_result", "tamcmc_summary_scan_regions", "tamcmc_summary_scan_kernel_time",
@@ -64,6 +65,13 @@ class SummaryPredictiveTotals(C.Structure):
     _fields_ = [("n_used", C.c_int64), ("n_rejected", C.c_int64), ("ks_D", C.c_double), ("min_log_sf", C.c_double),
                 ("min_log_cdf", C.c_double), ("bin_min_log_sf", C.c_int64), ("bin_min_log_cdf", C.c_int64),
                 ("pit_hist", C.c_int64 * PIT_CELLS)]
+
+
+class SummaryLooPitTotals(C.Structure):
+    """tamcmc_summary_loo_pit_totals"""
+    _fields_ = [("n_used", C.c_int64), ("n_rejected", C.c_int64), ("ks_D", C.c_double), ("min_log_sf", C.c_double),
+                ("min_log_cdf", C.c_double), ("min_is_ess", C.c_double), ("bin_min_log_sf", C.c_int64),
+                ("bin_min_log_cdf", C.c_int64), ("bin_min_is_ess", C.c_int64), ("pit_hist", C.c_int64 * PIT_CELLS)]
 
 
 class SummaryWindowTotals(C.Structure):
@@ -171,6 +179,9 @@ def load_library():
     lib.tamcmc_summary_loo_begin.argtypes = [vp]
     lib.tamcmc_summary_loo_result.argtypes = [vp, C.POINTER(SummaryLooTotals), dp, dp, dp, ip]
     lib.tamcmc_summary_loo_end.argtypes = [vp]
+    lib.tamcmc_summary_loo_pit_begin.argtypes = [vp]
+    lib.tamcmc_summary_loo_pit_result.argtypes = [vp, C.POINTER(SummaryLooPitTotals), dp, dp, dp, dp, dp]
+    lib.tamcmc_summary_loo_pit_kernel_time.argtypes = [vp, dp, C.POINTER(C.c_int64)]
     lib.tamcmc_summary_predictive_enable.argtypes = [vp]
     lib.tamcmc_summary_predictive_result.argtypes = [vp, C.POINTER(SummaryPredictiveTotals), dp, dp, dp, dp]
     lib.tamcmc_summary_predictive_kernel_time.argtypes = [vp, dp, C.POINTER(C.c_int64)]
@@ -511,7 +522,8 @@ class Summary:
     and of the pointwise log-likelihood over the parameter rows pushed so far, kept on the device.  Results do not depend,
     bit for bit, on block_chains or on how the rows are split over pushes.  quantiles() gives the exact per-bin quantiles
     of the model (credible bands) by pushing the same rows again a few times; loo() gives PSIS-LOO (elpd_loo and the
-    Pareto k-hat per bin) by pushing them once more, and ess() the effective sample size, Monte-Carlo standard error and
+    Pareto k-hat per bin) by pushing them once more -- with pit=True a third time, for LOO-PIT and the PSIS weights' effective
+    sample size per bin --, and ess() the effective sample size, Monte-Carlo standard error and
     split R-hat per bin by pushing them once more in the same order; band_ess() the quantiles together with the effective sample
     size of each of them (of the indicator M <= quantile), by one more pass after the selection.  With predictive=True every fold pass also accumulates the
     posterior predictive check (predictive_result(): PIT and both log tail probabilities per bin), and with window=W or
@@ -667,16 +679,53 @@ class Summary:
         self._check(self._lib.tamcmc_summary_loo_end(self._s), "tamcmc_summary_loo_end")
         self._loo = False
 
-    def loo(self, params):
+    def loo(self, params, pit=False):
         """PSIS-LOO over the rows already pushed, `params` being those rows: begin, one push, result, end.  Returns the
-        dict of loo_result() and always leaves the mode."""
+        dict of loo_result() and always leaves the mode.  pit=True: a third push for LOO-PIT, and the dict has the keys
+        of loo_pit_result() as well (its n_used / n_rejected are the same numbers)."""
         self.loo_begin()
         try:
             self.push(params)
-            return self.loo_result()
+            out = self.loo_result()
+            if pit:
+                self.loo_pit_begin()
+                self.push(params)
+                out.update(self.loo_pit_result())
+            return out
         finally:
             if getattr(self, "_loo", False):
                 self.loo_end()
+
+    # ---- LOO-PIT: the predictive tails under the PSIS weights, and the weights' ESS, a third pass in LOO mode ----
+    LOO_PIT_ARRAYS = ("loo_pit", "loo_log_cdf", "loo_log_sf", "is_ess", "log_wsum")
+    LOO_PIT_TOTALS = ("n_used", "n_rejected", "loo_ks_D", "min_loo_log_sf", "min_loo_log_cdf", "min_is_ess",
+                      "bin_min_loo_log_sf", "bin_min_loo_log_cdf", "bin_min_is_ess")
+
+    def loo_pit_begin(self):
+        """In LOO mode, after a complete pass: sorts the top sets, fills the table of log weights.  From here on push /
+        push_device feed the PIT kernel: push the same rows a third time, then loo_pit_result()."""
+        self._check(self._lib.tamcmc_summary_loo_pit_begin(self._s), "tamcmc_summary_loo_pit_begin")
+
+    def loo_pit_result(self):
+        """dict: loo_pit, loo_log_cdf, loo_log_sf, is_ess, log_wsum (Nx doubles), loo_pit_hist (20 int64) and the totals
+        n_used, n_rejected, loo_ks_D, min_loo_log_sf, min_loo_log_cdf, min_is_ess and the bins bin_min_*."""
+        out = {k: np.empty(self.accel.Nx) for k in self.LOO_PIT_ARRAYS}
+        t = SummaryLooPitTotals()
+        self._check(self._lib.tamcmc_summary_loo_pit_result(self._s, C.byref(t), *[_dptr(out[k]) for k in self.LOO_PIT_ARRAYS]),
+                    "tamcmc_summary_loo_pit_result")
+        out.update(n_used=int(t.n_used), n_rejected=int(t.n_rejected), loo_ks_D=t.ks_D, min_loo_log_sf=t.min_log_sf,
+                   min_loo_log_cdf=t.min_log_cdf, min_is_ess=t.min_is_ess, bin_min_loo_log_sf=int(t.bin_min_log_sf),
+                   bin_min_loo_log_cdf=int(t.bin_min_log_cdf), bin_min_is_ess=int(t.bin_min_is_ess),
+                   loo_pit_hist=np.array(list(t.pit_hist), dtype=np.int64))
+        return out
+
+    def loo_pit_kernel_time(self):
+        """(summed milliseconds, launches) of the PIT kernel since profile(True)."""
+        ms = C.c_double(0.0)
+        n = C.c_int64(0)
+        self._check(self._lib.tamcmc_summary_loo_pit_kernel_time(self._s, C.byref(ms), C.byref(n)),
+                    "tamcmc_summary_loo_pit_kernel_time")
+        return ms.value, n.value
 
     # ---- posterior predictive check: PIT and both log tail probabilities per bin, beside every fold pass ----
     PREDICTIVE_MAX_P = 64

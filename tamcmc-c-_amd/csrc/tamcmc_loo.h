@@ -112,7 +112,9 @@ struct TmlBin {
 
 // s[0 .. ncand): the values of the top set above its root, sorted ascending; root: the set's smallest value; has_rule:
 // n > M (the root is the (M+1)-th largest x); (body_a, body_r): the body's log-sum-exp, body_r = r - c; t[ncand], theta / ell
-// [TM_LOO_MAX_THETA]: work space shared by the lanes.  Every lane returns the same bits.
+// [TM_LOO_MAX_THETA]: work space shared by the lanes.  Every lane returns the same bits.  On return t[0 .. L) holds the
+// log weights zt_(j) of the tail, ascending (zt = z where there is no usable fit), each written by the lane that owns j: a
+// caller that reads them across lanes calls w.sync() first.
 template <class W>
 TML_FN TmlBin tml_finalize(W &w, const double *s, const int ncand, const double root, const bool has_rule, const long long n,
                            const double body_a, const double body_r, double *t, double *theta, double *ell)
@@ -181,9 +183,10 @@ TML_FN TmlBin tml_finalize(W &w, const double *s, const int ncand, const double 
             const double zt = fmin(log(inner + ec), 0.0);
             s1 += exp(zt - (zs[j] - xmax));
             s2 += exp(zt);
+            t[j] = zt;                    // (the fit is done with t: it leaves as the smoothed tail, for tamcmc_loopit.h)
         }
     } else {
-        for (int j = lane; j < L; j += lanes) { s1 += 1.0; s2 += exp(zs[j] - xmax); }
+        for (int j = lane; j < L; j += lanes) { s1 += 1.0; s2 += exp(zs[j] - xmax); t[j] = zs[j] - xmax; }
     }
     s1 = w.sum(s1);
     s2 = w.sum(s2);
@@ -193,6 +196,43 @@ TML_FN TmlBin tml_finalize(W &w, const double *s, const int ncand, const double 
     out.tail_len = (int32_t)L;
     return out;
 }
+
+#if defined(__HIPCC__)
+// One wave: the ncand values above the root of a bin's heap column (heap: the bin's slot 0, slots nx doubles apart) into
+// s[0 .. P), P the power of two >= ncand, padded with +inf, sorted ascending by a bitonic network.  Ends behind a barrier.
+__device__ __forceinline__ void tml_load_sorted(const double *heap, const size_t nx, const int ncand, double *s)
+{
+    const int lane = (int)threadIdx.x;
+    int P = 1;
+    while (P < ncand) P <<= 1;
+    for (int j = lane; j < P; j += TM_LOO_THREADS) s[j] = j < ncand ? heap[(size_t)(j + 1) * nx] : (double)INFINITY;
+    __syncthreads();
+    for (int k = 2; k <= P; k <<= 1)
+        for (int j = k >> 1; j > 0; j >>= 1) {
+            for (int i = lane; i < P; i += TM_LOO_THREADS) {
+                const int o = i ^ j;
+                if (o > i) {
+                    const double u = s[i], v = s[o];
+                    if ((u > v) == ((i & k) == 0)) { s[i] = v; s[o] = u; }
+                }
+            }
+            __syncthreads();
+        }
+}
+
+// the finalize kernel's wave (also tamcmc_loopit.hip's prepare kernel)
+struct TmlWave {
+    __device__ int lane() const { return (int)threadIdx.x; }
+    __device__ int lanes() const { return TM_LOO_THREADS; }
+    __device__ double sum(double v) const
+    {
+#pragma unroll
+        for (int o = TM_LOO_THREADS / 2; o > 0; o >>= 1) v += __shfl_xor(v, o, TM_LOO_THREADS);
+        return v;
+    }
+    __device__ void sync() const { __syncthreads(); }
+};
+#endif
 
 // ---- launch arguments (tamcmc_loo.hip) ----
 struct TmLooArgs {

@@ -57,18 +57,6 @@ __global__ __launch_bounds__(TM_LOO_THREADS) void tamcmc_loo_tail_kernel(const T
     if (bin == 0) { a.cnt_out[0] = n; a.cnt_out[1] = rej; }
 }
 
-struct TmlWave {
-    __device__ int lane() const { return (int)threadIdx.x; }
-    __device__ int lanes() const { return TM_LOO_THREADS; }
-    __device__ double sum(double v) const
-    {
-#pragma unroll
-        for (int o = TM_LOO_THREADS / 2; o > 0; o >>= 1) v += __shfl_xor(v, o, TM_LOO_THREADS);
-        return v;
-    }
-    __device__ void sync() const { __syncthreads(); }
-};
-
 __global__ __launch_bounds__(TM_LOO_THREADS) void tamcmc_loo_finalize_kernel(const TmLooArgs a)
 {
     __shared__ double s[TM_LOO_MAX_TAIL], t[TM_LOO_MAX_TAIL];
@@ -77,23 +65,9 @@ __global__ __launch_bounds__(TM_LOO_THREADS) void tamcmc_loo_finalize_kernel(con
     const size_t nx = (size_t)a.Nx;
     const int cnt = a.n < (long long)a.cap ? (int)a.n : a.cap;               // >= 1: the host does not launch for n = 0
     const int ncand = cnt - 1;                                               // <= M <= TM_LOO_MAX_TAIL
-    int P = 1;
-    while (P < ncand) P <<= 1;
     const double *heap = a.heap + bin;
-    for (int j = lane; j < P; j += TM_LOO_THREADS) s[j] = j < ncand ? heap[(size_t)(j + 1) * nx] : (double)INFINITY;
     const double root = heap[0];
-    __syncthreads();
-    for (int k = 2; k <= P; k <<= 1)
-        for (int j = k >> 1; j > 0; j >>= 1) {
-            for (int i = lane; i < P; i += TM_LOO_THREADS) {
-                const int o = i ^ j;
-                if (o > i) {
-                    const double u = s[i], v = s[o];
-                    if ((u > v) == ((i & k) == 0)) { s[i] = v; s[o] = u; }
-                }
-            }
-            __syncthreads();
-        }
+    tml_load_sorted(heap, nx, ncand, s);
     TmlWave w;
     const TmlBin r = tml_finalize(w, s, ncand, root, a.n >= (long long)a.cap, a.n, a.body[bin], a.body[nx + bin] - a.body[2 * nx + bin], t, theta, ell);
     if (lane == 0) {

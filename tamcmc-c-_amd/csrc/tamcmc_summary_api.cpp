@@ -3,7 +3,8 @@
 // context's own launches (tamcmc_host.h: tm_enqueue) with a row map covering every chain (stage 1) +
 // tamcmc_summary_fold_kernel (stage 2), both on the context's stream.  While the object selects quantiles
 // (tamcmc_summary_quantiles_*, tamcmc_quantile.h) stage 2 is the histogram kernel instead and the fold state is frozen;
-// in LOO mode (tamcmc_summary_loo_*, tamcmc_loo.h) it is the tail kernel.  With the predictive check enabled
+// in LOO mode (tamcmc_summary_loo_*, tamcmc_loo.h) it is the tail kernel, and after tamcmc_summary_loo_pit_begin the PIT
+// kernel (tamcmc_loopit.h).  With the predictive check enabled
 // (tamcmc_summary_predictive_*, tamcmc_predictive.h) a fold-mode block has a stage 3: tamcmc_summary_predictive_kernel on
 // the same rows; the other two modes never touch its state.  With the windowed check enabled (tamcmc_summary_window_*,
 // tamcmc_window.h) a stage 4 follows: the sums, tails and fold kernels of tamcmc_window.hip, again on the same rows.
@@ -19,6 +20,7 @@
 #include "tamcmc_ess.h"
 #include "tamcmc_host.h"
 #include "tamcmc_loo.h"
+#include "tamcmc_loopit.h"
 #include "tamcmc_predictive.h"
 #include "tamcmc_quantile.h"
 #include "tamcmc_scan.h"
@@ -63,6 +65,15 @@ struct TmLooMode : TmMode {
     char *d_state = nullptr;             // one allocation: body[3][Nx] | elpd | khat | cutoff | cnt[2][2] | tail_len
     double *body = nullptr, *elpd = nullptr, *khat = nullptr, *cutoff = nullptr;
     int32_t *tail_len = nullptr;
+    // the LOO-PIT sub-mode (tamcmc_loopit.h): its pass's counts, the table of log weights and the rest of its state
+    bool pit = false;
+    TmCountPair pit_cnt;
+    double *d_lw = nullptr;              // [cap - 1][Nx]
+    char *d_pit = nullptr;               // one allocation: sums[TM_LOOPIT_NSTATE][Nx] | xmax | c | cnt[2][2] | first | flag
+    double *pit_sums = nullptr, *pit_xmax = nullptr, *pit_c = nullptr;
+    int32_t *pit_first = nullptr, *pit_flag = nullptr;
+    int p = 1, nterms = 0;               // as TmPredictive
+    double lf_pm1 = 0.0, lf_p = 0.0;
 };
 
 // ESS mode: the lag products, the rings of centred values and the half-chain moments of the pass on the device, and what the
@@ -141,6 +152,7 @@ struct tamcmc_summary {
     TmTimer timer;
     TmQuantMode q;
     TmLooMode loo;
+    TmTimer pit_timer;                   // the LOO-PIT kernel alone (tamcmc_summary_loo_pit_kernel_time)
     TmEssMode ess;
     TmBandMode band;
     TmPredictive pred;
@@ -268,8 +280,40 @@ static int loo_pass_clear(tamcmc_summary *s)
 // the stream must be idle
 static void loo_free(tamcmc_summary *s)
 {
-    (void)hipFree(s->loo.d_state); (void)hipFree(s->loo.d_heap);
+    (void)hipFree(s->loo.d_state); (void)hipFree(s->loo.d_heap); (void)hipFree(s->loo.d_lw); (void)hipFree(s->loo.d_pit);
     s->loo = TmLooMode();
+}
+
+static TmLooPitArgs loopit_args(const tamcmc_summary *s)
+{
+    const TmLooMode &m = s->loo;
+    const tamcmc_ctx *c = s->c;
+    TmLooPitArgs a{};
+    a.rows = s->d_model; a.y = c->d_y; a.isig2 = c->d_isig2; a.heap = m.d_heap; a.body = m.body;
+    a.lw = m.d_lw; a.xmax = m.pit_xmax; a.c = m.pit_c; a.first = m.pit_first; a.state = m.pit_sums;
+    a.cnt_in = m.pit_cnt.in(); a.cnt_out = m.pit_cnt.out(); a.flag = m.pit_flag;
+    a.n = m.n_used;
+    a.Nx = c->L.Nx; a.likelihood_case = c->L.likelihood_case; a.cap = m.cap;
+    a.p = m.p; a.nterms = m.nterms; a.trips = tlp_trips(m.cap - 1);
+    a.like_p = c->L.like_p; a.lf_pm1 = m.lf_pm1; a.lf_p = m.lf_p;
+    return a;
+}
+
+// stage 2 of a block of the LOO-PIT pass: the PIT kernel in the tail kernel's place
+static int loopit_block(tamcmc_summary *s, int n, const int32_t *d_status)
+{
+    TmLooPitArgs a = loopit_args(s);
+    a.status = d_status; a.B = n;
+    return timed_launch(s, s->pit_timer, "summary loo pit", [&] { return tm_launch_loopit(a, s->c->stream); }, &s->loo.pit_cnt);
+}
+
+// a LOO-PIT pass starts from empty counts, empty sums and a clear flag
+static int loopit_pass_clear(tamcmc_summary *s)
+{
+    TmLooMode &m = s->loo;
+    TM_HIP(hipMemsetAsync(m.pit_sums, 0, (size_t)TM_LOOPIT_NSTATE * (size_t)s->c->L.Nx * sizeof(double), s->c->stream));
+    TM_HIP(hipMemsetAsync(m.pit_flag, 0, sizeof(int32_t), s->c->stream));
+    return m.pit_cnt.clear(s->c->stream);
 }
 
 static TmEssArgs ess_args(const tamcmc_summary *s)
@@ -419,7 +463,7 @@ static int summary_block(tamcmc_summary *s, int n, const double *d_params, doubl
     rc = tm_enqueue(c, n, d_params, s->d_T, d_logL, nullptr, d_status, s->d_rows, s->d_model);
     if (rc != TAMCMC_OK) return rc;
     if (s->q.on) return quantile_block(s, n, d_status);
-    if (s->loo.on) return loo_block(s, n, d_status);
+    if (s->loo.on) return s->loo.pit ? loopit_block(s, n, d_status) : loo_block(s, n, d_status);
     if (s->ess.on) return ess_block(s, n, d_status);
     if (s->band.on) return band_block(s, n, d_status);
     TmSummaryArgs a{};
@@ -501,6 +545,7 @@ extern "C" int tamcmc_summary_destroy(tamcmc_summary *s)
         if (s->ev_stage[p]) (void)hipEventDestroy(s->ev_stage[p]);
     }
     s->timer.destroy();
+    s->pit_timer.destroy();
     s->pred.timer.destroy();
     s->win.timer.destroy();
     s->scan.timer.destroy();
@@ -638,6 +683,7 @@ extern "C" int tamcmc_summary_profile(tamcmc_summary *s, int enable)
     TM_HIP(tm_ctx_stream_sync(s->c));
     s->profile = enable != 0;
     s->timer.used = 0;
+    s->pit_timer.used = 0;
     s->pred.timer.used = 0;
     s->win.timer.used = 0;
     s->scan.timer.used = 0;
@@ -778,6 +824,27 @@ extern "C" int tamcmc_summary_quantiles_end(tamcmc_summary *s)
     return rc;
 }
 
+// What the PIT totals of the per-bin check, the windowed check and LOO-PIT share: the cell of a PIT value, and the
+// Kolmogorov distance of a non-empty set of them from uniform, in long double (u is sorted in place).
+static int tm_pit_cell(const double pv)
+{
+    const int cell = (int)std::floor(20.0 * pv);
+    return cell > TAMCMC_SUMMARY_PIT_CELLS - 1 ? TAMCMC_SUMMARY_PIT_CELLS - 1 : (cell < 0 ? 0 : cell);
+}
+
+static double tm_ks_uniform(std::vector<double> &u)
+{
+    std::sort(u.begin(), u.end());
+    const long double N = (long double)u.size();
+    long double D = 0.0L;
+    for (size_t k = 0; k < u.size(); k++) {
+        const long double up = (long double)(k + 1) / N - (long double)u[k], dn = (long double)u[k] - (long double)k / N;
+        D = up > D ? up : D;
+        D = dn > D ? dn : D;
+    }
+    return (double)D;
+}
+
 // ---- PSIS-LOO (tamcmc_loo.h) ----
 
 extern "C" int tamcmc_summary_loo_begin(tamcmc_summary *s)
@@ -875,6 +942,116 @@ extern "C" int tamcmc_summary_loo_end(tamcmc_summary *s)
     return rc;
 }
 
+// ---- LOO-PIT (tamcmc_loopit.h) ----
+
+extern "C" int tamcmc_summary_loo_pit_begin(tamcmc_summary *s)
+{
+    if (!s || !s->loo.on || s->loo.pit) return TAMCMC_E_INVALID;
+    tamcmc_ctx *c = s->c;
+    const bool chi = c->L.likelihood_case == 0;
+    if (chi && !(c->L.like_p >= 1.0 && c->L.like_p <= (double)TAMCMC_SUMMARY_PREDICTIVE_MAX_P)) return TAMCMC_E_INVALID;
+    int rc = summary_enter(s);
+    if (rc != TAMCMC_OK) return rc;
+    TmLooMode &m = s->loo;
+    bool complete = false;
+    rc = pass_complete(m, &complete);
+    if (rc != TAMCMC_OK) return rc;
+    if (!complete) return TAMCMC_E_INVALID;                             // the pass under way stays as it is
+    const size_t nx = (size_t)c->L.Nx;
+    const size_t pit_bytes = ((size_t)TM_LOOPIT_NSTATE + 2) * nx * sizeof(double) + 4 * sizeof(long long) + (nx + 1) * sizeof(int32_t);
+    double *d_lw = nullptr;
+    char *d_pit = nullptr;
+    if (hipMalloc(&d_lw, (size_t)(m.cap - 1) * nx * sizeof(double)) != hipSuccess) { (void)hipGetLastError(); return TAMCMC_E_NOMEM; }
+    if (hipMalloc(&d_pit, pit_bytes) != hipSuccess) { (void)hipGetLastError(); (void)hipFree(d_lw); return TAMCMC_E_NOMEM; }
+    m.d_lw = d_lw; m.d_pit = d_pit;
+    m.pit_sums = reinterpret_cast<double *>(d_pit);
+    m.pit_xmax = m.pit_sums + (size_t)TM_LOOPIT_NSTATE * nx;
+    m.pit_c = m.pit_xmax + nx;
+    m.pit_cnt.d = reinterpret_cast<long long *>(m.pit_c + nx);
+    m.pit_cnt.parity = 0;
+    m.pit_first = reinterpret_cast<int32_t *>(m.pit_cnt.d + 4);
+    m.pit_flag = m.pit_first + nx;
+    m.p = chi ? (int)c->L.like_p : 1;
+    m.nterms = tmp_series_terms(m.p);
+    m.lf_pm1 = tmp_log_factorial(m.p - 1);
+    m.lf_p = tmp_log_factorial(m.p);
+    c->enq_seq++;
+    TmLooPitArgs a = loopit_args(s);
+    rc = timed_launch(s, s->timer, "summary loo pit prepare", [&] { return tm_launch_loopit_prepare(a, c->stream); });
+    if (rc == TAMCMC_OK) rc = loopit_pass_clear(s);
+    if (rc == TAMCMC_OK && hipStreamSynchronize(c->stream) != hipSuccess) rc = TAMCMC_E_HIP;
+    if (rc != TAMCMC_OK) {              // (a launch that was refused wrote nothing: the top sets are as the LOO pass left them)
+        (void)hipStreamSynchronize(c->stream);
+        (void)hipFree(d_lw); (void)hipFree(d_pit);
+        m.d_lw = nullptr; m.d_pit = nullptr;
+        return rc;
+    }
+    m.pit = true;
+    return TAMCMC_OK;
+}
+
+extern "C" int tamcmc_summary_loo_pit_result(tamcmc_summary *s, tamcmc_summary_loo_pit_totals *totals, double *loo_pit, double *loo_log_cdf,
+                                             double *loo_log_sf, double *is_ess, double *log_wsum)
+{
+    if (!s || !s->loo.on || !s->loo.pit) return TAMCMC_E_INVALID;
+    int rc = summary_enter(s);
+    if (rc != TAMCMC_OK) return rc;
+    tamcmc_ctx *c = s->c;
+    TmLooMode &m = s->loo;
+    c->enq_seq++;
+    long long cnt[2] = {0, 0};
+    int32_t flag = 0;
+    rc = m.pit_cnt.read(cnt);
+    if (rc != TAMCMC_OK) return rc;
+    TM_HIP(hipMemcpy(&flag, m.pit_flag, sizeof flag, hipMemcpyDeviceToHost));
+    if (cnt[0] != m.n_used || cnt[1] != m.n_rejected || flag != 0) {    // not the LOO pass's samples: the PIT pass is discarded
+        rc = loopit_pass_clear(s);
+        return rc != TAMCMC_OK ? rc : TAMCMC_E_INVALID;
+    }
+    const size_t nx = (size_t)c->L.Nx;
+    std::vector<double> st, u;
+    try { st.resize(((size_t)TM_LOOPIT_NSTATE + 1) * nx); u.reserve(nx); } catch (const std::bad_alloc &) { return TAMCMC_E_NOMEM; }
+    TM_HIP(hipMemcpy(st.data(), m.pit_sums, st.size() * sizeof(double), hipMemcpyDeviceToHost));         // sums | xmax
+    const double nan = std::nan("");
+    tamcmc_summary_loo_pit_totals t{};
+    t.n_used = m.n_used; t.n_rejected = m.n_rejected;
+    t.ks_D = nan; t.min_log_sf = nan; t.min_log_cdf = nan; t.min_is_ess = nan;
+    t.bin_min_log_sf = -1; t.bin_min_log_cdf = -1; t.bin_min_is_ess = -1;
+    for (size_t i = 0; i < nx; i++) {
+        auto word = [&](int k) { return st[(size_t)k * nx + i]; };
+        double lc = nan, ls = nan, ess = nan, lW = nan;
+        if (std::isfinite(word(TM_LOOPIT_NSTATE))) {
+            lW = tlp_lse(word(TM_LOOPIT_W_A), word(TM_LOOPIT_W_R), word(TM_LOOPIT_W_C));
+            lc = tlp_lse(word(TM_LOOPIT_A_A), word(TM_LOOPIT_A_R), word(TM_LOOPIT_A_C)) - lW;
+            ls = tlp_lse(word(TM_LOOPIT_B_A), word(TM_LOOPIT_B_R), word(TM_LOOPIT_B_C)) - lW;
+            ess = std::exp(2.0 * lW - tlp_lse(word(TM_LOOPIT_W2_A), word(TM_LOOPIT_W2_R), word(TM_LOOPIT_W2_C)));
+        }
+        const double pv = lc < ls ? std::exp(lc) : -std::expm1(ls);                 // from the smaller tail
+        if (loo_pit) loo_pit[i] = pv;
+        if (loo_log_cdf) loo_log_cdf[i] = lc;
+        if (loo_log_sf) loo_log_sf[i] = ls;
+        if (is_ess) is_ess[i] = ess;
+        if (log_wsum) log_wsum[i] = lW;
+        if (t.bin_min_log_sf < 0 ? !std::isnan(ls) : ls < t.min_log_sf) { t.min_log_sf = ls; t.bin_min_log_sf = (int64_t)i; }   // the first bin wins a tie
+        if (t.bin_min_log_cdf < 0 ? !std::isnan(lc) : lc < t.min_log_cdf) { t.min_log_cdf = lc; t.bin_min_log_cdf = (int64_t)i; }
+        if (t.bin_min_is_ess < 0 ? !std::isnan(ess) : ess < t.min_is_ess) { t.min_is_ess = ess; t.bin_min_is_ess = (int64_t)i; }
+        if (std::isnan(pv)) continue;
+        t.pit_hist[tm_pit_cell(pv)]++;
+        u.push_back(pv);
+    }
+    if (!u.empty()) t.ks_D = tm_ks_uniform(u);
+    if (totals) *totals = t;
+    return TAMCMC_OK;
+}
+
+extern "C" int tamcmc_summary_loo_pit_kernel_time(tamcmc_summary *s, double *total_ms, int64_t *launches)
+{
+    if (!s || !total_ms || !launches || !s->loo.on || !s->loo.pit || s->c->armed) return TAMCMC_E_INVALID;
+    TM_HIP(hipSetDevice(s->c->device));
+    TM_HIP(tm_ctx_stream_sync(s->c));
+    return s->pit_timer.total(total_ms, launches);
+}
+
 // ---- posterior predictive check (tamcmc_predictive.h) ----
 
 // A check is enabled on an object that holds no samples yet (otherwise: reset first).  Opens both _enable functions.
@@ -941,21 +1118,10 @@ static int tails_finish(const std::vector<double> &st, const size_t m, const lon
         if (t.at_min_log_sf < 0 ? !std::isnan(ls) : ls < t.min_log_sf) { t.min_log_sf = ls; t.at_min_log_sf = (int64_t)i; }      // the first item wins a tie
         if (t.at_min_log_cdf < 0 ? !std::isnan(lc) : lc < t.min_log_cdf) { t.min_log_cdf = lc; t.at_min_log_cdf = (int64_t)i; }
         if (std::isnan(pv)) continue;
-        const int cell = (int)std::floor(20.0 * pv);
-        t.pit_hist[cell > TAMCMC_SUMMARY_PIT_CELLS - 1 ? TAMCMC_SUMMARY_PIT_CELLS - 1 : (cell < 0 ? 0 : cell)]++;
+        t.pit_hist[tm_pit_cell(pv)]++;
         u.push_back(pv);
     }
-    if (!u.empty()) {                   // Kolmogorov distance of the pit_i from uniform, in long double
-        std::sort(u.begin(), u.end());
-        const long double N = (long double)u.size();
-        long double D = 0.0L;
-        for (size_t k = 0; k < u.size(); k++) {
-            const long double up = (long double)(k + 1) / N - (long double)u[k], dn = (long double)u[k] - (long double)k / N;
-            D = up > D ? up : D;
-            D = dn > D ? dn : D;
-        }
-        t.ks_D = (double)D;
-    }
+    if (!u.empty()) t.ks_D = tm_ks_uniform(u);
     *out = t;
     return TAMCMC_OK;
 }

@@ -4,7 +4,7 @@
 //   chainsummary_hip <config dir> <model file> <data file> <params root> <output file>
 //                    [--chain m] [--slice s] [--first i] [--last j] [--thin k] [--block B]
 //                    [--quantiles q1,q2,...] [--qbits b] [--loo] [--predictive] [--window W[,first]] [--ess [L]]
-//                    [--scan W0[,W1,...]] [--scan-below T] [--scan-null R[,seed]] [--band-ess [L]]
+//                    [--scan W0[,W1,...]] [--scan-below T] [--scan-null R[,seed]] [--band-ess [L]] [--loo-pit]
 //
 // <config dir> is the reference's Config/default; model id, likelihood, p, plength, the inputs row and the relax mask
 // come from the setup it describes (tamcmc_setup_create / tamcmc_setup_load, slice s counted from 0).  The samples are
@@ -22,6 +22,12 @@
 // `# elpd_loo= ...  p_loo= ...  looic= ...  k_max= ...  n_k_high= ...  n_k_inf= ...`, and two more columns follow the
 // quantiles: elpd_loo and pareto_k, the bin's leave-one-out log predictive density and its Pareto k-hat (above 0.7: not to
 // be trusted).
+// With --loo-pit (implies --loo) the selected samples are read a third time for the leave-one-out PIT
+// (tamcmc_summary_loo_pit_*): the predictive tails under the PSIS weights, and the weights' effective sample size.  The
+// output file is that of --loo; the results go to <output file>.loopit: `#` header lines -- the version, `# n_used= ...
+// n_rejected= ...`, `# ks_D= ...  min_log_sf= ...  bin_min_log_sf= ...  min_log_cdf= ...  bin_min_log_cdf= ...`,
+// `# min_is_ess= ...  bin_min_is_ess= ...`, `# pit_hist= c0 c1 ... c19` -- then one row per bin:
+//   x  loo_pit  loo_log_cdf  loo_log_sf  is_ess  pareto_k
 // With --predictive the first pass also accumulates the posterior predictive check (tamcmc_summary_predictive_*; no further
 // pass), the header gains two lines, `# ks_D= ...  min_log_sf= ...  bin_min_log_sf= ...  min_log_cdf= ...
 // bin_min_log_cdf= ...` and `# pit_hist= c0 c1 ... c19`, and four columns follow all the others: pit, log_cdf, log_sf and
@@ -76,7 +82,7 @@ static int usage()
     fprintf(stderr, " Usage: chainsummary_hip <config dir> <model file> <data file> <params root> <output file>\n"
                     "                         [--chain m] [--slice s] [--first i] [--last j] [--thin k] [--block B]\n"
                     "                         [--quantiles q1,q2,...] [--qbits b] [--loo] [--predictive] [--window W[,first]] [--ess [L]]\n"
-                    "                         [--scan W0[,W1,...]] [--scan-below T] [--scan-null R[,seed]] [--band-ess [L]]\n"
+                    "                         [--scan W0[,W1,...]] [--scan-below T] [--scan-null R[,seed]] [--band-ess [L]] [--loo-pit]\n"
                     "     [1] The directory of config_default.cfg, errors_default.cfg and the *_ctrl.list files (Config/default)\n"
                     "     [2] The .model file and [3] the .data file of the fit\n"
                     "     [4] The root of the parameter files: <root>_chain-<m>.bin and <root>.hdr\n"
@@ -110,6 +116,9 @@ static int usage()
                     "             from its autocorrelation up to lag L (0 ... 1023, default 0: the library's 255): written to <output file>.bandess,\n"
                     "             one row per bin, x and per quantile value count_le p_hat ess tau mcse_p cut (the samples are read once more\n"
                     "             after the selection; [5] is unchanged)\n"
+                    "     --loo-pit   implies --loo: the leave-one-out PIT, the predictive tails under the PSIS weights, and the weights'\n"
+                    "             effective sample size: written to <output file>.loopit, one row per bin,\n"
+                    "             x loo_pit loo_log_cdf loo_log_sf is_ess pareto_k (the samples are read a third time)\n"
                     " chainsummary_hip version   prints the library version\n");
     return EXIT_FAILURE;
 }
@@ -146,7 +155,7 @@ int main(int argc, char *argv[])
     long chain = 0, slice = 0, first = 0, last = -1, thin = 1, block = 0, qbits = 0;
     std::vector<double> quant;
     std::string quant_text;
-    bool loo = false, predictive = false;
+    bool loo = false, loo_pit = false, predictive = false;
     long win_W = 0, win_first = 0, ess_lag = -1;            // ess_lag < 0: no --ess
     long band_lag = -1;                                     // < 0: no --band-ess
     std::vector<int32_t> scan_W;
@@ -159,6 +168,7 @@ int main(int argc, char *argv[])
     for (int i = 6; i < argc; i++) {
         const std::string a = argv[i];
         if (a == "--loo") { loo = true; continue; }
+        if (a == "--loo-pit") { loo = loo_pit = true; continue; }
         if (a == "--predictive") { predictive = true; continue; }
         if (a == "--ess") {                         // alone, or followed by the lag limit
             if (ess_lag >= 0) return usage();
@@ -424,6 +434,9 @@ int main(int argc, char *argv[])
     // PSIS-LOO: the same samples once more
     tamcmc_summary_loo_totals lt{};
     std::vector<double> elpd(loo ? (size_t)Nx : 0), khat(loo ? (size_t)Nx : 0);
+    tamcmc_summary_loo_pit_totals lpt{};
+    const size_t Nlp = loo_pit ? (size_t)Nx : 0;
+    std::vector<double> lp_pit(Nlp), lp_cdf(Nlp), lp_sf(Nlp), lp_ess(Nlp);
     if (loo) {
         auto lfail = [&](const char *what) { return fail(std::string(what) + ": " + tamcmc_strerror(rc) + " " + tamcmc_last_hip_error()); };
         rc = tamcmc_summary_loo_begin(sum);
@@ -431,6 +444,13 @@ int main(int argc, char *argv[])
         if (push_selected() != 0) return EXIT_FAILURE;
         rc = tamcmc_summary_loo_result(sum, &lt, elpd.data(), khat.data(), nullptr, nullptr);
         if (rc != TAMCMC_OK) return lfail("tamcmc_summary_loo_result");
+        if (loo_pit) {                                              // LOO-PIT: and a third time
+            rc = tamcmc_summary_loo_pit_begin(sum);
+            if (rc != TAMCMC_OK) return lfail("tamcmc_summary_loo_pit_begin");
+            if (push_selected() != 0) return EXIT_FAILURE;
+            rc = tamcmc_summary_loo_pit_result(sum, &lpt, lp_pit.data(), lp_cdf.data(), lp_sf.data(), lp_ess.data(), nullptr);
+            if (rc != TAMCMC_OK) return lfail("tamcmc_summary_loo_pit_result");
+        }
         tamcmc_summary_loo_end(sum);
     }
     // ESS, MCSE and split R-hat: the same samples once more, in the same order
@@ -548,6 +568,23 @@ int main(int argc, char *argv[])
                 }
             }
         fclose(org);
+    }
+    if (loo_pit) {
+        const std::string pit_file = out_file + ".loopit";
+        FILE *op = fopen(pit_file.c_str(), "w");
+        if (!op) return fail("unable to open the output file " + pit_file);
+        fprintf(op, "# chainsummary_hip (%s)\n", tamcmc_version());
+        fprintf(op, "# n_used= %lld  n_rejected= %lld\n", (long long)lpt.n_used, (long long)lpt.n_rejected);
+        fprintf(op, "# ks_D= %.12g  min_log_sf= %.12g  bin_min_log_sf= %lld  min_log_cdf= %.12g  bin_min_log_cdf= %lld\n", lpt.ks_D, lpt.min_log_sf,
+                (long long)lpt.bin_min_log_sf, lpt.min_log_cdf, (long long)lpt.bin_min_log_cdf);
+        fprintf(op, "# min_is_ess= %.12g  bin_min_is_ess= %lld\n", lpt.min_is_ess, (long long)lpt.bin_min_is_ess);
+        fprintf(op, "# pit_hist=");
+        for (int k = 0; k < TAMCMC_SUMMARY_PIT_CELLS; k++) fprintf(op, " %lld", (long long)lpt.pit_hist[k]);
+        fprintf(op, "\n# x loo_pit loo_log_cdf loo_log_sf is_ess pareto_k\n");
+        for (int64_t i = 0; i < Nx; i++)
+            fprintf(op, "%.12g %.12g %.12g %.12g %.12g %.12g\n", x[(size_t)i], lp_pit[(size_t)i], lp_cdf[(size_t)i], lp_sf[(size_t)i], lp_ess[(size_t)i],
+                    khat[(size_t)i]);
+        fclose(op);
     }
     if (ess_lag >= 0) {
         const std::string ess_file = out_file + ".ess";

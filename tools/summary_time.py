@@ -45,6 +45,12 @@ Prints one JSON line:
                             fold kernel alone beside the band kernels alone (pack and lag kernels of every block,
                             Summary.kernel_time in the mode) and the eval launches, the finish kernels (one per threshold),
                             bandess_result on the host clock, and the device memory the mode allocates.  Only this leg runs.
+  l_loo_pit_*               with --loo-pit (and --like-p p, default 1): after a fold pass, in one run, the LOO tail pass and the
+                            LOO-PIT pass of the same rows through Summary.push, alternating (seconds per 1000 samples), and from
+                            profiled passes in the same session the PIT kernel alone (Summary.loo_pit_kernel_time) beside the tail
+                            kernel alone, the predictive kernel alone (a second object with the check on) and the eval launches,
+                            loo_pit_begin on the host clock and its prepare kernel alone, and the device memory the sub-mode
+                            allocates.  Only this leg runs.
 Every timed shape is warmed up first (--warmup pushes); host clocks stop after calls that end in a device synchronise.
 """
 import argparse
@@ -290,6 +296,71 @@ def ess_leg(a, w, y, P):
     return out
 
 
+def loo_pit_leg(a, w, y, P):
+    """(l) the LOO tail pass beside the LOO-PIT pass of the same rows, and the kernels' own times."""
+    out = dict(l_loo_pit_like_p=a.like_p)
+    per_1000 = 1000.0 / a.samples
+    with tamcmc_amd.Accel(2, w["plength"], w["x"], y, likelihood_p=float(a.like_p)) as acc:
+        with tamcmc_amd.Summary(acc, a.block) as s:
+            s.push(P)
+            times = {"tail": [], "pit": [], "begin": []}
+            for k in range(a.warmup + a.steps):             # every round in a mode of its own: begin, push, pit_begin, push, end
+                s.loo_begin()
+                acc.synchronize()
+                t0 = time.perf_counter()
+                s.push(P)                                   # synchronous: results are on the host on return
+                t1 = time.perf_counter()
+                s.loo_pit_begin()                           # ends in a device synchronise
+                t2 = time.perf_counter()
+                s.push(P)
+                t3 = time.perf_counter()
+                if k >= a.warmup:
+                    times["tail"].append(t1 - t0)
+                    times["begin"].append(t2 - t1)
+                    times["pit"].append(t3 - t2)
+                if k + 1 < a.warmup + a.steps:
+                    s.loo_end()
+            for key in ("tail", "pit"):
+                v = times[key]
+                out[f"l_loo_pit_{key}_pass_s_per_1000"] = float(np.median(v)) * per_1000
+                out[f"l_loo_pit_{key}_pass_spread"] = [float(min(v)) * per_1000, float(max(v)) * per_1000]
+            out["l_loo_pit_begin_s"] = float(np.median(times["begin"]))
+            r = s.loo_pit_result()
+            s.loo_end()
+            s.loo_begin()                                   # the kernels alone: a profiled tail pass, prepare, a profiled PIT pass
+            s.profile(True)
+            acc.profile(True)
+            s.push(P)
+            tail_ms, tail_launches = s.kernel_time()
+            eval_ms, eval_launches = acc.kernel_time()
+            acc.profile(False)
+            s.profile(True)                                 # (profile() starts the timers again)
+            s.loo_pit_begin()
+            prep_ms, _ = s.kernel_time()
+            s.profile(True)
+            s.push(P)
+            pit_ms, pit_launches = s.loo_pit_kernel_time()
+            s.profile(False)
+            s.loo_end()
+        with tamcmc_amd.Summary(acc, a.block, predictive=True) as s1:
+            s1.push(P)
+            s1.reset()
+            s1.profile(True)
+            s1.push(P)
+            pred_ms, pred_launches = s1.predictive_kernel_time()
+            s1.profile(False)
+    n = r["n_used"]
+    M = int(np.ceil(min(n / 5.0, 3.0 * np.sqrt(float(n)))))
+    out.update(l_loo_pit_M=M, l_loo_pit_launches=pit_launches, l_loo_pit_us_per_block=pit_ms * 1e3 / pit_launches,
+               l_loo_pit_kernel_s_per_1000=pit_ms * 1e-3 * per_1000, l_loo_pit_kernel_us_per_sample=pit_ms * 1e3 / a.samples,
+               l_loo_tail_kernel_s_per_1000=tail_ms * 1e-3 * per_1000, l_loo_tail_kernel_us_per_sample=tail_ms * 1e3 / a.samples,
+               l_predictive_kernel_s_per_1000=pred_ms * 1e-3 * per_1000, l_predictive_kernel_us_per_sample=pred_ms * 1e3 / a.samples,
+               l_eval_kernel_s_per_1000=eval_ms * 1e-3 * per_1000, l_loo_pit_prepare_ms=prep_ms,
+               l_loo_bytes=(M + 1) * a.nx * 8 + 52 * a.nx + 32, l_loo_pit_bytes=M * a.nx * 8 + 116 * a.nx + 36,
+               l_loo_pit_ks_D=r["loo_ks_D"], l_loo_pit_min_log_sf=r["min_loo_log_sf"], l_loo_pit_min_is_ess=r["min_is_ess"], n_used=n)
+    return out
+
+
 def bandess_leg(a, w, y, P):
     """(k) the fold pass beside the band ESS pass of the same rows, and the kernels' own times."""
     out = {}
@@ -366,6 +437,7 @@ def main():
     ap.add_argument("--qbits", type=int, default=0)
     ap.add_argument("--predictive", action="store_true")
     ap.add_argument("--like-p", type=int, default=1)
+    ap.add_argument("--loo-pit", action="store_true", help="the LOO-PIT pass beside the LOO tail pass and the predictive kernel")
     ap.add_argument("--window", type=int, default=0)
     ap.add_argument("--scan", default="", help="W0[,W1,...]: strictly ascending widths of the sliding-window scan")
     ap.add_argument("--ess", type=int, default=-1)
@@ -386,6 +458,10 @@ def main():
     assert st == 0
     y = synth.make_spectrum(m_true)
     out = dict(tool="summary_time", Nx=a.nx, samples=a.samples, steps=a.steps, warmup=a.warmup, version=tamcmc_amd.capi.version())
+    if a.loo_pit:
+        out.update(loo_pit_leg(a, w, y, P))
+        print(json.dumps(out))
+        return
     if a.predictive or a.window or a.scan or a.ess >= 0 or a.band_ess >= 0:
         out.update(bandess_leg(a, w, y, P) if a.band_ess >= 0 else ess_leg(a, w, y, P) if a.ess >= 0 else scan_leg(a, w, y, P) if a.scan else window_leg(a, w, y, P) if a.window
                    else predictive_leg(a, w, y, P))
