@@ -326,6 +326,56 @@ int tamcmc_group_members(const tamcmc_group *g, int32_t *n_members, int32_t *Npa
  *   loo_pit_kernel_time   as tamcmc_summary_predictive_kernel_time, for the PIT kernel alone; tamcmc_summary_kernel_time
  *                reports the prepare kernel with the tail and finalize kernels.
  *
+ * WINDOW-LOO: leave-one-WINDOW-out PSIS-LOO, and LOO-PIT per window.  Leaving one bin of a 20-bin mode out tests almost
+ * nothing -- the 19 neighbours pin the mode -- so per-bin elpd_loo and LOO-PIT are optimistic exactly where the question is
+ * whether the model predicts the feature, and the windowed check below uses each datum twice.  Bins are conditionally
+ * independent given the parameters, so leaving a window out is the same machinery fed with the window's sum of l: elpd and
+ * k-hat at the granularity of a feature, the unit at which two fits of one spectrum should be compared.  A mode of its own
+ * beside fold, quantile, LOO, ESS and band ESS mode, shaped like LOO mode and its LOO-PIT sub-mode; the windows are those of
+ * the windowed check (W in 1 ... TAMCMC_SUMMARY_WINDOW_MAX_BINS, first in 1 ... W, 0 = W; window 0 is [0, min(first, Nx)),
+ * window w >= 1 is [first + (w-1) W, min(first + w W, Nx))).  It does not need window_enable.
+ *   Definition.
+ *     Window sum: for window w and accepted sample s, S_ws = l_is (the fold kernel's l) added over the window's bins in
+ *       ascending bin order, starting from the first term, in plain double without contraction.  x_ws = -S_ws.
+ *     LOO per window: steps 1 - 5 of the PSIS-LOO definition above with "bin" read as "window" and x_ws for x_s: the same
+ *       M(n), cutoff, tail, fit, smoothing and elpd; totals in window order in long double: elpd_lwo; p_lwo = (the sum of lppd
+ *       over ALL bins, as tamcmc_summary_result forms it) - elpd_lwo; k_max, n_k_high, n_k_inf over the windows; n_windows,
+ *       W, first.  W = 1 is LOO mode bit for bit.
+ *     Sub-mode: steps 1 - 4 of the LOO-PIT definition above with x_ws for x, and for logP, logQ the windowed check's tails
+ *       of that sample and window (the window sum of the residuals through the Gamma(p len) or Gaussian tails described
+ *       under WINDOWED POSTERIOR PREDICTIVE CHECK, bit for bit what that check forms).  Per window: loo_pit, loo_log_cdf,
+ *       loo_log_sf, is_ess, log_wsum; the totals are those of LOO-PIT with windows in place of bins (bin_min_* hold window
+ *       indices).  W = 1 is LOO-PIT bit for bit where p is a power of two (as the windowed check is the per-bin check).
+ *   wloo_begin   freezes the fold state as loo_begin does, resolves first and n_windows (*n_windows, may be NULL), computes
+ *                M and allocates, with nw = n_windows and B = block_chains: 8 (M + 1) nw bytes for the per-window sets of the
+ *                M + 1 largest x, 52 nw + 32 bytes of state and 8 B nw bytes for a block's window sums; TAMCMC_E_NOMEM when
+ *                that fails, and the object stays as it was.  Refused with TAMCMC_E_INVALID: W or first out of range,
+ *                n_used < 1, M > TAMCMC_SUMMARY_LOO_MAX_TAIL, any mode already on (quantile, LOO, ESS, band ESS, this one), a
+ *                context with a batch in flight or armed.  While the mode is on every other mode's begin and the three
+ *                _enable functions are refused.
+ *   While the mode is on, push and push_device evaluate the rows as before and hand out the same logL and status bits, but
+ *   feed the sums and tail kernels (tamcmc_wloo.hip); the fold, predictive, window and scan states are not touched.  Every
+ *   result is bit for bit independent of block_chains and of how the pass is split over pushes.
+ *   wloo_result  totals and, per window, elpd_lwo, pareto_k, cutoff (doubles), tail_len (int32), first_bin and last_bin
+ *                (int64, inclusive) on the host, any of them may be NULL.  If the pass did not see exactly the fold pass's
+ *                accepted and rejected counts: TAMCMC_E_INVALID, the pass is discarded and may be repeated.  May be called
+ *                again without another pass.
+ *   wloo_pit_begin  allowed in the mode once its pass has seen exactly the fold pass's counts.  Allocates 8 M nw bytes for
+ *                the table of log weights, 116 nw + 36 bytes of state and 16 B nw bytes for a block's tails (TAMCMC_E_NOMEM
+ *                when that fails, and the object stays as it was), then sorts the top sets in place and fills the table (the
+ *                prepare kernel of LOO-PIT).  Refused with TAMCMC_E_INVALID: outside the mode; an incomplete pass, which is
+ *                left untouched; a second call; a chi(2,2p) context with p < 1 or p W > TAMCMC_SUMMARY_WINDOW_MAX_SHAPE; a
+ *                context with a batch armed or in flight.  From then on push and push_device feed the sub-mode's kernels.
+ *   wloo_pit_result  totals and five arrays of n_windows doubles on the host, any of them may be NULL.  If the third pass
+ *                did not see exactly the fold pass's counts, or a tail sample was not found bit for bit among the stored
+ *                values: TAMCMC_E_INVALID, the PIT pass is cleared and may be repeated.  May be called again.
+ *   wloo_end     frees the mode's memory, the sub-mode's included, and goes back to fold mode; tamcmc_summary_reset also
+ *                leaves the mode, tamcmc_summary_destroy works in any.  _result, _pit_* and _end outside the mode return
+ *                TAMCMC_E_INVALID.
+ *   profile / kernel_time in the mode: the sums and tail kernels of every block of the LOO pass, the finalize kernel of
+ *   every wloo_result and the prepare kernel; wloo_pit_kernel_time: the sums, tails and PIT kernels of every block of the
+ *   third pass together.
+ *
  * POSTERIOR PREDICTIVE CHECK: is the residual spectrum distributed as the likelihood claims, and in which bins is it not?
  * Per bin the predictive CDF of the datum averaged over the chain -- its probability integral transform (PIT) -- and both
  * tail probabilities as logarithms, which stay meaningful far below 1e-300: a missed mode has y / M of a few thousand.
@@ -636,6 +686,20 @@ int tamcmc_summary_window_enable(tamcmc_summary *s, int32_t W, int32_t first, in
 int tamcmc_summary_window_result(tamcmc_summary *s, tamcmc_summary_window_totals *totals,
                                  double *pit, double *log_cdf, double *log_sf, double *mean_resid);
 int tamcmc_summary_window_kernel_time(tamcmc_summary *s, double *total_ms, int64_t *launches);
+typedef struct {
+    int64_t n_used, n_rejected, n_windows, W, first;
+    double elpd_lwo, p_lwo, k_max;
+    int64_t n_k_high, n_k_inf;
+} tamcmc_summary_wloo_totals;
+int tamcmc_summary_wloo_begin(tamcmc_summary *s, int32_t W, int32_t first, int32_t *n_windows);
+int tamcmc_summary_wloo_result(tamcmc_summary *s, tamcmc_summary_wloo_totals *totals,
+                               double *elpd_lwo, double *pareto_k, double *cutoff, int32_t *tail_len,
+                               int64_t *first_bin, int64_t *last_bin);
+int tamcmc_summary_wloo_pit_begin(tamcmc_summary *s);
+int tamcmc_summary_wloo_pit_result(tamcmc_summary *s, tamcmc_summary_loo_pit_totals *totals,
+                                   double *loo_pit, double *loo_log_cdf, double *loo_log_sf, double *is_ess, double *log_wsum);
+int tamcmc_summary_wloo_pit_kernel_time(tamcmc_summary *s, double *total_ms, int64_t *launches);
+int tamcmc_summary_wloo_end(tamcmc_summary *s);
 #define TAMCMC_SUMMARY_SCAN_MAX_WIDTHS 8
 typedef struct {
     int64_t n_used, n_rejected, W, n_positions;

@@ -36,6 +36,8 @@ EXPORTS = [
     "tamcmc_summary_loo_pit_begin", "tamcmc_summary_loo_pit_result", "tamcmc_summary_loo_pit_kernel_time",
     "tamcmc_summary_predictive_enable", "tamcmc_summary_predictive_result", "tamcmc_summary_predictive_kernel_time",
     "tamcmc_summary_window_enable", "tamcmc_summary_window_result", "tamcmc_summary_window_kernel_time",
+    "tamcmc_summary_wloo_begin", "tamcmc_summary_wloo_result", "tamcmc_summary_wloo_pit_begin", "tamcmc_summary_wloo_pit_result",
+    "tamcmc_summary_wloo_pit_kernel_time", "tamcmc_summary_wloo_end",
     "tamcmc_summary_scan_enable", "tamcmc_summary_scan_result", "tamcmc_summary_scan_regions", "tamcmc_summary_scan_kernel_time",
     "tamcmc_summary_ess_begin", "tamcmc_summary_ess_result", "tamcmc_summary_ess_acov", "tamcmc_summary_ess_end",
     "tamcmc_summary_bandess_begin", "tamcmc_summary_bandess_result", "tamcmc_summary_bandess_counts", "tamcmc_summary_bandess_end",
@@ -79,6 +81,12 @@ class SummaryWindowTotals(C.Structure):
     _fields_ = [("n_used", C.c_int64), ("n_rejected", C.c_int64), ("n_windows", C.c_int64), ("W", C.c_int64), ("first", C.c_int64),
                 ("ks_D", C.c_double), ("min_log_sf", C.c_double), ("min_log_cdf", C.c_double),
                 ("win_min_log_sf", C.c_int64), ("win_min_log_cdf", C.c_int64), ("pit_hist", C.c_int64 * PIT_CELLS)]
+
+
+class SummaryWlooTotals(C.Structure):
+    """tamcmc_summary_wloo_totals"""
+    _fields_ = [("n_used", C.c_int64), ("n_rejected", C.c_int64), ("n_windows", C.c_int64), ("W", C.c_int64), ("first", C.c_int64),
+                ("elpd_lwo", C.c_double), ("p_lwo", C.c_double), ("k_max", C.c_double), ("n_k_high", C.c_int64), ("n_k_inf", C.c_int64)]
 
 
 class SummaryScanTotals(C.Structure):
@@ -188,6 +196,12 @@ def load_library():
     lib.tamcmc_summary_window_enable.argtypes = [vp, C.c_int32, C.c_int32, ip]
     lib.tamcmc_summary_window_result.argtypes = [vp, C.POINTER(SummaryWindowTotals), dp, dp, dp, dp]
     lib.tamcmc_summary_window_kernel_time.argtypes = [vp, dp, C.POINTER(C.c_int64)]
+    lib.tamcmc_summary_wloo_begin.argtypes = [vp, C.c_int32, C.c_int32, ip]
+    lib.tamcmc_summary_wloo_result.argtypes = [vp, C.POINTER(SummaryWlooTotals), dp, dp, dp, ip, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+    lib.tamcmc_summary_wloo_pit_begin.argtypes = [vp]
+    lib.tamcmc_summary_wloo_pit_result.argtypes = [vp, C.POINTER(SummaryLooPitTotals), dp, dp, dp, dp, dp]
+    lib.tamcmc_summary_wloo_pit_kernel_time.argtypes = [vp, dp, C.POINTER(C.c_int64)]
+    lib.tamcmc_summary_wloo_end.argtypes = [vp]
     lib.tamcmc_summary_scan_enable.argtypes = [vp, C.c_int32, ip]
     lib.tamcmc_summary_scan_result.argtypes = [vp, C.c_int32, C.POINTER(SummaryScanTotals), dp, dp, dp, dp]
     lib.tamcmc_summary_scan_regions.argtypes = [vp, C.c_int32, C.c_int32, C.c_double, C.c_int32, C.POINTER(SummaryScanRegion), ip]
@@ -525,7 +539,8 @@ class Summary:
     Pareto k-hat per bin) by pushing them once more -- with pit=True a third time, for LOO-PIT and the PSIS weights' effective
     sample size per bin --, and ess() the effective sample size, Monte-Carlo standard error and
     split R-hat per bin by pushing them once more in the same order; band_ess() the quantiles together with the effective sample
-    size of each of them (of the indicator M <= quantile), by one more pass after the selection.  With predictive=True every fold pass also accumulates the
+    size of each of them (of the indicator M <= quantile), by one more pass after the selection; window_loo() PSIS-LOO and LOO-PIT with a
+    whole window of bins left out, over the windows of the windowed check.  With predictive=True every fold pass also accumulates the
     posterior predictive check (predictive_result(): PIT and both log tail probabilities per bin), and with window=W or
     window=(W, first) the same check over disjoint windows of W bins (window_result()); with scan=W or scan=(W0, W1, ...) the
     windowed check at every start position for up to eight widths at once (scan_result(k), scan_regions(k)).  The Accel cannot be closed while
@@ -585,6 +600,7 @@ class Summary:
         self._loo = False                                       # and LOO mode
         self._ess_lag = 0                                       # and ESS mode
         self._band = None                                       # and band ESS mode
+        self._wloo = 0                                          # and window-LOO mode
 
     def profile(self, enable=True):
         self._check(self._lib.tamcmc_summary_profile(self._s, int(enable)), "tamcmc_summary_profile")
@@ -795,6 +811,83 @@ class Summary:
         self._check(self._lib.tamcmc_summary_window_kernel_time(self._s, C.byref(ms), C.byref(n)),
                     "tamcmc_summary_window_kernel_time")
         return ms.value, n.value
+
+    # ---- window-LOO: PSIS-LOO and LOO-PIT with a window of bins left out, the windows of the windowed check ----
+    WLOO_ARRAYS = ("elpd_lwo", "pareto_k", "cutoff")
+    WLOO_TOTALS = ("n_used", "n_rejected", "n_windows", "W", "first", "elpd_lwo_total", "p_lwo", "k_max", "n_k_high", "n_k_inf")
+
+    def wloo_begin(self, W, first=0):
+        """Enters window-LOO mode (W bins per window, the first window `first` bins, 0 = W; window_enable is not needed).
+        From here on push / push_device feed its kernels: push the same rows again, then wloo_result().  Returns the
+        number of windows."""
+        nw = C.c_int32(0)
+        self._check(self._lib.tamcmc_summary_wloo_begin(self._s, int(W), int(first), C.byref(nw)), "tamcmc_summary_wloo_begin")
+        self._wloo = int(nw.value)
+        return self._wloo
+
+    def wloo_result(self):
+        """dict: elpd_lwo, pareto_k, cutoff (n_windows doubles), tail_len (int32), first_bin and last_bin (int64,
+        inclusive) and the totals n_used, n_rejected, n_windows, W, first, elpd_lwo_total, p_lwo, k_max, n_k_high, n_k_inf."""
+        nw = max(getattr(self, "_wloo", 0), 1)                  # (outside the mode the library refuses before it writes)
+        out = {k: np.empty(nw) for k in self.WLOO_ARRAYS}
+        out["tail_len"] = np.empty(nw, dtype=np.int32)
+        out["first_bin"], out["last_bin"] = np.empty(nw, dtype=np.int64), np.empty(nw, dtype=np.int64)
+        t = SummaryWlooTotals()
+        lp = C.POINTER(C.c_int64)
+        self._check(self._lib.tamcmc_summary_wloo_result(self._s, C.byref(t), *[_dptr(out[k]) for k in self.WLOO_ARRAYS],
+                                                         _iptr(out["tail_len"]), out["first_bin"].ctypes.data_as(lp),
+                                                         out["last_bin"].ctypes.data_as(lp)), "tamcmc_summary_wloo_result")
+        out.update(n_used=int(t.n_used), n_rejected=int(t.n_rejected), n_windows=int(t.n_windows), W=int(t.W), first=int(t.first),
+                   elpd_lwo_total=t.elpd_lwo, p_lwo=t.p_lwo, k_max=t.k_max, n_k_high=int(t.n_k_high), n_k_inf=int(t.n_k_inf))
+        return out
+
+    def wloo_pit_begin(self):
+        """In window-LOO mode, after a complete pass: sorts the top sets, fills the table of log weights.  From here on
+        push / push_device feed the sub-mode's kernels: push the same rows a third time, then wloo_pit_result()."""
+        self._check(self._lib.tamcmc_summary_wloo_pit_begin(self._s), "tamcmc_summary_wloo_pit_begin")
+
+    def wloo_pit_result(self):
+        """dict with the keys of loo_pit_result(), per window: the arrays have n_windows entries and bin_min_* hold
+        window indices."""
+        nw = max(getattr(self, "_wloo", 0), 1)
+        out = {k: np.empty(nw) for k in self.LOO_PIT_ARRAYS}
+        t = SummaryLooPitTotals()
+        self._check(self._lib.tamcmc_summary_wloo_pit_result(self._s, C.byref(t), *[_dptr(out[k]) for k in self.LOO_PIT_ARRAYS]),
+                    "tamcmc_summary_wloo_pit_result")
+        out.update(n_used=int(t.n_used), n_rejected=int(t.n_rejected), loo_ks_D=t.ks_D, min_loo_log_sf=t.min_log_sf,
+                   min_loo_log_cdf=t.min_log_cdf, min_is_ess=t.min_is_ess, bin_min_loo_log_sf=int(t.bin_min_log_sf),
+                   bin_min_loo_log_cdf=int(t.bin_min_log_cdf), bin_min_is_ess=int(t.bin_min_is_ess),
+                   loo_pit_hist=np.array(list(t.pit_hist), dtype=np.int64))
+        return out
+
+    def wloo_pit_kernel_time(self):
+        """(summed milliseconds, blocks) of the sub-mode's sums, tails and PIT kernels since profile(True)."""
+        ms = C.c_double(0.0)
+        n = C.c_int64(0)
+        self._check(self._lib.tamcmc_summary_wloo_pit_kernel_time(self._s, C.byref(ms), C.byref(n)),
+                    "tamcmc_summary_wloo_pit_kernel_time")
+        return ms.value, n.value
+
+    def wloo_end(self):
+        self._check(self._lib.tamcmc_summary_wloo_end(self._s), "tamcmc_summary_wloo_end")
+        self._wloo = 0
+
+    def window_loo(self, params, W, first=0, pit=False):
+        """Leave-one-window-out PSIS-LOO over the rows already pushed, `params` being those rows: begin, one push, result,
+        end.  Returns the dict of wloo_result() and always leaves the mode.  pit=True: a third push, and the dict has the
+        keys of wloo_pit_result() as well."""
+        self.wloo_begin(W, first)
+        try:
+            self.push(params)
+            out = self.wloo_result()
+            if pit:
+                self.wloo_pit_begin()
+                self.push(params)
+                out.update(self.wloo_pit_result())
+            return out
+        finally:
+            if getattr(self, "_wloo", 0):
+                self.wloo_end()
 
     # ---- sliding-window predictive scan: the windowed check at every start position, several widths at once ----
     SCAN_MAX_WIDTHS = 8

@@ -12,6 +12,9 @@
 // kernels of tamcmc_scan.hip per chunk of the block, on the same rows.
 // In ESS mode (tamcmc_summary_ess_*, tamcmc_ess.h) stage 2 is the centre and lag kernels of tamcmc_ess.hip, once per chunk of
 // the block; in band ESS mode (tamcmc_summary_bandess_*, tamcmc_bandess.h) the pack and lag kernels of tamcmc_bandess.hip, likewise.
+// In window-LOO mode (tamcmc_summary_wloo_*, tamcmc_wloo.h) stage 2 is the sums and tail kernels of tamcmc_wloo.hip, and after
+// tamcmc_summary_wloo_pit_begin its sums, tails and PIT kernels; the per-window results come from LOO mode's finalize and
+// prepare kernels.
 #include <algorithm>
 #include <cmath>
 #include <new>
@@ -26,6 +29,7 @@
 #include "tamcmc_scan.h"
 #include "tamcmc_summary.h"
 #include "tamcmc_window.h"
+#include "tamcmc_wloo.h"
 
 // {accepted, rejected} of a pass on the device, [2][2] words: launch k reads pair k & 1 and writes the other, so no
 // workgroup reads a word that another workgroup of the same launch writes (TmSummaryArgs::cnt_in / cnt_out).  read(): idle stream.
@@ -74,6 +78,27 @@ struct TmLooMode : TmMode {
     int32_t *pit_first = nullptr, *pit_flag = nullptr;
     int p = 1, nterms = 0;               // as TmPredictive
     double lf_pm1 = 0.0, lf_p = 0.0;
+};
+
+// Window-LOO mode (tamcmc_wloo.h): LOO mode and its sub-mode over the windows of the windowed check.  The heap, body, results
+// and the sub-mode's state are laid out as TmLooMode's with n_windows in the place of Nx.
+struct TmWlooMode : TmMode {
+    int W = 0, first = 0, n_windows = 0;
+    int cap = 0;                         // M + 1 heap slots per window
+    double *d_heap = nullptr;            // [cap][n_windows]
+    char *d_state = nullptr;             // one allocation: body[3][nw] | elpd | khat | cutoff | cnt[2][2] | tail_len
+    double *d_sum = nullptr;             // [B][n_windows]: the window sums of l of the block in flight
+    double *body = nullptr, *elpd = nullptr, *khat = nullptr, *cutoff = nullptr;
+    int32_t *tail_len = nullptr;
+    bool pit = false;
+    TmCountPair pit_cnt;
+    double *d_lw = nullptr;              // [cap - 1][n_windows]
+    char *d_pit = nullptr;               // one allocation: sums[TM_LOOPIT_NSTATE][nw] | xmax | c | cnt[2][2] | first slot | flag
+    double *d_tails = nullptr;           // [2][B][n_windows]: logP (the residual sum before the tails kernel) | logQ
+    double *pit_sums = nullptr, *pit_xmax = nullptr, *pit_c = nullptr;
+    int32_t *pit_first = nullptr, *pit_flag = nullptr;
+    int p = 1;
+    TmWinShape shape[3] = {};            // first window, full windows, last window
 };
 
 // ESS mode: the lag products, the rings of centred values and the half-chain moments of the pass on the device, and what the
@@ -153,6 +178,8 @@ struct tamcmc_summary {
     TmQuantMode q;
     TmLooMode loo;
     TmTimer pit_timer;                   // the LOO-PIT kernel alone (tamcmc_summary_loo_pit_kernel_time)
+    TmWlooMode wloo;
+    TmTimer wpit_timer;                  // the blocks of window-LOO's PIT pass (tamcmc_summary_wloo_pit_kernel_time)
     TmEssMode ess;
     TmBandMode band;
     TmPredictive pred;
@@ -189,6 +216,7 @@ static const TmMode *active_mode(const tamcmc_summary *s)
     if (s->q.on) return &s->q;
     if (s->loo.on) return &s->loo;
     if (s->ess.on) return &s->ess;
+    if (s->wloo.on) return &s->wloo;
     return s->band.on ? &s->band : nullptr;
 }
 
@@ -314,6 +342,82 @@ static int loopit_pass_clear(tamcmc_summary *s)
     TM_HIP(hipMemsetAsync(m.pit_sums, 0, (size_t)TM_LOOPIT_NSTATE * (size_t)s->c->L.Nx * sizeof(double), s->c->stream));
     TM_HIP(hipMemsetAsync(m.pit_flag, 0, sizeof(int32_t), s->c->stream));
     return m.pit_cnt.clear(s->c->stream);
+}
+
+static TmWlooArgs wloo_args(const tamcmc_summary *s)
+{
+    const TmWlooMode &m = s->wloo;
+    const tamcmc_ctx *c = s->c;
+    const size_t plane = (size_t)s->B * (size_t)m.n_windows;
+    TmWlooArgs a{};
+    a.rows = s->d_model; a.y = c->d_y; a.isig2 = c->d_isig2;
+    a.sum = m.d_sum; a.logP = m.d_tails; a.logQ = m.d_tails ? m.d_tails + plane : nullptr;
+    a.heap = m.d_heap; a.body = m.body;
+    a.lw = m.d_lw; a.xmax = m.pit_xmax; a.c = m.pit_c; a.first_slot = m.pit_first; a.state = m.pit_sums; a.flag = m.pit_flag;
+    a.cnt_in = m.pit ? m.pit_cnt.in() : m.cnt.in(); a.cnt_out = m.pit ? m.pit_cnt.out() : m.cnt.out();
+    a.Nx = c->L.Nx; a.Bcap = s->B; a.n_windows = m.n_windows; a.W = m.W; a.first = m.first;
+    a.likelihood_case = c->L.likelihood_case; a.p = m.p; a.cap = m.cap; a.trips = tlp_trips(m.cap - 1);
+    a.like_p = c->L.like_p;
+    for (int k = 0; k < 3; k++) a.shape[k] = m.shape[k];
+    return a;
+}
+
+// The finalize kernel of LOO mode and the prepare kernel of LOO-PIT over the windows: n_windows in the place of Nx.  (Neither
+// kernel reads rows, y or the likelihood; the prepare launch's check of p is the per-bin check's, so it gets 1.)
+static TmLooArgs wloo_finalize_args(const tamcmc_summary *s)
+{
+    const TmWlooMode &m = s->wloo;
+    TmLooArgs a{};
+    a.heap = m.d_heap; a.body = m.body;
+    a.elpd = m.elpd; a.khat = m.khat; a.cutoff = m.cutoff; a.tail_len = m.tail_len;
+    a.n = m.n_used; a.Nx = m.n_windows; a.likelihood_case = s->c->L.likelihood_case; a.cap = m.cap; a.like_p = s->c->L.like_p;
+    return a;
+}
+
+static TmLooPitArgs wloo_prepare_args(const tamcmc_summary *s)
+{
+    const TmWlooMode &m = s->wloo;
+    TmLooPitArgs a{};
+    a.heap = m.d_heap; a.body = m.body;
+    a.lw = m.d_lw; a.xmax = m.pit_xmax; a.c = m.pit_c; a.first = m.pit_first; a.state = m.pit_sums;
+    a.n = m.n_used; a.Nx = m.n_windows; a.likelihood_case = s->c->L.likelihood_case; a.cap = m.cap;
+    a.p = 1; a.trips = tlp_trips(m.cap - 1);
+    return a;
+}
+
+// stage 2 of a block in window-LOO mode: the sums and tail kernels, or in the sub-mode the sums, tails and PIT kernels
+static int wloo_block(tamcmc_summary *s, int n, const int32_t *d_status)
+{
+    TmWlooArgs a = wloo_args(s);
+    a.status = d_status; a.B = n;
+    if (s->wloo.pit)
+        return timed_launch(s, s->wpit_timer, "summary wloo pit", [&] { return tm_launch_wloo_pit(a, s->c->stream); }, &s->wloo.pit_cnt);
+    return timed_launch(s, s->timer, "summary wloo tail", [&] { return tm_launch_wloo_tail(a, s->c->stream); }, &s->wloo.cnt);
+}
+
+// a pass starts from empty counts and empty body sums (with no sample counted the heap holds nothing)
+static int wloo_pass_clear(tamcmc_summary *s)
+{
+    TmWlooMode &m = s->wloo;
+    TM_HIP(hipMemsetAsync(m.body, 0, 3 * (size_t)m.n_windows * sizeof(double), s->c->stream));
+    return m.cnt.clear(s->c->stream);
+}
+
+// the sub-mode's pass starts from empty counts, empty sums and a clear flag
+static int wloo_pit_pass_clear(tamcmc_summary *s)
+{
+    TmWlooMode &m = s->wloo;
+    TM_HIP(hipMemsetAsync(m.pit_sums, 0, (size_t)TM_LOOPIT_NSTATE * (size_t)m.n_windows * sizeof(double), s->c->stream));
+    TM_HIP(hipMemsetAsync(m.pit_flag, 0, sizeof(int32_t), s->c->stream));
+    return m.pit_cnt.clear(s->c->stream);
+}
+
+// the stream must be idle
+static void wloo_free(tamcmc_summary *s)
+{
+    TmWlooMode &m = s->wloo;
+    (void)hipFree(m.d_state); (void)hipFree(m.d_heap); (void)hipFree(m.d_sum); (void)hipFree(m.d_lw); (void)hipFree(m.d_pit); (void)hipFree(m.d_tails);
+    s->wloo = TmWlooMode();
 }
 
 static TmEssArgs ess_args(const tamcmc_summary *s)
@@ -465,6 +569,7 @@ static int summary_block(tamcmc_summary *s, int n, const double *d_params, doubl
     if (s->q.on) return quantile_block(s, n, d_status);
     if (s->loo.on) return s->loo.pit ? loopit_block(s, n, d_status) : loo_block(s, n, d_status);
     if (s->ess.on) return ess_block(s, n, d_status);
+    if (s->wloo.on) return wloo_block(s, n, d_status);
     if (s->band.on) return band_block(s, n, d_status);
     TmSummaryArgs a{};
     a.rows = s->d_model; a.status = d_status; a.y = c->d_y; a.isig2 = c->d_isig2; a.state = s->d_state;
@@ -536,6 +641,7 @@ extern "C" int tamcmc_summary_destroy(tamcmc_summary *s)
     loo_free(s);
     ess_free(s);
     band_free(s);
+    wloo_free(s);
     (void)hipFree(s->d_model); (void)hipFree(s->d_state); (void)hipFree(s->cnt.d); (void)hipFree(s->d_rows);
     (void)hipFree(s->d_T); (void)hipFree(s->d_logL); (void)hipFree(s->d_status); (void)hipFree(s->pred.d_state);
     (void)hipFree(s->win.d_state); (void)hipFree(s->win.d_scratch);
@@ -546,6 +652,7 @@ extern "C" int tamcmc_summary_destroy(tamcmc_summary *s)
     }
     s->timer.destroy();
     s->pit_timer.destroy();
+    s->wpit_timer.destroy();
     s->pred.timer.destroy();
     s->win.timer.destroy();
     s->scan.timer.destroy();
@@ -558,12 +665,13 @@ extern "C" int tamcmc_summary_reset(tamcmc_summary *s)
     if (!s || s->c->in_flight || s->c->armed) return TAMCMC_E_INVALID;
     tamcmc_ctx *c = s->c;
     TM_HIP(hipSetDevice(c->device));
-    if (active_mode(s)) {                           // reset leaves quantile mode, LOO mode, ESS mode and band ESS mode
+    if (active_mode(s)) {                           // reset leaves quantile mode, LOO mode, ESS mode, band ESS mode and window-LOO mode
         TM_HIP(tm_ctx_stream_sync(c));
         quantile_free(s);
         loo_free(s);
         ess_free(s);
         band_free(s);
+        wloo_free(s);
     }
     TM_HIP(tm_ctx_settle(c));
     c->enq_seq++;
@@ -684,6 +792,7 @@ extern "C" int tamcmc_summary_profile(tamcmc_summary *s, int enable)
     s->profile = enable != 0;
     s->timer.used = 0;
     s->pit_timer.used = 0;
+    s->wpit_timer.used = 0;
     s->pred.timer.used = 0;
     s->win.timer.used = 0;
     s->scan.timer.used = 0;
@@ -877,6 +986,51 @@ extern "C" int tamcmc_summary_loo_begin(tamcmc_summary *s)
     return TAMCMC_OK;
 }
 
+// What loo_result and wloo_result share once their pass is known to be complete: `finalize` enqueues the finalize kernel
+// over m units (bins or windows), whose results lie at d_out (elpd | khat | cutoff, m doubles each) and d_tl; the arrays go
+// to the host (any may be NULL) and the totals are summed in unit order in long double, lppd over all bins.
+struct TmLooSums {
+    double elpd, p, k_max;
+    int64_t n_high, n_inf;
+};
+
+template <class F>
+static int loo_collect(tamcmc_summary *s, const size_t m, const double *d_out, const int32_t *d_tl, const long long n_used, F &&finalize,
+                       double *elpd_loo, double *pareto_k, double *cutoff, int32_t *tail_len, TmLooSums *sums)
+{
+    tamcmc_ctx *c = s->c;
+    const size_t nx = (size_t)c->L.Nx;
+    std::vector<double> out, lse;
+    std::vector<int32_t> tl;
+    try { out.resize(3 * m); lse.resize(2 * nx); tl.resize(m); } catch (const std::bad_alloc &) { return TAMCMC_E_NOMEM; }
+    const int rc = finalize();
+    if (rc != TAMCMC_OK) return rc;
+    TM_HIP(hipMemcpyAsync(out.data(), d_out, 3 * m * sizeof(double), hipMemcpyDeviceToHost, c->stream));      // elpd | khat | cutoff
+    TM_HIP(hipMemcpyAsync(tl.data(), d_tl, m * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    TM_HIP(hipMemcpyAsync(lse.data(), s->d_state + (size_t)TM_SUM_LSE_A * nx, 2 * nx * sizeof(double), hipMemcpyDeviceToHost, c->stream));   // a | r
+    TM_HIP(hipStreamSynchronize(c->stream));
+    const double dn = (double)n_used;
+    long double lppd_total = 0.0L, elpd_total = 0.0L;
+    double k_max = std::nan("");
+    int64_t n_high = 0, n_inf = 0;
+    for (size_t i = 0; i < nx; i++) lppd_total += (long double)tm_lppd(lse[i], lse[nx + i], dn);      // as tamcmc_summary_result, in bin order
+    for (size_t i = 0; i < m; i++) {
+        const double k = out[m + i];
+        elpd_total += (long double)out[i];
+        if (!(k <= k_max)) k_max = std::isnan(k) ? k_max : k;                 // (a NaN k-hat is never the maximum)
+        if (k > 0.7) n_high++;
+        if (std::isinf(k) && k > 0.0) n_inf++;
+    }
+    if (elpd_loo) std::memcpy(elpd_loo, out.data(), m * sizeof(double));
+    if (pareto_k) std::memcpy(pareto_k, out.data() + m, m * sizeof(double));
+    if (cutoff) std::memcpy(cutoff, out.data() + 2 * m, m * sizeof(double));
+    if (tail_len) std::memcpy(tail_len, tl.data(), m * sizeof(int32_t));
+    sums->elpd = (double)elpd_total;
+    sums->p = (double)(lppd_total - elpd_total);
+    sums->k_max = k_max; sums->n_high = n_high; sums->n_inf = n_inf;
+    return TAMCMC_OK;
+}
+
 extern "C" int tamcmc_summary_loo_result(tamcmc_summary *s, tamcmc_summary_loo_totals *totals, double *elpd_loo, double *pareto_k,
                                          double *cutoff, int32_t *tail_len)
 {
@@ -893,43 +1047,22 @@ extern "C" int tamcmc_summary_loo_result(tamcmc_summary *s, tamcmc_summary_loo_t
         rc = loo_pass_clear(s);
         return rc != TAMCMC_OK ? rc : TAMCMC_E_INVALID;
     }
-    const size_t nx = (size_t)c->L.Nx;
-    std::vector<double> out, lse;
-    std::vector<int32_t> tl;
-    try { out.resize(3 * nx); lse.resize(2 * nx); tl.resize(nx); } catch (const std::bad_alloc &) { return TAMCMC_E_NOMEM; }
     TmLooArgs a = loo_args(s);
     a.n = m.n_used;
-    rc = timed_launch(s, s->timer, "summary loo finalize", [&] { return tm_launch_loo_finalize(a, c->stream); });
+    TmLooSums f;
+    rc = loo_collect(s, (size_t)c->L.Nx, m.elpd, m.tail_len, m.n_used,
+                     [&] { return timed_launch(s, s->timer, "summary loo finalize", [&] { return tm_launch_loo_finalize(a, c->stream); }); },
+                     elpd_loo, pareto_k, cutoff, tail_len, &f);
     if (rc != TAMCMC_OK) return rc;
-    TM_HIP(hipMemcpyAsync(out.data(), m.elpd, 3 * nx * sizeof(double), hipMemcpyDeviceToHost, c->stream));      // elpd | khat | cutoff
-    TM_HIP(hipMemcpyAsync(tl.data(), m.tail_len, nx * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-    TM_HIP(hipMemcpyAsync(lse.data(), s->d_state + (size_t)TM_SUM_LSE_A * nx, 2 * nx * sizeof(double), hipMemcpyDeviceToHost, c->stream));   // a | r
-    TM_HIP(hipStreamSynchronize(c->stream));
-    const double dn = (double)m.n_used;
-    long double lppd_total = 0.0L, elpd_total = 0.0L;
-    double k_max = std::nan("");
-    int64_t n_high = 0, n_inf = 0;
-    for (size_t i = 0; i < nx; i++) {
-        const double k = out[nx + i];
-        lppd_total += (long double)tm_lppd(lse[i], lse[nx + i], dn);          // as tamcmc_summary_result, in bin order
-        elpd_total += (long double)out[i];
-        if (!(k <= k_max)) k_max = std::isnan(k) ? k_max : k;                 // (a NaN k-hat is never the maximum)
-        if (k > 0.7) n_high++;
-        if (std::isinf(k) && k > 0.0) n_inf++;
-    }
-    if (elpd_loo) std::memcpy(elpd_loo, out.data(), nx * sizeof(double));
-    if (pareto_k) std::memcpy(pareto_k, out.data() + nx, nx * sizeof(double));
-    if (cutoff) std::memcpy(cutoff, out.data() + 2 * nx, nx * sizeof(double));
-    if (tail_len) std::memcpy(tail_len, tl.data(), nx * sizeof(int32_t));
     if (totals) {
         totals->n_used = m.n_used;
         totals->n_rejected = m.n_rejected;
-        totals->elpd_loo = (double)elpd_total;
-        totals->p_loo = (double)(lppd_total - elpd_total);
-        totals->looic = (double)(-2.0L * elpd_total);
-        totals->k_max = k_max;
-        totals->n_k_high = n_high;
-        totals->n_k_inf = n_inf;
+        totals->elpd_loo = f.elpd;
+        totals->p_loo = f.p;
+        totals->looic = (double)(-2.0L * (long double)f.elpd);
+        totals->k_max = f.k_max;
+        totals->n_k_high = f.n_high;
+        totals->n_k_inf = f.n_inf;
     }
     return TAMCMC_OK;
 }
@@ -990,31 +1123,18 @@ extern "C" int tamcmc_summary_loo_pit_begin(tamcmc_summary *s)
     return TAMCMC_OK;
 }
 
-extern "C" int tamcmc_summary_loo_pit_result(tamcmc_summary *s, tamcmc_summary_loo_pit_totals *totals, double *loo_pit, double *loo_log_cdf,
-                                             double *loo_log_sf, double *is_ess, double *log_wsum)
+// What loo_pit_result and wloo_pit_result share once their pass is known to be complete: d_sums[TM_LOOPIT_NSTATE + 1][nx], the
+// four sums and xmax of nx units (bins or windows); the five arrays (any may be NULL) and the totals in unit order.
+static int loopit_collect(const double *d_sums, const size_t nx, const long long n_used, const long long n_rejected,
+                          tamcmc_summary_loo_pit_totals *totals, double *loo_pit, double *loo_log_cdf, double *loo_log_sf,
+                          double *is_ess, double *log_wsum)
 {
-    if (!s || !s->loo.on || !s->loo.pit) return TAMCMC_E_INVALID;
-    int rc = summary_enter(s);
-    if (rc != TAMCMC_OK) return rc;
-    tamcmc_ctx *c = s->c;
-    TmLooMode &m = s->loo;
-    c->enq_seq++;
-    long long cnt[2] = {0, 0};
-    int32_t flag = 0;
-    rc = m.pit_cnt.read(cnt);
-    if (rc != TAMCMC_OK) return rc;
-    TM_HIP(hipMemcpy(&flag, m.pit_flag, sizeof flag, hipMemcpyDeviceToHost));
-    if (cnt[0] != m.n_used || cnt[1] != m.n_rejected || flag != 0) {    // not the LOO pass's samples: the PIT pass is discarded
-        rc = loopit_pass_clear(s);
-        return rc != TAMCMC_OK ? rc : TAMCMC_E_INVALID;
-    }
-    const size_t nx = (size_t)c->L.Nx;
     std::vector<double> st, u;
     try { st.resize(((size_t)TM_LOOPIT_NSTATE + 1) * nx); u.reserve(nx); } catch (const std::bad_alloc &) { return TAMCMC_E_NOMEM; }
-    TM_HIP(hipMemcpy(st.data(), m.pit_sums, st.size() * sizeof(double), hipMemcpyDeviceToHost));         // sums | xmax
+    TM_HIP(hipMemcpy(st.data(), d_sums, st.size() * sizeof(double), hipMemcpyDeviceToHost));         // sums | xmax
     const double nan = std::nan("");
     tamcmc_summary_loo_pit_totals t{};
-    t.n_used = m.n_used; t.n_rejected = m.n_rejected;
+    t.n_used = n_used; t.n_rejected = n_rejected;
     t.ks_D = nan; t.min_log_sf = nan; t.min_log_cdf = nan; t.min_is_ess = nan;
     t.bin_min_log_sf = -1; t.bin_min_log_cdf = -1; t.bin_min_is_ess = -1;
     for (size_t i = 0; i < nx; i++) {
@@ -1044,12 +1164,196 @@ extern "C" int tamcmc_summary_loo_pit_result(tamcmc_summary *s, tamcmc_summary_l
     return TAMCMC_OK;
 }
 
+extern "C" int tamcmc_summary_loo_pit_result(tamcmc_summary *s, tamcmc_summary_loo_pit_totals *totals, double *loo_pit, double *loo_log_cdf,
+                                             double *loo_log_sf, double *is_ess, double *log_wsum)
+{
+    if (!s || !s->loo.on || !s->loo.pit) return TAMCMC_E_INVALID;
+    int rc = summary_enter(s);
+    if (rc != TAMCMC_OK) return rc;
+    tamcmc_ctx *c = s->c;
+    TmLooMode &m = s->loo;
+    c->enq_seq++;
+    long long cnt[2] = {0, 0};
+    int32_t flag = 0;
+    rc = m.pit_cnt.read(cnt);
+    if (rc != TAMCMC_OK) return rc;
+    TM_HIP(hipMemcpy(&flag, m.pit_flag, sizeof flag, hipMemcpyDeviceToHost));
+    if (cnt[0] != m.n_used || cnt[1] != m.n_rejected || flag != 0) {    // not the LOO pass's samples: the PIT pass is discarded
+        rc = loopit_pass_clear(s);
+        return rc != TAMCMC_OK ? rc : TAMCMC_E_INVALID;
+    }
+    return loopit_collect(m.pit_sums, (size_t)c->L.Nx, m.n_used, m.n_rejected, totals, loo_pit, loo_log_cdf, loo_log_sf, is_ess, log_wsum);
+}
+
 extern "C" int tamcmc_summary_loo_pit_kernel_time(tamcmc_summary *s, double *total_ms, int64_t *launches)
 {
     if (!s || !total_ms || !launches || !s->loo.on || !s->loo.pit || s->c->armed) return TAMCMC_E_INVALID;
     TM_HIP(hipSetDevice(s->c->device));
     TM_HIP(tm_ctx_stream_sync(s->c));
     return s->pit_timer.total(total_ms, launches);
+}
+
+// ---- window-LOO: PSIS-LOO and LOO-PIT with a window left out (tamcmc_wloo.h) ----
+
+extern "C" int tamcmc_summary_wloo_begin(tamcmc_summary *s, int32_t W, int32_t first, int32_t *n_windows)
+{
+    if (!s || W < 1 || W > TAMCMC_SUMMARY_WINDOW_MAX_BINS || first < 0 || first > W || active_mode(s)) return TAMCMC_E_INVALID;
+    tamcmc_ctx *c = s->c;
+    long long cnt[2] = {0, 0};
+    const int rc = summary_enter(s, cnt);
+    if (rc != TAMCMC_OK) return rc;
+    if (cnt[0] < 1) return TAMCMC_E_INVALID;
+    const int64_t M = tml_tail_M((int64_t)cnt[0]);
+    if (M > TAMCMC_SUMMARY_LOO_MAX_TAIL) return TAMCMC_E_INVALID;       // thin the chain
+    TmWlooMode m;
+    int f = first, len[3];
+    const size_t nw = (size_t)tmw_partition((long long)c->L.Nx, W, &f, len);
+    m.W = W; m.first = f; m.n_windows = (int)nw;
+    m.cap = (int)M + 1;
+    m.n_used = cnt[0]; m.n_rejected = cnt[1];
+    m.p = c->L.likelihood_case == 0 ? (int)c->L.like_p : 1;
+    if (hipMalloc(&m.d_state, twl_state_bytes(nw)) != hipSuccess) { (void)hipGetLastError(); return TAMCMC_E_NOMEM; }
+    if (hipMalloc(&m.d_heap, twl_heap_bytes(nw, (size_t)M)) != hipSuccess) { (void)hipGetLastError(); (void)hipFree(m.d_state); return TAMCMC_E_NOMEM; }
+    if (hipMalloc(&m.d_sum, twl_scratch_bytes(nw, (size_t)s->B)) != hipSuccess) {
+        (void)hipGetLastError(); (void)hipFree(m.d_state); (void)hipFree(m.d_heap);
+        return TAMCMC_E_NOMEM;
+    }
+    m.body = reinterpret_cast<double *>(m.d_state);
+    m.elpd = m.body + 3 * nw;
+    m.khat = m.elpd + nw;
+    m.cutoff = m.khat + nw;
+    m.cnt.d = reinterpret_cast<long long *>(m.cutoff + nw);
+    m.tail_len = reinterpret_cast<int32_t *>(m.cnt.d + 4);
+    m.on = true;
+    s->wloo = m;
+    c->enq_seq++;
+    if (wloo_pass_clear(s) != TAMCMC_OK) { (void)hipStreamSynchronize(c->stream); wloo_free(s); return TAMCMC_E_HIP; }
+    if (n_windows) *n_windows = (int32_t)nw;
+    return TAMCMC_OK;
+}
+
+extern "C" int tamcmc_summary_wloo_result(tamcmc_summary *s, tamcmc_summary_wloo_totals *totals, double *elpd_lwo, double *pareto_k,
+                                          double *cutoff, int32_t *tail_len, int64_t *first_bin, int64_t *last_bin)
+{
+    if (!s || !s->wloo.on) return TAMCMC_E_INVALID;
+    int rc = summary_enter(s);
+    if (rc != TAMCMC_OK) return rc;
+    tamcmc_ctx *c = s->c;
+    TmWlooMode &m = s->wloo;
+    c->enq_seq++;
+    bool complete = false;
+    rc = pass_complete(m, &complete);
+    if (rc != TAMCMC_OK) return rc;
+    if (!complete) {                                                    // not the fold pass's samples: the pass is discarded
+        rc = wloo_pass_clear(s);
+        return rc != TAMCMC_OK ? rc : TAMCMC_E_INVALID;
+    }
+    const TmLooArgs a = wloo_finalize_args(s);
+    TmLooSums f;
+    rc = loo_collect(s, (size_t)m.n_windows, m.elpd, m.tail_len, m.n_used,
+                     [&] { return timed_launch(s, s->timer, "summary wloo finalize", [&] { return tm_launch_loo_finalize(a, c->stream); }); },
+                     elpd_lwo, pareto_k, cutoff, tail_len, &f);
+    if (rc != TAMCMC_OK) return rc;
+    for (long long w = 0; w < m.n_windows; w++) {
+        if (first_bin) first_bin[w] = (int64_t)tmw_begin(w, m.W, m.first);
+        if (last_bin) last_bin[w] = (int64_t)tmw_end(w, m.W, m.first, c->L.Nx) - 1;
+    }
+    if (totals) {
+        totals->n_used = m.n_used;
+        totals->n_rejected = m.n_rejected;
+        totals->n_windows = m.n_windows; totals->W = m.W; totals->first = m.first;
+        totals->elpd_lwo = f.elpd;
+        totals->p_lwo = f.p;
+        totals->k_max = f.k_max;
+        totals->n_k_high = f.n_high;
+        totals->n_k_inf = f.n_inf;
+    }
+    return TAMCMC_OK;
+}
+
+extern "C" int tamcmc_summary_wloo_end(tamcmc_summary *s)
+{
+    if (!s || !s->wloo.on) return TAMCMC_E_INVALID;
+    const int rc = summary_enter(s);
+    if (rc == TAMCMC_OK) wloo_free(s);
+    return rc;
+}
+
+extern "C" int tamcmc_summary_wloo_pit_begin(tamcmc_summary *s)
+{
+    if (!s || !s->wloo.on || s->wloo.pit) return TAMCMC_E_INVALID;
+    tamcmc_ctx *c = s->c;
+    TmWlooMode &m = s->wloo;
+    const bool chi = c->L.likelihood_case == 0;
+    if (chi && !(c->L.like_p >= 1.0 && c->L.like_p <= (double)TAMCMC_SUMMARY_WINDOW_MAX_SHAPE && (int)c->L.like_p * m.W <= TAMCMC_SUMMARY_WINDOW_MAX_SHAPE))
+        return TAMCMC_E_INVALID;
+    int rc = summary_enter(s);
+    if (rc != TAMCMC_OK) return rc;
+    bool complete = false;
+    rc = pass_complete(m, &complete);
+    if (rc != TAMCMC_OK) return rc;
+    if (!complete) return TAMCMC_E_INVALID;                             // the pass under way stays as it is
+    const size_t nw = (size_t)m.n_windows;
+    double *d_lw = nullptr, *d_tails = nullptr;
+    char *d_pit = nullptr;
+    if (hipMalloc(&d_lw, twl_lw_bytes(nw, (size_t)(m.cap - 1))) != hipSuccess) { (void)hipGetLastError(); return TAMCMC_E_NOMEM; }
+    if (hipMalloc(&d_pit, twl_pit_state_bytes(nw)) != hipSuccess) { (void)hipGetLastError(); (void)hipFree(d_lw); return TAMCMC_E_NOMEM; }
+    if (hipMalloc(&d_tails, 2 * twl_scratch_bytes(nw, (size_t)s->B)) != hipSuccess) {
+        (void)hipGetLastError(); (void)hipFree(d_lw); (void)hipFree(d_pit);
+        return TAMCMC_E_NOMEM;
+    }
+    m.d_lw = d_lw; m.d_pit = d_pit; m.d_tails = d_tails;
+    m.pit_sums = reinterpret_cast<double *>(d_pit);
+    m.pit_xmax = m.pit_sums + (size_t)TM_LOOPIT_NSTATE * nw;
+    m.pit_c = m.pit_xmax + nw;
+    m.pit_cnt.d = reinterpret_cast<long long *>(m.pit_c + nw);
+    m.pit_cnt.parity = 0;
+    m.pit_first = reinterpret_cast<int32_t *>(m.pit_cnt.d + 4);
+    m.pit_flag = m.pit_first + nw;
+    int f = m.first, len[3];
+    (void)tmw_partition((long long)c->L.Nx, m.W, &f, len);
+    for (int k = 0; k < 3; k++) m.shape[k] = tmw_shape(len[k], m.p);
+    c->enq_seq++;
+    const TmLooPitArgs a = wloo_prepare_args(s);
+    rc = timed_launch(s, s->timer, "summary wloo pit prepare", [&] { return tm_launch_loopit_prepare(a, c->stream); });
+    if (rc == TAMCMC_OK) rc = wloo_pit_pass_clear(s);
+    if (rc == TAMCMC_OK && hipStreamSynchronize(c->stream) != hipSuccess) rc = TAMCMC_E_HIP;
+    if (rc != TAMCMC_OK) {              // (a launch that was refused wrote nothing: the top sets are as the LOO pass left them)
+        (void)hipStreamSynchronize(c->stream);
+        (void)hipFree(d_lw); (void)hipFree(d_pit); (void)hipFree(d_tails);
+        m.d_lw = nullptr; m.d_pit = nullptr; m.d_tails = nullptr;
+        return rc;
+    }
+    m.pit = true;
+    return TAMCMC_OK;
+}
+
+extern "C" int tamcmc_summary_wloo_pit_result(tamcmc_summary *s, tamcmc_summary_loo_pit_totals *totals, double *loo_pit, double *loo_log_cdf,
+                                              double *loo_log_sf, double *is_ess, double *log_wsum)
+{
+    if (!s || !s->wloo.on || !s->wloo.pit) return TAMCMC_E_INVALID;
+    int rc = summary_enter(s);
+    if (rc != TAMCMC_OK) return rc;
+    TmWlooMode &m = s->wloo;
+    s->c->enq_seq++;
+    long long cnt[2] = {0, 0};
+    int32_t flag = 0;
+    rc = m.pit_cnt.read(cnt);
+    if (rc != TAMCMC_OK) return rc;
+    TM_HIP(hipMemcpy(&flag, m.pit_flag, sizeof flag, hipMemcpyDeviceToHost));
+    if (cnt[0] != m.n_used || cnt[1] != m.n_rejected || flag != 0) {    // not the LOO pass's samples: the PIT pass is discarded
+        rc = wloo_pit_pass_clear(s);
+        return rc != TAMCMC_OK ? rc : TAMCMC_E_INVALID;
+    }
+    return loopit_collect(m.pit_sums, (size_t)m.n_windows, m.n_used, m.n_rejected, totals, loo_pit, loo_log_cdf, loo_log_sf, is_ess, log_wsum);
+}
+
+extern "C" int tamcmc_summary_wloo_pit_kernel_time(tamcmc_summary *s, double *total_ms, int64_t *launches)
+{
+    if (!s || !total_ms || !launches || !s->wloo.on || !s->wloo.pit || s->c->armed) return TAMCMC_E_INVALID;
+    TM_HIP(hipSetDevice(s->c->device));
+    TM_HIP(tm_ctx_stream_sync(s->c));
+    return s->wpit_timer.total(total_ms, launches);
 }
 
 // ---- posterior predictive check (tamcmc_predictive.h) ----

@@ -5,6 +5,7 @@
 //                    [--chain m] [--slice s] [--first i] [--last j] [--thin k] [--block B]
 //                    [--quantiles q1,q2,...] [--qbits b] [--loo] [--predictive] [--window W[,first]] [--ess [L]]
 //                    [--scan W0[,W1,...]] [--scan-below T] [--scan-null R[,seed]] [--band-ess [L]] [--loo-pit]
+//                    [--loo-window W[,first]]
 //
 // <config dir> is the reference's Config/default; model id, likelihood, p, plength, the inputs row and the relax mask
 // come from the setup it describes (tamcmc_setup_create / tamcmc_setup_load, slice s counted from 0).  The samples are
@@ -28,6 +29,13 @@
 // n_rejected= ...`, `# ks_D= ...  min_log_sf= ...  bin_min_log_sf= ...  min_log_cdf= ...  bin_min_log_cdf= ...`,
 // `# min_is_ess= ...  bin_min_is_ess= ...`, `# pit_hist= c0 c1 ... c19` -- then one row per bin:
 //   x  loo_pit  loo_log_cdf  loo_log_sf  is_ess  pareto_k
+// With --loo-window W[,first] the selected samples are read once more for leave-one-window-out PSIS-LOO over disjoint windows
+// of W bins, the first window `first` bins long (tamcmc_summary_wloo_*), and with --loo-pit a further time for the LOO-PIT
+// of every window.  The output file and the other files keep every byte; the results go to <output file>.loowin: `#` header
+// lines -- the version, `# W= ...  first= ...  n_windows= ...`, `# n_used= ...  n_rejected= ...`, `# elpd_lwo= ...  p_lwo= ...
+// k_max= ...  n_k_high= ...  n_k_inf= ...`, and with --loo-pit the three lines of .loopit's totals with windows for bins
+// -- then one row per window:
+//   first_bin  last_bin  x_first  x_last  elpd_lwo  pareto_k  tail_len  [loo_pit  loo_log_cdf  loo_log_sf  is_ess  log_wsum]
 // With --predictive the first pass also accumulates the posterior predictive check (tamcmc_summary_predictive_*; no further
 // pass), the header gains two lines, `# ks_D= ...  min_log_sf= ...  bin_min_log_sf= ...  min_log_cdf= ...
 // bin_min_log_cdf= ...` and `# pit_hist= c0 c1 ... c19`, and four columns follow all the others: pit, log_cdf, log_sf and
@@ -83,6 +91,7 @@ static int usage()
                     "                         [--chain m] [--slice s] [--first i] [--last j] [--thin k] [--block B]\n"
                     "                         [--quantiles q1,q2,...] [--qbits b] [--loo] [--predictive] [--window W[,first]] [--ess [L]]\n"
                     "                         [--scan W0[,W1,...]] [--scan-below T] [--scan-null R[,seed]] [--band-ess [L]] [--loo-pit]\n"
+                    "                         [--loo-window W[,first]]\n"
                     "     [1] The directory of config_default.cfg, errors_default.cfg and the *_ctrl.list files (Config/default)\n"
                     "     [2] The .model file and [3] the .data file of the fit\n"
                     "     [4] The root of the parameter files: <root>_chain-<m>.bin and <root>.hdr\n"
@@ -119,6 +128,11 @@ static int usage()
                     "     --loo-pit   implies --loo: the leave-one-out PIT, the predictive tails under the PSIS weights, and the weights'\n"
                     "             effective sample size: written to <output file>.loopit, one row per bin,\n"
                     "             x loo_pit loo_log_cdf loo_log_sf is_ess pareto_k (the samples are read a third time)\n"
+                    "     --loo-window W[,first]   leave-one-window-out PSIS-LOO over disjoint windows of W bins (1 ... 512), the first window\n"
+                    "             `first` bins long (1 ... W, default W): written to <output file>.loowin, one row per window,\n"
+                    "             first_bin last_bin x_first x_last elpd_lwo pareto_k tail_len, and with --loo-pit (likelihood p times W at\n"
+                    "             most 512) loo_pit loo_log_cdf loo_log_sf is_ess log_wsum as well (the samples are read once more, with\n"
+                    "             --loo-pit twice; [5] and the other files are unchanged)\n"
                     " chainsummary_hip version   prints the library version\n");
     return EXIT_FAILURE;
 }
@@ -158,6 +172,7 @@ int main(int argc, char *argv[])
     bool loo = false, loo_pit = false, predictive = false;
     long win_W = 0, win_first = 0, ess_lag = -1;            // ess_lag < 0: no --ess
     long band_lag = -1;                                     // < 0: no --band-ess
+    long lw_W = 0, lw_first = 0;                            // lw_W = 0: no --loo-window
     std::vector<int32_t> scan_W;
     std::string scan_text;
     double scan_below = std::nan("");                       // NaN: the library's default line per width
@@ -201,6 +216,20 @@ int main(int argc, char *argv[])
                 p = end + 1;
                 win_first = strtol(p, &end, 10);
                 if (end == p || win_first < 1 || win_first > win_W) return usage();
+            }
+            if (*end != '\0') return usage();
+            continue;
+        }
+        if (a == "--loo-window") {                  // W or W,first
+            if (i + 1 >= argc || lw_W != 0) return usage();
+            const char *p = argv[++i];
+            char *end = nullptr;
+            lw_W = strtol(p, &end, 10);
+            if (end == p || lw_W < 1 || lw_W > TAMCMC_SUMMARY_WINDOW_MAX_BINS) return usage();
+            if (*end == ',') {
+                p = end + 1;
+                lw_first = strtol(p, &end, 10);
+                if (end == p || lw_first < 1 || lw_first > lw_W) return usage();
             }
             if (*end != '\0') return usage();
             continue;
@@ -453,6 +482,31 @@ int main(int argc, char *argv[])
         }
         tamcmc_summary_loo_end(sum);
     }
+    // window-LOO: the same samples once more, and with --loo-pit a further time
+    tamcmc_summary_wloo_totals lwt{};
+    tamcmc_summary_loo_pit_totals lwpt{};
+    std::vector<double> lw_elpd, lw_khat, lw_pit, lw_cdf, lw_sf, lw_ess, lw_wsum;
+    std::vector<int32_t> lw_tail;
+    std::vector<int64_t> lw_b, lw_e;
+    if (lw_W) {
+        auto wfail = [&](const char *what) { return fail(std::string(what) + ": " + tamcmc_strerror(rc) + " " + tamcmc_last_hip_error()); };
+        int32_t nw = 0;
+        rc = tamcmc_summary_wloo_begin(sum, (int32_t)lw_W, (int32_t)lw_first, &nw);
+        if (rc != TAMCMC_OK) return wfail("tamcmc_summary_wloo_begin");
+        lw_elpd.resize((size_t)nw); lw_khat.resize((size_t)nw); lw_tail.resize((size_t)nw); lw_b.resize((size_t)nw); lw_e.resize((size_t)nw);
+        if (push_selected() != 0) return EXIT_FAILURE;
+        rc = tamcmc_summary_wloo_result(sum, &lwt, lw_elpd.data(), lw_khat.data(), nullptr, lw_tail.data(), lw_b.data(), lw_e.data());
+        if (rc != TAMCMC_OK) return wfail("tamcmc_summary_wloo_result");
+        if (loo_pit) {
+            lw_pit.resize((size_t)nw); lw_cdf.resize((size_t)nw); lw_sf.resize((size_t)nw); lw_ess.resize((size_t)nw); lw_wsum.resize((size_t)nw);
+            rc = tamcmc_summary_wloo_pit_begin(sum);
+            if (rc != TAMCMC_OK) return wfail("tamcmc_summary_wloo_pit_begin");
+            if (push_selected() != 0) return EXIT_FAILURE;
+            rc = tamcmc_summary_wloo_pit_result(sum, &lwpt, lw_pit.data(), lw_cdf.data(), lw_sf.data(), lw_ess.data(), lw_wsum.data());
+            if (rc != TAMCMC_OK) return wfail("tamcmc_summary_wloo_pit_result");
+        }
+        tamcmc_summary_wloo_end(sum);
+    }
     // ESS, MCSE and split R-hat: the same samples once more, in the same order
     tamcmc_summary_ess_totals et{};
     const size_t Ne = ess_lag >= 0 ? (size_t)Nx : 0;
@@ -585,6 +639,32 @@ int main(int argc, char *argv[])
             fprintf(op, "%.12g %.12g %.12g %.12g %.12g %.12g\n", x[(size_t)i], lp_pit[(size_t)i], lp_cdf[(size_t)i], lp_sf[(size_t)i], lp_ess[(size_t)i],
                     khat[(size_t)i]);
         fclose(op);
+    }
+    if (lw_W) {
+        const std::string lw_file = out_file + ".loowin";
+        FILE *ol = fopen(lw_file.c_str(), "w");
+        if (!ol) return fail("unable to open the output file " + lw_file);
+        fprintf(ol, "# chainsummary_hip (%s)\n", tamcmc_version());
+        fprintf(ol, "# W= %lld  first= %lld  n_windows= %lld\n", (long long)lwt.W, (long long)lwt.first, (long long)lwt.n_windows);
+        fprintf(ol, "# n_used= %lld  n_rejected= %lld\n", (long long)lwt.n_used, (long long)lwt.n_rejected);
+        fprintf(ol, "# elpd_lwo= %.12g  p_lwo= %.12g  k_max= %.12g  n_k_high= %lld  n_k_inf= %lld\n", lwt.elpd_lwo, lwt.p_lwo, lwt.k_max,
+                (long long)lwt.n_k_high, (long long)lwt.n_k_inf);
+        if (loo_pit) {
+            fprintf(ol, "# ks_D= %.12g  min_log_sf= %.12g  win_min_log_sf= %lld  min_log_cdf= %.12g  win_min_log_cdf= %lld\n", lwpt.ks_D, lwpt.min_log_sf,
+                    (long long)lwpt.bin_min_log_sf, lwpt.min_log_cdf, (long long)lwpt.bin_min_log_cdf);
+            fprintf(ol, "# min_is_ess= %.12g  win_min_is_ess= %lld\n", lwpt.min_is_ess, (long long)lwpt.bin_min_is_ess);
+            fprintf(ol, "# pit_hist=");
+            for (int k = 0; k < TAMCMC_SUMMARY_PIT_CELLS; k++) fprintf(ol, " %lld", (long long)lwpt.pit_hist[k]);
+            fprintf(ol, "\n");
+        }
+        fprintf(ol, "# first_bin last_bin x_first x_last elpd_lwo pareto_k tail_len%s\n", loo_pit ? " loo_pit loo_log_cdf loo_log_sf is_ess log_wsum" : "");
+        for (size_t w = 0; w < lw_elpd.size(); w++) {
+            fprintf(ol, "%lld %lld %.12g %.12g %.12g %.12g %d", (long long)lw_b[w], (long long)lw_e[w], x[(size_t)lw_b[w]], x[(size_t)lw_e[w]], lw_elpd[w],
+                    lw_khat[w], (int)lw_tail[w]);
+            if (loo_pit) fprintf(ol, " %.12g %.12g %.12g %.12g %.12g", lw_pit[w], lw_cdf[w], lw_sf[w], lw_ess[w], lw_wsum[w]);
+            fprintf(ol, "\n");
+        }
+        fclose(ol);
     }
     if (ess_lag >= 0) {
         const std::string ess_file = out_file + ".ess";

@@ -51,6 +51,13 @@ Prints one JSON line:
                             kernel alone, the predictive kernel alone (a second object with the check on) and the eval launches,
                             loo_pit_begin on the host clock and its prepare kernel alone, and the device memory the sub-mode
                             allocates.  Only this leg runs.
+  m_wloo_*                  with --loo-window W (and --like-p p, default 1; p W <= 512): after a fold pass, in one session, the
+                            window-LOO pass and its PIT pass of the same rows through Summary.push (seconds per 1000 samples),
+                            and from profiled passes the mode's kernels alone -- the sums and tail kernels of every block
+                            (Summary.kernel_time in the mode), the sums, tails and PIT kernels of every block of the third pass
+                            (Summary.wloo_pit_kernel_time) -- beside the per-bin LOO tail kernel and the per-bin LOO-PIT kernel
+                            of the same rows, the finalize and prepare kernels over the windows, and the device memory the mode
+                            and its sub-mode allocate.  Only this leg runs.
 Every timed shape is warmed up first (--warmup pushes); host clocks stop after calls that end in a device synchronise.
 """
 import argparse
@@ -361,6 +368,81 @@ def loo_pit_leg(a, w, y, P):
     return out
 
 
+def wloo_leg(a, w, y, P):
+    """(m) the window-LOO pass and its PIT pass beside the per-bin LOO tail and LOO-PIT kernels of the same rows."""
+    W = a.loo_window
+    out = dict(m_wloo_W=W, m_wloo_like_p=a.like_p)
+    per_1000 = 1000.0 / a.samples
+    with tamcmc_amd.Accel(2, w["plength"], w["x"], y, likelihood_p=float(a.like_p)) as acc:
+        with tamcmc_amd.Summary(acc, a.block) as s:
+            s.push(P)
+            times = {"tail": [], "pit": [], "begin": []}
+            for k in range(a.warmup + a.steps):             # every round in a mode of its own: begin, push, pit_begin, push, end
+                nw = s.wloo_begin(W)
+                acc.synchronize()
+                t0 = time.perf_counter()
+                s.push(P)                                   # synchronous: results are on the host on return
+                t1 = time.perf_counter()
+                s.wloo_pit_begin()                          # ends in a device synchronise
+                t2 = time.perf_counter()
+                s.push(P)
+                t3 = time.perf_counter()
+                if k >= a.warmup:
+                    times["tail"].append(t1 - t0)
+                    times["begin"].append(t2 - t1)
+                    times["pit"].append(t3 - t2)
+                if k + 1 < a.warmup + a.steps:
+                    s.wloo_end()
+            for key in ("tail", "pit"):
+                v = times[key]
+                out[f"m_wloo_{key}_pass_s_per_1000"] = float(np.median(v)) * per_1000
+                out[f"m_wloo_{key}_pass_spread"] = [float(min(v)) * per_1000, float(max(v)) * per_1000]
+            out["m_wloo_pit_begin_s"] = float(np.median(times["begin"]))
+            loo = s.wloo_result()
+            r = s.wloo_pit_result()
+            s.wloo_end()
+            s.wloo_begin(W)                                 # the mode's kernels alone: a profiled pass, finalize, prepare, a profiled PIT pass
+            s.profile(True)
+            acc.profile(True)
+            s.push(P)
+            tail_ms, tail_launches = s.kernel_time()
+            eval_ms, _ = acc.kernel_time()
+            acc.profile(False)
+            s.profile(True)                                 # (profile() starts the timers again)
+            s.wloo_result()
+            fin_ms, _ = s.kernel_time()
+            s.profile(True)
+            s.wloo_pit_begin()
+            prep_ms, _ = s.kernel_time()
+            s.profile(True)
+            s.push(P)
+            pit_ms, pit_launches = s.wloo_pit_kernel_time()
+            s.profile(False)
+            s.wloo_end()
+            s.loo_begin()                                   # the per-bin kernels of the same rows, the same way
+            s.profile(True)
+            s.push(P)
+            bin_tail_ms, _ = s.kernel_time()
+            s.loo_pit_begin()
+            s.profile(True)
+            s.push(P)
+            bin_pit_ms, _ = s.loo_pit_kernel_time()
+            s.profile(False)
+            s.loo_end()
+    n = r["n_used"]
+    M = int(np.ceil(min(n / 5.0, 3.0 * np.sqrt(float(n)))))
+    B = -(-a.samples // tail_launches)                      # samples per block (the last block may be shorter)
+    us = 1e3 / a.samples
+    out.update(m_wloo_n_windows=nw, m_wloo_M=M, m_wloo_block_chains=B, m_wloo_launches=tail_launches,
+               m_wloo_tail_kernels_us_per_sample=tail_ms * us, m_wloo_pit_kernels_us_per_sample=pit_ms * us,
+               m_loo_tail_kernel_us_per_sample=bin_tail_ms * us, m_loo_pit_kernel_us_per_sample=bin_pit_ms * us,
+               m_eval_kernel_us_per_sample=eval_ms * us, m_wloo_finalize_ms=fin_ms, m_wloo_prepare_ms=prep_ms,
+               m_wloo_bytes=8 * (M + 1) * nw + 52 * nw + 32 + 8 * B * nw, m_wloo_pit_bytes=8 * M * nw + 116 * nw + 36 + 16 * B * nw,
+               m_wloo_elpd_lwo=loo["elpd_lwo_total"], m_wloo_p_lwo=loo["p_lwo"], m_wloo_k_max=loo["k_max"], m_wloo_n_k_high=loo["n_k_high"],
+               m_wloo_ks_D=r["loo_ks_D"], m_wloo_min_log_sf=r["min_loo_log_sf"], m_wloo_min_is_ess=r["min_is_ess"], n_used=n)
+    return out
+
+
 def bandess_leg(a, w, y, P):
     """(k) the fold pass beside the band ESS pass of the same rows, and the kernels' own times."""
     out = {}
@@ -439,6 +521,7 @@ def main():
     ap.add_argument("--like-p", type=int, default=1)
     ap.add_argument("--loo-pit", action="store_true", help="the LOO-PIT pass beside the LOO tail pass and the predictive kernel")
     ap.add_argument("--window", type=int, default=0)
+    ap.add_argument("--loo-window", type=int, default=0, help="W: the window-LOO pass and its PIT pass beside the per-bin LOO kernels")
     ap.add_argument("--scan", default="", help="W0[,W1,...]: strictly ascending widths of the sliding-window scan")
     ap.add_argument("--ess", type=int, default=-1)
     ap.add_argument("--band-ess", type=int, default=-1, help="L: the band ESS pass at --quantiles thresholds (0: the library's lag limit)")
@@ -458,8 +541,8 @@ def main():
     assert st == 0
     y = synth.make_spectrum(m_true)
     out = dict(tool="summary_time", Nx=a.nx, samples=a.samples, steps=a.steps, warmup=a.warmup, version=tamcmc_amd.capi.version())
-    if a.loo_pit:
-        out.update(loo_pit_leg(a, w, y, P))
+    if a.loo_pit or a.loo_window:
+        out.update(wloo_leg(a, w, y, P) if a.loo_window else loo_pit_leg(a, w, y, P))
         print(json.dumps(out))
         return
     if a.predictive or a.window or a.scan or a.ess >= 0 or a.band_ess >= 0:
