@@ -300,12 +300,40 @@ template <int NC> __device__ __forceinline__ int tm_grad_store_slot(int v)
     return (v < NC) ? v : (v < SL::C) ? 7 + (v - NC) : (v == SL::C) ? 11 : 21 + (v - SL::ASYM0);
 }
 
+// (the arithmetic of one bin: x2 and the weight wk, already zero outside the window, are values here)
+template <int NC, bool ASYM>
+__device__ __forceinline__ void tm_grad_bin(const double (&nu2)[NC], const double (&hq)[NC], double g2, double aAh, double aB, double c2,
+                                            const double x2, const double wk, double (&g)[TM_GSLOTS])
+{
+    using SL = TmGradSlots<NC>;
+    double d[NC], r[NC];
+    const double Sv = tm_mult_value<NC>(x2, nu2, hq, g2, d, r);
+    double wA = wk;
+    if (ASYM) {
+        const double a = __builtin_fma(x2, aAh, aB);
+        wA = wk * __builtin_fma(a, a, c2);
+        const double ws = wk * Sv;
+        g[SL::ASYM0 + 0] += ws;
+        g[SL::ASYM0 + 1] = __builtin_fma(ws, a, g[SL::ASYM0 + 1]);
+        g[SL::ASYM0 + 2] = __builtin_fma(ws * a, 0.5 * x2, g[SL::ASYM0 + 2]);
+    }
+#pragma unroll
+    for (int m = 0; m < NC; m++) {
+        const double t1 = wA * r[m];
+        const double t2 = t1 * r[m];
+        const int am = (m >= SL::L) ? m - SL::L : SL::L - m;
+        g[SL::A0 + am] += t1;
+        g[m] = __builtin_fma(t2, d[m], g[m]);
+        g[SL::C] = __builtin_fma(hq[m], t2, g[SL::C]);
+    }
+}
+
+// One unit, fetched where it is used (the generic bodies): the wave waits for x and the weights at the head of the unit.
 template <int NC, bool ASYM>
 __device__ __forceinline__ void tm_grad_unit(const double (&nu2)[NC], const double (&hq)[NC], double g2, double aAh, double aB, double c2,
                                              int imin, int imax, const double *__restrict__ gx, const double *wq, int i0, int Nx,
                                              const bool edge, double (&g)[TM_GSLOTS])
 {
-    using SL = TmGradSlots<NC>;
 #pragma unroll
     for (int k = 0; k < 2; k++) {
         double x2, wk;
@@ -318,35 +346,79 @@ __device__ __forceinline__ void tm_grad_unit(const double (&nu2)[NC], const doub
             x2 = gx[i0 + k * TM_THREADS];
             wk = wq[k * TM_THREADS];
         }
-        double d[NC], r[NC];
-        const double Sv = tm_mult_value<NC>(x2, nu2, hq, g2, d, r);
-        double wA = wk;
-        if (ASYM) {
-            const double a = __builtin_fma(x2, aAh, aB);
-            wA = wk * __builtin_fma(a, a, c2);
-            const double ws = wk * Sv;
-            g[SL::ASYM0 + 0] += ws;
-            g[SL::ASYM0 + 1] = __builtin_fma(ws, a, g[SL::ASYM0 + 1]);
-            g[SL::ASYM0 + 2] = __builtin_fma(ws * a, 0.5 * x2, g[SL::ASYM0 + 2]);
-        }
-#pragma unroll
-        for (int m = 0; m < NC; m++) {
-            const double t1 = wA * r[m];
-            const double t2 = t1 * r[m];
-            const int am = (m >= SL::L) ? m - SL::L : SL::L - m;
-            g[SL::A0 + am] += t1;
-            g[m] = __builtin_fma(t2, d[m], g[m]);
-            g[SL::C] = __builtin_fma(hq[m], t2, g[SL::C]);
-        }
+        tm_grad_bin<NC, ASYM>(nu2, hq, g2, aAh, aB, c2, x2, wk, g);
     }
+}
+
+// The same unit with x and the weights fetched by the caller one unit ahead (tm_grad_fetch): values, not addresses.
+// Only the edge path's select on the weight is left of the fetch; the bins outside the grid hold a weight of zero from
+// pass 1 and a clamped x, and `inside` excludes them as above.
+template <int NC, bool ASYM>
+__device__ __forceinline__ void tm_grad_unit_held(const double (&nu2)[NC], const double (&hq)[NC], double g2, double aAh, double aB, double c2,
+                                                  int imin, int imax, const double (&xv)[2], const double (&wv)[2], int lo, int tid, int Nx,
+                                                  const bool edge, double (&g)[TM_GSLOTS])
+{
+    double wk[2] = {wv[0], wv[1]};
+    if (edge) {
+#pragma unroll
+        for (int k = 0; k < 2; k++) {
+            const int i = lo + tid + k * TM_THREADS;
+            const bool inside = (i >= imin) && (i < imax) && (i < Nx);
+            wk[k] = inside ? wk[k] : 0.0;
+        }
+        // (kept ONE branch: as selects on the scalar condition the tests cost 6 VALU per bin in every unit, and even the
+        // bin index is made only here)
+        asm volatile("" : "+v"(wk[0]), "+v"(wk[1]));
+    }
+#pragma unroll
+    for (int k = 0; k < 2; k++) tm_grad_bin<NC, ASYM>(nu2, hq, g2, aAh, aB, c2, xv[k], wk[k], g);
+}
+
+// Request x and the two weights of unit u (units [u0, u1) of the tile, weights in s_w as pass 1 left them) for thread tid.
+// Only the grid's last, partial unit needs its bin index clamped: a scalar test.
+__device__ __forceinline__ void tm_grad_fetch(const double *__restrict__ gx, const double *s_w, int u, int u0, int Nx, int tid,
+                                              double (&xv)[2], double (&wv)[2])
+{
+    const int lo = u << TM_UNIT_SHIFT;
+    if (lo + TM_UNIT_BINS <= Nx) {
+        // the unit's own base (scalar arithmetic) + the thread index: no vector instruction per unit for the address
+        // (behind an empty asm: otherwise the thread's part of the address is hoisted as a 64-bit pointer per thread and
+        // the unit's offset added to it with a vector instruction per unit)
+        typedef const __attribute__((address_space(1))) double *TmGlobalD;     // (stays a global_load behind the asm)
+        TmGlobalD xb = (TmGlobalD)(gx + lo);
+        asm volatile("" : "+s"(xb));
+#pragma unroll
+        for (int k = 0; k < 2; k++) xv[k] = xb[(unsigned)(tid + k * TM_THREADS)];
+    } else {
+#pragma unroll
+        for (int k = 0; k < 2; k++) { const int i = lo + tid + k * TM_THREADS; xv[k] = gx[i < Nx ? i : Nx - 1]; }
+        asm volatile("");     // (keeps the two forms of the loads apart: merged they address through a 64-bit pointer per thread)
+    }
+    const double *wq = s_w + (u - u0) * TM_UNIT_BINS + tid;
+#pragma unroll
+    for (int k = 0; k < 2; k++) wv[k] = wq[k * TM_THREADS];
 }
 
 // Backward: accumulate this thread's partial sums for multiplet `sm` over the tile's units [u0, u1), reduce over the wave
 // and leave the wave totals in s_red_row[slot].
-template <int NC, bool ASYM>
+// AHEAD (the common-case body): only the units that meet the window are walked -- the set the `continue` below selects --
+// and x and the weights of the NEXT such unit are requested before the current one is evaluated, so that a wave waits for
+// them behind ~30 NC fp64 instructions instead of in front of them.  The look-ahead index is clamped to the last unit of
+// the range: the last trip requests its own unit again and discards it, the LDS read stays inside what pass 1 wrote.
+// The empty asm behind the first fetch keeps the optimiser from folding the carried values back into loads of a carried
+// address at the top of the trip (the loop without look-ahead, at the same register count): it pins the first unit's
+// values in registers in front of the loop, where the only wait without work behind it is.
+// The loop takes two units per iteration, the two sets of registers swapping roles, so that no value is copied from
+// "next" to "current" (four v_mov_b64 per unit otherwise); what a unit costs beside its arithmetic is one vector
+// instruction (the LDS address of the weights) -- pass 2 runs at the issue rate, so every instruction saved is time.
+template <int NC, bool ASYM, bool AHEAD_>
 __device__ __forceinline__ void tm_grad_mult(TmMultK sm, const double *__restrict__ gx, const double *s_w,
                                              int u0, int u1, int Nx, int tid, int lane, double *s_red_row)
 {
+    // l = 3 (NC = 7) keeps the fetch in place: its 12 / 15 accumulators and 28 temporaries leave no room for a second set
+    // of x and weights (the kernel needs 123 VGPRs with look-ahead in the shape without asymmetry alone, 128 and 11
+    // spilled to scratch with both; tests/test_eval_hot_path_resources.py holds it to 117)
+    constexpr bool AHEAD = AHEAD_ && NC < 7;
     constexpr int V = TmGradSlots<NC>::count(ASYM);
     double g[TM_GSLOTS];
     double nu2[NC], hq[NC];
@@ -357,18 +429,50 @@ __device__ __forceinline__ void tm_grad_mult(TmMultK sm, const double *__restric
     const double aAh = ASYM ? 0.5 * sm->aA : 0.0, aB = ASYM ? sm->aB : 1.0, c2 = ASYM ? sm->c2 : 0.0;
 #pragma unroll
     for (int s = 0; s < TM_GSLOTS; s++) g[s] = 0.0;
+    if constexpr (AHEAD) {
+        int ua = imin >> TM_UNIT_SHIFT, ub = (imax + TM_UNIT_BINS - 1) >> TM_UNIT_SHIFT;
+        ua = ua > u0 ? ua : u0;
+        ub = ub < u1 ? ub : u1;
+        if (ua < ub) {
+            double xc[2], wc[2];
+            tm_grad_fetch(gx, s_w, ua, u0, Nx, tid, xc, wc);
+            asm volatile("" : "+v"(xc[0]), "+v"(xc[1]), "+v"(wc[0]), "+v"(wc[1]));
+            // two units per iteration, the two register sets swapping roles: no hand-over copies
+            double xd[2], wd[2];
 #pragma unroll 1
-    for (int u = u0; u < u1; u++) {
-        // units that do not meet the window are skipped, units inside it need no test per bin (wave-uniform)
-        const int lo = u << TM_UNIT_SHIFT, hi = lo + TM_UNIT_BINS;
-        if (hi <= imin || lo >= imax) continue;
-        const double *wq = s_w + (u - u0) * TM_UNIT_BINS + tid;
-        tm_grad_unit<NC, ASYM>(nu2, hq, g2, aAh, aB, c2, imin, imax, gx, wq, lo + tid, Nx, !(lo >= imin && hi <= imax && hi <= Nx), g);
+            for (int u = ua;;) {
+                tm_grad_fetch(gx, s_w, u + 1 < ub ? u + 1 : u, u0, Nx, tid, xd, wd);
+                {
+                    const int lo = u << TM_UNIT_SHIFT, hi = lo + TM_UNIT_BINS;
+                    tm_grad_unit_held<NC, ASYM>(nu2, hq, g2, aAh, aB, c2, imin, imax, xc, wc, lo, tid, Nx, !(lo >= imin && hi <= imax && hi <= Nx), g);
+                }
+                if (++u >= ub) break;
+                tm_grad_fetch(gx, s_w, u + 1 < ub ? u + 1 : u, u0, Nx, tid, xc, wc);
+                {
+                    const int lo = u << TM_UNIT_SHIFT, hi = lo + TM_UNIT_BINS;
+                    tm_grad_unit_held<NC, ASYM>(nu2, hq, g2, aAh, aB, c2, imin, imax, xd, wd, lo, tid, Nx, !(lo >= imin && hi <= imax && hi <= Nx), g);
+                }
+                if (++u >= ub) break;
+            }
+        }
+    } else {
+#pragma unroll 1
+        for (int u = u0; u < u1; u++) {
+            // units that do not meet the window are skipped, units inside it need no test per bin (wave-uniform)
+            const int lo = u << TM_UNIT_SHIFT, hi = lo + TM_UNIT_BINS;
+            if (hi <= imin || lo >= imax) continue;
+            const double *wq = s_w + (u - u0) * TM_UNIT_BINS + tid;
+            tm_grad_unit<NC, ASYM>(nu2, hq, g2, aAh, aB, c2, imin, imax, gx, wq, lo + tid, Nx, !(lo >= imin && hi <= imax && hi <= Nx), g);
+        }
     }
 #if defined(TM_ABLATE) && (TM_ABLATE & 1)   // timing-only build: no wave reduction of the partials
     if (lane == 0) s_red_row[0] = g[0] + g[1] + g[2];
     return;
 #endif
+    // AHEAD: the lane index behind an empty asm, so that the butterfly's lane masks and the store slot of each shape are
+    // made here, once per multiplet, instead of being hoisted in front of the multiplet loop -- eight shapes' worth of
+    // them -- and, with the registers the look-ahead holds, spilled across it (9 VGPRs went to scratch without this)
+    if constexpr (AHEAD) asm volatile("" : "+v"(lane));
     TmBfly<V, 32>::run(g, lane);
     // lanes whose plainly-reduced low bits are zero publish; padded slots are skipped
     constexpr int NSPLIT = (V > 16) ? 5 : (V > 8) ? 4 : (V > 4) ? 3 : (V > 2) ? 2 : 1;   // butterfly levels that split
@@ -385,6 +489,12 @@ __device__ __forceinline__ void tm_grad_mult(TmMultK sm, const double *__restric
 #endif
 #ifndef TM_LB_GRAD
 #define TM_LB_GRAD 4   // same for the gradient kernel: 128 VGPRs (the pair loop is written to fit: see tm_eval_body)
+#endif
+// Look-ahead of pass 2 in the common-case gradient body (GRAD && !GEN; tm_grad_mult<.., AHEAD>): on by default;
+// -DTM_LOOKAHEAD=0 builds the library without it for A/B runs (`make variant-la N=0`; profiles/README.md, "lookahead/").
+// The generic bodies (GEN) sit at their register caps and do not take it.
+#ifndef TM_LOOKAHEAD
+#define TM_LOOKAHEAD 1
 #endif
 #ifdef TM_TRACE   // developer build: per-workgroup time stamps (tools/block_trace.py)
 __device__ unsigned long long *g_tm_trace = nullptr;
@@ -524,7 +634,9 @@ __device__ __forceinline__ void tm_eval_body(const TmEvalArgs &a, const int chai
             // Likelihood kernel (SGPRs to spare): the list entry of the NEXT multiplet is requested before the current one
             // is evaluated (one 16-byte scalar load, in flight beside the record's), so a wave waits once per multiplet
             // instead of three times in a row (window; index and shape; record) -- waits that a wave with few
-            // neighbours on its SIMD cannot hide (the tail of a launch).
+            // neighbours on its SIMD cannot hide (the tail of a launch).  (The common-case gradient kernel has the SGPRs for
+            // it since the cell-kind split; there it measured 0.5 - 0.9 us slower, in pass 2 no different: profiles/README.md,
+            // "lookahead/".)
             TmEntry e = tm_load_entry(tix);
             asm volatile("" :: "s"(e.x));             // a use: the first entry is waited for here, not inside the loop
             for (int jj = 0; jj < nact; jj++) {
@@ -892,6 +1004,7 @@ __device__ __forceinline__ void tm_eval_body(const TmEvalArgs &a, const int chai
 #endif
     // ---------------- pass 2: gradient partial sums ----------------
     if constexpr (GRAD) {
+        constexpr bool AHEAD = !GEN && TM_LOOKAHEAD != 0;     // tm_grad_mult: x and the weights of the next unit ahead of use
         __syncthreads();   // s_red[0] (likelihood) consumed; s_w complete; s_red[1] (noise) consumed before multiplet 0 reuses it
 #if defined(TM_ABLATE) && (TM_ABLATE & 2)   // timing-only build: no multiplet pass 2 at all
         for (int jj = 0; jj < 0; jj++) {
@@ -908,14 +1021,14 @@ __device__ __forceinline__ void tm_eval_body(const TmEvalArgs &a, const int chai
                 if (shape < 256) { red[21] = 0.0; red[22] = 0.0; red[23] = 0.0; }
             }
             switch (shape) {
-            case 1: tm_grad_mult<1, false>(sm, a.x2, s_w, u0, u1, a.Nx, tid, lane, red); break;
-            case 3: tm_grad_mult<3, false>(sm, a.x2, s_w, u0, u1, a.Nx, tid, lane, red); break;
-            case 5: tm_grad_mult<5, false>(sm, a.x2, s_w, u0, u1, a.Nx, tid, lane, red); break;
-            case 7: tm_grad_mult<7, false>(sm, a.x2, s_w, u0, u1, a.Nx, tid, lane, red); break;
-            case 256 + 1: tm_grad_mult<1, true>(sm, a.x2, s_w, u0, u1, a.Nx, tid, lane, red); break;
-            case 256 + 3: tm_grad_mult<3, true>(sm, a.x2, s_w, u0, u1, a.Nx, tid, lane, red); break;
-            case 256 + 5: tm_grad_mult<5, true>(sm, a.x2, s_w, u0, u1, a.Nx, tid, lane, red); break;
-            default: tm_grad_mult<7, true>(sm, a.x2, s_w, u0, u1, a.Nx, tid, lane, red); break;
+            case 1: tm_grad_mult<1, false, AHEAD>(sm, a.x2, s_w, u0, u1, a.Nx, tid, lane, red); break;
+            case 3: tm_grad_mult<3, false, AHEAD>(sm, a.x2, s_w, u0, u1, a.Nx, tid, lane, red); break;
+            case 5: tm_grad_mult<5, false, AHEAD>(sm, a.x2, s_w, u0, u1, a.Nx, tid, lane, red); break;
+            case 7: tm_grad_mult<7, false, AHEAD>(sm, a.x2, s_w, u0, u1, a.Nx, tid, lane, red); break;
+            case 256 + 1: tm_grad_mult<1, true, AHEAD>(sm, a.x2, s_w, u0, u1, a.Nx, tid, lane, red); break;
+            case 256 + 3: tm_grad_mult<3, true, AHEAD>(sm, a.x2, s_w, u0, u1, a.Nx, tid, lane, red); break;
+            case 256 + 5: tm_grad_mult<5, true, AHEAD>(sm, a.x2, s_w, u0, u1, a.Nx, tid, lane, red); break;
+            default: tm_grad_mult<7, true, AHEAD>(sm, a.x2, s_w, u0, u1, a.Nx, tid, lane, red); break;
             }
 #if defined(TM_ABLATE) && (TM_ABLATE & 64)   // timing-only build: no workgroup barrier per multiplet (wave 0 publishes its own partial)
             if (tid < TM_GSLOTS) a.gmult[(((size_t)chain * a.tiles + tile) * a.n_mult + idx) * TM_GSLOTS + tid] = red[tid];
