@@ -37,7 +37,13 @@
 //   instead of one per bin.
 //   Reductions: likelihood: wave exchanges (v_permlane*_swap, DPP) -> one LDS slot per wave -> one partial per (chain,
 //   tile); gradient: a transposing butterfly (V values per lane cost ~V exchanges, not 6V) -> LDS -> one partial per
-//   (chain, tile, multiplet, slot).  The sums over tiles run in a fixed order (last-arriving workgroup of the chain, or
+//   (chain, tile, multiplet, slot).  In the gradient kernels every wave writes rows of its own in LDS -- the likelihood
+//   triple, the noise sums of the tile's one or two cells, the butterfly results of up to TM_ROW_K = 6 consecutive
+//   active multiplets -- and the four waves run through the whole tile, both passes, without meeting: the workgroup
+//   takes ONE barrier per chunk of TM_ROW_K multiplets (one per tile in the common case) and then adds the four waves'
+//   rows in the order 0, 1, 2, 3, one (row, slot) per thread (tamcmc_eval_body.h, TM_ROWS: 6912 B beside the 32 KiB of
+//   weights, four workgroups per CU).  The likelihood-only kernels keep their one barrier in front of the in-launch
+//   finalize.  The sums over tiles run in a fixed order (last-arriving workgroup of the chain, or
 //   tamcmc_backward_kernel on the gradient path); the only atomic is an arrival counter, never a floating-point
 //   accumulation: results are bitwise reproducible.
 #include <hip/hip_runtime.h>

@@ -9,6 +9,30 @@
 
 #define TM_WAVES (TM_THREADS / 64)
 
+// The gradient kernels' cross-wave sums.  Every wave owns TM_ROWS rows of TM_GSLOTS doubles in LDS that only it writes:
+// row 0 the likelihood partial (S1, Pm, Pe), rows 1 and 2 the noise sums of the (at most two) cells a tile meets, rows
+// 3 .. 3 + TM_ROW_K - 1 the butterfly results of up to TM_ROW_K consecutive active multiplets.  The workgroup adds the
+// four waves' rows ONCE per chunk of TM_ROW_K multiplets (tm_eval_body, "flush"), behind the tile's only barrier in the
+// common case.  4 waves x 9 rows x 192 B = 6912 B beside the 32 KiB of weights: 39 680 B = 31 LDS granules of 1280 B,
+// so four workgroups stay resident on a CU's 160 KiB (one more row per wave would still fit, with nothing to spare).
+#define TM_ROW_K 6
+#define TM_ROWS (3 + TM_ROW_K)
+static_assert(TM_ROWS * TM_GSLOTS <= TM_THREADS, "the flush takes one (row, slot) per thread");
+// -DTM_TILE_BARRIERS=1: timing-only A/B build that keeps the rows and the flush but waits at every site where the
+// workgroup used to synchronise inside the tile (profiles/README.md, "rowsums/")
+#ifndef TM_TILE_BARRIERS
+#define TM_TILE_BARRIERS 0
+#endif
+// pass 2 with look-ahead: the grid's partial last unit behind the pipelined loop (tm_grad_mult); -DTM_TAIL_APART=0/1 for A/B runs
+#ifndef TM_TAIL_APART
+#define TM_TAIL_APART 1
+#endif
+#if TM_TILE_BARRIERS
+#define TM_TILE_SYNC() __syncthreads()
+#else
+#define TM_TILE_SYNC() do { } while (0)
+#endif
+
 // A multiplet record addressed through the CONSTANT address space: with a wave-uniform address the compiler
 // fetches it with scalar loads (s_load_dwordx8/x16) into SGPRs, which VALU instructions take directly as one
 // operand -- no LDS read, no VGPRs for the record.  The table was written by the previous kernel (setup), so
@@ -375,12 +399,14 @@ __device__ __forceinline__ void tm_grad_unit_held(const double (&nu2)[NC], const
 }
 
 // Request x and the two weights of unit u (units [u0, u1) of the tile, weights in s_w as pass 1 left them) for thread tid.
-// Only the grid's last, partial unit needs its bin index clamped: a scalar test.
+// Only the grid's last, partial unit needs its bin index clamped: a scalar test.  WHOLE: the caller keeps that unit out of
+// its range, and the one form of the loads is left.
+template <bool WHOLE>
 __device__ __forceinline__ void tm_grad_fetch(const double *__restrict__ gx, const double *s_w, int u, int u0, int Nx, int tid,
                                               double (&xv)[2], double (&wv)[2])
 {
     const int lo = u << TM_UNIT_SHIFT;
-    if (lo + TM_UNIT_BINS <= Nx) {
+    if (WHOLE || lo + TM_UNIT_BINS <= Nx) {
         // the unit's own base (scalar arithmetic) + the thread index: no vector instruction per unit for the address
         // (behind an empty asm: otherwise the thread's part of the address is hoisted as a 64-bit pointer per thread and
         // the unit's offset added to it with a vector instruction per unit)
@@ -400,7 +426,8 @@ __device__ __forceinline__ void tm_grad_fetch(const double *__restrict__ gx, con
 }
 
 // Backward: accumulate this thread's partial sums for multiplet `sm` over the tile's units [u0, u1), reduce over the wave
-// and leave the wave totals in s_red_row[slot].
+// and leave the wave totals in s_red_row[slot]: a row of the wave's own (TM_ROWS), so nothing here waits for another wave;
+// the slots the shape does not use are left as they are (the flush stores them as zero without reading them).
 // AHEAD (the common-case body): only the units that meet the window are walked -- the set the `continue` below selects --
 // and x and the weights of the NEXT such unit are requested before the current one is evaluated, so that a wave waits for
 // them behind ~30 NC fp64 instructions instead of in front of them.  The look-ahead index is clamped to the last unit of
@@ -433,21 +460,28 @@ __device__ __forceinline__ void tm_grad_mult(TmMultK sm, const double *__restric
         int ua = imin >> TM_UNIT_SHIFT, ub = (imax + TM_UNIT_BINS - 1) >> TM_UNIT_SHIFT;
         ua = ua > u0 ? ua : u0;
         ub = ub < u1 ? ub : u1;
+        // TM_TAIL_APART: the grid's partial last unit -- one tile per chain has it -- is taken out of the pipelined range and
+        // evaluated behind the loop with the in-place fetch (it is last in the order of summation either way), so that the
+        // loop holds the whole-unit form of the loads alone
+        constexpr bool APART = TM_TAIL_APART != 0;
+        const int uw = Nx >> TM_UNIT_SHIFT;                       // whole units of the grid
+        const bool tail = APART && ub > uw && ua <= uw;           // (then the range ends with unit uw, the partial one)
+        if (APART && ub > uw) ub = uw;
         if (ua < ub) {
             double xc[2], wc[2];
-            tm_grad_fetch(gx, s_w, ua, u0, Nx, tid, xc, wc);
+            tm_grad_fetch<APART>(gx, s_w, ua, u0, Nx, tid, xc, wc);
             asm volatile("" : "+v"(xc[0]), "+v"(xc[1]), "+v"(wc[0]), "+v"(wc[1]));
             // two units per iteration, the two register sets swapping roles: no hand-over copies
             double xd[2], wd[2];
 #pragma unroll 1
             for (int u = ua;;) {
-                tm_grad_fetch(gx, s_w, u + 1 < ub ? u + 1 : u, u0, Nx, tid, xd, wd);
+                tm_grad_fetch<APART>(gx, s_w, u + 1 < ub ? u + 1 : u, u0, Nx, tid, xd, wd);
                 {
                     const int lo = u << TM_UNIT_SHIFT, hi = lo + TM_UNIT_BINS;
                     tm_grad_unit_held<NC, ASYM>(nu2, hq, g2, aAh, aB, c2, imin, imax, xc, wc, lo, tid, Nx, !(lo >= imin && hi <= imax && hi <= Nx), g);
                 }
                 if (++u >= ub) break;
-                tm_grad_fetch(gx, s_w, u + 1 < ub ? u + 1 : u, u0, Nx, tid, xc, wc);
+                tm_grad_fetch<APART>(gx, s_w, u + 1 < ub ? u + 1 : u, u0, Nx, tid, xc, wc);
                 {
                     const int lo = u << TM_UNIT_SHIFT, hi = lo + TM_UNIT_BINS;
                     tm_grad_unit_held<NC, ASYM>(nu2, hq, g2, aAh, aB, c2, imin, imax, xd, wd, lo, tid, Nx, !(lo >= imin && hi <= imax && hi <= Nx), g);
@@ -455,6 +489,7 @@ __device__ __forceinline__ void tm_grad_mult(TmMultK sm, const double *__restric
                 if (++u >= ub) break;
             }
         }
+        if (tail) tm_grad_unit<NC, ASYM>(nu2, hq, g2, aAh, aB, c2, imin, imax, gx, s_w + (uw - u0) * TM_UNIT_BINS + tid, (uw << TM_UNIT_SHIFT) + tid, Nx, true, g);
     } else {
 #pragma unroll 1
         for (int u = u0; u < u1; u++) {
@@ -544,7 +579,9 @@ __device__ __forceinline__ void tm_eval_body(const TmEvalArgs &a, const int chai
 #if defined(TM_ABLATE) && (TM_ABLATE & 16)   // timing-only build: empty workgroups (dispatch cost only)
     if (a.Nx > 0) return;
 #endif
-    __shared__ double s_red[2][TM_WAVES][TM_GSLOTS];   // double-buffered: one barrier per multiplet in pass 2
+    __shared__ double s_red[2][TM_WAVES][TM_GSLOTS];   // likelihood-only kernels: the waves' partials ([0] alone is used)
+    __shared__ double s_rows[TM_WAVES][TM_ROWS][TM_GSLOTS];   // gradient kernels: the waves' rows (TM_ROWS above)
+    // (an instantiation refers to one of the two; the other is not allocated)
 
     // ---------------- prologue: nothing but scalar loads ----------------
     // Everything a tile needs -- its bounds, its list of active multiplets (table order), the cells' background
@@ -794,27 +831,22 @@ __device__ __forceinline__ void tm_eval_body(const TmEvalArgs &a, const int chai
         }   // halves of the group
     };
 
-    // GRAD: the noise partial sums of the cell just finished -> gnoise[chain][tile][part]
+    // GRAD: the noise partial sums of the cell just finished -> the wave's row 1 + part; the flush behind pass 2 adds the
+    // four waves and stores gnoise[chain][tile][part].  No barrier: the row is this wave's own and is written once.
     auto flush_noise = [&](const int part, auto cold_c) __attribute__((always_inline)) {
         if constexpr (GRAD) {
-            // the cold loop's copy: lane and thread index behind an empty asm, so that its lane masks are made here, once
+            // the cold loop's copy: the lane index behind an empty asm, so that its lane masks are made here, once
             // per flush, instead of being hoisted in front of that loop and spilled across it (8 SGPRs)
-            int ln = lane, td = tid;
-            if constexpr (decltype(cold_c)::value) asm volatile("" : "+v"(ln), "+v"(td));
+            int ln = lane;
+            if constexpr (decltype(cold_c)::value) asm volatile("" : "+v"(ln));
             static_assert(TM_NSLOTS == 16, "butterfly below assumes 16 noise slots");
             TmBfly<TM_NSLOTS, 32>::run(gn_, ln);
             bool valid = true;
             const int slot = TmBfly<TM_NSLOTS, 32>::slot_of(ln, valid);
-            double *red = s_red[1][wave];
+            double *red = s_rows[wave][1 + part];
             if ((ln & 3) == 0) red[slot] = gn_[0];
-            __syncthreads();
-            if (td < TM_NSLOTS) {
-                double t = 0.0;
-#pragma unroll
-                for (int wv = 0; wv < TM_WAVES; wv++) t += s_red[1][wv][td];
-                a.gnoise[(((size_t)chain * a.tiles + tile) * 2 + part) * TM_NSLOTS + td] = t;
-            }
-            __syncthreads();
+            TM_TILE_SYNC();
+            TM_TILE_SYNC();
 #pragma unroll
             for (int s_ = 0; s_ < TM_GSLOTS; s_++) gn_[s_] = 0.0;
         }
@@ -915,18 +947,14 @@ __device__ __forceinline__ void tm_eval_body(const TmEvalArgs &a, const int chai
         if (__builtin_amdgcn_ballot_w64(sgn < 0) != 0) Pm = __builtin_nan("");     // a negative model value anywhere: log -> NaN
     }
     S1 = tm_wave_sum(S1);
-    if (lane == 0) { s_red[0][wave][0] = S1; s_red[0][wave][1] = Pm; s_red[0][wave][2] = Pe; }
-    __syncthreads();
+    if constexpr (!GRAD) {
+        if (lane == 0) { s_red[0][wave][0] = S1; s_red[0][wave][1] = Pm; s_red[0][wave][2] = Pe; }
+        __syncthreads();
+    }
     if constexpr (GRAD) {
-        if (tid == 0) {
-            double t1 = 0.0, tm = 1.0, te = 0.0;
-#pragma unroll
-            for (int wv = 0; wv < TM_WAVES; wv++) { t1 += s_red[0][wv][0]; tm *= s_red[0][wv][1]; te += s_red[0][wv][2]; }
-            double *out = a.part + ((size_t)chain * a.tiles + tile) * 4;   // summed by the backward kernel
-            out[0] = t1;
-            out[1] = tm;
-            out[2] = te;
-        }
+        // the wave's row 0, no barrier; the flush behind pass 2 combines the four waves into part[]
+        if (lane == 0) { s_rows[wave][0][0] = S1; s_rows[wave][0][1] = Pm; s_rows[wave][0][2] = Pe; }
+        TM_TILE_SYNC();
     } else if (wave == 0) {
         // Finalize inside this launch: the workgroup that publishes the LAST tile partial of a chain sums all of them
         // in a fixed order (lane-strided, then a wave tree), so the result does not depend on which workgroup that is.
@@ -1005,44 +1033,77 @@ __device__ __forceinline__ void tm_eval_body(const TmEvalArgs &a, const int chai
     // ---------------- pass 2: gradient partial sums ----------------
     if constexpr (GRAD) {
         constexpr bool AHEAD = !GEN && TM_LOOKAHEAD != 0;     // tm_grad_mult: x and the weights of the next unit ahead of use
-        __syncthreads();   // s_red[0] (likelihood) consumed; s_w complete; s_red[1] (noise) consumed before multiplet 0 reuses it
+        // No barrier in front of pass 2: a thread reads only its own entries of s_w, and rows 0..2 are not written again.
+        // The waves run decoupled through the active list, TM_ROW_K multiplets at a time, each into its own rows; the
+        // workgroup meets once per chunk -- in the common case (nact <= TM_ROW_K) once per tile -- at the flush below.
+        TM_TILE_SYNC();
 #if defined(TM_ABLATE) && (TM_ABLATE & 2)   // timing-only build: no multiplet pass 2 at all
-        for (int jj = 0; jj < 0; jj++) {
+        const int nrun = 0;
 #else
-        for (int jj = 0; jj < nact; jj++) {
+        const int nrun = nact;
 #endif
-            const int idx = tix[jj].idx, shape = tix[jj].shape;
-            TmMultK sm = (TmMultK)(gm + idx);
-            const int nc = shape & 255;
-            double *red = s_red[(jj + 1) & 1][wave];
-            if (lane == 0) {      // slots this multiplet does not write (A_am beyond its L; the asymmetry sums)
-                const int Lm = (nc - 1) >> 1;
-                for (int am = Lm + 1; am <= 3; am++) red[7 + am] = 0.0;
-                if (shape < 256) { red[21] = 0.0; red[22] = 0.0; red[23] = 0.0; }
-            }
-            switch (shape) {
-            case 1: tm_grad_mult<1, false, AHEAD>(sm, a.x2, s_w, u0, u1, a.Nx, tid, lane, red); break;
-            case 3: tm_grad_mult<3, false, AHEAD>(sm, a.x2, s_w, u0, u1, a.Nx, tid, lane, red); break;
-            case 5: tm_grad_mult<5, false, AHEAD>(sm, a.x2, s_w, u0, u1, a.Nx, tid, lane, red); break;
-            case 7: tm_grad_mult<7, false, AHEAD>(sm, a.x2, s_w, u0, u1, a.Nx, tid, lane, red); break;
-            case 256 + 1: tm_grad_mult<1, true, AHEAD>(sm, a.x2, s_w, u0, u1, a.Nx, tid, lane, red); break;
-            case 256 + 3: tm_grad_mult<3, true, AHEAD>(sm, a.x2, s_w, u0, u1, a.Nx, tid, lane, red); break;
-            case 256 + 5: tm_grad_mult<5, true, AHEAD>(sm, a.x2, s_w, u0, u1, a.Nx, tid, lane, red); break;
-            default: tm_grad_mult<7, true, AHEAD>(sm, a.x2, s_w, u0, u1, a.Nx, tid, lane, red); break;
-            }
-#if defined(TM_ABLATE) && (TM_ABLATE & 64)   // timing-only build: no workgroup barrier per multiplet (wave 0 publishes its own partial)
-            if (tid < TM_GSLOTS) a.gmult[(((size_t)chain * a.tiles + tile) * a.n_mult + idx) * TM_GSLOTS + tid] = red[tid];
-#else
-            __syncthreads();
-            if (tid < TM_GSLOTS) {
-                double t = 0.0;
-                if (tid < nc || (tid >= 7 && tid < 12) || tid >= 21) {      // B_k, A_am, C, asymmetry sums (tm_grad_store_slot)
-#pragma unroll
-                    for (int wv = 0; wv < TM_WAVES; wv++) t += s_red[(jj + 1) & 1][wv][tid];
+#pragma unroll 1
+        for (int base = 0;; base += TM_ROW_K) {
+            const int nrow = nrun - base < TM_ROW_K ? nrun - base : TM_ROW_K;      // multiplets of this chunk
+            const bool last = base + TM_ROW_K >= nrun;
+#pragma unroll 1
+            for (int j = 0; j < nrow; j++) {
+                const int jj = base + j;
+                const int idx = tix[jj].idx, shape = tix[jj].shape;
+                TmMultK sm = (TmMultK)(gm + idx);
+                double *red = s_rows[wave][3 + j];
+                switch (shape) {
+                case 1: tm_grad_mult<1, false, AHEAD>(sm, a.x2, s_w, u0, u1, a.Nx, tid, lane, red); break;
+                case 3: tm_grad_mult<3, false, AHEAD>(sm, a.x2, s_w, u0, u1, a.Nx, tid, lane, red); break;
+                case 5: tm_grad_mult<5, false, AHEAD>(sm, a.x2, s_w, u0, u1, a.Nx, tid, lane, red); break;
+                case 7: tm_grad_mult<7, false, AHEAD>(sm, a.x2, s_w, u0, u1, a.Nx, tid, lane, red); break;
+                case 256 + 1: tm_grad_mult<1, true, AHEAD>(sm, a.x2, s_w, u0, u1, a.Nx, tid, lane, red); break;
+                case 256 + 3: tm_grad_mult<3, true, AHEAD>(sm, a.x2, s_w, u0, u1, a.Nx, tid, lane, red); break;
+                case 256 + 5: tm_grad_mult<5, true, AHEAD>(sm, a.x2, s_w, u0, u1, a.Nx, tid, lane, red); break;
+                default: tm_grad_mult<7, true, AHEAD>(sm, a.x2, s_w, u0, u1, a.Nx, tid, lane, red); break;
                 }
-                a.gmult[(((size_t)chain * a.tiles + tile) * a.n_mult + idx) * TM_GSLOTS + tid] = t;
+                TM_TILE_SYNC();
             }
+            // The flush: thread t takes row t / TM_GSLOTS, slot t % TM_GSLOTS, adds the four waves in the order 0, 1, 2, 3 and
+            // stores the total: here the chunk's gmult rows.  A slot the multiplet's shape does not write
+            // (tm_grad_store_slot) is stored as zero and never read from LDS, so nothing has to clear a row before it is reused.
+#if !(defined(TM_ABLATE) && (TM_ABLATE & 64))   // (bit 64, timing-only build: no flush barrier)
+            __syncthreads();
 #endif
+            const int r = tid / TM_GSLOTS, s = tid - r * TM_GSLOTS;
+            if (r >= 3 && r - 3 < nrow) {
+                const int idx = tix[base + r - 3].idx, shape = tix[base + r - 3].shape;
+                const int nc = shape & 255;
+                double t = 0.0;
+                if (s < nc || (s >= 7 && s <= 7 + ((nc - 1) >> 1)) || s == 11 || (s >= 21 && shape >= 256)) {      // B_k, A_am, C, asymmetry sums
+#pragma unroll
+                    for (int wv = 0; wv < TM_WAVES; wv++) t += s_rows[wv][r][s];
+                }
+                a.gmult[(((size_t)chain * a.tiles + tile) * a.n_mult + idx) * TM_GSLOTS + s] = t;
+            }
+            if (last) break;
+            __syncthreads();   // the rows are free again: only tiles with nact > TM_ROW_K come here
+        }
+        // Behind the last chunk's barrier rows 0..2 of every wave are complete as well: the likelihood triple (a product for
+        // the mantissas) -> part[], summed by the backward kernel, and the noise sums of the cells the tile met -> gnoise.
+        // Kept behind the chunk loop, not in it: inside, the generic kernel spilled ten more SGPRs.
+        {
+            const int r = tid / TM_GSLOTS, s = tid - r * TM_GSLOTS;
+            const size_t ct = (size_t)chain * a.tiles + tile;
+            if (r == 0) {
+                if (s < 3) {
+                    double t = (s == 1) ? 1.0 : 0.0;
+#pragma unroll
+                    for (int wv = 0; wv < TM_WAVES; wv++) { const double v = s_rows[wv][0][s]; t = (s == 1) ? t * v : t + v; }
+                    a.part[ct * 4 + s] = t;
+                }
+            } else if (r < 3 && s < TM_NSLOTS && (r == 1 || ((u1 - 1) >> TM_CELL_SHIFT) > (u0 >> TM_CELL_SHIFT))) {
+                // part 1 exists where the tile's last unit lies in another cell than its first (a tile meets at most two)
+                double t = 0.0;
+#pragma unroll
+                for (int wv = 0; wv < TM_WAVES; wv++) t += s_rows[wv][r][s];
+                a.gnoise[(ct * 2 + (r - 1)) * TM_NSLOTS + s] = t;
+            }
         }
         TM_STAMP(2);   // gradient kernel: slot 2 = end of pass 2
     }
