@@ -1,7 +1,7 @@
 """What two or more of the posterior-summary suites use (tests/test_summary_*_gpu.py, tests/test_cli_*_gpu.py,
 tests/test_scan_null_gpu.py, tests/test_summary_*_host.py): the cases and their references, the bit-for-bit comparisons, the
-common body of the three tail checks, the accumulation-alone reference of the fold, the PSIS-LOO reference with its check, the
-ESS and band-ESS passes with the checks of the lag products and the finish, and the stored chain of the command-line tests.
+common body of the three tail checks, the accumulation-alone reference of the fold, the PSIS-LOO reference with its check and
+the exact cutoff from the library's own l, the ESS and band-ESS passes with the checks of the lag products and the finish, and the stored chain of the command-line tests.
 Importing this module needs no GPU.
 
 Tolerances of reference() / check() are derived, not tuned: the project's per-bin model bar eps = 1e-12 (RTOL_MODEL,
@@ -562,6 +562,34 @@ def check_loo_reference(tag, res, x_ld, groups, rel, seeds, x64=None, totals=Tru
     assert res["n_k_high"] == int((kh > 0.7).sum()) and res["n_k_inf"] == int(np.isposinf(kh).sum()), tag
     assert res["k_max"] == np.nanmax(kh), tag
     return ref
+
+
+def library_l(acc, P):
+    """l_is bit for bit from the library: after a reset and one sample, mean_l is l."""
+    out = np.empty((len(P), acc.Nx))
+    with capi.Summary(acc, 1) as s:
+        for k in range(len(P)):
+            s.reset()
+            _, st = s.push(P[k:k + 1])
+            assert st[0] == 0
+            out[k] = s.result()["mean_l"]
+    return out
+
+
+def exact_structure(tag, res, l):
+    """cutoff and tail_len from the library's own l (n, Nx), no tolerance."""
+    n = len(l)
+    M = tail_M(n)
+    xs = np.sort(-l, axis=0)
+    assert res["n_used"] == n
+    if n <= M:
+        assert np.all(np.isnan(res["cutoff"])) and np.all(res["tail_len"] == 0), tag
+        return
+    cut = xs[n - M - 1]
+    assert np.array_equal(bits(res["cutoff"] + 0.0), bits(cut + 0.0)), (tag, "cutoff")
+    z = xs - xs[-1]
+    c = np.maximum(z[n - M - 1], np.log(np.finfo(np.float64).tiny))
+    assert np.array_equal(res["tail_len"], (z > c).sum(axis=0)), (tag, "tail_len")
 
 
 # ---- ESS and band ESS: the passes and the checks of the lag products and the finish ----

@@ -9,6 +9,12 @@ object that depends on the length of the grid, on both sides of its edge.  The o
   LOO tail        M = ceil(min(n / 5, 3 sqrt n)) candidates sorted in LDS arrays of 2048: 1024 at n = 116 508 (P = 1024), 1025 at
                   116 509 and 116 510 (P = 2048); 2048 at 466 033 fills the arrays (passed, not kept: OBSERVED), 466 034 is refused
   tiles, groups   GB is one bin past 512 fold workgroups, 64 scan tiles and 2048 lag groups
+  LOO, LOO-PIT    the LOO tail and LOO-PIT kernels give a bin to a thread, the finalize and prepare kernels a workgroup to a bin
+                  (4.2e6 workgroups on GC / GD); fold, LOO and PIT pass in the default blocks of 63 (GB), 2 (GC) and 1 (GD)
+                  against 7, 3 and 3; M = 14 with the 70 samples of GB, 1 with the 5 of GC / GD (no Pareto fit: k-hat = +inf)
+  window-LOO      scratch [block_chains][n_windows], sized at wloo_begin; a sums tile holds min(256, 4096 / W) windows: on GB
+                  W = 20 is 6554 windows in 33 tiles, W = 512 257 in 33; on GD W = 1 is 4 194 305 windows, 16 385 tiles a sample
+                  and 65 537 workgroups of the tail and PIT kernels; W = 7 with first = 3, 20 and 512 on both grids
 
 Chains: id 2 on the C2 star's grid (c2_chain); 70 accepted samples on GA / GB with a rejected row at pushes 5 and 63 -- inside
 the first block, and the last row of a block of 64 / the first of the second block of 63 --, 5 accepted and one rejected on
@@ -44,7 +50,17 @@ to (n - 1) 2^-51; r / n adds 2^-53; all of it goes into log(r / n) as an absolut
 tests/test_summary_large_gpu.py is unchanged.
 
 The launch splits `per` of tm_launch_window and tm_launch_scan (2^23 workgroups, 2^30 / 2^31 threads a launch) are not reached
-here or anywhere: with the block and chunk rules as they are a launch that large needs tens of GB of model rows.
+here or anywhere: with the block and chunk rules as they are a launch that large needs tens of GB of model rows.  Nor, in
+LOO and window-LOO mode: heap and log-weight offsets past 2^31 elements, which need M Nx > 2^31 -- M = 512 on GD, for example,
+is 29 128 samples in blocks of one row and 17 GB each for the heap and the log weights (the code casts every such offset to
+size_t) --; and the launch split `per` of wloo_launch_sums (2^23 workgroups, 2^31 threads), reached only with far more samples
+in a block than the block rule allows on a grid with that many windows.
+
+In LOO and window-LOO mode on GB and GD (tests of section 7) cutoff and tail_len are exact on every bin and window against the
+library's own l (summary_support.library_l: one push per sample, affordable at 70 and at 5 samples; for a window the float64
+sum of its bins' l in ascending order, wloo_support.exact_windows); the references -- check_loo_reference, the LOO-PIT suite's
+and the window-LOO suite's check_reference (loopit_support, wloo_support), the latter on the gathered grid of the windows that
+hold the subset with the first and the last window -- run on subset_bins().
 
 Worst ratios to the bounds, memory and times observed on an MI355X (pytest -s prints them): see OBSERVED below.
 """
@@ -55,15 +71,17 @@ import numpy as np
 import pytest
 
 import bandess_reference as B
+import loopit_support as LP
+import wloo_support as WL
 from predictive_reference import _log_mean_exp, _seq_sum, log_gamma_tails, predictive_reference, totals_from_pit
 from scan_reference import scan_reference, scan_totals
 from summary_support import (ESS_WORST, LD, Q8, accepted, accumulation_reference, band_pass, c2_chain, check, check_acov, check_finish,
-                             check_loo_reference, check_pit, check_tails_reference, gpu_rows, ranks_of, rows_around, run_ess, same, same_pred,
-                             same_scan, same_scans, same_traj, same_win, select, spectrum_for, steps, summarize, tail_M,
+                             check_loo_reference, check_pit, check_tails_reference, exact_structure, gpu_rows, library_l, ranks_of, rows_around,
+                             run_ess, same, same_pred, same_scan, same_scans, same_traj, same_win, select, spectrum_for, steps, summarize, tail_M,
                              truth_of, unresolved_bits, with_rejected, x_of)
 from support import bits
 from tamcmc_amd import capi, synth
-from window_reference import partition, window_reference, window_totals
+from window_reference import partition, window_reference, window_totals, windows_holding
 
 pytestmark = pytest.mark.gpu
 
@@ -79,12 +97,23 @@ Worst ratios to the bounds (22 cases, 982 GPU tests in the session):
   band ESS                                  counts and E_k exact, tau and ess 0 ulp
   LOO, n = 116 508 / 116 509 / 116 510      elpd_loo 0.10, k-hat 0.013; n = 466 033: 0.10 and 0.010
   |P + Q - 1|                               1.8e-14 or less
+  LOO on GB / GD (subset_bins)              elpd_loo 0.083 / 0.047, k-hat 0.0097 / 0 (every k-hat +inf with 5 samples, in the reference too)
+  LOO-PIT on GB / GD                        loo_log_cdf 0.073 / 0.075, loo_log_sf 0.080 / 0.044, loo_pit 0.076 / 0.058, is_ess 0.067 / 0.029, log_wsum
+                                            0.0084 / 0.0043, elpd_loo against the reference's weights 0.055 / 0.028
+  window-LOO, W = 1, 7, 20, 512 on GB, GD   elpd_lwo 0.1, k-hat 0.1, cutoff 0.1, loo_log_cdf 0.075, loo_log_sf 0.080, loo_pit 0.076, is_ess 0.1, log_wsum 0.1
+                                            (0.1, all at W = 512: the result equals the float64 reference, whose distance from the long-double
+                                            one is the bound's tenth; below W = 512 0.099 for elpd_lwo at W = 1 on GB and 0.077 and under otherwise)
 Device memory: the largest case is the scan of (7, 20, 40) on GD, about 1.5 GB (state 805 MB, scratch 302 MB, the fold's and the
 rows').  Slowest case: test_scan_on_the_longest_grid, 6.1 s (5.7 s on the device side); the 4.2e6-bin fold and window cases
 take 5.6 ... 5.7 s, most of it the long-double reduction of all bins on the host.
 LOO at n = 466 033 (M = 2048): 8.8 s, of which the fold and the LOO pass take 0.69 s; the slowest case of
 tests/test_summary_large_gpu.py took 3.6 s in the same session.  The project has no marker for slow cases, so that case is not
 kept; the refusal at 466 034, which needs the fold pass alone, takes 0.7 s.
+LOO, LOO-PIT and window-LOO (11 cases): the largest is window-LOO with W = 1 on GD and block_chains = 3, about 1.5 GB: 264 bytes a
+window for the mode and its sub-mode (heap, state and scratch 386 MB, log weights, state and scratch 721 MB: tamcmc_wloo.h) beside
+the fold's state and the rows'; the per-bin LOO-PIT state on GD is about 0.5 GB.  Slowest: test_loo_and_loo_pit on GD, 5.1 s (3.4 s
+on the device side, one push per sample for the library's own l among it), on GC 3.9 s, test_window_loo with W = 1 on GD 3.6 s; every
+other case 1.9 s or less.
 """
 
 GA, GB, GC, GD = 131072, 131073, 4194304, 4194305
@@ -145,15 +174,15 @@ def open_grid(accel_mod, Nx):
 
 
 @functools.lru_cache(maxsize=None)
-def subset_bins(Nx):
-    """The bins at which the heavier references are evaluated (module docstring), ascending."""
+def subset_bins(Nx, drawn=512):
+    """The bins at which the heavier references are evaluated (module docstring), ascending; `drawn` of them are drawn."""
     b = {0, 1, Nx - 2, Nx - 1}
     for T in (64, 256, 2048, 4096):
         full = (Nx // T) * T                                 # the first bin behind the last full group of T
         b.update((T - 1, T, T + 1, full - 1, full))
     for k in (31, 32, 62, 63):
         b.update((2047 + 2048 * k - 1, 2047 + 2048 * k, 2047 + 2048 * k + 1))
-    b.update(int(v) for v in np.random.default_rng(20262).integers(0, Nx, size=512))
+    b.update(int(v) for v in np.random.default_rng(20262).integers(0, Nx, size=drawn))
     out = np.array(sorted(v for v in b if 0 <= v < Nx), dtype=np.int64)
     out.setflags(write=False)
     return out
@@ -239,18 +268,6 @@ def window_totals_exact(tag, res, n, n_bad, Nx, W, first):
     t = window_totals(pit, lc, ls)
     assert res["ks_D"] == t["ks_D"] and np.array_equal(res["pit_hist"], t["pit_hist"]), tag
     assert all(res[k] == t[k] for k in ("win_min_log_sf", "min_log_sf", "win_min_log_cdf", "min_log_cdf")), tag
-
-
-def windows_holding(bins, Nx, W, first):
-    """(indices of the windows that hold `bins`, with window 0 and the last one; the bins of those windows in order; first as
-    resolved).  Window 0 comes first and only the last window can be short, so the gathered bins are a grid whose partition
-    (W, first) has exactly these windows."""
-    f, begin, end = partition(Nx, W, first)
-    idx = np.where(bins < f, 0, 1 + (bins - f) // W)
-    sel = np.unique(np.concatenate([idx, [0, len(begin) - 1]]))
-    cols = np.concatenate([np.arange(begin[i], end[i]) for i in sel])
-    assert np.all((end - begin)[sel[1:-1]] == W)
-    return sel, cols, f
 
 
 @pytest.mark.parametrize("Nx", [GB, GD])
@@ -579,6 +596,152 @@ def test_loo_refused_past_the_full_tail(accel_mod):
             assert same(s.result(), before)
             s.quantiles_begin((0.5,))                        # not left inside a mode
             s.quantiles_end()
+
+
+# ---- 7. LOO, LOO-PIT and window-LOO on the long grids ----
+
+_L, _PER_BIN = {}, {}
+
+
+def accepted_rows(P):
+    """The pushed rows without the rejected ones of with_rejected (a NaN parameter)."""
+    return P[~np.isnan(P).any(axis=1)]
+
+
+def l_of(acc, Nx):
+    """The library's own l of the accepted samples on every bin (library_l: one push per sample); computed once per grid."""
+    if Nx not in _L:
+        _L[Nx] = library_l(acc, accepted_rows(chain(Nx)[2]))
+        _L[Nx].setflags(write=False)
+    return _L[Nx]
+
+
+def per_bin_loo(acc, Nx):
+    """(LOO-PIT result, LOO result, fold result) of the three passes with the default block; computed once per grid."""
+    if Nx not in _PER_BIN:
+        _PER_BIN[Nx] = LP.run_pit(acc, [chain(Nx)[2]], 0)
+    return _PER_BIN[Nx]
+
+
+def own_worst(mod, call):
+    """The worst ratios that `call`, a check_reference of the support module `mod`, adds to mod.WORST, apart from what the
+    module's own suite recorded there in the same session."""
+    before = mod.WORST.pop("own", {})
+    try:
+        call()
+    finally:
+        mine = mod.WORST.get("own", {})
+        mod.WORST["own"] = {k: max(before.get(k, 0.0), mine.get(k, 0.0)) for k in set(before) | set(mine)}
+    return mine
+
+
+def loo_totals_exact(tag, loo, fold):
+    """The totals of loo_result from the library's own arrays, summed in bin order in long double as the host does (np.cumsum)."""
+    e = np.cumsum(np.asarray(loo["elpd_loo"]).astype(LD))[-1]
+    assert loo["elpd_loo_total"] == float(e) and loo["looic"] == float(-2 * LD(float(e))), tag
+    assert loo["p_loo"] == float(np.cumsum(np.asarray(fold["lppd"]).astype(LD))[-1] - e), (tag, "p_loo")
+    kh = np.asarray(loo["pareto_k"])
+    with np.errstate(invalid="ignore"):
+        assert loo["n_k_high"] == int((kh > 0.7).sum()) and loo["n_k_inf"] == int(np.isposinf(kh).sum()), tag
+    assert np.isnan(loo["k_max"]) if np.all(np.isnan(kh)) else loo["k_max"] == np.nanmax(kh), tag
+
+
+@pytest.mark.parametrize("Nx", [GB, GC, GD])
+def test_loo_and_loo_pit(accel_mod, Nx):
+    """Fold pass, LOO pass and PIT pass with the default block (63 on GB, 1 on GD) and with block_chains = 7 (3 on GD); on GC
+    block 2 against block 3: every array and total has the same bits, the fold results are those the object gave before it
+    entered the mode, n_used and n_rejected are exact.  One workgroup per bin in the finalize and prepare kernels: 4.2e6
+    workgroups on GC / GD.  On GB and GD cutoff and tail_len are exact in every bin against the library's own l, the totals
+    are recomputed from the library's own arrays, and the bins of subset_bins() are held to psis_reference
+    (check_loo_reference) and loopit_reference (the LOO-PIT suite's check_reference) on the GPU's own rows.  With the 5 samples
+    of GD M = 1, no bin has a Pareto fit and every k-hat is +inf, in the reference too."""
+    _, y, P, n_bad = chain(Nx)
+    b0, b1 = {GB: (0, 7), GC: (2, 3), GD: (0, 3)}[Nx]
+    assert default_block(Nx) == {GB: 63, GC: 2, GD: 1}[Nx]
+    tag = f"long-loo Nx={Nx}"
+    t0 = time.perf_counter()
+    with open_grid(accel_mod, Nx) as acc:
+        rows = rows_of(acc, Nx) if Nx != GC else None
+        res, loo, fold = per_bin_loo(acc, Nx) if b0 == 0 else LP.run_pit(acc, [P], b0)
+        with capi.Summary(acc, b1) as s:                        # the other block: each result fetched once
+            s.push(P)
+            plain = s.result()
+            both = s.loo(P, pit=True)
+            fold_b = s.result()
+        l = l_of(acc, Nx) if Nx != GC else None
+    print(f"TIME {tag}: {time.perf_counter() - t0:.2f} s on the device side")
+    n = len(P) - n_bad
+    assert LP.same_pit(res, both) and LP.same_loo(loo, both) and same(fold, fold_b), ("block_chains", b0, b1)
+    assert same(fold, plain), "the fold results before LOO mode, another block"
+    assert tail_M(n) == (14 if Nx == GB else 1)
+    for r in (res, loo, fold):
+        assert r["n_used"] == n and r["n_rejected"] == n_bad, tag
+    assert all(np.asarray(loo[k]).shape == (Nx,) for k in LP.LOO_KEYS + ("tail_len",)) and all(np.asarray(res[k]).shape == (Nx,) for k in LP.PIT_ARRAYS)
+    if Nx == GC:
+        return
+    exact_structure(tag, loo, l)
+    loo_totals_exact(tag, loo, fold)
+    LP.check_totals(tag, res)
+    sub = subset_bins(Nx)
+    part = dict(loo, **{k: np.asarray(loo[k])[sub] for k in LP.LOO_KEYS + ("tail_len",)})
+    with np.errstate(over="ignore"):
+        check_loo_reference(tag, part, x_of(rows[:, sub], y[sub]), np.arange(n), 2.0 ** -50, (1,), x64=x_of(rows[:, sub], y[sub], dtype=np.float64),
+                            totals=False)
+        record("loopit", own_worst(LP, lambda: LP.check_reference(tag, res, loo, rows, y, np.arange(n), 2.0 ** -50, sel=sub)))
+
+
+@pytest.mark.parametrize("Wd,first", [(1, 0), (7, 3), (20, 0), (512, 0)])
+@pytest.mark.parametrize("Nx", [GB, GD])
+def test_window_loo(accel_mod, Nx, Wd, first):
+    """Window-LOO with its PIT pass, the default block against block_chains = 7 (3 on GD) bit for bit.  On GB W = 20 gives 6554
+    windows in 33 tiles of the sums kernel and W = 512 gives 257 windows in 33 tiles; on GD W = 1 gives 4 194 305 windows: 16 385
+    tiles per sample, 65 537 workgroups of the tail and PIT kernels, a scratch of one sample (three with block 3).  Exact on
+    every window: n_windows, first_bin and last_bin are the partition's; cutoff and tail_len from the float64 ascending sums of
+    the library's own l (wloo_support.exact_windows); the totals from the returned arrays; at W = 1 every array and total is
+    the per-bin LOO and LOO-PIT result of test_loo_and_loo_pit (p = 1).  At W = 20 the object with the other block then runs a
+    per-bin LOO and PIT pass, which gives the bits of an object that never saw the mode, and the fold keeps its bytes.  Against
+    wloo_reference in its gathered form: the windows that hold subset_bins(), with the first and the last window -- at W = 512
+    on GB those of subset_bins(GB, 32), 41 windows, since the long-double reference of all 221 with 70 samples takes 11 s on the host."""
+    _, y, P, n_bad = chain(Nx)
+    other = 7 if Nx == GB else 3
+    tag = f"long-wloo Nx={Nx} W={Wd} first={first}"
+    t0 = time.perf_counter()
+    with open_grid(accel_mod, Nx) as acc:
+        rows = rows_of(acc, Nx)
+        res, loo, fold = WL.run_wloo(acc, [P], Wd, first, 0)
+        with capi.Summary(acc, other) as s:                     # the other block: each result fetched once
+            s.push(P)
+            both = s.window_loo(P, Wd, first, pit=True)
+            later = s.loo(P, pit=True) if Wd == 20 else None
+            fold_b = s.result()
+        l = l_of(acc, Nx)
+        if Wd in (1, 20):
+            pit1, loo1, fold1 = per_bin_loo(acc, Nx)
+    print(f"TIME {tag}: {time.perf_counter() - t0:.2f} s on the device side")
+    n = len(rows)
+    assert LP.same_pit(res, both) and WL.same_wloo(loo, both) and same(fold, fold_b), ("block_chains", other)
+    for r in (res, loo, fold):
+        assert r["n_used"] == n and r["n_rejected"] == n_bad, tag
+    WL.check_geometry(tag, loo, Nx, Wd, first)
+    nw = loo["n_windows"]
+    if Nx == GB:
+        assert nw == {1: GB, 7: 18726, 20: 6554, 512: 257}[Wd]
+    WL.check_totals(tag, res, loo, fold)
+    WL.exact_windows(tag, loo, l, Nx, Wd, first)
+    if Wd == 1:
+        for a, b in (("elpd_lwo", "elpd_loo"), ("pareto_k", "pareto_k"), ("cutoff", "cutoff"), ("tail_len", "tail_len")):
+            assert np.array_equal(bits(loo[a]), bits(loo1[b])), (tag, a)
+        for a, b in (("elpd_lwo_total", "elpd_loo_total"), ("p_lwo", "p_loo"), ("k_max", "k_max"), ("n_k_high", "n_k_high"), ("n_k_inf", "n_k_inf")):
+            assert np.array_equal(bits(float(loo[a])), bits(float(loo1[b]))), (tag, a)
+        assert LP.same_pit(res, pit1), (tag, "the PIT arrays and totals against the per-bin LOO-PIT")
+    if Wd == 20:
+        assert LP.same_pit(later, pit1) and LP.same_loo(later, loo1), (tag, "a per-bin LOO pass after window-LOO mode")
+        assert same(fold, fold1), (tag, "the fold results")
+    sub = subset_bins(GB, 32) if (Nx, Wd) == (GB, 512) else subset_bins(Nx)
+    sel, cols, f = windows_holding(sub, Nx, Wd, first)
+    with np.errstate(over="ignore"):
+        record("wloo", own_worst(WL, lambda: WL.check_reference(tag, WL.at_windows(res, sel, nw), WL.at_windows(loo, sel, nw), rows[:, cols], y[cols],
+                                                                np.arange(n), 2.0 ** -50, Wd, f)))
 
 
 def test_print_worst():

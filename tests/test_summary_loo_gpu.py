@@ -29,7 +29,7 @@ import numpy as np
 import pytest
 
 import workloads as W
-from summary_support import (c2_case, c2_chain, f12, gpu_rows, header_values, other_cases, row_groups,
+from summary_support import (c2_case, c2_chain, exact_structure, f12, gpu_rows, header_values, library_l, other_cases, row_groups,
                              same, spectrum_for, stored_chain, tail_M, x_of)
 from summary_support import check_loo_reference as check_reference
 from support import LD, bits, in_torch_process, pyorc
@@ -58,34 +58,6 @@ def run_loo(acc, pushes, block=0):
 def same_loo(r1, r2):
     return all(np.array_equal(bits(r1[k]), bits(r2[k])) for k in LOO_KEYS[:3]) and np.array_equal(r1["tail_len"], r2["tail_len"]) and \
         all(np.array_equal(bits(float(r1[k])), bits(float(r2[k]))) for k in LOO_TOTALS)
-
-
-def library_l(acc, P):
-    """l_is bit for bit from the library: after a reset and one sample, mean_l is l."""
-    out = np.empty((len(P), acc.Nx))
-    with capi.Summary(acc, 1) as s:
-        for k in range(len(P)):
-            s.reset()
-            _, st = s.push(P[k:k + 1])
-            assert st[0] == 0
-            out[k] = s.result()["mean_l"]
-    return out
-
-
-def exact_structure(tag, res, l):
-    """cutoff and tail_len from the library's own l (n, Nx), no tolerance."""
-    n = len(l)
-    M = tail_M(n)
-    xs = np.sort(-l, axis=0)
-    assert res["n_used"] == n
-    if n <= M:
-        assert np.all(np.isnan(res["cutoff"])) and np.all(res["tail_len"] == 0), tag
-        return
-    cut = xs[n - M - 1]
-    assert np.array_equal(bits(res["cutoff"] + 0.0), bits(cut + 0.0)), (tag, "cutoff")
-    z = xs - xs[-1]
-    c = np.maximum(z[n - M - 1], np.log(np.finfo(np.float64).tiny))
-    assert np.array_equal(res["tail_len"], (z > c).sum(axis=0)), (tag, "tail_len")
 
 
 @pytest.mark.parametrize("Nx", [2, 63, 64, 65, 257, 700])

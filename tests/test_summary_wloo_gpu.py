@@ -10,7 +10,9 @@ says, so there the PIT arrays are held to the reference instead); n_windows, fir
 result is bitwise independent of block_chains (1, 7, 64, n, n + 1) and of the split of either pass into pushes, pushes of one
 row included; host and device pointers give the same bits; a chain with rejected rows gives the bits of the chain without
 them; wloo_result returns the same bits before wloo_pit_begin, after it and after the pass; the fold, predictive, window and
-scan results and a later per-bin LOO pass keep their bytes.
+scan results and a later per-bin LOO pass keep their bytes; across the tiles of the sums kernel and the workgroups of the tail
+and PIT kernels (test_across_sums_tiles, test_across_tail_workgroups: grids of up to 8704 bins, every class of W) cutoff is the
+order statistic of the float64 ascending window sums of the library's own l in every window, and tail_len the count above it.
 
 Against the reference the bound is the LOO-PIT suite's: per case and per quantity (the maximum over the windows; relative to
 max(1, |value|), absolute for loo_pit), 10 x the larger of
@@ -20,171 +22,27 @@ max(1, |value|), absolute for loo_pit), 10 x the larger of
 tail_len and the places where k-hat is +inf must be equal.  On the oracle's rows the perturbation is 1e-12 relative, the
 project's per-bin model bar.  Every worst ratio is printed before it is asserted (pytest -s).
 
-Worst ratios observed on an MI355X over all cases below, on the GPU's own rows: elpd_lwo 0.12, pareto_k 0.1, cutoff 0.028, loo_log_cdf 0.083,
-loo_log_sf 0.12, loo_pit 0.1, is_ess 0.099, log_wsum 0.11, elpd_lwo against the reference's weights 0.11; on the oracle's rows 0.00025, 5.8e-5, 3.2e-5,
+Worst ratios observed on an MI355X over all cases below, on the GPU's own rows: elpd_lwo 0.12, pareto_k 0.11, cutoff 0.1, loo_log_cdf 0.083,
+loo_log_sf 0.12, loo_pit 0.1, is_ess 0.1, log_wsum 0.11, elpd_lwo against the reference's weights 0.11 (across the tiles and workgroups
+alone: 0.1, 0.11, 0.1, 0.076, 0.077, 0.1, 0.1, 0.11 and 0.1; a ratio of 0.1 is a result that equals the float64 reference where the
+bound is 10 x that reference's distance from the long-double one); on the oracle's rows 0.00025, 5.8e-5, 3.2e-5,
 0.00094, 0.00092, 0.0014, 0.00014, 6e-5 and 0.00025.  The planted window: loo_log_sf = -8.63901 against the windowed check's -8.63862, is_ess 99.96 of 100.
 """
+import time
+
 import numpy as np
 import pytest
 
 import workloads as W
-from predictive_reference import totals_from_pit
-from summary_support import (ULP, c2_case, c2_chain, diff, gpu_rows, other_cases, perturbed, perturbed_rows, row_groups, same,
-                             same_pred, same_scans, same_win, spectrum_for, tail_M, true_model, x_of)
+from loopit_support import PIT_ARRAYS, PIT_TOTALS, same_pit
+from summary_support import (ULP, c2_case, c2_chain, gpu_rows, library_l, other_cases, row_groups, same, same_pred, same_scans, same_win,
+                             spectrum_for, tail_M, true_model)
 from support import bits, in_torch_process, pyorc
 from tamcmc_amd import capi, synth
-from window_reference import partition
-from wloo_reference import wloo_reference
+from wloo_support import (LOO_KEYS, check_geometry, check_pool, check_reference, check_reference_at, check_totals,
+                          exact_windows, run_wloo, same_wloo)
 
 pytestmark = pytest.mark.gpu
-
-PIT_ARRAYS = capi.Summary.LOO_PIT_ARRAYS
-PIT_TOTALS = capi.Summary.LOO_PIT_TOTALS
-LOO_KEYS = ("elpd_lwo", "pareto_k", "cutoff")
-SEEDS = (1, 2, 3)
-CHECKED = LOO_KEYS + ("loo_log_cdf", "loo_log_sf", "loo_pit", "is_ess", "log_wsum")
-
-
-def same_wloo(r1, r2):
-    return all(np.array_equal(bits(r1[k]), bits(r2[k])) for k in LOO_KEYS) and \
-        all(np.array_equal(r1[k], r2[k]) for k in ("tail_len", "first_bin", "last_bin")) and \
-        all(np.array_equal(bits(float(r1[k])), bits(float(r2[k]))) for k in capi.Summary.WLOO_TOTALS)
-
-
-def same_pit(r1, r2):
-    return all(np.array_equal(bits(r1[k]), bits(r2[k])) for k in PIT_ARRAYS) and np.array_equal(r1["loo_pit_hist"], r2["loo_pit_hist"]) and \
-        all(np.array_equal(bits(float(r1[k])), bits(float(r2[k]))) for k in PIT_TOTALS)
-
-
-def run_wloo(acc, pushes, Wd, first=0, block=0, loo_pushes=None, pit_pushes=None, **kw):
-    """Fold pass, window-LOO pass and PIT pass.  Returns (pit result, loo result, fold result); wloo_result must give the
-    same bits before wloo_pit_begin, after it and after the pass, and the fold results must not move."""
-    with capi.Summary(acc, block, **kw) as s:
-        for P in pushes:
-            s.push(P)
-        fold = s.result()
-        nw = s.wloo_begin(Wd, first)
-        for P in (pushes if loo_pushes is None else loo_pushes):
-            s.push(P)
-        loo = s.wloo_result()
-        assert loo["n_windows"] == nw and loo["elpd_lwo"].shape == (nw,)
-        s.wloo_pit_begin()
-        assert same_wloo(s.wloo_result(), loo), "wloo_result changed over wloo_pit_begin"
-        for P in (pushes if pit_pushes is None else pit_pushes):
-            s.push(P)
-        r = s.wloo_pit_result()
-        assert same_wloo(s.wloo_result(), loo), "wloo_result changed over the PIT pass"
-        assert same_pit(s.wloo_pit_result(), r), "a second wloo_pit_result without another pass"
-        assert same(s.result(), fold), "the fold results changed in window-LOO mode"
-        s.wloo_end()
-    return r, loo, fold
-
-
-def check_geometry(tag, loo, Nx, Wd, first):
-    f, begin, end = partition(Nx, Wd, first)
-    assert loo["n_windows"] == begin.size and loo["W"] == Wd and loo["first"] == f, tag
-    assert np.array_equal(loo["first_bin"], begin) and np.array_equal(loo["last_bin"], end - 1), tag
-
-
-def check_totals(tag, res, loo, fold):
-    """The totals are their stated expressions on the returned arrays."""
-    LDt = np.longdouble                                        # (np.cumsum: one term after the other, as the host adds them)
-    e = np.cumsum(np.asarray(loo["elpd_lwo"]).astype(LDt))[-1]
-    assert loo["elpd_lwo_total"] == float(e), tag
-    assert loo["p_lwo"] == float(np.cumsum(np.asarray(fold["lppd"]).astype(LDt))[-1] - e), (tag, "p_lwo")
-    kh = np.asarray(loo["pareto_k"])
-    assert loo["n_k_high"] == int((kh > 0.7).sum()) and loo["n_k_inf"] == int(np.isposinf(kh).sum()) and loo["k_max"] == np.nanmax(kh), tag
-    pit, lc, ls, ess = (np.asarray(res[k]) for k in ("loo_pit", "loo_log_cdf", "loo_log_sf", "is_ess"))
-    ok = ~np.isnan(pit)
-    want = np.where(lc < ls, np.exp(lc), -np.expm1(ls))
-    assert np.all(np.abs(pit[ok] - want[ok]) <= 2.0 * np.spacing(want[ok])), (tag, "loo_pit from the smaller tail")
-    assert np.all((pit[ok] >= 0) & (pit[ok] <= 1)) and np.all(lc[ok] <= 0) and np.all(ls[ok] <= 0), tag
-    if ok.any():
-        D, hist = totals_from_pit(pit[ok])
-        assert res["loo_ks_D"] == D and np.array_equal(res["loo_pit_hist"], hist), (tag, "ks_D / pit_hist")
-    for key, arr in (("min_loo_log_sf", ls), ("min_loo_log_cdf", lc), ("min_is_ess", ess)):
-        v = np.asarray(arr, dtype=np.float64)
-        k = -1 if np.all(np.isnan(v)) else int(np.argmin(np.where(np.isnan(v), np.inf, v)))
-        assert res["bin_" + key] == k and (k < 0 or bits(res[key]) == bits(v[k])), (tag, key)
-
-
-def _key(k):
-    return "pit" if k == "loo_pit" else k                     # summary_support.diff: absolute for a pit, relative otherwise
-
-
-def _diff(k, a, b):
-    a, b = np.asarray(a), np.asarray(b)
-    if k == "cutoff":                                          # NaN where there is no tail rule (n = 1): both, or neither
-        na, nb = np.isnan(a.astype(np.float64)), np.isnan(b.astype(np.float64))
-        if not np.array_equal(na, nb):
-            return np.inf
-        a, b = a[~na], b[~nb]
-        if a.size == 0:
-            return 0.0
-    return diff(_key(k), a, b)
-
-
-WORST = {}
-
-
-def check_reference(tag, res, loo, rows, y, groups, rel, Wd, first=0, like=0, p=1, sigma=None, pool=None):
-    """res and loo against wloo_reference on `rows`, with the bounds of the module docstring.  Returns the reference.
-    With `pool`, a dict, the case is made of several grids: the errors and the two bounds are maxima over the windows of all
-    of them -- this call adds its own, and check_pool() holds the one against the other once the case is complete."""
-    n = len(rows)
-    ref = wloo_reference(rows, y, Wd, first, like, p, sigma)
-    keys = CHECKED + ("elpd_from_weights", "log_wsum_direct")
-    d = {k: 0.0 for k in keys}
-    for seed in SEEDS:
-        pr = perturbed_rows(rows, rel, seed, groups)
-        px = perturbed(x_of(pr, y, like, p, sigma), rel, seed + 1000, groups)
-        pert = wloo_reference(pr, y, Wd, first, like, p, sigma, xbins=px)
-        for k in keys:
-            d[k] = max(d[k], _diff(k, pert[k], ref[k]))
-    r64 = wloo_reference(rows, y, Wd, first, like, p, sigma, dtype=np.float64)
-    b64 = {k: _diff(k, r64[k], ref[k]) for k in keys}
-    for k in keys:
-        d[k] = max(d[k], b64[k])
-    for k, dk in d.items():
-        assert np.isfinite(dk), (tag, k, "the reference runs disagree on where the value is finite: the case has no bound")
-    assert np.array_equal(loo["tail_len"], ref["tail_len"]), (tag, "tail_len")
-    assert np.array_equal(np.isinf(loo["pareto_k"]), np.isinf(ref["pareto_k"])), (tag, "where k-hat is +inf")
-    got = dict(res, elpd_from_weights=loo["elpd_lwo"], log_wsum_direct=res["log_wsum"], **{k: loo[k] for k in LOO_KEYS})
-    ratios = {}
-    for k, dk in d.items():
-        err = _diff(k, got[k], ref[k])
-        ratios[k] = err / (10.0 * dk) if dk > 0 else (0.0 if err == 0 else np.inf)
-    print(f"RATIO wloo {tag}: " + " ".join(f"{k}={v:.3g} (bound {10.0 * d[k]:.3g})" for k, v in ratios.items()))
-    if pool is not None:
-        for k in keys:
-            pool.setdefault("d", {})[k] = max(pool.get("d", {}).get(k, 0.0), d[k])
-            pool.setdefault("err", {})[k] = max(pool.get("err", {}).get(k, 0.0), _diff(k, got[k], ref[k]))
-        ratios = {}
-    seen = WORST.setdefault("oracle" if tag.startswith("oracle") else "own", {})
-    for k, v in ratios.items():
-        seen[k] = max(seen.get(k, 0.0), v)
-    print("WORST wloo so far: " + repr(WORST))
-    lc, ls, ess = np.asarray(res["loo_log_cdf"]), np.asarray(res["loo_log_sf"]), np.asarray(res["is_ess"])
-    one = np.abs(np.exp(lc) + np.exp(ls) - 1.0)
-    shape = int(p) * Wd
-    slack = (n + 2) * ULP + (10.0 * max(b64["loo_log_cdf"], b64["loo_log_sf"]) if like == 0 and shape > 1 else 0.0)
-    print(f"SELF wloo {tag}: |P + Q - 1| = {float(np.nanmax(one)):.3g} (bound {slack:.3g}); is_ess in [{float(np.nanmin(ess)):.6g}, "
-          f"{float(np.nanmax(ess)):.6g}] of n = {n}")
-    for k, v in ratios.items():
-        assert v <= 1.0, (tag, k, v)
-    assert np.all(one[~np.isnan(one)] <= slack), (tag, float(np.nanmax(one)), slack)
-    fin = ~np.isnan(ess)
-    assert np.all(ess[fin] >= 1.0 - 1e-12) and np.all(ess[fin] <= n * (1.0 + 1e-12)), (tag, "is_ess outside 1 ... n")
-    return ref
-
-
-def check_pool(tag, pool):
-    ratios = {k: (pool["err"][k] / (10.0 * dk) if dk > 0 else (0.0 if pool["err"][k] == 0 else np.inf)) for k, dk in pool["d"].items()}
-    print(f"RATIO wloo {tag}: " + " ".join(f"{k}={v:.3g} (bound {10.0 * pool['d'][k]:.3g})" for k, v in ratios.items()))
-    seen = WORST.setdefault("own", {})
-    for k, v in ratios.items():
-        seen[k] = max(seen.get(k, 0.0), v)
-        assert v <= 1.0, (tag, k, v)
 
 
 def open_cfg(accel_mod, w, y, cfg, mid=2):
@@ -252,8 +110,9 @@ def grids(Wd, f):
 
 @pytest.mark.parametrize("Wd", [2, 3, 5, 20, 64, 511, 512])
 def test_geometry(accel_mod, Wd):
-    """first in {0, 1, W - 1, W}; the last window full, partial and a single bin; Nx < first (one window); a tile of the
-    sums kernel that holds 256 windows (W <= 16) or 4096 / W.  n_windows, first_bin and last_bin are the partition's, and
+    """first in {0, 1, W - 1, W}; the last window full, partial and a single bin; Nx < first (one window).  These grids of
+    at most f + 2 W + 1 bins hold one to four windows, all in the first tile of the sums kernel; only the 700-bin grid of
+    W = 2 reaches a second tile (test_across_sums_tiles crosses the tiles).  n_windows, first_bin and last_bin are the partition's, and
     every window's results are the reference's within the bound, so every bin went to its own window and every window got
     its own shape.  The case is W: its grids hold one to a few windows each, and a maximum over one window of how far two
     reference runs happen to differ is no bound (at one window of 62 bins the float64 run lands within 3e-17 of the
@@ -275,6 +134,85 @@ def test_geometry(accel_mod, Wd):
             check_totals(tag, res, loo, fold)
             check_reference(tag, res, loo, rows, y, np.arange(len(P)), 2.0 ** -50, Wd, first, pool=pool)
     check_pool(f"geometry W={Wd}", pool)
+
+
+def windows_per_tile(Wd):
+    """The whole windows a workgroup of the sums kernel stages (wloo_launch_sums, tamcmc_wloo.hip): 4096 bins, at most 256."""
+    return min(256, 4096 // Wd)
+
+
+def grid_of(N, r, Wd, f):
+    """The grid of N windows whose last one has r bins: n_windows = 1 + ceil((Nx - f) / W)."""
+    return f + (N - 2) * Wd + r
+
+
+def across(accel_mod, name, Wd, counts):
+    """Body of the two tests below.  first in {0, 1, W - 1, W} x the window counts `counts`, the last window full, half and a
+    single bin -- one of the three per (first, count), in rotation, so that every length meets every count and every first:
+    the 16 grids of a width take 1.1 ... 2.2 s on an MI355X box, 0.9 ... 1.9 s of it the long-double reference on the host, and
+    with all three lengths would take three times that.  Every grid goes through run_wloo with block 16, then
+      exact, every window: the partition; the totals from the returned arrays; cutoff bit for bit the order statistic
+        sort(-S)[n - M - 1] of the float64 ascending sums S of the library's own l, tail_len the count above it (exact_windows);
+      the reference, on the gathered grid of check_reference_at: the windows at a tile edge (wpt - 1, wpt, 2 wpt - 1, 2 wpt), the
+        first two, the last two and 32 drawn by default_rng(20262); errors and bounds pooled over the case's grids.
+    Not checked: that the windows of the first tile have the bits they have on the grid cut down to that tile.  The model's
+    value in a bin depends on the grid's length: at W = 20, first = 0 the rows of the 4090-bin grid and of its first 4080 bins
+    (the same x, y and parameters) differ by one ulp in bin 1 of the first sample and in others, so l and every window result
+    differ too.  The exact cutoff above takes that check's place."""
+    wpt = windows_per_tile(Wd)
+    assert tail_M(37) == 8
+    lengths = sorted({Wd, max(Wd // 2, 1), 1}, reverse=True)
+    pool, seen, t_dev, t_ref = {}, set(), 0.0, 0.0
+    for a, first in enumerate(sorted({0, 1, Wd - 1, Wd})):
+        f = Wd if first == 0 else first
+        for b, N in enumerate(counts):
+            r = lengths[(a + b) % len(lengths)]
+            Nx = grid_of(N, r, Wd, f)
+            if (first, Nx) in seen:
+                continue
+            seen.add((first, Nx))
+            w, y, P = c2_chain(Nx, 37)
+            tag = f"{name} W={Wd} first={first} N={N} r={r} Nx={Nx}"
+            t0 = time.perf_counter()
+            with accel_mod.Accel(2, w["plength"], w["x"], y) as acc:
+                _, st, rows = gpu_rows(acc, P)
+                assert np.all(st == 0)
+                res, loo, fold = run_wloo(acc, [P], Wd, first, 16)
+                l = library_l(acc, P)
+            t1 = time.perf_counter()
+            assert loo["n_windows"] == N, tag
+            check_geometry(tag, loo, Nx, Wd, first)
+            check_totals(tag, res, loo, fold)
+            exact_windows(tag, loo, l, Nx, Wd, first)
+            edges = [v for v in (wpt - 1, wpt, 2 * wpt - 1, 2 * wpt, 0, 1, N - 2, N - 1) if 0 <= v < N]
+            drawn = np.random.default_rng(20262).choice(N, size=min(32, N), replace=False)
+            t2 = time.perf_counter()
+            check_reference_at(tag, np.concatenate([edges, drawn]), res, loo, rows, y, np.arange(len(P)), 2.0 ** -50, Wd, first, pool=pool)
+            t_dev, t_ref = t_dev + t1 - t0, t_ref + time.perf_counter() - t2
+    print(f"TIME {name} W={Wd}: {len(seen)} grids, {t_dev:.2f} s on the device side, {t_ref:.2f} s in the reference")
+    check_pool(f"{name} W={Wd}", pool)
+
+
+@pytest.mark.parametrize("Wd", [2, 3, 16, 17, 20, 64, 511, 512])
+def test_across_sums_tiles(accel_mod, Wd):
+    """N = wpt, wpt + 1, 2 wpt and 2 wpt + 1 windows, wpt = min(256, 4096 / W) the windows of a tile of the sums kernel: the
+    second tile (w0 > 0), the tile edge and a last tile of one window, which test_geometry's grids never reach.  W = 2 with a
+    partial first window; 3, the smallest width that otherwise never leaves the first tile; 16 and 17 on either side of
+    wpt = 256 | 240; 20 (204); 64 (64); 511 (8 windows of 4088 bins) and 512 (8).  The longest grid has 8704 bins.  What is
+    checked: across().
+    Mutant (not committed): in tamcmc_wloo_sums_kernel, for W >= 3 and w0 > 0, the thread of a tile's first window adds len - 1
+    terms; in bounds.  This module before this test: 38 passed; this test: fails at every W >= 3 on the exact cutoff (W = 2 spared)."""
+    wpt = windows_per_tile(Wd)
+    across(accel_mod, "tiles", Wd, (wpt, wpt + 1, 2 * wpt, 2 * wpt + 1))
+
+
+@pytest.mark.parametrize("Wd", [3, 20])
+def test_across_tail_workgroups(accel_mod, Wd):
+    """N = 63, 64, 65 and 129 windows: the tail and PIT kernels give a window to a thread and 64 threads to a workgroup, and
+    with W >= 3 the suite had at most 43 windows.  One wave short of full, full, one window in a second workgroup, one in a
+    third.  What is checked: across()."""
+    across(accel_mod, "workgroups", Wd, (63, 64, 65, 129))
+
 
 
 # ---- 3. against the reference ----

@@ -118,6 +118,42 @@ def test_core_arithmetic_against_long_double(tmp_path):
         assert "runtime error" not in r.stderr and "Sanitizer" not in r.stderr, r.stderr[-3000:]
 
 
+def test_gathered_reference_is_the_reference():
+    """The form in which the GPU suites evaluate wloo_reference on chosen windows only (wloo_support.check_reference_at): the
+    reference given window 0's bins, the chosen whole middle windows and the last window's bins, with the same W and first,
+    returns for those windows the bits of the reference given the whole grid -- 700 bins, 37 rows, float64 and long double; a
+    full and a partial first window, a full, a partial and a one-bin last window; the perturbed-x argument too."""
+    from window_reference import gathered, partition, windows_holding
+    from wloo_reference import wloo_reference
+    rng = np.random.default_rng(20263)
+    Nx, n = 700, 37
+    rows = 1.0 + rng.random((n, Nx))
+    y = rows[0] * rng.exponential(size=Nx)
+    for Wd, first, top in ((20, 0, 700), (20, 7, 700), (3, 1, 700), (7, 3, 697), (64, 64, 641), (512, 1, 700), (2, 1, 700)):
+        f, begin, end = partition(top, Wd, first)
+        nw = len(begin)
+        chosen = np.unique(np.concatenate([rng.integers(0, nw, size=min(8, nw)), [min(1, nw - 1), max(nw - 2, 0)]]))
+        sel, cols, f1 = gathered(chosen, top, Wd, first)
+        assert f1 == f and sel[0] == 0 and sel[-1] == nw - 1 and set(chosen) <= set(sel)
+        _, b1, e1 = partition(len(cols), Wd, f)
+        assert len(b1) == len(sel) and np.array_equal(e1 - b1, (end - begin)[sel])            # the gathered grid's partition is those windows
+        assert np.array_equal(cols, np.concatenate([np.arange(begin[i], end[i]) for i in sel]))
+        sel2, cols2, _ = windows_holding(begin[chosen], top, Wd, first)                        # by a bin each holds: the same windows
+        assert np.array_equal(sel2, sel) and np.array_equal(cols2, cols)
+        for dtype in (np.longdouble, np.float64):
+            whole = wloo_reference(rows[:, :top], y[:top], Wd, first, dtype=dtype)
+            part = wloo_reference(rows[:, cols], y[cols], Wd, f, dtype=dtype)
+            assert set(whole) == set(part)
+            for k in whole:
+                assert part[k].dtype == whole[k].dtype and part[k].shape == (len(sel),), (Wd, first, k)
+                assert np.array_equal(part[k], whole[k][sel], equal_nan=True), (Wd, first, dtype, k)
+            xb = (np.log(rows) + y / rows).astype(dtype) * dtype(1.0 + 2.0 ** -50)
+            whole = wloo_reference(rows[:, :top], y[:top], Wd, first, dtype=dtype, xbins=xb[:, :top])
+            part = wloo_reference(rows[:, cols], y[cols], Wd, f, dtype=dtype, xbins=xb[:, cols])
+            for k in whole:
+                assert np.array_equal(part[k], whole[k][sel], equal_nan=True), (Wd, first, dtype, k, "xbins")
+
+
 @needs_hipcc
 def test_kernel_resources():
     """The five kernels of tamcmc_wloo.hip cross-compiled for gfx950 (make resource-usage-wloo): none uses scratch or spills a

@@ -23,6 +23,25 @@ def partition(Nx, W, first=0):
     return first, begin, end
 
 
+def gathered(windows, Nx, W, first=0):
+    """(the windows `windows` with window 0 and the last one, ascending and each once; the bins of those windows in order; first
+    as resolved).  Window 0 comes first and only the last window can be short, so the gathered bins are a grid whose partition
+    (W, first) has exactly these windows: a reference given that grid evaluates the chosen windows alone."""
+    f, begin, end = partition(Nx, W, first)
+    sel = np.unique(np.concatenate([np.asarray(windows, dtype=np.int64).reshape(-1), [0, len(begin) - 1]]))
+    assert sel[0] == 0 and sel[-1] == len(begin) - 1
+    cols = np.concatenate([np.arange(begin[i], end[i]) for i in sel])
+    assert np.all((end - begin)[sel[1:-1]] == W) and (len(sel) == 1 or end[0] == f)
+    return sel, cols, f
+
+
+def windows_holding(bins, Nx, W, first=0):
+    """gathered() of the windows that hold the bins `bins`."""
+    f = W if first == 0 else first
+    bins = np.asarray(bins, dtype=np.int64)
+    return gathered(np.where(bins < f, 0, 1 + (bins - f) // W), Nx, W, first)
+
+
 def window_sums(rows, y, W, first=0, like=0, sigma=None, dtype=LD):
     """(S[n, n_windows], len[n_windows]): the sum over each window of y / M (like 0) or (y - M) / sigma, ascending."""
     M = np.asarray(rows).astype(dtype)
