@@ -801,6 +801,80 @@ int tamcmc_scan_null_profile(tamcmc_scan_null *h, int enable);
 int tamcmc_scan_null_kernel_time(tamcmc_scan_null *h, double *total_ms, int64_t *launches);
 int tamcmc_scan_null_destroy(tamcmc_scan_null *h);
 
+/* ---- Posterior mode table: the derived mode parameters of a stored chain --------------------------------------------
+ * Per params row the quantities the kernels derive from it -- the derivation of the setup and backward kernels, run on the
+ * device for all 11 ids that have modes -- and their statistics over the rows pushed: count, mean, standard deviation,
+ * minimum, maximum, exact quantiles.  The spectrum plays no part.
+ *   Columns, a function of the context's layout alone (tamcmc_modetable_column describes each):
+ *     chain level, first:   inclination (degrees, 0 where the model has none), eta, a3, asymmetry
+ *     per multiplet j = 0 ... n_mult - 1, in the chain's table order, l its degree:
+ *       freq, width, height (= sum of the h_m, added in the order m = -l ... l), amplitude (= sqrt((pi height) width), the
+ *       reference's H = A^2 / (pi Gamma)), splitting (exactly 0 for l = 0), window_lo, window_hi (the truncation window
+ *       [lo, hi) in bins, as doubles), nu_m for m = -l ... l, h_m for m = -l ... l
+ *     n_cols = 4 + sum_j (7 + 2 (2 l_j + 1)).  A row describes the sample's mode spectrum completely: with the noise
+ *     parameters the model can be rebuilt from it.
+ *   tamcmc_modetable_col: mult = -1 (and order = l = -1) for chain-level columns; order = the radial index n of the
+ *     multiplet; m = 0 except on nu_m and h_m columns; param_index = the params index of the mode frequency on freq
+ *     columns (the column equals that entry bit for bit), -1 elsewhere.
+ *   Status of a sample: the largest status of its multiplets (an empty truncation window: TAMCMC_CHAIN_EMPTY_WINDOW), else
+ *     TAMCMC_CHAIN_NAN when any of its columns is a NaN, else TAMCMC_CHAIN_OK -- the code tamcmc_eval_batch gives a row whose
+ *     noise parameters are healthy.  A sample whose status is not OK, or whose entry of `skip` is not 0, enters neither the
+ *     statistics nor the table, and is counted in n_rejected.
+ *   create       max_samples >= 0 rows of the table are kept on the device for the quantiles: 8 max_samples n_cols bytes,
+ *                plus 8 B (Nparams + n_cols + 1) bytes for a block of B = min(4096, 2^23 / n_cols) samples and
+ *                128 n_cols + 64 bytes of state; TAMCMC_E_NOMEM when that fails.  max_samples = 0: statistics only.  Refused
+ *                with TAMCMC_E_INVALID: NULL arguments, max_samples < 0 or >= 2^31, a context of model id 0 or 1 (no
+ *                multiplets), a context with a batch in flight or armed.  tamcmc_ctx_destroy is refused while the object lives.
+ *   columns / column   the numbers of columns and multiplets; the description of column col (TAMCMC_E_INVALID out of range).
+ *   derive       the plain map: Nsamples x Nparams params rows -> Nsamples x n_cols rows (and status, which may be NULL), host
+ *                pointers; nothing is accumulated or stored.
+ *   push         derives the rows, folds the accepted ones into the statistics in push order and appends them to the table.
+ *                skip (Nsamples entries) and status may be NULL.  A push after which the table would hold more than
+ *                max_samples accepted rows (max_samples > 0) is refused whole with TAMCMC_E_INVALID: nothing changes, status
+ *                is not written.  No result bit depends on how the rows are cut into pushes.
+ *   result       totals and four arrays of n_cols doubles, any may be NULL; sd with n - 1, NaN for fewer than two samples (every
+ *                array NaN for none).
+ *   quantiles    Nq = 1 ... TAMCMC_SUMMARY_MAX_QUANTILES probabilities in [0, 1]; ranks (Nq, may be NULL) are those of numpy's
+ *                inverted_cdf: the smallest accepted sample whose empirical CDF reaches q; out[k * n_cols + col] is that order
+ *                statistic of column col itself, bit for bit (a zero comes back as +0).  TAMCMC_E_INVALID: no accepted sample,
+ *                max_samples = 0, Nq out of range, a q that is NaN or outside [0, 1].
+ *   reset        forgets every sample (and puts the kernel time back to zero).   destroy   NULL is fine.
+ *   kernel_time  summed milliseconds and launch count of the derive and fold kernels of the pushes since create or reset.
+ * Work goes on the context's stream; every entry point but _destroy is refused with TAMCMC_E_INVALID while the context has a
+ * batch in flight or armed (_destroy: armed), and NULL arguments and an Nparams mismatch before a device is touched. */
+#define TAMCMC_MODETABLE_INCLINATION 0
+#define TAMCMC_MODETABLE_ETA         1
+#define TAMCMC_MODETABLE_A3          2
+#define TAMCMC_MODETABLE_ASYMMETRY   3
+#define TAMCMC_MODETABLE_FREQ        4
+#define TAMCMC_MODETABLE_WIDTH       5
+#define TAMCMC_MODETABLE_HEIGHT      6
+#define TAMCMC_MODETABLE_AMPLITUDE   7
+#define TAMCMC_MODETABLE_SPLITTING   8
+#define TAMCMC_MODETABLE_WINDOW_LO   9
+#define TAMCMC_MODETABLE_WINDOW_HI  10
+#define TAMCMC_MODETABLE_NU_M       11
+#define TAMCMC_MODETABLE_H_M        12
+typedef struct tamcmc_modetable tamcmc_modetable;
+typedef struct {
+    int32_t kind, mult, order, l, m, param_index;
+} tamcmc_modetable_col;
+typedef struct {
+    int64_t n_used, n_rejected, n_cols, n_mult;
+} tamcmc_modetable_totals;
+int tamcmc_modetable_create(tamcmc_modetable **out, tamcmc_ctx *ctx, int64_t max_samples);
+int tamcmc_modetable_columns(tamcmc_modetable *mt, int32_t *n_cols, int32_t *n_mult);
+int tamcmc_modetable_column(tamcmc_modetable *mt, int32_t col, tamcmc_modetable_col *out);
+int tamcmc_modetable_derive(tamcmc_modetable *mt, int32_t Nsamples, int32_t Nparams, const double *params, double *rows,
+                            int32_t *status);
+int tamcmc_modetable_push(tamcmc_modetable *mt, int32_t Nsamples, int32_t Nparams, const double *params, const int32_t *skip,
+                          int32_t *status);
+int tamcmc_modetable_result(tamcmc_modetable *mt, tamcmc_modetable_totals *t, double *mean, double *sd, double *min, double *max);
+int tamcmc_modetable_quantiles(tamcmc_modetable *mt, int32_t Nq, const double *q, int64_t *ranks, double *out);
+int tamcmc_modetable_reset(tamcmc_modetable *mt);
+int tamcmc_modetable_destroy(tamcmc_modetable *mt);
+int tamcmc_modetable_kernel_time(tamcmc_modetable *mt, double *total_ms, int64_t *launches);
+
 /* Replaces: the `for chain` loop of generate_model() calls (MALA.cpp:632-639, model_def.cpp:139-143).
  * Host pointers, row-major.  Synchronous: results are valid on return.
  *   params      Nchains x Nparams

@@ -44,6 +44,9 @@ EXPORTS = [
     "tamcmc_scan_null_create", "tamcmc_scan_null_run", "tamcmc_scan_null_replicates", "tamcmc_scan_null_result",
     "tamcmc_scan_null_line", "tamcmc_scan_null_pvalue", "tamcmc_scan_null_variates", "tamcmc_scan_null_profile",
     "tamcmc_scan_null_kernel_time", "tamcmc_scan_null_destroy",
+    "tamcmc_modetable_create", "tamcmc_modetable_columns", "tamcmc_modetable_column", "tamcmc_modetable_derive",
+    "tamcmc_modetable_push", "tamcmc_modetable_result", "tamcmc_modetable_quantiles", "tamcmc_modetable_reset",
+    "tamcmc_modetable_destroy", "tamcmc_modetable_kernel_time",
 ]
 
 
@@ -117,6 +120,22 @@ class SummaryBandEssTotals(C.Structure):
     _fields_ = [("n_used", C.c_int64), ("n_rejected", C.c_int64), ("lag", C.c_int64), ("n_thresholds", C.c_int64),
                 ("min_ess", C.c_double * MAX_QUANTILES), ("bin_min_ess", C.c_int64 * MAX_QUANTILES),
                 ("n_truncated", C.c_int64 * MAX_QUANTILES), ("n_constant", C.c_int64 * MAX_QUANTILES)]
+
+
+class ModeTableCol(C.Structure):
+    """tamcmc_modetable_col"""
+    _fields_ = [("kind", C.c_int32), ("mult", C.c_int32), ("order", C.c_int32), ("l", C.c_int32), ("m", C.c_int32),
+                ("param_index", C.c_int32)]
+
+
+class ModeTableTotals(C.Structure):
+    """tamcmc_modetable_totals"""
+    _fields_ = [("n_used", C.c_int64), ("n_rejected", C.c_int64), ("n_cols", C.c_int64), ("n_mult", C.c_int64)]
+
+
+# TAMCMC_MODETABLE_* kind codes, in order
+MODETABLE_KINDS = ("inclination", "eta", "a3", "asymmetry", "freq", "width", "height", "amplitude", "splitting",
+                   "window_lo", "window_hi", "nu_m", "h_m")
 
 
 class AccelError(RuntimeError):
@@ -225,6 +244,16 @@ def load_library():
     lib.tamcmc_scan_null_profile.argtypes = [vp, C.c_int]
     lib.tamcmc_scan_null_kernel_time.argtypes = [vp, dp, lp]
     lib.tamcmc_scan_null_destroy.argtypes = [vp]
+    lib.tamcmc_modetable_create.argtypes = [C.POINTER(vp), vp, C.c_int64]
+    lib.tamcmc_modetable_columns.argtypes = [vp, ip, ip]
+    lib.tamcmc_modetable_column.argtypes = [vp, C.c_int32, C.POINTER(ModeTableCol)]
+    lib.tamcmc_modetable_derive.argtypes = [vp, C.c_int32, C.c_int32, dp, dp, ip]
+    lib.tamcmc_modetable_push.argtypes = [vp, C.c_int32, C.c_int32, dp, ip, ip]
+    lib.tamcmc_modetable_result.argtypes = [vp, C.POINTER(ModeTableTotals), dp, dp, dp, dp]
+    lib.tamcmc_modetable_quantiles.argtypes = [vp, C.c_int32, dp, lp, dp]
+    lib.tamcmc_modetable_reset.argtypes = [vp]
+    lib.tamcmc_modetable_destroy.argtypes = [vp]
+    lib.tamcmc_modetable_kernel_time.argtypes = [vp, dp, lp]
     for name in EXPORTS:
         fn = getattr(lib, name)
         if fn.restype is not C.c_char_p:
@@ -1144,6 +1173,120 @@ class ScanNull:
         if getattr(self, "_h", None) is not None and self._h.value:
             self._check(self._lib.tamcmc_scan_null_destroy(self._h), "tamcmc_scan_null_destroy")
             self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
+class ModeTable:
+    """The posterior mode table (tamcmc_accel.h, tamcmc_modetable_*): per params row the derived quantities of every
+    multiplet and of the chain -- frequency, width, height, amplitude, splitting, truncation window, component frequencies
+    and heights; inclination, eta, a3, asymmetry -- produced on the device by the derivation the kernels use, and their
+    statistics over the rows pushed: count, mean, sd, min, max, and with max_samples > 0 (rows of the table kept on the
+    device) exact quantiles.  No result bit depends on how the rows are split over pushes.  The Accel cannot be closed
+    while the table is open."""
+
+    KINDS = MODETABLE_KINDS
+    ARRAYS = ("mean", "sd", "min", "max")
+    COL_DTYPE = np.dtype([("kind", np.int32), ("mult", np.int32), ("order", np.int32), ("l", np.int32), ("m", np.int32),
+                          ("param_index", np.int32)])
+
+    def __init__(self, accel, max_samples=0):
+        self._lib = load_library()
+        self.accel = accel
+        self._mt = C.c_void_p()
+        self._check(self._lib.tamcmc_modetable_create(C.byref(self._mt), accel._ctx, int(max_samples)), "tamcmc_modetable_create")
+        nc, nm = C.c_int32(0), C.c_int32(0)
+        self._check(self._lib.tamcmc_modetable_columns(self._mt, C.byref(nc), C.byref(nm)), "tamcmc_modetable_columns")
+        self.n_cols, self.n_mult = int(nc.value), int(nm.value)
+        self.max_samples = int(max_samples)
+
+    _check = Accel._check
+
+    def columns(self):
+        """Structured array (kind, mult, order, l, m, param_index) of the n_cols columns; KINDS[kind] is the kind's name."""
+        out = np.zeros(self.n_cols, dtype=self.COL_DTYPE)
+        c = ModeTableCol()
+        for k in range(self.n_cols):
+            self._check(self._lib.tamcmc_modetable_column(self._mt, k, C.byref(c)), "tamcmc_modetable_column")
+            out[k] = (c.kind, c.mult, c.order, c.l, c.m, c.param_index)
+        return out
+
+    def _params(self, params):
+        params = _c64(params)
+        if params.ndim != 2 or params.shape[1] != self.accel.Nparams:
+            raise ValueError(f"params must be (Nsamples, {self.accel.Nparams})")
+        return params
+
+    def derive(self, params):
+        """The plain map: (rows (n, n_cols), status (n)) of the params rows; nothing is accumulated."""
+        params = self._params(params)
+        n = params.shape[0]
+        rows = np.empty((n, self.n_cols))
+        status = np.empty(n, dtype=np.int32)
+        self._check(self._lib.tamcmc_modetable_derive(self._mt, n, self.accel.Nparams, _dptr(params), _dptr(rows), _iptr(status)),
+                    "tamcmc_modetable_derive")
+        return rows, status
+
+    def push(self, params, skip=None):
+        """Derives the rows and folds the accepted ones (status 0, skip entry 0) into the statistics and the table.  Returns
+        the status codes."""
+        params = self._params(params)
+        n = params.shape[0]
+        sk = None
+        if skip is not None:
+            sk = np.ascontiguousarray(skip, dtype=np.int32)
+            if sk.shape != (n,):
+                raise ValueError(f"skip must have {n} entries")
+        status = np.empty(n, dtype=np.int32)
+        self._check(self._lib.tamcmc_modetable_push(self._mt, n, self.accel.Nparams, _dptr(params), _iptr(sk), _iptr(status)),
+                    "tamcmc_modetable_push")
+        return status
+
+    def result(self):
+        """dict: mean, sd, min, max (n_cols doubles) and the totals n_used, n_rejected, n_cols, n_mult."""
+        out = {k: np.empty(self.n_cols) for k in self.ARRAYS}
+        t = ModeTableTotals()
+        self._check(self._lib.tamcmc_modetable_result(self._mt, C.byref(t), *[_dptr(out[k]) for k in self.ARRAYS]),
+                    "tamcmc_modetable_result")
+        out.update(n_used=int(t.n_used), n_rejected=int(t.n_rejected), n_cols=int(t.n_cols), n_mult=int(t.n_mult))
+        return out
+
+    def quantiles(self, q):
+        """dict: q, ranks (Nq int64) and values (Nq, n_cols): the exact order statistics of every column over the accepted
+        rows, by numpy's inverted_cdf rule."""
+        q = _c64(np.atleast_1d(q))
+        if q.ndim != 1:
+            raise ValueError("q must be a sequence of probabilities")
+        ranks = np.zeros(max(q.size, 1), dtype=np.int64)
+        values = np.empty((max(q.size, 1), self.n_cols))
+        self._check(self._lib.tamcmc_modetable_quantiles(self._mt, q.size, _dptr(q), ranks.ctypes.data_as(C.POINTER(C.c_int64)),
+                                                         _dptr(values)), "tamcmc_modetable_quantiles")
+        return dict(q=q.copy(), ranks=ranks[:q.size], values=values[:q.size])
+
+    def reset(self):
+        self._check(self._lib.tamcmc_modetable_reset(self._mt), "tamcmc_modetable_reset")
+
+    def kernel_time(self):
+        """(summed milliseconds, launches) of the derive and fold kernels since the object was created or reset."""
+        ms = C.c_double(0.0)
+        n = C.c_int64(0)
+        self._check(self._lib.tamcmc_modetable_kernel_time(self._mt, C.byref(ms), C.byref(n)), "tamcmc_modetable_kernel_time")
+        return ms.value, n.value
+
+    def close(self):
+        if getattr(self, "_mt", None) is not None and self._mt.value:
+            self._check(self._lib.tamcmc_modetable_destroy(self._mt), "tamcmc_modetable_destroy")
+            self._mt = C.c_void_p()
 
     def __del__(self):
         try:

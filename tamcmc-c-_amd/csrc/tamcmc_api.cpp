@@ -292,6 +292,7 @@ extern "C" int tamcmc_ctx_destroy(tamcmc_ctx *c)
     if (!c) return TAMCMC_OK;
     if (c->groups > 0) return TAMCMC_E_INVALID;     // a fit group still refers to it: destroy the group first
     if (c->summaries > 0) return TAMCMC_E_INVALID;  // and so does a summary object
+    if (c->modetables > 0) return TAMCMC_E_INVALID; // or a mode table
     (void)hipSetDevice(c->device);
     if (c->armed && gate_word(c)) { __atomic_store_n(gate_word(c), c->gate_seq, __ATOMIC_RELEASE); c->armed = 0; }   // let the gate go
     if (c->stream) (void)tm_ctx_stream_sync(c);

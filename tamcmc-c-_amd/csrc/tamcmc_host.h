@@ -167,6 +167,7 @@ struct tamcmc_ctx {
     TmTimer timer;
     int groups = 0;               // fit groups this context is a member of (tamcmc_group_create); destroy is refused meanwhile
     int summaries = 0;            // summary objects bound to this context (tamcmc_summary_create); destroy is refused meanwhile
+    int modetables = 0;           // mode tables bound to this context (tamcmc_modetable_create), counted like the groups
     // ordering against fit groups (tamcmc_group_eval_begin): enq_seq counts what this library put on the stream, so that a
     // group can tell whether anything came since it last ordered itself against it; after_ev is a group's "launches done"
     // event this stream has still to wait for -- the wait is enqueued by the next use of the stream (tm_ctx_settle), not by

@@ -5,7 +5,7 @@
 //                    [--chain m] [--slice s] [--first i] [--last j] [--thin k] [--block B]
 //                    [--quantiles q1,q2,...] [--qbits b] [--loo] [--predictive] [--window W[,first]] [--ess [L]]
 //                    [--scan W0[,W1,...]] [--scan-below T] [--scan-null R[,seed]] [--band-ess [L]] [--loo-pit]
-//                    [--loo-window W[,first]]
+//                    [--loo-window W[,first]] [--modes [q1,q2,...]]
 //
 // <config dir> is the reference's Config/default; model id, likelihood, p, plength, the inputs row and the relax mask
 // come from the setup it describes (tamcmc_setup_create / tamcmc_setup_load, slice s counted from 0).  The samples are
@@ -74,6 +74,12 @@
 // `# quantiles= q1,q2,...`, `# n_used= ...  n_rejected= ...  lag= ...`, per quantile `# q= ...  min_ess= ...  bin_min_ess= ...
 // n_truncated= ...  n_constant= ...` -- then one row per bin, x and per quantile seven columns:
 //   value  count_le  p_hat  ess  tau  mcse_p  cut
+// With --modes [q1,q2,...] the selected samples are read once more for the posterior mode table (tamcmc_modetable_*): the
+// derived quantities of every multiplet and of the chain, their mean, sd, minimum, maximum and exact quantiles (default
+// 0.16,0.5,0.84) over the samples the fold used.  The output file keeps every byte; the results go to <output file>.modes:
+// `#` header lines -- the version, `# quantiles= q1,q2,...`, `# n_used= ...  n_rejected= ...  n_cols= ...  n_mult= ...` (the
+// samples the fold skipped are counted among the rejected) and the column names -- then one row per quantity:
+//   col  kind  mult  order  l  m  param_index  mean  sd  min  max  [one column per quantile]        (17 significant digits)
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -91,7 +97,7 @@ static int usage()
                     "                         [--chain m] [--slice s] [--first i] [--last j] [--thin k] [--block B]\n"
                     "                         [--quantiles q1,q2,...] [--qbits b] [--loo] [--predictive] [--window W[,first]] [--ess [L]]\n"
                     "                         [--scan W0[,W1,...]] [--scan-below T] [--scan-null R[,seed]] [--band-ess [L]] [--loo-pit]\n"
-                    "                         [--loo-window W[,first]]\n"
+                    "                         [--loo-window W[,first]] [--modes [q1,q2,...]]\n"
                     "     [1] The directory of config_default.cfg, errors_default.cfg and the *_ctrl.list files (Config/default)\n"
                     "     [2] The .model file and [3] the .data file of the fit\n"
                     "     [4] The root of the parameter files: <root>_chain-<m>.bin and <root>.hdr\n"
@@ -133,6 +139,12 @@ static int usage()
                     "             first_bin last_bin x_first x_last elpd_lwo pareto_k tail_len, and with --loo-pit (likelihood p times W at\n"
                     "             most 512) loo_pit loo_log_cdf loo_log_sf is_ess log_wsum as well (the samples are read once more, with\n"
                     "             --loo-pit twice; [5] and the other files are unchanged)\n"
+                    "     --modes [q1,q2,...]   the posterior mode table: per derived quantity of every multiplet and of the chain (frequency,\n"
+                    "             width, height, amplitude, splitting, truncation window, component frequencies and heights; inclination,\n"
+                    "             eta, a3, asymmetry) its mean, sd, min, max and exact quantiles (up to 8 values in [0, 1], default\n"
+                    "             0.16,0.5,0.84) over the samples the summary used: written to <output file>.modes, one row per quantity,\n"
+                    "             col kind mult order l m param_index mean sd min max and one column per quantile, 17 significant digits\n"
+                    "             (the samples are read once more; [5] and the other files are unchanged)\n"
                     " chainsummary_hip version   prints the library version\n");
     return EXIT_FAILURE;
 }
@@ -173,6 +185,9 @@ int main(int argc, char *argv[])
     long win_W = 0, win_first = 0, ess_lag = -1;            // ess_lag < 0: no --ess
     long band_lag = -1;                                     // < 0: no --band-ess
     long lw_W = 0, lw_first = 0;                            // lw_W = 0: no --loo-window
+    bool modes = false;                                     // --modes
+    std::vector<double> mquant;
+    std::string mquant_text = "0.16,0.5,0.84";
     std::vector<int32_t> scan_W;
     std::string scan_text;
     double scan_below = std::nan("");                       // NaN: the library's default line per width
@@ -192,6 +207,21 @@ int main(int argc, char *argv[])
                 char *end = nullptr;
                 ess_lag = strtol(argv[++i], &end, 10);
                 if (*end != '\0' || ess_lag > TAMCMC_SUMMARY_ESS_MAX_LAG) return usage();
+            }
+            continue;
+        }
+        if (a == "--modes") {                       // alone, or followed by the list of quantiles
+            if (modes) return usage();
+            modes = true;
+            if (i + 1 < argc && ((argv[i + 1][0] >= '0' && argv[i + 1][0] <= '9') || argv[i + 1][0] == '.')) mquant_text = argv[++i];
+            for (const char *p = mquant_text.c_str();;) {
+                char *end = nullptr;
+                const double q = strtod(p, &end);
+                if (end == p || !(q >= 0.0 && q <= 1.0) || mquant.size() >= TAMCMC_SUMMARY_MAX_QUANTILES) return usage();
+                mquant.push_back(q);
+                if (*end == '\0') break;
+                if (*end != ',') return usage();
+                p = end + 1;
             }
             continue;
         }
@@ -354,6 +384,11 @@ int main(int argc, char *argv[])
     const long long chunk = 4096;
     std::vector<double> vars((size_t)Nvars), P;
     long long last_used = first;
+    // --modes: the status of every selected sample in the fold pass (what the fold skipped the mode table skips), and,
+    // while mt_push is set, the pass that feeds the mode table instead of the summary
+    std::vector<int32_t> fold_status(modes ? (size_t)Nsel : 0), mt_skip;
+    bool fold_pass = true;
+    tamcmc_modetable *mt_push = nullptr;
     auto push_selected = [&]() -> int {
         for (long long k0 = 0; k0 < Nsel; k0 += chunk) {
             const long long n = Nsel - k0 < chunk ? Nsel - k0 : chunk;
@@ -367,12 +402,19 @@ int main(int argc, char *argv[])
                 std::memcpy(row, inputs.data(), (size_t)Nparams * sizeof(double));
                 for (int32_t v = 0; v < Nvars; v++) row[idx[(size_t)v]] = vars[(size_t)v];
             }
-            rc = tamcmc_summary_push(sum, (int32_t)n, Nparams, P.data(), nullptr, nullptr);
+            if (mt_push) {
+                mt_skip.assign(fold_status.begin() + k0, fold_status.begin() + k0 + n);
+                rc = tamcmc_modetable_push(mt_push, (int32_t)n, Nparams, P.data(), mt_skip.data(), nullptr);
+                if (rc != TAMCMC_OK) return fail(std::string("tamcmc_modetable_push: ") + tamcmc_strerror(rc) + " " + tamcmc_last_hip_error());
+                continue;
+            }
+            rc = tamcmc_summary_push(sum, (int32_t)n, Nparams, P.data(), nullptr, modes && fold_pass ? fold_status.data() + k0 : nullptr);
             if (rc != TAMCMC_OK) return fail(std::string("tamcmc_summary_push: ") + tamcmc_strerror(rc) + " " + tamcmc_last_hip_error());
         }
         return 0;
     };
     if (push_selected() != 0) return EXIT_FAILURE;
+    fold_pass = false;
     tamcmc_summary_totals t;
     std::vector<double> mean_M(Nx), var_M(Nx), min_M(Nx), max_M(Nx), var_l(Nx), lppd(Nx);
     rc = tamcmc_summary_result(sum, &t, mean_M.data(), var_M.data(), min_M.data(), max_M.data(), nullptr, var_l.data(), lppd.data());
@@ -523,6 +565,32 @@ int main(int argc, char *argv[])
         tamcmc_summary_ess_end(sum);
     }
     tamcmc_summary_destroy(sum);
+    // the mode table: the same samples once more; those the fold skipped are skipped
+    tamcmc_modetable_totals mtt{};
+    std::vector<tamcmc_modetable_col> m_col;
+    std::vector<double> m_mean, m_sd, m_min, m_max, m_q;
+    if (modes) {
+        auto mfail = [&](const char *what) { return fail(std::string(what) + ": " + tamcmc_strerror(rc) + " " + tamcmc_last_hip_error()); };
+        tamcmc_modetable *mt = nullptr;
+        rc = tamcmc_modetable_create(&mt, ctx, (int64_t)Nsel);
+        if (rc != TAMCMC_OK) return mfail("tamcmc_modetable_create");
+        int32_t n_cols = 0, n_mult = 0;
+        tamcmc_modetable_columns(mt, &n_cols, &n_mult);
+        const size_t nc = (size_t)n_cols;
+        m_col.resize(nc); m_mean.resize(nc); m_sd.resize(nc); m_min.resize(nc); m_max.resize(nc);
+        m_q.assign(mquant.size() * nc, std::nan(""));
+        for (int32_t k = 0; k < n_cols; k++) tamcmc_modetable_column(mt, k, &m_col[(size_t)k]);
+        mt_push = mt;
+        if (push_selected() != 0) return EXIT_FAILURE;
+        mt_push = nullptr;
+        rc = tamcmc_modetable_result(mt, &mtt, m_mean.data(), m_sd.data(), m_min.data(), m_max.data());
+        if (rc != TAMCMC_OK) return mfail("tamcmc_modetable_result");
+        if (mtt.n_used > 0) {
+            rc = tamcmc_modetable_quantiles(mt, (int32_t)mquant.size(), mquant.data(), nullptr, m_q.data());
+            if (rc != TAMCMC_OK) return mfail("tamcmc_modetable_quantiles");
+        }
+        tamcmc_modetable_destroy(mt);
+    }
     tamcmc_ctx_destroy(ctx);
 
     FILE *o = fopen(out_file.c_str(), "w");
@@ -708,6 +776,28 @@ int main(int argc, char *argv[])
             fprintf(ob, "\n");
         }
         fclose(ob);
+    }
+    if (modes) {
+        static const char *const kind_name[] = {"inclination", "eta", "a3", "asymmetry", "freq", "width", "height", "amplitude", "splitting",
+                                                "window_lo", "window_hi", "nu_m", "h_m"};
+        const std::string modes_file = out_file + ".modes";
+        FILE *om = fopen(modes_file.c_str(), "w");
+        if (!om) return fail("unable to open the output file " + modes_file);
+        fprintf(om, "# chainsummary_hip (%s)\n", tamcmc_version());
+        fprintf(om, "# quantiles= %s\n", mquant_text.c_str());
+        fprintf(om, "# n_used= %lld  n_rejected= %lld  n_cols= %lld  n_mult= %lld\n", (long long)mtt.n_used, (long long)mtt.n_rejected,
+                (long long)mtt.n_cols, (long long)mtt.n_mult);
+        fprintf(om, "# col kind mult order l m param_index mean sd min max");
+        for (size_t j = 0; j < mquant.size(); j++) fprintf(om, " q%.6g", mquant[j]);
+        fprintf(om, "\n");
+        for (size_t k = 0; k < m_col.size(); k++) {
+            const tamcmc_modetable_col &c = m_col[k];
+            fprintf(om, "%zu %s %d %d %d %d %d %.17g %.17g %.17g %.17g", k, kind_name[c.kind], (int)c.mult, (int)c.order, (int)c.l, (int)c.m,
+                    (int)c.param_index, m_mean[k], m_sd[k], m_min[k], m_max[k]);
+            for (size_t j = 0; j < mquant.size(); j++) fprintf(om, " %.17g", m_q[j * m_col.size() + k]);
+            fprintf(om, "\n");
+        }
+        fclose(om);
     }
     printf("Summary of %lld samples (%lld rejected) written to %s\n", (long long)t.n_used, (long long)t.n_rejected, out_file.c_str());
     return 0;

@@ -58,6 +58,12 @@ Prints one JSON line:
                             (Summary.wloo_pit_kernel_time) -- beside the per-bin LOO tail kernel and the per-bin LOO-PIT kernel
                             of the same rows, the finalize and prepare kernels over the windows, and the device memory the mode
                             and its sub-mode allocate.  Only this leg runs.
+  n_modetable_*             with --modes: the posterior mode table (tamcmc_amd.ModeTable) of the same rows, no spectrum involved:
+                            ModeTable.push on the host clock (seconds per 1000 samples, staging and the per-block status
+                            round trip included), the derive and fold kernels alone from the object's HIP events
+                            (ModeTable.kernel_time: microseconds per sample, launches), the quantile call for three
+                            probabilities on the host clock (--quantiles sets their number), the number of columns and the
+                            device memory of the table.  Only this leg runs.
 Every timed shape is warmed up first (--warmup pushes); host clocks stop after calls that end in a device synchronise.
 """
 import argparse
@@ -443,6 +449,39 @@ def wloo_leg(a, w, y, P):
     return out
 
 
+def modetable_leg(a, w, P):
+    """(n) the mode table: push on the host clock, the derive and fold kernels alone, the quantile call."""
+    out = {}
+    q = [0.16, 0.5, 0.84, 0.025, 0.975, 0.0, 1.0, 0.25][:a.quantiles]
+    with tamcmc_amd.Accel(2, w["plength"], w["x"], np.ones(a.nx)) as acc:
+        with tamcmc_amd.ModeTable(acc, a.samples) as mt:
+            push, kern, quant = [], [], []
+            for k in range(a.warmup + a.steps):
+                mt.reset()
+                acc.synchronize()
+                t0 = time.perf_counter()
+                mt.push(P)                                  # synchronous
+                t1 = time.perf_counter()
+                ms, launches = mt.kernel_time()
+                t2 = time.perf_counter()
+                r = mt.quantiles(q)                         # synchronous
+                t3 = time.perf_counter()
+                if k >= a.warmup:
+                    push.append(t1 - t0); kern.append(ms); quant.append(t3 - t2)
+            res = mt.result()
+            out.update(n_modetable_cols=mt.n_cols, n_modetable_mult=mt.n_mult, n_modetable_launches=launches,
+                       n_modetable_push_s_per_1000=float(np.median(push)) * 1000.0 / a.samples,
+                       n_modetable_push_spread=[float(min(push)) * 1000.0 / a.samples, float(max(push)) * 1000.0 / a.samples],
+                       n_modetable_kernels_us_per_sample=float(np.median(kern)) * 1e3 / a.samples,
+                       n_modetable_kernels_spread_us=[float(min(kern)) * 1e3 / a.samples, float(max(kern)) * 1e3 / a.samples],
+                       n_modetable_Nq=len(q), n_modetable_quantiles_call_ms=float(np.median(quant)) * 1e3,
+                       n_modetable_quantiles_spread_ms=[float(min(quant)) * 1e3, float(max(quant)) * 1e3],
+                       n_modetable_table_bytes=8 * a.samples * mt.n_cols,
+                       n_modetable_first_freq_quantiles=[float(v) for v in r["values"][:, 4]],
+                       n_used=res["n_used"], n_rejected=res["n_rejected"])
+    return out
+
+
 def bandess_leg(a, w, y, P):
     """(k) the fold pass beside the band ESS pass of the same rows, and the kernels' own times."""
     out = {}
@@ -525,6 +564,7 @@ def main():
     ap.add_argument("--scan", default="", help="W0[,W1,...]: strictly ascending widths of the sliding-window scan")
     ap.add_argument("--ess", type=int, default=-1)
     ap.add_argument("--band-ess", type=int, default=-1, help="L: the band ESS pass at --quantiles thresholds (0: the library's lag limit)")
+    ap.add_argument("--modes", action="store_true", help="the posterior mode table: push, the derive and fold kernels, the quantile call")
     ap.add_argument("--scan-null", type=int, default=0, help="R: replicates per run of the scan's Monte-Carlo null (widths of --scan)")
     a = ap.parse_args()
     if a.steps < 1 or a.warmup < 0 or a.samples < 1 or a.samples_b < 2 or a.scan_null < 0:
@@ -536,6 +576,11 @@ def main():
         return
     w = synth.workload_c2(Nx=a.nx)
     P = synth.chain_params(w, a.samples)
+    if a.modes:
+        out = dict(tool="summary_time", Nx=a.nx, samples=a.samples, steps=a.steps, warmup=a.warmup, version=tamcmc_amd.capi.version())
+        out.update(modetable_leg(a, w, P))
+        print(json.dumps(out))
+        return
     with tamcmc_amd.Accel(2, w["plength"], w["x"], np.ones(a.nx)) as acc:
         m_true, st = acc.model_explicit(w["params_true"])
     assert st == 0
