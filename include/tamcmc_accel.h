@@ -875,6 +875,61 @@ int tamcmc_modetable_reset(tamcmc_modetable *mt);
 int tamcmc_modetable_destroy(tamcmc_modetable *mt);
 int tamcmc_modetable_kernel_time(tamcmc_modetable *mt, double *total_ms, int64_t *launches);
 
+/* ---- Mode table diagnostics: ESS, MCSE, split R-hat and correlations of its columns ---------------------------------
+ * Each call works on the accepted rows a mode table created with max_samples > 0 holds on the device; the caller makes no
+ * second pass over the chain, and nothing of the table's state is written (result and quantiles return the same bits
+ * before and after).  n = n_used; v_t = column c of the t-th accepted row in push order, t = 0 ... n - 1 (rejected and
+ * skipped samples are not in the table and do not advance t).
+ *   ESS, MCSE, R-hat of column c: steps 1-6 of "EFFECTIVE SAMPLE SIZE" above, applied to a column instead of a bin.
+ *     1  d_t = v_t - mean_c, mean_c the double tamcmc_modetable_result returns; one subtraction, never contracted.
+ *     2  L = the largest odd number <= min(max_lag | 1, n - 1); max_lag = 0 ... TAMCMC_MODEDIAG_MAX_LAG, 0 meaning 255.
+ *     3  A_k = sum_{t=k}^{n-1} d_t d_{t-k}, k = 0 ... L: one accumulator per (column, k), started at +0.0 and advanced in
+ *        ascending t by A = fma(d_t, d_{t-k}, A).  No (column, lag) sum is split over threads; no atomics.
+ *     4  Geyer's initial monotone sequence as stated there (rho_k = A_k / A_0, P_m = rho_2m + rho_2m+1, ...), with
+ *        tau_floor = 1 / log10(n) formed on the host: tau, ess = n / tau, cut (cut = L + 1: truncated).  A_0 zero or not finite:
+ *        tau = ess = NaN, cut = 0.  A constant column (splitting at l = 0, inclination where the model has none, a window
+ *        edge that never moves) centres to exact zeros -- Welford's mean of equal values is that value -- so A_0 = 0, and
+ *        n_constant counts it.
+ *     5  split R-hat: h = floor(n / 2), the halves [0, h) and [n - h, n), each by the Welford recurrence over d_t in t order
+ *        (the centred values of step 1: R-hat does not change with the shift, and the recurrence's mean update then rounds
+ *        at the size of the column's spread instead of its value), then
+ *        W = (s1^2 + s2^2) / 2, Bn = (m1 - mb)^2 + (m2 - mb)^2, rhat = sqrt(((h - 1) / h W + Bn) / W); W = 0: NaN.
+ *     6  mcse = sd / sqrt(ess), sd the double tamcmc_modetable_result returns; NaN where ess is NaN.
+ *     7  totals, in column order (the first column wins a tie, a NaN is skipped): n_used, lag = L, min_ess with col_min_ess
+ *        (NaN and -1 if every value is a NaN), max_rhat with col_max_rhat likewise, n_truncated (cut = L + 1), n_constant
+ *        (A_0 = 0), n_rhat_high (rhat > 1.01).
+ *   Covariance of columns i, j: S_ij = sum_t d_{i,t} d_{j,t} from +0.0 in ascending t by S = fma(d_{i,t}, d_{j,t}, S), d as in
+ *     step 1; cov_ij = S_ij / (double)(n - 1).  cov is symmetric bit for bit, and S_ii is A_0 of the same column bit for bit.
+ *   Correlation, on the host without contraction: r_ij = cov_ij / (sqrt(cov_ii) sqrt(cov_jj)) clamped to [-1, 1]; r_ii = 1.0
+ *     exactly where cov_ii > 0 and finite; r_ij = NaN where either variance is 0 or not finite.
+ *   ess          five arrays of n_cols entries and the totals, any may be NULL.  The lag products and the results stay on the
+ *                device: 8 (L + 4) n_cols + 4 n_cols bytes, allocated at the first call, reallocated only when L grows, freed
+ *                by tamcmc_modetable_destroy; TAMCMC_E_NOMEM leaves the object as it was.
+ *   acov         the (L + 1) x n_cols lag products of the last _ess call, A_k of column c at acov[k * n_cols + c]; refused when
+ *                there was no _ess call since the last push or reset.
+ *   cov / corr   n_sel x n_sel doubles of the columns cols[0 ... n_sel - 1], in that order (cols NULL: the first n_sel
+ *                columns); 8 n_sel^2 + 4 n_sel bytes on the device, allocated at the first call, reallocated only when n_sel
+ *                grows.
+ *   kernel_time  summed milliseconds and launch count of the lag, finish and covariance kernels since create or reset
+ *                (tamcmc_modetable_reset puts it back to zero).
+ * All calls are synchronous, on the context's stream.  Refused with TAMCMC_E_INVALID, before a device is touched: a NULL
+ * handle, a context with a batch in flight or armed, max_samples = 0, n < 4 (_ess, _acov) or n < 2 (_cov, _corr), max_lag
+ * outside 0 ... 1023, n_sel outside 1 ... min(n_cols, TAMCMC_MODEDIAG_MAX_COLS), a column index out of range or repeated, a
+ * NULL acov, cov or corr. */
+#define TAMCMC_MODEDIAG_MAX_LAG 1023
+#define TAMCMC_MODEDIAG_MAX_COLS 1024
+typedef struct {
+    int64_t n_used, lag;
+    double  min_ess, max_rhat;
+    int64_t col_min_ess, col_max_rhat, n_truncated, n_constant, n_rhat_high;
+} tamcmc_modediag_totals;
+int tamcmc_modediag_ess(tamcmc_modetable *mt, int32_t max_lag, tamcmc_modediag_totals *totals,
+                        double *ess, double *tau, double *mcse, double *rhat, int32_t *cut);
+int tamcmc_modediag_acov(tamcmc_modetable *mt, double *acov);
+int tamcmc_modediag_cov(tamcmc_modetable *mt, int32_t n_sel, const int32_t *cols, double *cov);
+int tamcmc_modediag_corr(tamcmc_modetable *mt, int32_t n_sel, const int32_t *cols, double *corr);
+int tamcmc_modediag_kernel_time(tamcmc_modetable *mt, double *total_ms, int64_t *launches);
+
 /* Replaces: the `for chain` loop of generate_model() calls (MALA.cpp:632-639, model_def.cpp:139-143).
  * Host pointers, row-major.  Synchronous: results are valid on return.
  *   params      Nchains x Nparams

@@ -47,6 +47,7 @@ EXPORTS = [
     "tamcmc_modetable_create", "tamcmc_modetable_columns", "tamcmc_modetable_column", "tamcmc_modetable_derive",
     "tamcmc_modetable_push", "tamcmc_modetable_result", "tamcmc_modetable_quantiles", "tamcmc_modetable_reset",
     "tamcmc_modetable_destroy", "tamcmc_modetable_kernel_time",
+    "tamcmc_modediag_ess", "tamcmc_modediag_acov", "tamcmc_modediag_cov", "tamcmc_modediag_corr", "tamcmc_modediag_kernel_time",
 ]
 
 
@@ -132,6 +133,16 @@ class ModeTableTotals(C.Structure):
     """tamcmc_modetable_totals"""
     _fields_ = [("n_used", C.c_int64), ("n_rejected", C.c_int64), ("n_cols", C.c_int64), ("n_mult", C.c_int64)]
 
+
+class ModeDiagTotals(C.Structure):
+    """tamcmc_modediag_totals"""
+    _fields_ = [("n_used", C.c_int64), ("lag", C.c_int64), ("min_ess", C.c_double), ("max_rhat", C.c_double),
+                ("col_min_ess", C.c_int64), ("col_max_rhat", C.c_int64), ("n_truncated", C.c_int64), ("n_constant", C.c_int64),
+                ("n_rhat_high", C.c_int64)]
+
+
+MODEDIAG_MAX_LAG = 1023     # TAMCMC_MODEDIAG_MAX_LAG
+MODEDIAG_MAX_COLS = 1024    # TAMCMC_MODEDIAG_MAX_COLS
 
 # TAMCMC_MODETABLE_* kind codes, in order
 MODETABLE_KINDS = ("inclination", "eta", "a3", "asymmetry", "freq", "width", "height", "amplitude", "splitting",
@@ -254,6 +265,11 @@ def load_library():
     lib.tamcmc_modetable_reset.argtypes = [vp]
     lib.tamcmc_modetable_destroy.argtypes = [vp]
     lib.tamcmc_modetable_kernel_time.argtypes = [vp, dp, lp]
+    lib.tamcmc_modediag_ess.argtypes = [vp, C.c_int32, C.POINTER(ModeDiagTotals), dp, dp, dp, dp, ip]
+    lib.tamcmc_modediag_acov.argtypes = [vp, dp]
+    lib.tamcmc_modediag_cov.argtypes = [vp, C.c_int32, ip, dp]
+    lib.tamcmc_modediag_corr.argtypes = [vp, C.c_int32, ip, dp]
+    lib.tamcmc_modediag_kernel_time.argtypes = [vp, dp, lp]
     for name in EXPORTS:
         fn = getattr(lib, name)
         if fn.restype is not C.c_char_p:
@@ -1281,6 +1297,56 @@ class ModeTable:
         ms = C.c_double(0.0)
         n = C.c_int64(0)
         self._check(self._lib.tamcmc_modetable_kernel_time(self._mt, C.byref(ms), C.byref(n)), "tamcmc_modetable_kernel_time")
+        return ms.value, n.value
+
+    DIAG_ARRAYS = ("ess", "tau", "mcse", "rhat")
+
+    def ess(self, max_lag=0):
+        """dict: ess, tau, mcse, rhat (n_cols doubles) and cut (n_cols int32) of every column over the accepted rows in the
+        table (max_samples > 0, at least 4 rows), from the autocorrelation up to lag max_lag (0 ... 1023, 0: 255), and the
+        totals n_used, lag, min_ess, col_min_ess, max_rhat, col_max_rhat, n_truncated, n_constant, n_rhat_high."""
+        out = {k: np.empty(self.n_cols) for k in self.DIAG_ARRAYS}
+        out["cut"] = np.empty(self.n_cols, dtype=np.int32)
+        t = ModeDiagTotals()
+        self._check(self._lib.tamcmc_modediag_ess(self._mt, int(max_lag), C.byref(t), *[_dptr(out[k]) for k in self.DIAG_ARRAYS],
+                                                  _iptr(out["cut"])), "tamcmc_modediag_ess")
+        out.update(n_used=int(t.n_used), lag=int(t.lag), min_ess=float(t.min_ess), col_min_ess=int(t.col_min_ess),
+                   max_rhat=float(t.max_rhat), col_max_rhat=int(t.col_max_rhat), n_truncated=int(t.n_truncated),
+                   n_constant=int(t.n_constant), n_rhat_high=int(t.n_rhat_high))
+        self._diag_lag = int(t.lag)
+        return out
+
+    def acov(self):
+        """(L + 1, n_cols): the lag products A_k of the last ess() call (refused after a push or a reset)."""
+        out = np.empty((getattr(self, "_diag_lag", 0) + 1, self.n_cols))
+        self._check(self._lib.tamcmc_modediag_acov(self._mt, _dptr(out)), "tamcmc_modediag_acov")
+        return out
+
+    def _between(self, fn, name, cols):
+        if cols is None:
+            n_sel, sel = self.n_cols, None          # (more than 1024 columns: the library refuses)
+        else:
+            sel = np.ascontiguousarray(cols, dtype=np.int32)
+            if sel.ndim != 1:
+                raise ValueError("cols must be a sequence of column indices")
+            n_sel = sel.size
+        out = np.empty((max(n_sel, 1), max(n_sel, 1)))
+        self._check(fn(self._mt, n_sel, _iptr(sel), _dptr(out)), name)
+        return out
+
+    def cov(self, cols=None):
+        """(n_sel, n_sel) covariances (n - 1) of the columns `cols`, in that order; None: all columns (at most 1024)."""
+        return self._between(self._lib.tamcmc_modediag_cov, "tamcmc_modediag_cov", cols)
+
+    def corr(self, cols=None):
+        """(n_sel, n_sel) correlations of the columns `cols`; NaN where a column is constant, 1.0 on the diagonal."""
+        return self._between(self._lib.tamcmc_modediag_corr, "tamcmc_modediag_corr", cols)
+
+    def diag_kernel_time(self):
+        """(summed milliseconds, launches) of the lag, finish and covariance kernels since the object was created or reset."""
+        ms = C.c_double(0.0)
+        n = C.c_int64(0)
+        self._check(self._lib.tamcmc_modediag_kernel_time(self._mt, C.byref(ms), C.byref(n)), "tamcmc_modediag_kernel_time")
         return ms.value, n.value
 
     def close(self):

@@ -1,6 +1,6 @@
 // tamcmc_modetable_api.cpp -- host side of the posterior mode table (tamcmc_modetable_* in include/tamcmc_accel.h): the
 // object, its blocks and the results.  The kernels are in tamcmc_modetable.hip, the column layout and the shared
-// arithmetic in tamcmc_modetable.h.
+// arithmetic in tamcmc_modetable.h, the object's struct in tamcmc_modetable_obj.h (tamcmc_modediag_api.cpp works on it too).
 //
 // A push takes its samples in blocks of B on the context's stream: the params rows go to the device, the derive kernel
 // writes B x n_cols rows and B status codes, the status codes come back, the host decides which samples are accepted
@@ -10,27 +10,7 @@
 #include <cmath>
 #include <new>
 
-#include "tamcmc_host.h"
-#include "tamcmc_modetable.h"
-
-struct tamcmc_modetable {
-    tamcmc_ctx *c = nullptr;
-    bool counted = false;                // the context's count includes this object
-    int n_cols = 0, B = 0;
-    long long max_samples = 0;
-    std::vector<TmMtCol> cols;
-    double *d_params = nullptr;          // [B][Nparams]
-    double *d_rows = nullptr;            // [B][n_cols]
-    int32_t *d_status = nullptr, *d_accept = nullptr;   // [B]
-    double *d_state = nullptr;           // [TM_MT_NSTATE][n_cols], then the copy a push can be undone from, then [TM_Q_MAXQ][n_cols] quantiles
-    uint64_t *d_ranks = nullptr;         // [TM_Q_MAXQ]
-    double *d_table = nullptr;           // [n_cols][max_samples]
-    long long n_used = 0, n_rejected = 0;
-    hipEvent_t ev[2] = {nullptr, nullptr};
-    double ms = 0.0;                     // derive and fold kernels since create / reset
-    int64_t launches = 0;
-    size_t state_doubles() const { return (size_t)TM_MT_NSTATE * (size_t)n_cols; }
-};
+#include "tamcmc_modetable_obj.h"          // struct tamcmc_modetable
 
 static int mt_enter(tamcmc_modetable *mt)
 {
@@ -87,6 +67,7 @@ static int mt_derive_block(tamcmc_modetable *mt, int n, const double *params, bo
 static int mt_clear(tamcmc_modetable *mt)
 {
     mt->n_used = 0; mt->n_rejected = 0; mt->ms = 0.0; mt->launches = 0;
+    mt->acov_valid = false; mt->diag_ms = 0.0; mt->diag_launches = 0;      // tamcmc_modediag_*
     TM_HIP(hipMemsetAsync(mt->d_state, 0, mt->state_doubles() * sizeof(double), mt->c->stream));
     return TAMCMC_OK;
 }
@@ -137,6 +118,7 @@ extern "C" int tamcmc_modetable_destroy(tamcmc_modetable *mt)
     if (mt->counted) c->modetables--;
     (void)hipFree(mt->d_params); (void)hipFree(mt->d_rows); (void)hipFree(mt->d_status); (void)hipFree(mt->d_accept);
     (void)hipFree(mt->d_state); (void)hipFree(mt->d_ranks); (void)hipFree(mt->d_table);
+    (void)hipFree(mt->d_acc); (void)hipFree(mt->d_cut); (void)hipFree(mt->d_S); (void)hipFree(mt->d_sel);
     for (hipEvent_t e : mt->ev) if (e) (void)hipEventDestroy(e);
     delete mt;
     return TAMCMC_OK;
@@ -188,6 +170,7 @@ extern "C" int tamcmc_modetable_push(tamcmc_modetable *mt, int32_t Nsamples, int
     if (rc != TAMCMC_OK) return rc;
     tamcmc_ctx *c = mt->c;
     TM_HIP(hipSetDevice(c->device));
+    mt->acov_valid = false;              // tamcmc_modediag_acov: the lag products are those of the table before this push
     const size_t np = (size_t)Nparams, ns = mt->state_doubles();
     std::vector<int32_t> st, acc;
     try { st.resize((size_t)Nsamples); acc.resize((size_t)mt->B); } catch (const std::bad_alloc &) { return TAMCMC_E_NOMEM; }

@@ -1,0 +1,36 @@
+// tamcmc_modetable_obj.h -- internal to csrc/: the posterior mode table's object, shared by the two source files that work on
+// it: tamcmc_modetable_api.cpp (the table, its statistics and quantiles) and tamcmc_modediag_api.cpp (ESS, MCSE, split
+// R-hat, covariances and correlations of its columns).
+#pragma once
+#include "tamcmc_host.h"
+#include "tamcmc_modetable.h"
+
+struct tamcmc_modetable {
+    tamcmc_ctx *c = nullptr;
+    bool counted = false;                // the context's count includes this object
+    int n_cols = 0, B = 0;
+    long long max_samples = 0;
+    std::vector<TmMtCol> cols;
+    double *d_params = nullptr;          // [B][Nparams]
+    double *d_rows = nullptr;            // [B][n_cols]
+    int32_t *d_status = nullptr, *d_accept = nullptr;   // [B]
+    double *d_state = nullptr;           // [TM_MT_NSTATE][n_cols], then the copy a push can be undone from, then [TM_Q_MAXQ][n_cols] quantiles
+    uint64_t *d_ranks = nullptr;         // [TM_Q_MAXQ]
+    double *d_table = nullptr;           // [n_cols][max_samples]
+    long long n_used = 0, n_rejected = 0;
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    double ms = 0.0;                     // derive and fold kernels since create / reset
+    int64_t launches = 0;
+    size_t state_doubles() const { return (size_t)TM_MT_NSTATE * (size_t)n_cols; }
+    // tamcmc_modediag_* (tamcmc_modediag_api.cpp); nothing below is allocated before the first call that needs it
+    double *d_acc = nullptr;             // [acc_lags][n_cols] lag products, then [TM_MD_NFIN][n_cols] tau, ess, rhat
+    int32_t *d_cut = nullptr;            // [n_cols]
+    int acc_lags = 0;                    // lags (L + 1) d_acc has room for
+    int diag_L = 0;                      // L of the last _ess call, while acov_valid
+    bool acov_valid = false;             // d_acc holds the lag products of the table as it is: no push or reset since
+    double *d_S = nullptr;               // [sel_cap][sel_cap] sums of products of the last _cov / _corr call
+    int32_t *d_sel = nullptr;            // [sel_cap] its columns
+    int sel_cap = 0;
+    double diag_ms = 0.0;                // lag, finish and covariance kernels since create / reset
+    int64_t diag_launches = 0;
+};

@@ -5,7 +5,7 @@
 //                    [--chain m] [--slice s] [--first i] [--last j] [--thin k] [--block B]
 //                    [--quantiles q1,q2,...] [--qbits b] [--loo] [--predictive] [--window W[,first]] [--ess [L]]
 //                    [--scan W0[,W1,...]] [--scan-below T] [--scan-null R[,seed]] [--band-ess [L]] [--loo-pit]
-//                    [--loo-window W[,first]] [--modes [q1,q2,...]]
+//                    [--loo-window W[,first]] [--modes [q1,q2,...]] [--modes-ess [L]] [--modes-corr]
 //
 // <config dir> is the reference's Config/default; model id, likelihood, p, plength, the inputs row and the relax mask
 // come from the setup it describes (tamcmc_setup_create / tamcmc_setup_load, slice s counted from 0).  The samples are
@@ -80,6 +80,15 @@
 // `#` header lines -- the version, `# quantiles= q1,q2,...`, `# n_used= ...  n_rejected= ...  n_cols= ...  n_mult= ...` (the
 // samples the fold skipped are counted among the rejected) and the column names -- then one row per quantity:
 //   col  kind  mult  order  l  m  param_index  mean  sd  min  max  [one column per quantile]        (17 significant digits)
+// With --modes-ess [L] (needs --modes; L as for --ess) the table's columns get their effective sample size, Monte-Carlo
+// standard error and split R-hat (tamcmc_modediag_ess) from the rows the table already holds: <output file>.modes.ess, `#`
+// header lines -- the version, the .modes totals, `# lag= ...  min_ess= ...  col_min_ess= ...  max_rhat= ...  col_max_rhat= ...
+// n_truncated= ...  n_constant= ...  n_rhat_high= ...` and the column names -- then one row per quantity:
+//   col  kind  mult  order  l  m  param_index  ess  tau  mcse  rhat  cut                             (17 significant digits)
+// With --modes-corr (needs --modes) the correlation matrix of the headline columns -- the four chain-level columns and freq,
+// width, height, amplitude, splitting of every multiplet, in table order -- goes to <output file>.modes.corr: the version, the
+// .modes totals, `# cols = c0 c1 ...`, then the matrix, one row per line (17 significant digits; nan where a column is constant).
+// Neither reads the samples again; the output file and .modes keep every byte.
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -97,7 +106,7 @@ static int usage()
                     "                         [--chain m] [--slice s] [--first i] [--last j] [--thin k] [--block B]\n"
                     "                         [--quantiles q1,q2,...] [--qbits b] [--loo] [--predictive] [--window W[,first]] [--ess [L]]\n"
                     "                         [--scan W0[,W1,...]] [--scan-below T] [--scan-null R[,seed]] [--band-ess [L]] [--loo-pit]\n"
-                    "                         [--loo-window W[,first]] [--modes [q1,q2,...]]\n"
+                    "                         [--loo-window W[,first]] [--modes [q1,q2,...]] [--modes-ess [L]] [--modes-corr]\n"
                     "     [1] The directory of config_default.cfg, errors_default.cfg and the *_ctrl.list files (Config/default)\n"
                     "     [2] The .model file and [3] the .data file of the fit\n"
                     "     [4] The root of the parameter files: <root>_chain-<m>.bin and <root>.hdr\n"
@@ -145,6 +154,12 @@ static int usage()
                     "             0.16,0.5,0.84) over the samples the summary used: written to <output file>.modes, one row per quantity,\n"
                     "             col kind mult order l m param_index mean sd min max and one column per quantile, 17 significant digits\n"
                     "             (the samples are read once more; [5] and the other files are unchanged)\n"
+                    "     --modes-ess [L]   needs --modes: effective sample size, Monte-Carlo standard error and split R-hat of every quantity of\n"
+                    "             the mode table from its autocorrelation up to lag L (0 ... 1023, default 0: the library's 255): written to\n"
+                    "             <output file>.modes.ess, one row per quantity, col kind mult order l m param_index ess tau mcse rhat cut\n"
+                    "     --modes-corr   needs --modes: the correlation matrix of the chain-level quantities and of freq width height amplitude\n"
+                    "             splitting of every multiplet (at most 1024 columns): written to <output file>.modes.corr, `# cols = ...` and\n"
+                    "             one matrix row per line (neither option reads the samples again; [5] and .modes are unchanged)\n"
                     " chainsummary_hip version   prints the library version\n");
     return EXIT_FAILURE;
 }
@@ -186,6 +201,8 @@ int main(int argc, char *argv[])
     long band_lag = -1;                                     // < 0: no --band-ess
     long lw_W = 0, lw_first = 0;                            // lw_W = 0: no --loo-window
     bool modes = false;                                     // --modes
+    long modes_ess_lag = -1;                                // < 0: no --modes-ess
+    bool modes_corr = false;                                // --modes-corr
     std::vector<double> mquant;
     std::string mquant_text = "0.16,0.5,0.84";
     std::vector<int32_t> scan_W;
@@ -223,6 +240,21 @@ int main(int argc, char *argv[])
                 if (*end != ',') return usage();
                 p = end + 1;
             }
+            continue;
+        }
+        if (a == "--modes-ess") {                   // alone, or followed by the lag limit
+            if (modes_ess_lag >= 0) return usage();
+            modes_ess_lag = 0;
+            if (i + 1 < argc && argv[i + 1][0] >= '0' && argv[i + 1][0] <= '9') {
+                char *end = nullptr;
+                modes_ess_lag = strtol(argv[++i], &end, 10);
+                if (*end != '\0' || modes_ess_lag > TAMCMC_MODEDIAG_MAX_LAG) return usage();
+            }
+            continue;
+        }
+        if (a == "--modes-corr") {
+            if (modes_corr) return usage();
+            modes_corr = true;
             continue;
         }
         if (a == "--band-ess") {                    // alone, or followed by the lag limit
@@ -327,6 +359,7 @@ int main(int argc, char *argv[])
     }
     if (chain < 0 || slice < 0 || first < 0 || thin < 1 || block < 0 || block > 0x7FFFFFFF || qbits < 0 || qbits > 6) return usage();
     if ((have_below || null_R) && scan_W.empty()) return usage();
+    if ((modes_ess_lag >= 0 || modes_corr) && !modes) { fprintf(stderr, "chainsummary_hip: --modes-ess and --modes-corr need --modes\n"); return usage(); }
     if (band_lag >= 0 && quant.empty()) { fprintf(stderr, "chainsummary_hip: --band-ess needs --quantiles\n"); return usage(); }
 
     tamcmc_setup *S = nullptr;
@@ -569,6 +602,9 @@ int main(int argc, char *argv[])
     tamcmc_modetable_totals mtt{};
     std::vector<tamcmc_modetable_col> m_col;
     std::vector<double> m_mean, m_sd, m_min, m_max, m_q;
+    tamcmc_modediag_totals mdt{};                           // --modes-ess
+    std::vector<double> d_ess, d_tau, d_mcse, d_rhat, d_corr;
+    std::vector<int32_t> d_cut, head_cols;                  // --modes-corr: the headline columns
     if (modes) {
         auto mfail = [&](const char *what) { return fail(std::string(what) + ": " + tamcmc_strerror(rc) + " " + tamcmc_last_hip_error()); };
         tamcmc_modetable *mt = nullptr;
@@ -580,6 +616,13 @@ int main(int argc, char *argv[])
         m_col.resize(nc); m_mean.resize(nc); m_sd.resize(nc); m_min.resize(nc); m_max.resize(nc);
         m_q.assign(mquant.size() * nc, std::nan(""));
         for (int32_t k = 0; k < n_cols; k++) tamcmc_modetable_column(mt, k, &m_col[(size_t)k]);
+        if (modes_corr) {
+            for (int32_t k = 0; k < n_cols; k++)
+                if (m_col[(size_t)k].kind <= TAMCMC_MODETABLE_SPLITTING) head_cols.push_back(k);
+            if (head_cols.size() > TAMCMC_MODEDIAG_MAX_COLS)
+                return fail("--modes-corr: " + std::to_string(head_cols.size()) + " headline columns, more than " +
+                            std::to_string(TAMCMC_MODEDIAG_MAX_COLS) + " of one correlation matrix");
+        }
         mt_push = mt;
         if (push_selected() != 0) return EXIT_FAILURE;
         mt_push = nullptr;
@@ -588,6 +631,18 @@ int main(int argc, char *argv[])
         if (mtt.n_used > 0) {
             rc = tamcmc_modetable_quantiles(mt, (int32_t)mquant.size(), mquant.data(), nullptr, m_q.data());
             if (rc != TAMCMC_OK) return mfail("tamcmc_modetable_quantiles");
+        }
+        if (modes_ess_lag >= 0) {
+            if (mtt.n_used < 4) return fail("--modes-ess needs at least 4 accepted samples");
+            d_ess.resize(nc); d_tau.resize(nc); d_mcse.resize(nc); d_rhat.resize(nc); d_cut.resize(nc);
+            rc = tamcmc_modediag_ess(mt, (int32_t)modes_ess_lag, &mdt, d_ess.data(), d_tau.data(), d_mcse.data(), d_rhat.data(), d_cut.data());
+            if (rc != TAMCMC_OK) return mfail("tamcmc_modediag_ess");
+        }
+        if (modes_corr) {
+            if (mtt.n_used < 2) return fail("--modes-corr needs at least 2 accepted samples");
+            d_corr.resize(head_cols.size() * head_cols.size());
+            rc = tamcmc_modediag_corr(mt, (int32_t)head_cols.size(), head_cols.data(), d_corr.data());
+            if (rc != TAMCMC_OK) return mfail("tamcmc_modediag_corr");
         }
         tamcmc_modetable_destroy(mt);
     }
@@ -798,6 +853,41 @@ int main(int argc, char *argv[])
             fprintf(om, "\n");
         }
         fclose(om);
+        if (modes_ess_lag >= 0) {
+            const std::string ess_file = modes_file + ".ess";
+            FILE *oe = fopen(ess_file.c_str(), "w");
+            if (!oe) return fail("unable to open the output file " + ess_file);
+            fprintf(oe, "# chainsummary_hip (%s)\n", tamcmc_version());
+            fprintf(oe, "# n_used= %lld  n_rejected= %lld  n_cols= %lld  n_mult= %lld\n", (long long)mtt.n_used, (long long)mtt.n_rejected,
+                    (long long)mtt.n_cols, (long long)mtt.n_mult);
+            fprintf(oe, "# lag= %lld  min_ess= %.17g  col_min_ess= %lld  max_rhat= %.17g  col_max_rhat= %lld  n_truncated= %lld  n_constant= %lld  n_rhat_high= %lld\n",
+                    (long long)mdt.lag, mdt.min_ess, (long long)mdt.col_min_ess, mdt.max_rhat, (long long)mdt.col_max_rhat, (long long)mdt.n_truncated,
+                    (long long)mdt.n_constant, (long long)mdt.n_rhat_high);
+            fprintf(oe, "# col kind mult order l m param_index ess tau mcse rhat cut\n");
+            for (size_t k = 0; k < m_col.size(); k++) {
+                const tamcmc_modetable_col &c = m_col[k];
+                fprintf(oe, "%zu %s %d %d %d %d %d %.17g %.17g %.17g %.17g %d\n", k, kind_name[c.kind], (int)c.mult, (int)c.order, (int)c.l, (int)c.m,
+                        (int)c.param_index, d_ess[k], d_tau[k], d_mcse[k], d_rhat[k], (int)d_cut[k]);
+            }
+            fclose(oe);
+        }
+        if (modes_corr) {
+            const std::string corr_file = modes_file + ".corr";
+            FILE *oc = fopen(corr_file.c_str(), "w");
+            if (!oc) return fail("unable to open the output file " + corr_file);
+            fprintf(oc, "# chainsummary_hip (%s)\n", tamcmc_version());
+            fprintf(oc, "# n_used= %lld  n_rejected= %lld  n_cols= %lld  n_mult= %lld\n", (long long)mtt.n_used, (long long)mtt.n_rejected,
+                    (long long)mtt.n_cols, (long long)mtt.n_mult);
+            fprintf(oc, "# cols =");
+            for (const int32_t k : head_cols) fprintf(oc, " %d", (int)k);
+            fprintf(oc, "\n");
+            const size_t nh = head_cols.size();
+            for (size_t i = 0; i < nh; i++) {
+                for (size_t j = 0; j < nh; j++) fprintf(oc, j ? " %.17g" : "%.17g", d_corr[i * nh + j]);
+                fprintf(oc, "\n");
+            }
+            fclose(oc);
+        }
     }
     printf("Summary of %lld samples (%lld rejected) written to %s\n", (long long)t.n_used, (long long)t.n_rejected, out_file.c_str());
     return 0;

@@ -64,6 +64,13 @@ Prints one JSON line:
                             (ModeTable.kernel_time: microseconds per sample, launches), the quantile call for three
                             probabilities on the host clock (--quantiles sets their number), the number of columns and the
                             device memory of the table.  Only this leg runs.
+  o_modediag_*              with --modes and --modes-ess L and / or --modes-cov: the diagnostics of that table's columns
+                            (ModeTable.ess / ModeTable.cov) on the rows it holds: per call the kernels alone from the object's HIP
+                            events (ModeTable.diag_kernel_time: lag and finish kernels of an ess call together, the covariance
+                            kernel of a cov call) and the call on the host clock; beside them the table's own derive and fold
+                            kernels of the same rows, and the same lag products and sums of products by the header's serial
+                            functions on one host thread (tools/modediag_host_time.cpp, built with g++ when the leg runs) with
+                            the ratios.  Only this leg runs.
 Every timed shape is warmed up first (--warmup pushes); host clocks stop after calls that end in a device synchronise.
 """
 import argparse
@@ -482,6 +489,57 @@ def modetable_leg(a, w, P):
     return out
 
 
+def modediag_leg(a, w, P):
+    """(o) the diagnostics of the mode table's columns: the kernels of an ess and of a cov call, the host's serial loops."""
+    import subprocess
+    import tempfile
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    out = {}
+    with tamcmc_amd.Accel(2, w["plength"], w["x"], np.ones(a.nx)) as acc:
+        with tamcmc_amd.ModeTable(acc, a.samples) as mt:
+            mt.push(P)
+            table_ms, table_launches = mt.kernel_time()
+            n = mt.result()["n_used"]
+            L = -1
+            ess_k, ess_h, cov_k, cov_h = [], [], [], []
+            for k in range(a.warmup + a.steps):
+                if a.modes_ess >= 0:
+                    ms0, _ = mt.diag_kernel_time()
+                    t0 = time.perf_counter()
+                    r = mt.ess(a.modes_ess)                  # synchronous
+                    t1 = time.perf_counter()
+                    L = r["lag"]
+                    if k >= a.warmup:
+                        ess_k.append(mt.diag_kernel_time()[0] - ms0); ess_h.append((t1 - t0) * 1e3)
+                if a.modes_cov:
+                    ms0, _ = mt.diag_kernel_time()
+                    t0 = time.perf_counter()
+                    mt.cov()                                # synchronous
+                    t1 = time.perf_counter()
+                    if k >= a.warmup:
+                        cov_k.append(mt.diag_kernel_time()[0] - ms0); cov_h.append((t1 - t0) * 1e3)
+            out.update(o_modediag_cols=mt.n_cols, o_modediag_n=n, o_modediag_table_kernels_ms=table_ms, o_modediag_table_launches=table_launches)
+            if ess_k:
+                out.update(o_modediag_lag=L, o_modediag_ess_kernels_ms=float(np.median(ess_k)), o_modediag_ess_kernels_spread_ms=[min(ess_k), max(ess_k)],
+                           o_modediag_ess_call_ms=float(np.median(ess_h)), o_modediag_lag_fma=float(sum(n - k for k in range(L + 1))) * mt.n_cols,
+                           o_modediag_min_ess=r["min_ess"], o_modediag_n_constant=r["n_constant"])
+            if cov_k:
+                out.update(o_modediag_cov_kernel_ms=float(np.median(cov_k)), o_modediag_cov_kernel_spread_ms=[min(cov_k), max(cov_k)],
+                           o_modediag_cov_call_ms=float(np.median(cov_h)), o_modediag_cov_fma=float(n) * mt.n_cols * (mt.n_cols + 1) / 2)
+            n_cols = mt.n_cols
+    with tempfile.TemporaryDirectory() as tmp:
+        exe = os.path.join(tmp, "modediag_host_time")
+        subprocess.run(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-I", os.path.join(root, "tamcmc-c-_amd", "csrc"),
+                        os.path.join(root, "tools", "modediag_host_time.cpp"), "-o", exe], check=True)
+        host = json.loads(subprocess.run([exe, str(n), str(n_cols), str(max(L, 0)), str(n_cols if a.modes_cov else 0)], check=True,
+                                         capture_output=True, text=True).stdout)
+    if ess_k:
+        out.update(o_modediag_host_lag_ms=host["host_lag_ms"], o_modediag_host_over_ess_kernels=host["host_lag_ms"] / out["o_modediag_ess_kernels_ms"])
+    if cov_k:
+        out.update(o_modediag_host_cov_ms=host["host_cov_ms"], o_modediag_host_over_cov_kernel=host["host_cov_ms"] / out["o_modediag_cov_kernel_ms"])
+    return out
+
+
 def bandess_leg(a, w, y, P):
     """(k) the fold pass beside the band ESS pass of the same rows, and the kernels' own times."""
     out = {}
@@ -565,10 +623,14 @@ def main():
     ap.add_argument("--ess", type=int, default=-1)
     ap.add_argument("--band-ess", type=int, default=-1, help="L: the band ESS pass at --quantiles thresholds (0: the library's lag limit)")
     ap.add_argument("--modes", action="store_true", help="the posterior mode table: push, the derive and fold kernels, the quantile call")
+    ap.add_argument("--modes-ess", type=int, default=-1, help="L: with --modes, ESS / MCSE / R-hat of the table's columns (0: the library's lag limit)")
+    ap.add_argument("--modes-cov", action="store_true", help="with --modes, the covariance matrix of all columns")
     ap.add_argument("--scan-null", type=int, default=0, help="R: replicates per run of the scan's Monte-Carlo null (widths of --scan)")
     a = ap.parse_args()
     if a.steps < 1 or a.warmup < 0 or a.samples < 1 or a.samples_b < 2 or a.scan_null < 0:
         ap.error("--steps >= 1, --warmup >= 0, --samples >= 1, --samples-b >= 2, --scan-null >= 0")
+    if (a.modes_ess >= 0 or a.modes_cov) and not a.modes:
+        ap.error("--modes-ess and --modes-cov need --modes")
     if a.scan_null:
         out = dict(tool="summary_time", Nx=a.nx, steps=a.steps, warmup=a.warmup, version=tamcmc_amd.capi.version())
         out.update(scan_null_leg(a))
@@ -578,7 +640,7 @@ def main():
     P = synth.chain_params(w, a.samples)
     if a.modes:
         out = dict(tool="summary_time", Nx=a.nx, samples=a.samples, steps=a.steps, warmup=a.warmup, version=tamcmc_amd.capi.version())
-        out.update(modetable_leg(a, w, P))
+        out.update(modediag_leg(a, w, P) if a.modes_ess >= 0 or a.modes_cov else modetable_leg(a, w, P))
         print(json.dumps(out))
         return
     with tamcmc_amd.Accel(2, w["plength"], w["x"], np.ones(a.nx)) as acc:
