@@ -930,6 +930,66 @@ int tamcmc_modediag_cov(tamcmc_modetable *mt, int32_t n_sel, const int32_t *cols
 int tamcmc_modediag_corr(tamcmc_modetable *mt, int32_t n_sel, const int32_t *cols, double *corr);
 int tamcmc_modediag_kernel_time(tamcmc_modetable *mt, double *total_ms, int64_t *launches);
 
+/* ---- Mode table diagnostics on ranks: bulk and tail ESS, rank-normalised and folded split R-hat ------------------------
+ * The diagnostics of Vehtari, Gelman, Simpson, Carpenter and Buerkner, "Rank-normalization, folding, and localization"
+ * (2021), of the columns of a mode table created with max_samples > 0: what the block above says of the raw values, said of
+ * their ranks, which heavy tails, skewness and ties (window edges are integers) cannot mislead.  ESS here is this project's
+ * single-chain Geyer estimate (steps 2-4 of the block above) applied to the transformed series, NOT Stan's multi-chain
+ * formula; R-hat is the split R-hat of step 5 of the transformed series.  Nothing of the table's state and nothing of
+ * tamcmc_modediag_*'s buffers is written.  n = n_used >= 4; v_t = column c of the t-th accepted row in push order; order
+ * is that of the quantiles' keys (-0 and +0 are one value; the table holds no NaN).
+ *     1  rank2_t = #{s : v_s < v_t} + #{s : v_s <= v_t} + 1: twice the average rank, an integer in [2, 2n]; sum_t rank2_t =
+ *        n (n + 1) exactly.
+ *     2  z_t: a = 4 rank2_t - 3, D = 8 n + 2, b = D - a (p = a / D is Blom's (r - 3/8) / (n + 1/4)).  a < b: z = -g(a / D);
+ *        a > b: z = +g(b / D); a = b: z = +0.0, where g(q) = -Phi^-1(q) for 0 < q < 1/2 from the one division
+ *        (double)a / (double)D.  The smaller tail is always the one inverted, so z(rank2) = -z(2 (n + 1) - rank2) bit for
+ *        bit.  g is a closed-form start and two Halley steps on erfc; host and device use their own libm, and either meets
+ *        |z - z_exact| <= 10 2^-50 q / phi(z) + 4 2^-52 |z|.
+ *     3  fold: med = 0.5 s_[(n-1)/2] + 0.5 s_[n/2] of the sorted column (a zero as +0), f_t = |v_t - med| (one subtraction,
+ *        never contracted); rank2 and z of f by steps 1-2 give zf_t.
+ *     4  tail indicators: i05_t = (v_t <= Q05), i95_t = (v_t <= Q95) as 0.0 / 1.0, Q the order statistic
+ *        tamcmc_modetable_quantiles returns for 0.05 and 0.95, bit for bit.
+ *     5  each of the four series (Z, ZFOLD, I05, I95) gets its mean by the Welford recurrence in t order, then goes through
+ *        steps 1-5 of the block above unchanged, by the same kernels: centred values, lag products A_k, Geyer's finish,
+ *        split R-hat of the centred halves.
+ *     6  per column, out[k][n_sel], k = 0 ... TAMCMC_MODERANK_NOUT - 1: ess_bulk = ess(Z); ess_tail = the smaller of ess(I05) and
+ *        ess(I95), a NaN skipped, NaN if both are; rhat = the larger of rhat(Z) and rhat(ZFOLD), likewise; tau_bulk = tau(Z);
+ *        rhat_bulk = rhat(Z); rhat_fold = rhat(ZFOLD); ess_q05 = ess(I05); ess_q95 = ess(I95).  cut[s][n_sel]: cut of series s.
+ *        A constant column has every rank2 = n + 1, so z = +0 throughout and A_0 = 0: NaN, cut 0, counted in n_constant.
+ *     7  totals, in the order of the selection (the first wins a tie, a NaN is skipped): n_used, lag = L; min_ess_bulk,
+ *        min_ess_tail, max_rhat, each with the table's column it belongs to (NaN and -1 if every value is a NaN);
+ *        n_truncated (cut of Z = L + 1), n_constant (A_0 of Z = 0), n_rhat_high (rhat > 1.01).
+ *   diag         cols[0 ... n_sel - 1] are the columns, in that order (cols NULL: the first n_sel columns); totals, out and
+ *                cut may be NULL.  The columns are processed in chunks sized so that a chunk fits scratch_bytes of device
+ *                memory (0: 256 MiB): per column 16 P + 32 (n + L + 5) + 44 bytes, P the smallest power of two >= n (two
+ *                buffers of sorted keys, four series, their means, lag products and finish arrays).  At least one column
+ *                goes in a chunk; when even that cannot be allocated, TAMCMC_E_NOMEM, and the object is as it was.  No
+ *                result bit depends on the chunking or on the selection.  The scratch is kept for the next call and freed by
+ *                tamcmc_modetable_destroy.
+ *   acov         the (L + 1) x n_sel lag products of series `series` (0 ... TAMCMC_MODERANK_NSERIES - 1) of the last _diag call,
+ *                A_k of selected column j at acov[k * n_sel + j]; refused when there was no _diag call since the last push or
+ *                reset.
+ *   series       one column recomputed by the same kernels, for tests and plots: rank2 and rank2_fold (n each), the four
+ *                series ([TAMCMC_MODERANK_NSERIES][n]), their means, and {med, Q05, Q95}; any may be NULL.
+ *   kernel_time  summed milliseconds and launch count of the sort, transform, mean, lag and finish kernels of _diag and
+ *                _series since create or reset.
+ * All calls are synchronous, on the context's stream.  Refused with TAMCMC_E_INVALID, before a device is touched: a NULL
+ * handle, a context with a batch in flight or armed, max_samples = 0, n < 4, max_lag outside 0 ... 1023, n_sel outside
+ * 1 ... n_cols, a column index out of range or repeated, a negative scratch_bytes, a NULL acov, a series outside 0 ... 3. */
+#define TAMCMC_MODERANK_NOUT 8     /* ess_bulk, ess_tail, rhat, tau_bulk, rhat_bulk, rhat_fold, ess_q05, ess_q95 */
+#define TAMCMC_MODERANK_NSERIES 4  /* Z, ZFOLD, I05, I95 */
+typedef struct {
+    int64_t n_used, lag;
+    double  min_ess_bulk, min_ess_tail, max_rhat;
+    int64_t col_min_ess_bulk, col_min_ess_tail, col_max_rhat, n_truncated, n_constant, n_rhat_high;
+} tamcmc_moderank_totals;
+int tamcmc_moderank_diag(tamcmc_modetable *mt, int32_t max_lag, int32_t n_sel, const int32_t *cols, int64_t scratch_bytes,
+                         tamcmc_moderank_totals *totals, double *out, int32_t *cut);
+int tamcmc_moderank_acov(tamcmc_modetable *mt, int32_t series, double *acov);
+int tamcmc_moderank_series(tamcmc_modetable *mt, int32_t col, int64_t *rank2, int64_t *rank2_fold, double *series, double *mean,
+                           double *med_q);
+int tamcmc_moderank_kernel_time(tamcmc_modetable *mt, double *total_ms, int64_t *launches);
+
 /* Replaces: the `for chain` loop of generate_model() calls (MALA.cpp:632-639, model_def.cpp:139-143).
  * Host pointers, row-major.  Synchronous: results are valid on return.
  *   params      Nchains x Nparams

@@ -48,6 +48,7 @@ EXPORTS = [
     "tamcmc_modetable_push", "tamcmc_modetable_result", "tamcmc_modetable_quantiles", "tamcmc_modetable_reset",
     "tamcmc_modetable_destroy", "tamcmc_modetable_kernel_time",
     "tamcmc_modediag_ess", "tamcmc_modediag_acov", "tamcmc_modediag_cov", "tamcmc_modediag_corr", "tamcmc_modediag_kernel_time",
+    "tamcmc_moderank_diag", "tamcmc_moderank_acov", "tamcmc_moderank_series", "tamcmc_moderank_kernel_time",
 ]
 
 
@@ -139,6 +140,27 @@ class ModeDiagTotals(C.Structure):
     _fields_ = [("n_used", C.c_int64), ("lag", C.c_int64), ("min_ess", C.c_double), ("max_rhat", C.c_double),
                 ("col_min_ess", C.c_int64), ("col_max_rhat", C.c_int64), ("n_truncated", C.c_int64), ("n_constant", C.c_int64),
                 ("n_rhat_high", C.c_int64)]
+
+
+class ModeRankTotals(C.Structure):
+    """tamcmc_moderank_totals"""
+    _fields_ = [("n_used", C.c_int64), ("lag", C.c_int64), ("min_ess_bulk", C.c_double), ("min_ess_tail", C.c_double),
+                ("max_rhat", C.c_double), ("col_min_ess_bulk", C.c_int64), ("col_min_ess_tail", C.c_int64),
+                ("col_max_rhat", C.c_int64), ("n_truncated", C.c_int64), ("n_constant", C.c_int64), ("n_rhat_high", C.c_int64)]
+
+
+MODERANK_NOUT = 8           # TAMCMC_MODERANK_NOUT
+MODERANK_NSERIES = 4        # TAMCMC_MODERANK_NSERIES
+MODERANK_OUT = ("ess_bulk", "ess_tail", "rhat", "tau_bulk", "rhat_bulk", "rhat_fold", "ess_q05", "ess_q95")
+MODERANK_SERIES = ("z", "zfold", "i05", "i95")
+
+
+def moderank_col_bytes(n, lag):
+    """Device bytes one column of a rank_diag chunk takes at n rows and lag L (tamcmc_accel.h, tamcmc_moderank_diag)."""
+    P = 2
+    while P < n:
+        P *= 2
+    return 16 * P + 32 * (n + lag + 5) + 44
 
 
 MODEDIAG_MAX_LAG = 1023     # TAMCMC_MODEDIAG_MAX_LAG
@@ -270,6 +292,10 @@ def load_library():
     lib.tamcmc_modediag_cov.argtypes = [vp, C.c_int32, ip, dp]
     lib.tamcmc_modediag_corr.argtypes = [vp, C.c_int32, ip, dp]
     lib.tamcmc_modediag_kernel_time.argtypes = [vp, dp, lp]
+    lib.tamcmc_moderank_diag.argtypes = [vp, C.c_int32, C.c_int32, ip, C.c_int64, C.POINTER(ModeRankTotals), dp, ip]
+    lib.tamcmc_moderank_acov.argtypes = [vp, C.c_int32, dp]
+    lib.tamcmc_moderank_series.argtypes = [vp, C.c_int32, lp, lp, dp, dp, dp]
+    lib.tamcmc_moderank_kernel_time.argtypes = [vp, dp, lp]
     for name in EXPORTS:
         fn = getattr(lib, name)
         if fn.restype is not C.c_char_p:
@@ -1347,6 +1373,57 @@ class ModeTable:
         ms = C.c_double(0.0)
         n = C.c_int64(0)
         self._check(self._lib.tamcmc_modediag_kernel_time(self._mt, C.byref(ms), C.byref(n)), "tamcmc_modediag_kernel_time")
+        return ms.value, n.value
+
+    def rank_diag(self, max_lag=0, cols=None, scratch_bytes=0):
+        """Rank-normalised diagnostics (tamcmc_moderank_diag) of the columns `cols`, in that order (None: all): dict of
+        ess_bulk, ess_tail, rhat, tau_bulk, rhat_bulk, rhat_fold, ess_q05, ess_q95 (n_sel doubles each), cut (4, n_sel) of
+        the series z, zfold, i05, i95, cols, and the totals n_used, lag, min_ess_bulk, col_min_ess_bulk, min_ess_tail,
+        col_min_ess_tail, max_rhat, col_max_rhat, n_truncated, n_constant, n_rhat_high.  The columns are processed in
+        chunks that fit scratch_bytes of device memory (0: 256 MiB); no result bit depends on it."""
+        if cols is None:
+            n_sel, sel = self.n_cols, None
+        else:
+            sel = np.ascontiguousarray(cols, dtype=np.int32)
+            if sel.ndim != 1:
+                raise ValueError("cols must be a sequence of column indices")
+            n_sel = sel.size
+        arr = np.empty((MODERANK_NOUT, max(n_sel, 1)))
+        cut = np.empty((MODERANK_NSERIES, max(n_sel, 1)), dtype=np.int32)
+        t = ModeRankTotals()
+        self._check(self._lib.tamcmc_moderank_diag(self._mt, int(max_lag), n_sel, _iptr(sel), int(scratch_bytes), C.byref(t),
+                                                   _dptr(arr), _iptr(cut)), "tamcmc_moderank_diag")
+        out = {k: arr[i].copy() for i, k in enumerate(MODERANK_OUT)}
+        out["cut"] = cut
+        out["cols"] = np.arange(n_sel, dtype=np.int32) if sel is None else sel.copy()
+        out.update({k: (float if k.startswith(("min_", "max_")) else int)(getattr(t, k)) for k, _ in ModeRankTotals._fields_})
+        self._rank_lag, self._rank_nsel = int(t.lag), n_sel
+        return out
+
+    def rank_acov(self, series):
+        """(L + 1, n_sel): the lag products of series `series` (0 ... 3 or "z", "zfold", "i05", "i95") of the last rank_diag()
+        call (refused after a push or a reset)."""
+        s = MODERANK_SERIES.index(series) if isinstance(series, str) else int(series)
+        out = np.empty((getattr(self, "_rank_lag", 0) + 1, getattr(self, "_rank_nsel", 1)))
+        self._check(self._lib.tamcmc_moderank_acov(self._mt, s, _dptr(out)), "tamcmc_moderank_acov")
+        return out
+
+    def rank_series(self, col):
+        """One column recomputed by the rank kernels: dict of rank2, rank2_fold (n int64), series (4, n), mean (4) and
+        med, q05, q95."""
+        n = self.result()["n_used"]
+        r2, r2f = np.empty(max(n, 1), dtype=np.int64), np.empty(max(n, 1), dtype=np.int64)
+        series, mean, mq = np.empty((MODERANK_NSERIES, max(n, 1))), np.empty(MODERANK_NSERIES), np.empty(3)
+        l64 = C.POINTER(C.c_int64)
+        self._check(self._lib.tamcmc_moderank_series(self._mt, int(col), r2.ctypes.data_as(l64), r2f.ctypes.data_as(l64), _dptr(series),
+                                                     _dptr(mean), _dptr(mq)), "tamcmc_moderank_series")
+        return dict(rank2=r2, rank2_fold=r2f, series=series, mean=mean, med=float(mq[0]), q05=float(mq[1]), q95=float(mq[2]))
+
+    def rank_kernel_time(self):
+        """(summed milliseconds, launches) of the rank diagnostics' kernels since the object was created or reset."""
+        ms = C.c_double(0.0)
+        n = C.c_int64(0)
+        self._check(self._lib.tamcmc_moderank_kernel_time(self._mt, C.byref(ms), C.byref(n)), "tamcmc_moderank_kernel_time")
         return ms.value, n.value
 
     def close(self):

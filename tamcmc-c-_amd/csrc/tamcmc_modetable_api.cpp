@@ -1,6 +1,7 @@
 // tamcmc_modetable_api.cpp -- host side of the posterior mode table (tamcmc_modetable_* in include/tamcmc_accel.h): the
 // object, its blocks and the results.  The kernels are in tamcmc_modetable.hip, the column layout and the shared
-// arithmetic in tamcmc_modetable.h, the object's struct in tamcmc_modetable_obj.h (tamcmc_modediag_api.cpp works on it too).
+// arithmetic in tamcmc_modetable.h, the object's struct in tamcmc_modetable_obj.h (tamcmc_modediag_api.cpp and
+// tamcmc_moderank_api.cpp work on it too).
 //
 // A push takes its samples in blocks of B on the context's stream: the params rows go to the device, the derive kernel
 // writes B x n_cols rows and B status codes, the status codes come back, the host decides which samples are accepted
@@ -68,6 +69,7 @@ static int mt_clear(tamcmc_modetable *mt)
 {
     mt->n_used = 0; mt->n_rejected = 0; mt->ms = 0.0; mt->launches = 0;
     mt->acov_valid = false; mt->diag_ms = 0.0; mt->diag_launches = 0;      // tamcmc_modediag_*
+    mt->rk_valid = false; mt->rk_ms = 0.0; mt->rk_launches = 0;            // tamcmc_moderank_*
     TM_HIP(hipMemsetAsync(mt->d_state, 0, mt->state_doubles() * sizeof(double), mt->c->stream));
     return TAMCMC_OK;
 }
@@ -119,6 +121,7 @@ extern "C" int tamcmc_modetable_destroy(tamcmc_modetable *mt)
     (void)hipFree(mt->d_params); (void)hipFree(mt->d_rows); (void)hipFree(mt->d_status); (void)hipFree(mt->d_accept);
     (void)hipFree(mt->d_state); (void)hipFree(mt->d_ranks); (void)hipFree(mt->d_table);
     (void)hipFree(mt->d_acc); (void)hipFree(mt->d_cut); (void)hipFree(mt->d_S); (void)hipFree(mt->d_sel);
+    (void)hipFree(mt->d_rk);
     for (hipEvent_t e : mt->ev) if (e) (void)hipEventDestroy(e);
     delete mt;
     return TAMCMC_OK;
@@ -171,6 +174,7 @@ extern "C" int tamcmc_modetable_push(tamcmc_modetable *mt, int32_t Nsamples, int
     tamcmc_ctx *c = mt->c;
     TM_HIP(hipSetDevice(c->device));
     mt->acov_valid = false;              // tamcmc_modediag_acov: the lag products are those of the table before this push
+    mt->rk_valid = false;                // tamcmc_moderank_acov likewise
     const size_t np = (size_t)Nparams, ns = mt->state_doubles();
     std::vector<int32_t> st, acc;
     try { st.resize((size_t)Nsamples); acc.resize((size_t)mt->B); } catch (const std::bad_alloc &) { return TAMCMC_E_NOMEM; }

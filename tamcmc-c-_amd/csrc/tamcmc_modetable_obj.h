@@ -1,6 +1,6 @@
 // tamcmc_modetable_obj.h -- internal to csrc/: the posterior mode table's object, shared by the two source files that work on
-// it: tamcmc_modetable_api.cpp (the table, its statistics and quantiles) and tamcmc_modediag_api.cpp (ESS, MCSE, split
-// R-hat, covariances and correlations of its columns).
+// it: tamcmc_modetable_api.cpp (the table, its statistics and quantiles), tamcmc_modediag_api.cpp (ESS, MCSE, split
+// R-hat, covariances and correlations of its columns) and tamcmc_moderank_api.cpp (their rank-normalised counterparts).
 #pragma once
 #include "tamcmc_host.h"
 #include "tamcmc_modetable.h"
@@ -33,4 +33,12 @@ struct tamcmc_modetable {
     int sel_cap = 0;
     double diag_ms = 0.0;                // lag, finish and covariance kernels since create / reset
     int64_t diag_launches = 0;
+    // tamcmc_moderank_* (tamcmc_moderank_api.cpp); nothing below is allocated before the first call that needs it
+    void *d_rk = nullptr;                // a chunk's key buffers, series, means, lag products, finish arrays (tmr_col_bytes each column)
+    size_t rk_bytes = 0;                 // its size
+    std::vector<double> rk_acov;         // [TM_MR_NSERIES][rk_L + 1][rk_nsel] lag products of the last _diag call, on the host
+    int rk_L = 0, rk_nsel = 0;
+    bool rk_valid = false;               // rk_acov is that of the table as it is: no push or reset since
+    double rk_ms = 0.0;                  // sort, transform, mean, lag and finish kernels of _diag / _series since create / reset
+    int64_t rk_launches = 0;
 };

@@ -6,6 +6,7 @@
 //                    [--quantiles q1,q2,...] [--qbits b] [--loo] [--predictive] [--window W[,first]] [--ess [L]]
 //                    [--scan W0[,W1,...]] [--scan-below T] [--scan-null R[,seed]] [--band-ess [L]] [--loo-pit]
 //                    [--loo-window W[,first]] [--modes [q1,q2,...]] [--modes-ess [L]] [--modes-corr]
+//                    [--modes-rank [L]]
 //
 // <config dir> is the reference's Config/default; model id, likelihood, p, plength, the inputs row and the relax mask
 // come from the setup it describes (tamcmc_setup_create / tamcmc_setup_load, slice s counted from 0).  The samples are
@@ -88,7 +89,14 @@
 // With --modes-corr (needs --modes) the correlation matrix of the headline columns -- the four chain-level columns and freq,
 // width, height, amplitude, splitting of every multiplet, in table order -- goes to <output file>.modes.corr: the version, the
 // .modes totals, `# cols = c0 c1 ...`, then the matrix, one row per line (17 significant digits; nan where a column is constant).
-// Neither reads the samples again; the output file and .modes keep every byte.
+// With --modes-rank [L] (needs --modes; L as for --modes-ess) the table's columns get their rank-normalised diagnostics
+// (tamcmc_moderank_diag): bulk and tail effective sample size, rank-normalised and folded split R-hat, to
+// <output file>.modes.rank: the version, the .modes totals, `# lag= ...  min_ess_bulk= ...  col_min_ess_bulk= ...  min_ess_tail= ...
+// col_min_ess_tail= ...  max_rhat= ...  col_max_rhat= ...  n_truncated= ...  n_constant= ...  n_rhat_high= ...`, the column names, then
+// one row per quantity in the order of .modes.ess:
+//   col  kind  mult  order  l  m  param_index  ess_bulk  ess_tail  rhat  tau_bulk  rhat_bulk  rhat_fold  ess_q05  ess_q95
+//   cut_z  cut_zfold  cut_i05  cut_i95                                                               (17 significant digits)
+// None of the three reads the samples again; the output file, .modes and .modes.ess keep every byte.
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -107,6 +115,7 @@ static int usage()
                     "                         [--quantiles q1,q2,...] [--qbits b] [--loo] [--predictive] [--window W[,first]] [--ess [L]]\n"
                     "                         [--scan W0[,W1,...]] [--scan-below T] [--scan-null R[,seed]] [--band-ess [L]] [--loo-pit]\n"
                     "                         [--loo-window W[,first]] [--modes [q1,q2,...]] [--modes-ess [L]] [--modes-corr]\n"
+                    "                         [--modes-rank [L]]\n"
                     "     [1] The directory of config_default.cfg, errors_default.cfg and the *_ctrl.list files (Config/default)\n"
                     "     [2] The .model file and [3] the .data file of the fit\n"
                     "     [4] The root of the parameter files: <root>_chain-<m>.bin and <root>.hdr\n"
@@ -160,6 +169,10 @@ static int usage()
                     "     --modes-corr   needs --modes: the correlation matrix of the chain-level quantities and of freq width height amplitude\n"
                     "             splitting of every multiplet (at most 1024 columns): written to <output file>.modes.corr, `# cols = ...` and\n"
                     "             one matrix row per line (neither option reads the samples again; [5] and .modes are unchanged)\n"
+                    "     --modes-rank [L]   needs --modes: rank-normalised diagnostics of every quantity of the mode table (bulk and tail\n"
+                    "             effective sample size, rank-normalised and folded split R-hat; lag limit L as for --modes-ess): written to\n"
+                    "             <output file>.modes.rank, one row per quantity, col kind mult order l m param_index ess_bulk ess_tail rhat\n"
+                    "             tau_bulk rhat_bulk rhat_fold ess_q05 ess_q95 cut_z cut_zfold cut_i05 cut_i95\n"
                     " chainsummary_hip version   prints the library version\n");
     return EXIT_FAILURE;
 }
@@ -203,6 +216,7 @@ int main(int argc, char *argv[])
     bool modes = false;                                     // --modes
     long modes_ess_lag = -1;                                // < 0: no --modes-ess
     bool modes_corr = false;                                // --modes-corr
+    long modes_rank_lag = -1;                               // < 0: no --modes-rank
     std::vector<double> mquant;
     std::string mquant_text = "0.16,0.5,0.84";
     std::vector<int32_t> scan_W;
@@ -249,6 +263,16 @@ int main(int argc, char *argv[])
                 char *end = nullptr;
                 modes_ess_lag = strtol(argv[++i], &end, 10);
                 if (*end != '\0' || modes_ess_lag > TAMCMC_MODEDIAG_MAX_LAG) return usage();
+            }
+            continue;
+        }
+        if (a == "--modes-rank") {                  // alone, or followed by the lag limit
+            if (modes_rank_lag >= 0) return usage();
+            modes_rank_lag = 0;
+            if (i + 1 < argc && argv[i + 1][0] >= '0' && argv[i + 1][0] <= '9') {
+                char *end = nullptr;
+                modes_rank_lag = strtol(argv[++i], &end, 10);
+                if (*end != '\0' || modes_rank_lag > TAMCMC_MODEDIAG_MAX_LAG) return usage();
             }
             continue;
         }
@@ -360,6 +384,7 @@ int main(int argc, char *argv[])
     if (chain < 0 || slice < 0 || first < 0 || thin < 1 || block < 0 || block > 0x7FFFFFFF || qbits < 0 || qbits > 6) return usage();
     if ((have_below || null_R) && scan_W.empty()) return usage();
     if ((modes_ess_lag >= 0 || modes_corr) && !modes) { fprintf(stderr, "chainsummary_hip: --modes-ess and --modes-corr need --modes\n"); return usage(); }
+    if (modes_rank_lag >= 0 && !modes) { fprintf(stderr, "chainsummary_hip: --modes-rank needs --modes\n"); return usage(); }
     if (band_lag >= 0 && quant.empty()) { fprintf(stderr, "chainsummary_hip: --band-ess needs --quantiles\n"); return usage(); }
 
     tamcmc_setup *S = nullptr;
@@ -605,6 +630,9 @@ int main(int argc, char *argv[])
     tamcmc_modediag_totals mdt{};                           // --modes-ess
     std::vector<double> d_ess, d_tau, d_mcse, d_rhat, d_corr;
     std::vector<int32_t> d_cut, head_cols;                  // --modes-corr: the headline columns
+    tamcmc_moderank_totals mrt{};                           // --modes-rank
+    std::vector<double> r_out;
+    std::vector<int32_t> r_cut;
     if (modes) {
         auto mfail = [&](const char *what) { return fail(std::string(what) + ": " + tamcmc_strerror(rc) + " " + tamcmc_last_hip_error()); };
         tamcmc_modetable *mt = nullptr;
@@ -643,6 +671,12 @@ int main(int argc, char *argv[])
             d_corr.resize(head_cols.size() * head_cols.size());
             rc = tamcmc_modediag_corr(mt, (int32_t)head_cols.size(), head_cols.data(), d_corr.data());
             if (rc != TAMCMC_OK) return mfail("tamcmc_modediag_corr");
+        }
+        if (modes_rank_lag >= 0) {
+            if (mtt.n_used < 4) return fail("--modes-rank needs at least 4 accepted samples");
+            r_out.resize((size_t)TAMCMC_MODERANK_NOUT * nc); r_cut.resize((size_t)TAMCMC_MODERANK_NSERIES * nc);
+            rc = tamcmc_moderank_diag(mt, (int32_t)modes_rank_lag, n_cols, nullptr, 0, &mrt, r_out.data(), r_cut.data());
+            if (rc != TAMCMC_OK) return mfail("tamcmc_moderank_diag");
         }
         tamcmc_modetable_destroy(mt);
     }
@@ -887,6 +921,28 @@ int main(int argc, char *argv[])
                 fprintf(oc, "\n");
             }
             fclose(oc);
+        }
+        if (modes_rank_lag >= 0) {
+            const std::string rank_file = modes_file + ".rank";
+            FILE *orank = fopen(rank_file.c_str(), "w");
+            if (!orank) return fail("unable to open the output file " + rank_file);
+            fprintf(orank, "# chainsummary_hip (%s)\n", tamcmc_version());
+            fprintf(orank, "# n_used= %lld  n_rejected= %lld  n_cols= %lld  n_mult= %lld\n", (long long)mtt.n_used, (long long)mtt.n_rejected,
+                    (long long)mtt.n_cols, (long long)mtt.n_mult);
+            fprintf(orank, "# lag= %lld  min_ess_bulk= %.17g  col_min_ess_bulk= %lld  min_ess_tail= %.17g  col_min_ess_tail= %lld  max_rhat= %.17g  "
+                           "col_max_rhat= %lld  n_truncated= %lld  n_constant= %lld  n_rhat_high= %lld\n",
+                    (long long)mrt.lag, mrt.min_ess_bulk, (long long)mrt.col_min_ess_bulk, mrt.min_ess_tail, (long long)mrt.col_min_ess_tail,
+                    mrt.max_rhat, (long long)mrt.col_max_rhat, (long long)mrt.n_truncated, (long long)mrt.n_constant, (long long)mrt.n_rhat_high);
+            fprintf(orank, "# col kind mult order l m param_index ess_bulk ess_tail rhat tau_bulk rhat_bulk rhat_fold ess_q05 ess_q95 cut_z cut_zfold cut_i05 cut_i95\n");
+            const size_t nc = m_col.size();
+            for (size_t k = 0; k < nc; k++) {
+                const tamcmc_modetable_col &c = m_col[k];
+                fprintf(orank, "%zu %s %d %d %d %d %d", k, kind_name[c.kind], (int)c.mult, (int)c.order, (int)c.l, (int)c.m, (int)c.param_index);
+                for (size_t j = 0; j < TAMCMC_MODERANK_NOUT; j++) fprintf(orank, " %.17g", r_out[j * nc + k]);
+                for (size_t j = 0; j < TAMCMC_MODERANK_NSERIES; j++) fprintf(orank, " %d", (int)r_cut[j * nc + k]);
+                fprintf(orank, "\n");
+            }
+            fclose(orank);
         }
     }
     printf("Summary of %lld samples (%lld rejected) written to %s\n", (long long)t.n_used, (long long)t.n_rejected, out_file.c_str());

@@ -64,6 +64,9 @@ Prints one JSON line:
                             (ModeTable.kernel_time: microseconds per sample, launches), the quantile call for three
                             probabilities on the host clock (--quantiles sets their number), the number of columns and the
                             device memory of the table.  Only this leg runs.
+  p_moderank_*              with --modes and --modes-rank L: the rank-normalised diagnostics of that table's columns -- the summed
+                            kernel time of a rank_diag call (sort twice, transform, mean, lag, finish per chunk), the call's wall
+                            time, and the same statements on one host thread (tools/moderank_host_time.cpp, std::sort)
   o_modediag_*              with --modes and --modes-ess L and / or --modes-cov: the diagnostics of that table's columns
                             (ModeTable.ess / ModeTable.cov) on the rows it holds: per call the kernels alone from the object's HIP
                             events (ModeTable.diag_kernel_time: lag and finish kernels of an ess call together, the covariance
@@ -540,6 +543,46 @@ def modediag_leg(a, w, P):
     return out
 
 
+def moderank_leg(a, w, P):
+    """(p) the rank-normalised diagnostics of the mode table's columns: the kernels of a rank_diag call (sort, transform, mean,
+    lag, finish together), the call, and the serial statements on one host thread (tools/moderank_host_time.cpp)."""
+    import subprocess
+    import tempfile
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    out = {}
+    with tamcmc_amd.Accel(2, w["plength"], w["x"], np.ones(a.nx)) as acc:
+        with tamcmc_amd.ModeTable(acc, a.samples) as mt:
+            mt.push(P)
+            table_ms, table_launches = mt.kernel_time()
+            n = mt.result()["n_used"]
+            ker, call = [], []
+            for k in range(a.warmup + a.steps):
+                ms0, l0 = mt.rank_kernel_time()
+                t0 = time.perf_counter()
+                r = mt.rank_diag(a.modes_rank)                # synchronous
+                t1 = time.perf_counter()
+                if k >= a.warmup:
+                    ker.append(mt.rank_kernel_time()[0] - ms0); call.append((t1 - t0) * 1e3)
+                launches = mt.rank_kernel_time()[1] - l0
+            L, n_cols = r["lag"], mt.n_cols
+            out.update(p_moderank_cols=n_cols, p_moderank_n=n, p_moderank_lag=L, p_moderank_table_kernels_ms=table_ms,
+                       p_moderank_table_launches=table_launches, p_moderank_kernels_ms=float(np.median(ker)),
+                       p_moderank_kernels_spread_ms=[min(ker), max(ker)], p_moderank_call_ms=float(np.median(call)),
+                       p_moderank_call_spread_ms=[min(call), max(call)], p_moderank_launches=launches,
+                       p_moderank_chunks=launches // 6, p_moderank_col_bytes=tamcmc_amd.capi.moderank_col_bytes(n, L),
+                       p_moderank_min_ess_bulk=r["min_ess_bulk"], p_moderank_min_ess_tail=r["min_ess_tail"], p_moderank_max_rhat=r["max_rhat"],
+                       p_moderank_n_constant=r["n_constant"])
+    with tempfile.TemporaryDirectory() as tmp:
+        exe = os.path.join(tmp, "moderank_host_time")
+        subprocess.run(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-I", os.path.join(root, "tamcmc-c-_amd", "csrc"),
+                        os.path.join(root, "tools", "moderank_host_time.cpp"), "-o", exe], check=True)
+        host = json.loads(subprocess.run([exe, str(n), str(n_cols), str(L)], check=True, capture_output=True, text=True).stdout)
+    total = host["host_sort_ms"] + host["host_transform_ms"] + host["host_lag_ms"]
+    out.update(p_moderank_host_sort_ms=host["host_sort_ms"], p_moderank_host_transform_ms=host["host_transform_ms"],
+               p_moderank_host_lag_ms=host["host_lag_ms"], p_moderank_host_ms=total, p_moderank_host_over_kernels=total / out["p_moderank_kernels_ms"])
+    return out
+
+
 def bandess_leg(a, w, y, P):
     """(k) the fold pass beside the band ESS pass of the same rows, and the kernels' own times."""
     out = {}
@@ -625,12 +668,13 @@ def main():
     ap.add_argument("--modes", action="store_true", help="the posterior mode table: push, the derive and fold kernels, the quantile call")
     ap.add_argument("--modes-ess", type=int, default=-1, help="L: with --modes, ESS / MCSE / R-hat of the table's columns (0: the library's lag limit)")
     ap.add_argument("--modes-cov", action="store_true", help="with --modes, the covariance matrix of all columns")
+    ap.add_argument("--modes-rank", type=int, default=-1, help="L: with --modes, the rank-normalised diagnostics of the table's columns (0: the library's lag limit)")
     ap.add_argument("--scan-null", type=int, default=0, help="R: replicates per run of the scan's Monte-Carlo null (widths of --scan)")
     a = ap.parse_args()
     if a.steps < 1 or a.warmup < 0 or a.samples < 1 or a.samples_b < 2 or a.scan_null < 0:
         ap.error("--steps >= 1, --warmup >= 0, --samples >= 1, --samples-b >= 2, --scan-null >= 0")
-    if (a.modes_ess >= 0 or a.modes_cov) and not a.modes:
-        ap.error("--modes-ess and --modes-cov need --modes")
+    if (a.modes_ess >= 0 or a.modes_cov or a.modes_rank >= 0) and not a.modes:
+        ap.error("--modes-ess, --modes-cov and --modes-rank need --modes")
     if a.scan_null:
         out = dict(tool="summary_time", Nx=a.nx, steps=a.steps, warmup=a.warmup, version=tamcmc_amd.capi.version())
         out.update(scan_null_leg(a))
@@ -640,7 +684,7 @@ def main():
     P = synth.chain_params(w, a.samples)
     if a.modes:
         out = dict(tool="summary_time", Nx=a.nx, samples=a.samples, steps=a.steps, warmup=a.warmup, version=tamcmc_amd.capi.version())
-        out.update(modediag_leg(a, w, P) if a.modes_ess >= 0 or a.modes_cov else modetable_leg(a, w, P))
+        out.update(moderank_leg(a, w, P) if a.modes_rank >= 0 else modediag_leg(a, w, P) if a.modes_ess >= 0 or a.modes_cov else modetable_leg(a, w, P))
         print(json.dumps(out))
         return
     with tamcmc_amd.Accel(2, w["plength"], w["x"], np.ones(a.nx)) as acc:
