@@ -1099,4 +1099,8 @@ const char *tamcmc_version(void);
 #ifdef __cplusplus
 }
 #endif
+
+/* The seismic indices of the mode table (large separation, epsilon, nu_max, small separations, frequency ratios as further
+ * columns of the table): the kind codes after TAMCMC_MODETABLE_H_M and the entry points, in a header of their own. */
+#include "tamcmc_accel_seismic.h"
 #endif /* TAMCMC_ACCEL_H */

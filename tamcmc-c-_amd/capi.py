@@ -50,6 +50,9 @@ EXPORTS = [
     "tamcmc_modediag_ess", "tamcmc_modediag_acov", "tamcmc_modediag_cov", "tamcmc_modediag_corr", "tamcmc_modediag_kernel_time",
     "tamcmc_moderank_diag", "tamcmc_moderank_acov", "tamcmc_moderank_series", "tamcmc_moderank_kernel_time",
 ]
+# what include/tamcmc_accel_seismic.h declares (tamcmc_accel.h includes it)
+SEISMIC_EXPORTS = ["tamcmc_modetable_indices_enable", "tamcmc_modetable_indices_info", "tamcmc_modetable_index_terms",
+                   "tamcmc_seismic_kernel_time"]
 
 
 class SummaryTotals(C.Structure):
@@ -149,6 +152,12 @@ class ModeRankTotals(C.Structure):
                 ("col_max_rhat", C.c_int64), ("n_truncated", C.c_int64), ("n_constant", C.c_int64), ("n_rhat_high", C.c_int64)]
 
 
+class SeismicInfo(C.Structure):
+    """tamcmc_seismic_info"""
+    _fields_ = [("n_base_cols", C.c_int64), ("n_index_cols", C.c_int64), ("n_radial", C.c_int64), ("n_unassigned", C.c_int64),
+                ("n_base", C.c_int64), ("dnu_ref", C.c_double), ("eps_ref", C.c_double)]
+
+
 MODERANK_NOUT = 8           # TAMCMC_MODERANK_NOUT
 MODERANK_NSERIES = 4        # TAMCMC_MODERANK_NSERIES
 MODERANK_OUT = ("ess_bulk", "ess_tail", "rhat", "tau_bulk", "rhat_bulk", "rhat_fold", "ess_q05", "ess_q95")
@@ -169,6 +178,8 @@ MODEDIAG_MAX_COLS = 1024    # TAMCMC_MODEDIAG_MAX_COLS
 # TAMCMC_MODETABLE_* kind codes, in order
 MODETABLE_KINDS = ("inclination", "eta", "a3", "asymmetry", "freq", "width", "height", "amplitude", "splitting",
                    "window_lo", "window_hi", "nu_m", "h_m")
+# ... and those of the seismic indices (tamcmc_accel_seismic.h), which follow them
+SEISMIC_KINDS = ("dnu_fit", "epsilon", "numax", "dnu_nl", "d2nu", "d02", "d13", "d01", "d10", "r02", "r01", "r13", "r10")
 
 
 class AccelError(RuntimeError):
@@ -296,7 +307,11 @@ def load_library():
     lib.tamcmc_moderank_acov.argtypes = [vp, C.c_int32, dp]
     lib.tamcmc_moderank_series.argtypes = [vp, C.c_int32, lp, lp, dp, dp, dp]
     lib.tamcmc_moderank_kernel_time.argtypes = [vp, dp, lp]
-    for name in EXPORTS:
+    lib.tamcmc_modetable_indices_enable.argtypes = [vp, C.c_int32, dp, C.POINTER(SeismicInfo)]
+    lib.tamcmc_modetable_indices_info.argtypes = [vp, C.POINTER(SeismicInfo)]
+    lib.tamcmc_modetable_index_terms.argtypes = [vp, C.c_int32, C.c_int32, ip, ip, ip, ip, dp, dp]
+    lib.tamcmc_seismic_kernel_time.argtypes = [vp, dp, lp]
+    for name in EXPORTS + SEISMIC_EXPORTS:
         fn = getattr(lib, name)
         if fn.restype is not C.c_char_p:
             fn.restype = C.c_int
@@ -1237,7 +1252,7 @@ class ModeTable:
     device) exact quantiles.  No result bit depends on how the rows are split over pushes.  The Accel cannot be closed
     while the table is open."""
 
-    KINDS = MODETABLE_KINDS
+    KINDS = MODETABLE_KINDS + SEISMIC_KINDS
     ARRAYS = ("mean", "sd", "min", "max")
     COL_DTYPE = np.dtype([("kind", np.int32), ("mult", np.int32), ("order", np.int32), ("l", np.int32), ("m", np.int32),
                           ("param_index", np.int32)])
@@ -1323,6 +1338,46 @@ class ModeTable:
         ms = C.c_double(0.0)
         n = C.c_int64(0)
         self._check(self._lib.tamcmc_modetable_kernel_time(self._mt, C.byref(ms), C.byref(n)), "tamcmc_modetable_kernel_time")
+        return ms.value, n.value
+
+    def enable_indices(self, ref_params):
+        """Appends the seismic indices (tamcmc_modetable_indices_enable) as further columns: the plan is fixed from the
+        params row ref_params.  Allowed once, on a table that has taken no sample.  Returns the info dict: n_base_cols,
+        n_index_cols, n_radial, n_unassigned, n_base, dnu_ref, eps_ref; n_cols and columns() then cover all columns."""
+        ref = _c64(ref_params)
+        if ref.shape != (self.accel.Nparams,):
+            raise ValueError(f"ref_params must have {self.accel.Nparams} entries")
+        info = SeismicInfo()
+        self._check(self._lib.tamcmc_modetable_indices_enable(self._mt, self.accel.Nparams, _dptr(ref), C.byref(info)),
+                    "tamcmc_modetable_indices_enable")
+        self.n_cols = int(info.n_base_cols + info.n_index_cols)
+        return {k: (float if k.endswith("_ref") else int)(getattr(info, k)) for k, _ in SeismicInfo._fields_}
+
+    def indices_info(self):
+        """The info dict of enable_indices() again."""
+        info = SeismicInfo()
+        self._check(self._lib.tamcmc_modetable_indices_info(self._mt, C.byref(info)), "tamcmc_modetable_indices_info")
+        return {k: (float if k.endswith("_ref") else int)(getattr(info, k)) for k, _ in SeismicInfo._fields_}
+
+    def index_terms(self, col):
+        """What index column col is: dict of n_num, n_den, src, wsrc (int32), coef (n_num + n_den entries each, the terms of
+        num first) and offset; value = num / den - offset (tamcmc_accel_seismic.h)."""
+        nn, nd = C.c_int32(0), C.c_int32(0)
+        rc = self._lib.tamcmc_modetable_index_terms(self._mt, int(col), 0, C.byref(nn), C.byref(nd), None, None, None, None)
+        if rc != E_INVALID or nn.value + nd.value < 1:
+            self._check(rc if rc != OK else E_INVALID, "tamcmc_modetable_index_terms")
+        n = nn.value + nd.value
+        src, wsrc, coef = np.empty(n, dtype=np.int32), np.empty(n, dtype=np.int32), np.empty(n)
+        off = C.c_double(0.0)
+        self._check(self._lib.tamcmc_modetable_index_terms(self._mt, int(col), n, C.byref(nn), C.byref(nd), _iptr(src), _iptr(wsrc),
+                                                           _dptr(coef), C.byref(off)), "tamcmc_modetable_index_terms")
+        return dict(n_num=int(nn.value), n_den=int(nd.value), src=src, wsrc=wsrc, coef=coef, offset=float(off.value))
+
+    def seismic_kernel_time(self):
+        """(summed milliseconds, launches) of the indices kernel since the object was created or reset."""
+        ms = C.c_double(0.0)
+        n = C.c_int64(0)
+        self._check(self._lib.tamcmc_seismic_kernel_time(self._mt, C.byref(ms), C.byref(n)), "tamcmc_seismic_kernel_time")
         return ms.value, n.value
 
     DIAG_ARRAYS = ("ess", "tau", "mcse", "rhat")

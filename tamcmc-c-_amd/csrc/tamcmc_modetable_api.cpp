@@ -1,7 +1,8 @@
 // tamcmc_modetable_api.cpp -- host side of the posterior mode table (tamcmc_modetable_* in include/tamcmc_accel.h): the
 // object, its blocks and the results.  The kernels are in tamcmc_modetable.hip, the column layout and the shared
-// arithmetic in tamcmc_modetable.h, the object's struct in tamcmc_modetable_obj.h (tamcmc_modediag_api.cpp and
-// tamcmc_moderank_api.cpp work on it too).
+// arithmetic in tamcmc_modetable.h, the object's struct in tamcmc_modetable_obj.h (tamcmc_modediag_api.cpp,
+// tamcmc_moderank_api.cpp and tamcmc_seismic_api.cpp work on it too; the last one appends the seismic indices as further
+// columns, and a block then runs its indices kernel between the derive and the fold kernel).
 //
 // A push takes its samples in blocks of B on the context's stream: the params rows go to the device, the derive kernel
 // writes B x n_cols rows and B status codes, the status codes come back, the host decides which samples are accepted
@@ -49,7 +50,8 @@ static int mt_timed_done(tamcmc_modetable *mt)
     return TAMCMC_OK;
 }
 
-// params rows of a block to the device, the derive kernel behind them (timed when `timed`)
+// params rows of a block to the device, the derive kernel behind them (timed when `timed`), and behind that the indices
+// kernel of a table whose seismic indices are enabled
 static int mt_derive_block(tamcmc_modetable *mt, int n, const double *params, bool timed)
 {
     tamcmc_ctx *c = mt->c;
@@ -60,9 +62,14 @@ static int mt_derive_block(tamcmc_modetable *mt, int n, const double *params, bo
     TmMtDeriveArgs a{};
     a.L = c->L; a.params = mt->d_params; a.rows = mt->d_rows; a.status = mt->d_status; a.B = n; a.n_cols = mt->n_cols;
     const size_t lds = ((np + 1) & ~(size_t)1) * sizeof(double);
-    if (timed) return mt_timed(mt, "modetable derive", [&] { return tm_launch_modetable_derive(a, lds, c->stream); });
-    const int hr = tm_launch_modetable_derive(a, lds, c->stream);
-    return hr != 0 ? tm_launch_failed("modetable derive", hr) : TAMCMC_OK;
+    int rc;
+    if (timed) rc = mt_timed(mt, "modetable derive", [&] { return tm_launch_modetable_derive(a, lds, c->stream); });
+    else {
+        const int hr = tm_launch_modetable_derive(a, lds, c->stream);
+        rc = hr != 0 ? tm_launch_failed("modetable derive", hr) : TAMCMC_OK;
+    }
+    if (rc != TAMCMC_OK || mt->n_index_cols == 0) return rc;
+    return tm_seis_block(mt, n, timed);             // the seismic indices behind the derive kernel (tamcmc_seismic_api.cpp)
 }
 
 static int mt_clear(tamcmc_modetable *mt)
@@ -70,6 +77,7 @@ static int mt_clear(tamcmc_modetable *mt)
     mt->n_used = 0; mt->n_rejected = 0; mt->ms = 0.0; mt->launches = 0;
     mt->acov_valid = false; mt->diag_ms = 0.0; mt->diag_launches = 0;      // tamcmc_modediag_*
     mt->rk_valid = false; mt->rk_ms = 0.0; mt->rk_launches = 0;            // tamcmc_moderank_*
+    mt->seis_ms = 0.0; mt->seis_launches = 0;                              // tamcmc_modetable_indices_* (the plan stays)
     TM_HIP(hipMemsetAsync(mt->d_state, 0, mt->state_doubles() * sizeof(double), mt->c->stream));
     return TAMCMC_OK;
 }
@@ -90,6 +98,7 @@ extern "C" int tamcmc_modetable_create(tamcmc_modetable **out, tamcmc_ctx *c, in
         mt->cols.resize((size_t)mt->n_cols);
     } catch (const std::bad_alloc &) { return fail(TAMCMC_E_NOMEM); }
     tm_mt_layout(c->L, mt->cols.data());
+    mt->n_base_cols = mt->n_cols;
     mt->B = tm_mt_block(mt->n_cols);
     const size_t nc = (size_t)mt->n_cols, b = (size_t)mt->B, np = (size_t)c->L.Nparams;
     if (((np + 1) & ~(size_t)1) * sizeof(double) > 60 * 1024) return fail(TAMCMC_E_INVALID);       // the row does not fit the derive kernel's LDS
@@ -122,6 +131,8 @@ extern "C" int tamcmc_modetable_destroy(tamcmc_modetable *mt)
     (void)hipFree(mt->d_state); (void)hipFree(mt->d_ranks); (void)hipFree(mt->d_table);
     (void)hipFree(mt->d_acc); (void)hipFree(mt->d_cut); (void)hipFree(mt->d_S); (void)hipFree(mt->d_sel);
     (void)hipFree(mt->d_rk);
+    (void)hipFree(mt->d_seis_i); (void)hipFree(mt->d_seis_d);
+    for (hipEvent_t e : mt->seis_ev) if (e) (void)hipEventDestroy(e);
     for (hipEvent_t e : mt->ev) if (e) (void)hipEventDestroy(e);
     delete mt;
     return TAMCMC_OK;
@@ -193,7 +204,8 @@ extern "C" int tamcmc_modetable_push(tamcmc_modetable *mt, int32_t Nsamples, int
         rc = mt_derive_block(mt, n, params + (size_t)k * np, true);
         if (rc != TAMCMC_OK) return undo(rc);
         if (hipMemcpyAsync(st.data() + k, mt->d_status, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
-            hipStreamSynchronize(c->stream) != hipSuccess || mt_timed_done(mt) != TAMCMC_OK)
+            hipStreamSynchronize(c->stream) != hipSuccess || mt_timed_done(mt) != TAMCMC_OK ||
+            (mt->n_index_cols > 0 && tm_seis_timed_done(mt) != TAMCMC_OK))
             return undo(TAMCMC_E_HIP);
         long long take = 0;
         for (int i = 0; i < n; i++) {

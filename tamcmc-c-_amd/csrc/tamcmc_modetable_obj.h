@@ -1,9 +1,11 @@
-// tamcmc_modetable_obj.h -- internal to csrc/: the posterior mode table's object, shared by the two source files that work on
+// tamcmc_modetable_obj.h -- internal to csrc/: the posterior mode table's object, shared by the source files that work on
 // it: tamcmc_modetable_api.cpp (the table, its statistics and quantiles), tamcmc_modediag_api.cpp (ESS, MCSE, split
-// R-hat, covariances and correlations of its columns) and tamcmc_moderank_api.cpp (their rank-normalised counterparts).
+// R-hat, covariances and correlations of its columns), tamcmc_moderank_api.cpp (their rank-normalised counterparts) and
+// tamcmc_seismic_api.cpp (the seismic indices appended to its columns).
 #pragma once
 #include "tamcmc_host.h"
 #include "tamcmc_modetable.h"
+#include "tamcmc_seismic.h"
 
 struct tamcmc_modetable {
     tamcmc_ctx *c = nullptr;
@@ -41,4 +43,18 @@ struct tamcmc_modetable {
     bool rk_valid = false;               // rk_acov is that of the table as it is: no push or reset since
     double rk_ms = 0.0;                  // sort, transform, mean, lag and finish kernels of _diag / _series since create / reset
     int64_t rk_launches = 0;
+    // tamcmc_modetable_indices_* (tamcmc_seismic_api.cpp); n_index_cols = 0 and nothing below allocated until _indices_enable
+    int n_base_cols = 0, n_index_cols = 0;          // n_cols = n_base_cols + n_index_cols
+    TmSeisPlan plan;
+    int32_t *d_seis_i = nullptr;         // first [n_index + 1], n_num [n_index], src [n_terms], wsrc [n_terms]
+    double *d_seis_d = nullptr;          // coef [n_terms], offset [n_index]
+    hipEvent_t seis_ev[2] = {nullptr, nullptr};
+    double seis_ms = 0.0;                // indices kernel since create / reset
+    int64_t seis_launches = 0;
 };
+
+// tamcmc_seismic_api.cpp, called by a block of tamcmc_modetable_derive / _push behind the derive kernel when n_index_cols > 0:
+// the indices kernel on the block's n rows (between the object's seis_ev events when `timed`), and the addition of that time
+// once the stream has been waited for.
+int tm_seis_block(tamcmc_modetable *mt, int n, bool timed);
+int tm_seis_timed_done(tamcmc_modetable *mt);

@@ -6,7 +6,7 @@
 //                    [--quantiles q1,q2,...] [--qbits b] [--loo] [--predictive] [--window W[,first]] [--ess [L]]
 //                    [--scan W0[,W1,...]] [--scan-below T] [--scan-null R[,seed]] [--band-ess [L]] [--loo-pit]
 //                    [--loo-window W[,first]] [--modes [q1,q2,...]] [--modes-ess [L]] [--modes-corr]
-//                    [--modes-rank [L]]
+//                    [--modes-rank [L]] [--modes-indices]
 //
 // <config dir> is the reference's Config/default; model id, likelihood, p, plength, the inputs row and the relax mask
 // come from the setup it describes (tamcmc_setup_create / tamcmc_setup_load, slice s counted from 0).  The samples are
@@ -97,6 +97,18 @@
 //   col  kind  mult  order  l  m  param_index  ess_bulk  ess_tail  rhat  tau_bulk  rhat_bulk  rhat_fold  ess_q05  ess_q95
 //   cut_z  cut_zfold  cut_i05  cut_i95                                                               (17 significant digits)
 // None of the three reads the samples again; the output file, .modes and .modes.ess keep every byte.
+// With --modes-indices (needs --modes) the seismic indices (tamcmc_modetable_indices_enable: Dnu and epsilon of the radial
+// ridge, nu_max, per-order separations and second differences, d02, d13, d01, d10, r02, r01, r13, r10) are computed per
+// sample in a mode table of their own, whose reference row is the first selected sample the derivation accepts; the samples
+// are read once more and every other file keeps every byte.  <output file>.modes.indices: the version, `# quantiles= ...`, `#
+// n_used= ...  n_rejected= ...  n_base_cols= ...  n_index_cols= ...  n_radial= ...  n_unassigned= ...  n_base= ...  dnu_ref= ...
+// eps_ref= ...`, the column names, then one row per index column:
+//   col  kind  l  n  mean  sd  [one column per quantile]  [ess tau mcse rhat cut with --modes-ess]
+//   [ess_bulk ess_tail rhat_rank tau_bulk rhat_bulk rhat_fold ess_q05 ess_q95 cut_z cut_zfold cut_i05 cut_i95 with --modes-rank]
+// <output file>.modes.indices.cov: the covariance matrix (tamcmc_modediag_cov) of the ratio columns r02, r01, r13, r10 in
+// column order: the version, the totals, `# cols = c0 c1 ...`, `# rows = r02_n<n> ...`, then one matrix row per line.  A
+// star the plan refuses (fewer than 3 radial modes, a missing radial order), or a chain of which fewer than 2 samples (4 with
+// --modes-ess or --modes-rank) are accepted with their indices, gets a message and neither file; every other file is written.
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -115,7 +127,7 @@ static int usage()
                     "                         [--quantiles q1,q2,...] [--qbits b] [--loo] [--predictive] [--window W[,first]] [--ess [L]]\n"
                     "                         [--scan W0[,W1,...]] [--scan-below T] [--scan-null R[,seed]] [--band-ess [L]] [--loo-pit]\n"
                     "                         [--loo-window W[,first]] [--modes [q1,q2,...]] [--modes-ess [L]] [--modes-corr]\n"
-                    "                         [--modes-rank [L]]\n"
+                    "                         [--modes-rank [L]] [--modes-indices]\n"
                     "     [1] The directory of config_default.cfg, errors_default.cfg and the *_ctrl.list files (Config/default)\n"
                     "     [2] The .model file and [3] the .data file of the fit\n"
                     "     [4] The root of the parameter files: <root>_chain-<m>.bin and <root>.hdr\n"
@@ -173,6 +185,11 @@ static int usage()
                     "             effective sample size, rank-normalised and folded split R-hat; lag limit L as for --modes-ess): written to\n"
                     "             <output file>.modes.rank, one row per quantity, col kind mult order l m param_index ess_bulk ess_tail rhat\n"
                     "             tau_bulk rhat_bulk rhat_fold ess_q05 ess_q95 cut_z cut_zfold cut_i05 cut_i95\n"
+                    "     --modes-indices   needs --modes: the seismic indices per sample (Dnu and epsilon of the radial ridge, nu_max,\n"
+                    "             separations, second differences, d02 d13 d01 d10, r02 r01 r13 r10), reference row = the first accepted\n"
+                    "             sample: written to <output file>.modes.indices, one row per index, col kind l n mean sd, one column per\n"
+                    "             quantile of --modes, and the columns of --modes-ess / --modes-rank where given; the covariance matrix of\n"
+                    "             the ratios to <output file>.modes.indices.cov (the samples are read once more; the other files are unchanged)\n"
                     " chainsummary_hip version   prints the library version\n");
     return EXIT_FAILURE;
 }
@@ -217,6 +234,7 @@ int main(int argc, char *argv[])
     long modes_ess_lag = -1;                                // < 0: no --modes-ess
     bool modes_corr = false;                                // --modes-corr
     long modes_rank_lag = -1;                               // < 0: no --modes-rank
+    bool modes_indices = false;                             // --modes-indices
     std::vector<double> mquant;
     std::string mquant_text = "0.16,0.5,0.84";
     std::vector<int32_t> scan_W;
@@ -279,6 +297,11 @@ int main(int argc, char *argv[])
         if (a == "--modes-corr") {
             if (modes_corr) return usage();
             modes_corr = true;
+            continue;
+        }
+        if (a == "--modes-indices") {
+            if (modes_indices) return usage();
+            modes_indices = true;
             continue;
         }
         if (a == "--band-ess") {                    // alone, or followed by the lag limit
@@ -385,6 +408,7 @@ int main(int argc, char *argv[])
     if ((have_below || null_R) && scan_W.empty()) return usage();
     if ((modes_ess_lag >= 0 || modes_corr) && !modes) { fprintf(stderr, "chainsummary_hip: --modes-ess and --modes-corr need --modes\n"); return usage(); }
     if (modes_rank_lag >= 0 && !modes) { fprintf(stderr, "chainsummary_hip: --modes-rank needs --modes\n"); return usage(); }
+    if (modes_indices && !modes) { fprintf(stderr, "chainsummary_hip: --modes-indices needs --modes\n"); return usage(); }
     if (band_lag >= 0 && quant.empty()) { fprintf(stderr, "chainsummary_hip: --band-ess needs --quantiles\n"); return usage(); }
 
     tamcmc_setup *S = nullptr;
@@ -447,18 +471,22 @@ int main(int argc, char *argv[])
     std::vector<int32_t> fold_status(modes ? (size_t)Nsel : 0), mt_skip;
     bool fold_pass = true;
     tamcmc_modetable *mt_push = nullptr;
+    // the params row of sample `at` of the file: the model's inputs with the stored variables put in
+    auto read_row = [&](long long at, double *row) -> bool {
+        f.seekg(at * rowb, std::ios::beg);
+        f.read(reinterpret_cast<char *>(vars.data()), (std::streamsize)rowb);
+        if (!f) return false;
+        std::memcpy(row, inputs.data(), (size_t)Nparams * sizeof(double));
+        for (int32_t v = 0; v < Nvars; v++) row[idx[(size_t)v]] = vars[(size_t)v];
+        return true;
+    };
     auto push_selected = [&]() -> int {
         for (long long k0 = 0; k0 < Nsel; k0 += chunk) {
             const long long n = Nsel - k0 < chunk ? Nsel - k0 : chunk;
             P.assign((size_t)n * (size_t)Nparams, 0.0);
             for (long long k = 0; k < n; k++) {
                 last_used = first + (k0 + k) * thin;
-                f.seekg(last_used * rowb, std::ios::beg);
-                f.read(reinterpret_cast<char *>(vars.data()), (std::streamsize)rowb);
-                if (!f) return fail("short read in " + bin);
-                double *row = P.data() + (size_t)k * (size_t)Nparams;
-                std::memcpy(row, inputs.data(), (size_t)Nparams * sizeof(double));
-                for (int32_t v = 0; v < Nvars; v++) row[idx[(size_t)v]] = vars[(size_t)v];
+                if (!read_row(last_used, P.data() + (size_t)k * (size_t)Nparams)) return fail("short read in " + bin);
             }
             if (mt_push) {
                 mt_skip.assign(fold_status.begin() + k0, fold_status.begin() + k0 + n);
@@ -473,6 +501,21 @@ int main(int argc, char *argv[])
     };
     if (push_selected() != 0) return EXIT_FAILURE;
     fold_pass = false;
+    // --modes-indices: the reference row of the indices, the first selected sample that the fold took and whose derivation the
+    // mode table accepts.  The samples the fold took are derived one at a time until one is accepted: usually the first.
+    std::vector<double> ref_row;
+    auto find_reference = [&](tamcmc_modetable *probe, int32_t n_cols) -> int {
+        std::vector<double> row((size_t)Nparams), derived((size_t)n_cols);
+        for (long long k = 0; k < Nsel; k++) {
+            if (fold_status[(size_t)k] != TAMCMC_CHAIN_OK) continue;
+            if (!read_row(first + k * thin, row.data())) return fail("short read in " + bin);
+            int32_t st = -1;
+            rc = tamcmc_modetable_derive(probe, 1, Nparams, row.data(), derived.data(), &st);
+            if (rc != TAMCMC_OK) return fail(std::string("tamcmc_modetable_derive: ") + tamcmc_strerror(rc) + " " + tamcmc_last_hip_error());
+            if (st == TAMCMC_CHAIN_OK) { ref_row = row; break; }
+        }
+        return 0;
+    };
     tamcmc_summary_totals t;
     std::vector<double> mean_M(Nx), var_M(Nx), min_M(Nx), max_M(Nx), var_l(Nx), lppd(Nx);
     rc = tamcmc_summary_result(sum, &t, mean_M.data(), var_M.data(), min_M.data(), max_M.data(), nullptr, var_l.data(), lppd.data());
@@ -633,6 +676,11 @@ int main(int argc, char *argv[])
     tamcmc_moderank_totals mrt{};                           // --modes-rank
     std::vector<double> r_out;
     std::vector<int32_t> r_cut;
+    tamcmc_seismic_info sinfo{};                            // --modes-indices
+    tamcmc_modetable_totals stt{};
+    std::vector<tamcmc_modetable_col> s_col;
+    std::vector<double> s_mean, s_sd, s_q, s_ess, s_tau, s_mcse, s_rhat, s_rout, s_cov;
+    std::vector<int32_t> s_cut, s_rcut, ratio_cols;
     if (modes) {
         auto mfail = [&](const char *what) { return fail(std::string(what) + ": " + tamcmc_strerror(rc) + " " + tamcmc_last_hip_error()); };
         tamcmc_modetable *mt = nullptr;
@@ -679,6 +727,67 @@ int main(int argc, char *argv[])
             if (rc != TAMCMC_OK) return mfail("tamcmc_moderank_diag");
         }
         tamcmc_modetable_destroy(mt);
+        mt = nullptr;
+        // --modes-indices: a table of its own with the indices enabled, the same samples once more
+        if (modes_indices) {
+            rc = tamcmc_modetable_create(&mt, ctx, (int64_t)Nsel);
+            if (rc != TAMCMC_OK) return mfail("tamcmc_modetable_create");
+            if (find_reference(mt, n_cols) != 0) return EXIT_FAILURE;
+            rc = ref_row.empty() ? TAMCMC_E_INVALID : tamcmc_modetable_indices_enable(mt, Nparams, ref_row.data(), &sinfo);
+            if (rc == TAMCMC_E_INVALID) {
+                fprintf(stderr, "chainsummary_hip: --modes-indices refused: %s; no .modes.indices file is written\n",
+                        ref_row.empty() ? "no sample with an accepted derivation"
+                                        : "the reference sample gives no plan (fewer than 3 radial modes, a radial order missing or the radial ridge "
+                                          "not ascending, no index column, or a row too long for the kernel)");
+                modes_indices = false;
+            } else if (rc != TAMCMC_OK) return mfail("tamcmc_modetable_indices_enable");
+        }
+        if (modes_indices) {
+            const size_t nb = (size_t)sinfo.n_base_cols, ni = (size_t)sinfo.n_index_cols, na = nb + ni;
+            mt_push = mt;
+            if (push_selected() != 0) return EXIT_FAILURE;
+            mt_push = nullptr;
+            s_col.resize(na); s_mean.resize(na); s_sd.resize(na); s_q.assign(mquant.size() * na, std::nan(""));
+            for (size_t k = 0; k < na; k++) tamcmc_modetable_column(mt, (int32_t)k, &s_col[k]);
+            rc = tamcmc_modetable_result(mt, &stt, s_mean.data(), s_sd.data(), nullptr, nullptr);
+            if (rc != TAMCMC_OK) return mfail("tamcmc_modetable_result");
+            const long long need = (modes_ess_lag >= 0 || modes_rank_lag >= 0) ? 4 : 2;
+            if (stt.n_used < need) {
+                fprintf(stderr, "chainsummary_hip: --modes-indices: %lld samples accepted with their indices, %lld needed; no .modes.indices file is written\n",
+                        (long long)stt.n_used, need);
+                modes_indices = false;
+            }
+        }
+        if (modes_indices) {
+            const size_t nb = (size_t)sinfo.n_base_cols, ni = (size_t)sinfo.n_index_cols, na = nb + ni;
+            rc = tamcmc_modetable_quantiles(mt, (int32_t)mquant.size(), mquant.data(), nullptr, s_q.data());
+            if (rc != TAMCMC_OK) return mfail("tamcmc_modetable_quantiles");
+            if (modes_ess_lag >= 0) {
+                tamcmc_modediag_totals unused{};
+                s_ess.resize(na); s_tau.resize(na); s_mcse.resize(na); s_rhat.resize(na); s_cut.resize(na);
+                rc = tamcmc_modediag_ess(mt, (int32_t)modes_ess_lag, &unused, s_ess.data(), s_tau.data(), s_mcse.data(), s_rhat.data(), s_cut.data());
+                if (rc != TAMCMC_OK) return mfail("tamcmc_modediag_ess");
+            }
+            std::vector<int32_t> icols(ni);
+            for (size_t k = 0; k < ni; k++) icols[k] = (int32_t)(nb + k);
+            if (modes_rank_lag >= 0) {
+                tamcmc_moderank_totals unused{};
+                s_rout.resize((size_t)TAMCMC_MODERANK_NOUT * ni); s_rcut.resize((size_t)TAMCMC_MODERANK_NSERIES * ni);
+                rc = tamcmc_moderank_diag(mt, (int32_t)modes_rank_lag, (int32_t)ni, icols.data(), 0, &unused, s_rout.data(), s_rcut.data());
+                if (rc != TAMCMC_OK) return mfail("tamcmc_moderank_diag");
+            }
+            for (size_t k = nb; k < na; k++)
+                if (s_col[k].kind >= TAMCMC_MODETABLE_R02 && s_col[k].kind <= TAMCMC_MODETABLE_R10) ratio_cols.push_back((int32_t)k);
+            if (ratio_cols.size() > TAMCMC_MODEDIAG_MAX_COLS)
+                return fail("--modes-indices: " + std::to_string(ratio_cols.size()) + " ratio columns, more than " +
+                            std::to_string(TAMCMC_MODEDIAG_MAX_COLS) + " of one covariance matrix");
+            s_cov.resize(ratio_cols.size() * ratio_cols.size());
+            if (!ratio_cols.empty()) {
+                rc = tamcmc_modediag_cov(mt, (int32_t)ratio_cols.size(), ratio_cols.data(), s_cov.data());
+                if (rc != TAMCMC_OK) return mfail("tamcmc_modediag_cov");
+            }
+        }
+        if (mt) tamcmc_modetable_destroy(mt);
     }
     tamcmc_ctx_destroy(ctx);
 
@@ -943,6 +1052,52 @@ int main(int argc, char *argv[])
                 fprintf(orank, "\n");
             }
             fclose(orank);
+        }
+        if (modes_indices) {
+            static const char *const index_name[] = {"dnu_fit", "epsilon", "numax", "dnu_nl", "d2nu", "d02", "d13", "d01", "d10", "r02", "r01", "r13", "r10"};
+            const size_t nb = (size_t)sinfo.n_base_cols, ni = (size_t)sinfo.n_index_cols, na = nb + ni;
+            const std::string ind_file = modes_file + ".indices";
+            FILE *oi = fopen(ind_file.c_str(), "w");
+            if (!oi) return fail("unable to open the output file " + ind_file);
+            fprintf(oi, "# chainsummary_hip (%s)\n", tamcmc_version());
+            fprintf(oi, "# quantiles= %s\n", mquant_text.c_str());
+            fprintf(oi, "# n_used= %lld  n_rejected= %lld  n_base_cols= %lld  n_index_cols= %lld  n_radial= %lld  n_unassigned= %lld  n_base= %lld  dnu_ref= %.17g  eps_ref= %.17g\n",
+                    (long long)stt.n_used, (long long)stt.n_rejected, (long long)sinfo.n_base_cols, (long long)sinfo.n_index_cols, (long long)sinfo.n_radial,
+                    (long long)sinfo.n_unassigned, (long long)sinfo.n_base, sinfo.dnu_ref, sinfo.eps_ref);
+            fprintf(oi, "# col kind l n mean sd");
+            for (size_t j = 0; j < mquant.size(); j++) fprintf(oi, " q%.6g", mquant[j]);
+            if (modes_ess_lag >= 0) fprintf(oi, " ess tau mcse rhat cut");
+            if (modes_rank_lag >= 0) fprintf(oi, " ess_bulk ess_tail rhat_rank tau_bulk rhat_bulk rhat_fold ess_q05 ess_q95 cut_z cut_zfold cut_i05 cut_i95");
+            fprintf(oi, "\n");
+            for (size_t k = nb; k < na; k++) {
+                const tamcmc_modetable_col &c = s_col[k];
+                fprintf(oi, "%zu %s %d %d %.17g %.17g", k, index_name[c.kind - TAMCMC_MODETABLE_DNU_FIT], (int)c.l, (int)c.order, s_mean[k], s_sd[k]);
+                for (size_t j = 0; j < mquant.size(); j++) fprintf(oi, " %.17g", s_q[j * na + k]);
+                if (modes_ess_lag >= 0) fprintf(oi, " %.17g %.17g %.17g %.17g %d", s_ess[k], s_tau[k], s_mcse[k], s_rhat[k], (int)s_cut[k]);
+                if (modes_rank_lag >= 0) {
+                    for (size_t j = 0; j < TAMCMC_MODERANK_NOUT; j++) fprintf(oi, " %.17g", s_rout[j * ni + (k - nb)]);
+                    for (size_t j = 0; j < TAMCMC_MODERANK_NSERIES; j++) fprintf(oi, " %d", (int)s_rcut[j * ni + (k - nb)]);
+                }
+                fprintf(oi, "\n");
+            }
+            fclose(oi);
+            const std::string cov_file = ind_file + ".cov";
+            FILE *oc = fopen(cov_file.c_str(), "w");
+            if (!oc) return fail("unable to open the output file " + cov_file);
+            fprintf(oc, "# chainsummary_hip (%s)\n", tamcmc_version());
+            fprintf(oc, "# n_used= %lld  n_rejected= %lld  n_base_cols= %lld  n_index_cols= %lld\n", (long long)stt.n_used, (long long)stt.n_rejected,
+                    (long long)sinfo.n_base_cols, (long long)sinfo.n_index_cols);
+            fprintf(oc, "# cols =");
+            for (const int32_t k : ratio_cols) fprintf(oc, " %d", (int)k);
+            fprintf(oc, "\n# rows =");
+            for (const int32_t k : ratio_cols) fprintf(oc, " %s_n%d", index_name[s_col[(size_t)k].kind - TAMCMC_MODETABLE_DNU_FIT], (int)s_col[(size_t)k].order);
+            fprintf(oc, "\n");
+            const size_t nr = ratio_cols.size();
+            for (size_t i = 0; i < nr; i++) {
+                for (size_t j = 0; j < nr; j++) fprintf(oc, j ? " %.17g" : "%.17g", s_cov[i * nr + j]);
+                fprintf(oc, "\n");
+            }
+            fclose(oc);
         }
     }
     printf("Summary of %lld samples (%lld rejected) written to %s\n", (long long)t.n_used, (long long)t.n_rejected, out_file.c_str());

@@ -74,6 +74,11 @@ Prints one JSON line:
                             kernels of the same rows, and the same lag products and sums of products by the header's serial
                             functions on one host thread (tools/modediag_host_time.cpp, built with g++ when the leg runs) with
                             the ratios.  Only this leg runs.
+  q_seismic_*               with --modes and --modes-indices: the seismic indices (ModeTable.enable_indices, reference row
+                            params_true).  The same rows through a table without and a table with the indices: push on the host
+                            clock, the derive and fold kernels (ModeTable.kernel_time) and the indices kernel alone
+                            (ModeTable.seismic_kernel_time) in microseconds per sample, and the quantile (three
+                            probabilities), ess and rank_diag calls of either table on the host clock.  Only this leg runs.
 Every timed shape is warmed up first (--warmup pushes); host clocks stop after calls that end in a device synchronise.
 """
 import argparse
@@ -492,6 +497,52 @@ def modetable_leg(a, w, P):
     return out
 
 
+def seismic_leg(a, w, P):
+    """(q) the seismic indices: the same rows through a table without and a table with the indices enabled (reference row:
+    params_true) -- push on the host clock, the derive and fold kernels (ModeTable.kernel_time), the indices kernel alone
+    (ModeTable.seismic_kernel_time), and the quantile, ess and rank_diag calls of either table on the host clock."""
+    out = {}
+    q = [0.16, 0.5, 0.84]
+    with tamcmc_amd.Accel(2, w["plength"], w["x"], np.ones(a.nx)) as acc:
+        for tag in ("base", "indices"):
+            with tamcmc_amd.ModeTable(acc, a.samples) as mt:
+                if tag == "indices":
+                    info = mt.enable_indices(w["params_true"])
+                    out.update(q_seismic_index_cols=info["n_index_cols"], q_seismic_base_cols=info["n_base_cols"], q_seismic_n_radial=info["n_radial"],
+                               q_seismic_dnu_ref=info["dnu_ref"], q_seismic_eps_ref=info["eps_ref"])
+                push, kern, seis, quant, ess, rank = [], [], [], [], [], []
+                for k in range(a.warmup + a.steps):
+                    mt.reset()
+                    acc.synchronize()
+                    t0 = time.perf_counter()
+                    mt.push(P)                                  # synchronous
+                    t1 = time.perf_counter()
+                    mt.quantiles(q)
+                    t2 = time.perf_counter()
+                    mt.ess(0)
+                    t3 = time.perf_counter()
+                    mt.rank_diag(0)
+                    t4 = time.perf_counter()
+                    if k >= a.warmup:
+                        push.append(t1 - t0); kern.append(mt.kernel_time()[0]); seis.append(mt.seismic_kernel_time()[0])
+                        quant.append(t2 - t1); ess.append(t3 - t2); rank.append(t4 - t3)
+                res = mt.result()
+                us = 1e3 / a.samples
+                out.update({f"q_seismic_{tag}_cols": mt.n_cols, f"q_seismic_{tag}_block": min(4096, (1 << 23) // mt.n_cols),
+                            f"q_seismic_{tag}_push_s_per_1000": float(np.median(push)) * 1000.0 / a.samples,
+                            f"q_seismic_{tag}_derive_fold_us_per_sample": float(np.median(kern)) * us,
+                            f"q_seismic_{tag}_derive_fold_spread_us": [float(min(kern)) * us, float(max(kern)) * us],
+                            f"q_seismic_{tag}_quantiles_call_ms": float(np.median(quant)) * 1e3,
+                            f"q_seismic_{tag}_ess_call_ms": float(np.median(ess)) * 1e3,
+                            f"q_seismic_{tag}_rank_diag_call_ms": float(np.median(rank)) * 1e3,
+                            f"q_seismic_{tag}_n_used": res["n_used"]})
+                if tag == "indices":
+                    out.update(q_seismic_kernel_us_per_sample=float(np.median(seis)) * us,
+                               q_seismic_kernel_spread_us=[float(min(seis)) * us, float(max(seis)) * us],
+                               q_seismic_kernel_launches=mt.seismic_kernel_time()[1])
+    return out
+
+
 def modediag_leg(a, w, P):
     """(o) the diagnostics of the mode table's columns: the kernels of an ess and of a cov call, the host's serial loops."""
     import subprocess
@@ -669,12 +720,14 @@ def main():
     ap.add_argument("--modes-ess", type=int, default=-1, help="L: with --modes, ESS / MCSE / R-hat of the table's columns (0: the library's lag limit)")
     ap.add_argument("--modes-cov", action="store_true", help="with --modes, the covariance matrix of all columns")
     ap.add_argument("--modes-rank", type=int, default=-1, help="L: with --modes, the rank-normalised diagnostics of the table's columns (0: the library's lag limit)")
+    ap.add_argument("--modes-indices", action="store_true", help="with --modes, the seismic indices: the indices kernel beside derive and fold, the "
+                    "quantile, ess and rank_diag calls on the enlarged table beside the base table")
     ap.add_argument("--scan-null", type=int, default=0, help="R: replicates per run of the scan's Monte-Carlo null (widths of --scan)")
     a = ap.parse_args()
     if a.steps < 1 or a.warmup < 0 or a.samples < 1 or a.samples_b < 2 or a.scan_null < 0:
         ap.error("--steps >= 1, --warmup >= 0, --samples >= 1, --samples-b >= 2, --scan-null >= 0")
-    if (a.modes_ess >= 0 or a.modes_cov or a.modes_rank >= 0) and not a.modes:
-        ap.error("--modes-ess, --modes-cov and --modes-rank need --modes")
+    if (a.modes_ess >= 0 or a.modes_cov or a.modes_rank >= 0 or a.modes_indices) and not a.modes:
+        ap.error("--modes-ess, --modes-cov, --modes-rank and --modes-indices need --modes")
     if a.scan_null:
         out = dict(tool="summary_time", Nx=a.nx, steps=a.steps, warmup=a.warmup, version=tamcmc_amd.capi.version())
         out.update(scan_null_leg(a))
@@ -684,7 +737,7 @@ def main():
     P = synth.chain_params(w, a.samples)
     if a.modes:
         out = dict(tool="summary_time", Nx=a.nx, samples=a.samples, steps=a.steps, warmup=a.warmup, version=tamcmc_amd.capi.version())
-        out.update(moderank_leg(a, w, P) if a.modes_rank >= 0 else modediag_leg(a, w, P) if a.modes_ess >= 0 or a.modes_cov else modetable_leg(a, w, P))
+        out.update(seismic_leg(a, w, P) if a.modes_indices else moderank_leg(a, w, P) if a.modes_rank >= 0 else modediag_leg(a, w, P) if a.modes_ess >= 0 or a.modes_cov else modetable_leg(a, w, P))
         print(json.dumps(out))
         return
     with tamcmc_amd.Accel(2, w["plength"], w["x"], np.ones(a.nx)) as acc:
