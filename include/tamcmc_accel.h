@@ -1103,4 +1103,7 @@ const char *tamcmc_version(void);
 /* The seismic indices of the mode table (large separation, epsilon, nu_max, small separations, frequency ratios as further
  * columns of the table): the kind codes after TAMCMC_MODETABLE_H_M and the entry points, in a header of their own. */
 #include "tamcmc_accel_seismic.h"
+/* Marginal histograms, shortest (HPD) intervals and pair densities of the mode table's columns: the tamcmc_modepdf_* entry
+ * points, in a header of their own. */
+#include "tamcmc_accel_pdf.h"
 #endif /* TAMCMC_ACCEL_H */

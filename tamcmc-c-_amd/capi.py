@@ -53,6 +53,9 @@ EXPORTS = [
 # what include/tamcmc_accel_seismic.h declares (tamcmc_accel.h includes it)
 SEISMIC_EXPORTS = ["tamcmc_modetable_indices_enable", "tamcmc_modetable_indices_info", "tamcmc_modetable_index_terms",
                    "tamcmc_seismic_kernel_time"]
+# what include/tamcmc_accel_pdf.h declares (tamcmc_accel.h includes it)
+PDF_EXPORTS = ["tamcmc_modepdf_hist", "tamcmc_modepdf_hpd", "tamcmc_modepdf_hist2d", "tamcmc_modepdf_kernel_time"]
+MODEPDF_MAX_BINS, MODEPDF_MAX_BINS2D, MODEPDF_MAX_PAIRS, MODEPDF_MAX_MASS, MODEPDF_RANGE = 4096, 128, 1024, 8, 1
 
 
 class SummaryTotals(C.Structure):
@@ -311,7 +314,11 @@ def load_library():
     lib.tamcmc_modetable_indices_info.argtypes = [vp, C.POINTER(SeismicInfo)]
     lib.tamcmc_modetable_index_terms.argtypes = [vp, C.c_int32, C.c_int32, ip, ip, ip, ip, dp, dp]
     lib.tamcmc_seismic_kernel_time.argtypes = [vp, dp, lp]
-    for name in EXPORTS + SEISMIC_EXPORTS:
+    lib.tamcmc_modepdf_hist.argtypes = [vp, C.c_int32, C.c_int32, ip, dp, dp, lp, lp, lp, dp, ip]
+    lib.tamcmc_modepdf_hpd.argtypes = [vp, C.c_int32, dp, C.c_int32, ip, C.c_int64, lp, lp, dp, dp]
+    lib.tamcmc_modepdf_hist2d.argtypes = [vp, C.c_int32, C.c_int32, ip, dp, dp, C.c_int32, dp, lp, lp, lp, ip]
+    lib.tamcmc_modepdf_kernel_time.argtypes = [vp, dp, lp]
+    for name in EXPORTS + SEISMIC_EXPORTS + PDF_EXPORTS:
         fn = getattr(lib, name)
         if fn.restype is not C.c_char_p:
             fn.restype = C.c_int
@@ -1479,6 +1486,99 @@ class ModeTable:
         ms = C.c_double(0.0)
         n = C.c_int64(0)
         self._check(self._lib.tamcmc_moderank_kernel_time(self._mt, C.byref(ms), C.byref(n)), "tamcmc_moderank_kernel_time")
+        return ms.value, n.value
+
+    def _selection(self, cols):
+        if cols is None:
+            return self.n_cols, None
+        sel = np.ascontiguousarray(cols, dtype=np.int32)
+        if sel.ndim != 1:
+            raise ValueError("cols must be a sequence of column indices")
+        return sel.size, sel
+
+    @staticmethod
+    def _range(lo, hi, m):
+        """(lo, hi) as m doubles each, or (None, None)"""
+        if lo is None and hi is None:
+            return None, None
+        if lo is None or hi is None:
+            raise ValueError("lo and hi go together")
+        lo, hi = _c64(np.ravel(lo)), _c64(np.ravel(hi))
+        if lo.size != m or hi.size != m:
+            raise ValueError(f"lo and hi must have {m} entries each")
+        return lo, hi
+
+    def hist(self, bins, cols=None, lo=None, hi=None):
+        """Marginal histograms (tamcmc_modepdf_hist) of the columns `cols`, in that order (None: all), in `bins` uniform
+        classes over lo ... hi (n_sel doubles each; None: the column's min and max): dict of counts (n_sel, bins), below,
+        above (n_sel) int64, range (n_sel, 2), status (n_sel int32; 1: a default range that is not finite, every count 0)
+        and cols.  The class rule is that of tamcmc_accel_pdf.h; hist_edges() gives the edges for a plot."""
+        n_sel, sel = self._selection(cols)
+        m, nb = max(n_sel, 1), max(int(bins), 1)
+        lo, hi = self._range(lo, hi, n_sel)
+        counts = np.zeros((m, nb), dtype=np.int64)
+        below, above = np.zeros(m, dtype=np.int64), np.zeros(m, dtype=np.int64)
+        rng, status = np.zeros((m, 2)), np.zeros(m, dtype=np.int32)
+        l64 = C.POINTER(C.c_int64)
+        self._check(self._lib.tamcmc_modepdf_hist(self._mt, int(bins), n_sel, _iptr(sel), _dptr(lo), _dptr(hi), counts.ctypes.data_as(l64),
+                                                  below.ctypes.data_as(l64), above.ctypes.data_as(l64), _dptr(rng), _iptr(status)),
+                    "tamcmc_modepdf_hist")
+        return dict(counts=counts, below=below, above=above, range=rng, status=status,
+                    cols=np.arange(n_sel, dtype=np.int32) if sel is None else sel.copy())
+
+    @staticmethod
+    def hist_edges(range, bins):
+        """The bins + 1 plot edges lo + (hi - lo) * (b / bins) of one range (lo, hi), the last one hi exactly.  For plots:
+        the counts follow the class rule, not these edges."""
+        lo, hi = (float(v) for v in range)
+        e = np.float64(lo) + (np.float64(hi) - np.float64(lo)) * (np.arange(bins + 1, dtype=np.float64) / np.float64(bins))
+        e[bins] = hi
+        return e
+
+    def hpd(self, mass, cols=None, scratch_bytes=0):
+        """Shortest intervals (tamcmc_modepdf_hpd) holding each of `mass` (in (0, 1]) of the columns `cols`: dict of mass,
+        k (n_mass int64: the window lengths), start (n_mass, n_sel) int64, lo, hi (n_mass, n_sel) and cols.  The columns are
+        sorted in chunks that fit scratch_bytes of device memory (0: 256 MiB); no result bit depends on it."""
+        mass = _c64(np.atleast_1d(mass))
+        if mass.ndim != 1:
+            raise ValueError("mass must be a sequence of probabilities")
+        n_sel, sel = self._selection(cols)
+        nm, m = max(mass.size, 1), max(n_sel, 1)
+        k, start = np.zeros(nm, dtype=np.int64), np.zeros((nm, m), dtype=np.int64)
+        lo, hi = np.zeros((nm, m)), np.zeros((nm, m))
+        l64 = C.POINTER(C.c_int64)
+        self._check(self._lib.tamcmc_modepdf_hpd(self._mt, mass.size, _dptr(mass), n_sel, _iptr(sel), int(scratch_bytes), k.ctypes.data_as(l64),
+                                                 start.ctypes.data_as(l64), _dptr(lo), _dptr(hi)), "tamcmc_modepdf_hpd")
+        return dict(mass=mass.copy(), k=k[:mass.size], start=start[:mass.size], lo=lo[:mass.size], hi=hi[:mass.size],
+                    cols=np.arange(n_sel, dtype=np.int32) if sel is None else sel.copy())
+
+    def hist2d(self, pairs, bins, lo=None, hi=None, mass=()):
+        """Pair densities (tamcmc_modepdf_hist2d) of the column pairs `pairs` (n_pairs, 2) in bins x bins classes over
+        lo ... hi ((n_pairs, 2) each; None: the columns' min and max): dict of counts (n_pairs, bins, bins) int64, the first
+        axis the pair's first column, outside (n_pairs), level (n_mass, n_pairs) int64 -- the contour levels of `mass` -- and
+        status (n_pairs)."""
+        pr = np.ascontiguousarray(pairs, dtype=np.int32)
+        if pr.ndim != 2 or pr.shape[1] != 2:
+            raise ValueError("pairs must be (n_pairs, 2) column indices")
+        n_pairs = pr.shape[0]
+        mass = _c64(np.atleast_1d(mass)) if np.size(mass) else np.zeros(0)
+        lo, hi = self._range(lo, hi, 2 * n_pairs)
+        m, nb = max(n_pairs, 1), max(int(bins), 1)
+        counts = np.zeros((m, nb, nb), dtype=np.int64)
+        outside, level = np.zeros(m, dtype=np.int64), np.zeros((max(mass.size, 1), m), dtype=np.int64)
+        status = np.zeros(m, dtype=np.int32)
+        l64 = C.POINTER(C.c_int64)
+        self._check(self._lib.tamcmc_modepdf_hist2d(self._mt, int(bins), n_pairs, _iptr(pr), _dptr(lo), _dptr(hi), mass.size,
+                                                    _dptr(mass) if mass.size else None, counts.ctypes.data_as(l64), outside.ctypes.data_as(l64),
+                                                    level.ctypes.data_as(l64) if mass.size else None, _iptr(status)), "tamcmc_modepdf_hist2d")
+        return dict(counts=counts, outside=outside, level=level[:mass.size], status=status, pairs=pr.copy())
+
+    def pdf_kernel_time(self):
+        """(summed milliseconds, launches) of the histogram, pair and HPD kernels, hpd's sort launches included, since the
+        object was created or reset."""
+        ms = C.c_double(0.0)
+        n = C.c_int64(0)
+        self._check(self._lib.tamcmc_modepdf_kernel_time(self._mt, C.byref(ms), C.byref(n)), "tamcmc_modepdf_kernel_time")
         return ms.value, n.value
 
     def close(self):

@@ -1,8 +1,8 @@
 // tamcmc_modetable_api.cpp -- host side of the posterior mode table (tamcmc_modetable_* in include/tamcmc_accel.h): the
 // object, its blocks and the results.  The kernels are in tamcmc_modetable.hip, the column layout and the shared
 // arithmetic in tamcmc_modetable.h, the object's struct in tamcmc_modetable_obj.h (tamcmc_modediag_api.cpp,
-// tamcmc_moderank_api.cpp and tamcmc_seismic_api.cpp work on it too; the last one appends the seismic indices as further
-// columns, and a block then runs its indices kernel between the derive and the fold kernel).
+// tamcmc_moderank_api.cpp, tamcmc_modepdf_api.cpp and tamcmc_seismic_api.cpp work on it too; the last one appends the seismic
+// indices as further columns, and a block then runs its indices kernel between the derive and the fold kernel).
 //
 // A push takes its samples in blocks of B on the context's stream: the params rows go to the device, the derive kernel
 // writes B x n_cols rows and B status codes, the status codes come back, the host decides which samples are accepted
@@ -78,6 +78,7 @@ static int mt_clear(tamcmc_modetable *mt)
     mt->acov_valid = false; mt->diag_ms = 0.0; mt->diag_launches = 0;      // tamcmc_modediag_*
     mt->rk_valid = false; mt->rk_ms = 0.0; mt->rk_launches = 0;            // tamcmc_moderank_*
     mt->seis_ms = 0.0; mt->seis_launches = 0;                              // tamcmc_modetable_indices_* (the plan stays)
+    mt->pdf_ms = 0.0; mt->pdf_launches = 0;                                // tamcmc_modepdf_*
     TM_HIP(hipMemsetAsync(mt->d_state, 0, mt->state_doubles() * sizeof(double), mt->c->stream));
     return TAMCMC_OK;
 }
@@ -132,6 +133,7 @@ extern "C" int tamcmc_modetable_destroy(tamcmc_modetable *mt)
     (void)hipFree(mt->d_acc); (void)hipFree(mt->d_cut); (void)hipFree(mt->d_S); (void)hipFree(mt->d_sel);
     (void)hipFree(mt->d_rk);
     (void)hipFree(mt->d_seis_i); (void)hipFree(mt->d_seis_d);
+    (void)hipFree(mt->d_pdf);
     for (hipEvent_t e : mt->seis_ev) if (e) (void)hipEventDestroy(e);
     for (hipEvent_t e : mt->ev) if (e) (void)hipEventDestroy(e);
     delete mt;

@@ -1,7 +1,8 @@
 // tamcmc_modetable_obj.h -- internal to csrc/: the posterior mode table's object, shared by the source files that work on
 // it: tamcmc_modetable_api.cpp (the table, its statistics and quantiles), tamcmc_modediag_api.cpp (ESS, MCSE, split
-// R-hat, covariances and correlations of its columns), tamcmc_moderank_api.cpp (their rank-normalised counterparts) and
-// tamcmc_seismic_api.cpp (the seismic indices appended to its columns).
+// R-hat, covariances and correlations of its columns), tamcmc_moderank_api.cpp (their rank-normalised counterparts),
+// tamcmc_seismic_api.cpp (the seismic indices appended to its columns) and tamcmc_modepdf_api.cpp (histograms, shortest
+// intervals and pair densities of its columns).
 #pragma once
 #include "tamcmc_host.h"
 #include "tamcmc_modetable.h"
@@ -51,6 +52,11 @@ struct tamcmc_modetable {
     hipEvent_t seis_ev[2] = {nullptr, nullptr};
     double seis_ms = 0.0;                // indices kernel since create / reset
     int64_t seis_launches = 0;
+    // tamcmc_modepdf_* (tamcmc_modepdf_api.cpp); nothing below is allocated before the first call that needs it
+    void *d_pdf = nullptr;               // a call's arguments and counters, or an HPD chunk's keys and results
+    size_t pdf_bytes = 0;                // its size
+    double pdf_ms = 0.0;                 // histogram, pair and HPD kernels and the sort launches of _hpd since create / reset
+    int64_t pdf_launches = 0;
 };
 
 // tamcmc_seismic_api.cpp, called by a block of tamcmc_modetable_derive / _push behind the derive kernel when n_index_cols > 0:

@@ -6,7 +6,8 @@
 //                    [--quantiles q1,q2,...] [--qbits b] [--loo] [--predictive] [--window W[,first]] [--ess [L]]
 //                    [--scan W0[,W1,...]] [--scan-below T] [--scan-null R[,seed]] [--band-ess [L]] [--loo-pit]
 //                    [--loo-window W[,first]] [--modes [q1,q2,...]] [--modes-ess [L]] [--modes-corr]
-//                    [--modes-rank [L]] [--modes-indices]
+//                    [--modes-rank [L]] [--modes-indices] [--modes-hist [N]] [--modes-hpd m1[,m2,...]]
+//                    [--modes-pairs c1:c2[,c3:c4,...] [N]]
 //
 // <config dir> is the reference's Config/default; model id, likelihood, p, plength, the inputs row and the relax mask
 // come from the setup it describes (tamcmc_setup_create / tamcmc_setup_load, slice s counted from 0).  The samples are
@@ -109,6 +110,20 @@
 // column order: the version, the totals, `# cols = c0 c1 ...`, `# rows = r02_n<n> ...`, then one matrix row per line.  A
 // star the plan refuses (fewer than 3 radial modes, a missing radial order), or a chain of which fewer than 2 samples (4 with
 // --modes-ess or --modes-rank) are accepted with their indices, gets a message and neither file; every other file is written.
+// With --modes-hist [N] (needs --modes; N classes, 1 ... 4096, default 50) the marginal histogram of every column of the
+// table (tamcmc_modepdf_hist over the column's min ... max) goes to <output file>.modes.hist: the version, the .modes totals,
+// `# n_bins= N`, then per column a block: `# col kind mult order l m param_index`, `# range= lo hi  status= s`, `# below= b
+// above= a`, then N lines `edge count` (the class' lower plot edge, 17 significant digits) and a last line `hi` alone.  The
+// edges are for plotting; the counts follow the library's class rule.
+// With --modes-hpd m1[,m2,...] (needs --modes; up to 8 masses in (0, 1], at least 4 accepted samples) the shortest interval
+// holding each mass (tamcmc_modepdf_hpd) goes to <output file>.modes.hpd: the version, the .modes totals, `# mass= m1,m2,...`,
+// `# k= k1 k2 ...`, the column names, then one row per column:
+//   col  kind  mult  order  l  m  param_index  median  [k lo hi per mass]                           (17 significant digits)
+// With --modes-pairs c1:c2[,c3:c4,...] [N] (needs --modes; column indices of the table, N classes an axis, 1 ... 128, default
+// 32) the joint histogram of each pair (tamcmc_modepdf_hist2d over the columns' min ... max) and its contour levels at 68 %
+// and 95 % go to <output file>.modes.pairs: the version, the .modes totals, `# n_bins= N`, then per pair a block: `# pair c1
+// c2`, `# range= lo1 hi1 lo2 hi2  status= s`, `# outside= o  level68= t  level95= t`, then N lines of N counts, the row the
+// class of c1.  None of the three reads the samples again; every other file keeps every byte.
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -127,7 +142,8 @@ static int usage()
                     "                         [--quantiles q1,q2,...] [--qbits b] [--loo] [--predictive] [--window W[,first]] [--ess [L]]\n"
                     "                         [--scan W0[,W1,...]] [--scan-below T] [--scan-null R[,seed]] [--band-ess [L]] [--loo-pit]\n"
                     "                         [--loo-window W[,first]] [--modes [q1,q2,...]] [--modes-ess [L]] [--modes-corr]\n"
-                    "                         [--modes-rank [L]] [--modes-indices]\n"
+                    "                         [--modes-rank [L]] [--modes-indices] [--modes-hist [N]] [--modes-hpd m1[,m2,...]]\n"
+                    "                         [--modes-pairs c1:c2[,c3:c4,...] [N]]\n"
                     "     [1] The directory of config_default.cfg, errors_default.cfg and the *_ctrl.list files (Config/default)\n"
                     "     [2] The .model file and [3] the .data file of the fit\n"
                     "     [4] The root of the parameter files: <root>_chain-<m>.bin and <root>.hdr\n"
@@ -190,6 +206,15 @@ static int usage()
                     "             sample: written to <output file>.modes.indices, one row per index, col kind l n mean sd, one column per\n"
                     "             quantile of --modes, and the columns of --modes-ess / --modes-rank where given; the covariance matrix of\n"
                     "             the ratios to <output file>.modes.indices.cov (the samples are read once more; the other files are unchanged)\n"
+                    "     --modes-hist [N]   needs --modes: the marginal histogram of every quantity of the mode table in N uniform classes\n"
+                    "             (1 ... 4096, default 50) over its min ... max: written to <output file>.modes.hist, one block per quantity,\n"
+                    "             range, below / above, then edge and count per class\n"
+                    "     --modes-hpd m1[,m2,...]   needs --modes: the shortest interval holding each mass (up to 8 values in (0, 1]) of every\n"
+                    "             quantity of the mode table: written to <output file>.modes.hpd, one row per quantity, col kind mult order l m\n"
+                    "             param_index median and per mass k lo hi\n"
+                    "     --modes-pairs c1:c2[,c3:c4,...] [N]   needs --modes: the joint histogram of each pair of table columns in N x N classes\n"
+                    "             (1 ... 128, default 32) with its 68 %% and 95 %% contour levels: written to <output file>.modes.pairs (none of\n"
+                    "             the three reads the samples again; the other files are unchanged)\n"
                     " chainsummary_hip version   prints the library version\n");
     return EXIT_FAILURE;
 }
@@ -235,6 +260,11 @@ int main(int argc, char *argv[])
     bool modes_corr = false;                                // --modes-corr
     long modes_rank_lag = -1;                               // < 0: no --modes-rank
     bool modes_indices = false;                             // --modes-indices
+    long hist_bins = 0;                                     // 0: no --modes-hist
+    std::vector<double> hpd_mass;                           // empty: no --modes-hpd
+    std::string hpd_text;
+    std::vector<int32_t> pair_cols;                         // empty: no --modes-pairs
+    long pair_bins = 32;
     std::vector<double> mquant;
     std::string mquant_text = "0.16,0.5,0.84";
     std::vector<int32_t> scan_W;
@@ -302,6 +332,52 @@ int main(int argc, char *argv[])
         if (a == "--modes-indices") {
             if (modes_indices) return usage();
             modes_indices = true;
+            continue;
+        }
+        if (a == "--modes-hist") {                  // alone, or followed by the number of classes
+            if (hist_bins != 0) return usage();
+            hist_bins = 50;
+            if (i + 1 < argc && argv[i + 1][0] >= '0' && argv[i + 1][0] <= '9') {
+                char *end = nullptr;
+                hist_bins = strtol(argv[++i], &end, 10);
+                if (*end != '\0' || hist_bins < 1 || hist_bins > TAMCMC_MODEPDF_MAX_BINS) return usage();
+            }
+            continue;
+        }
+        if (a == "--modes-hpd") {
+            if (i + 1 >= argc || !hpd_mass.empty()) return usage();
+            hpd_text = argv[++i];
+            for (const char *p = hpd_text.c_str();;) {
+                char *end = nullptr;
+                const double m = strtod(p, &end);
+                if (end == p || !(m > 0.0 && m <= 1.0) || hpd_mass.size() >= TAMCMC_MODEPDF_MAX_MASS) return usage();
+                hpd_mass.push_back(m);
+                if (*end == '\0') break;
+                if (*end != ',') return usage();
+                p = end + 1;
+            }
+            continue;
+        }
+        if (a == "--modes-pairs") {                 // the pairs, then alone or followed by the number of classes an axis
+            if (i + 1 >= argc || !pair_cols.empty()) return usage();
+            for (const char *p = argv[++i];;) {
+                char *end = nullptr;
+                if (*p < '0' || *p > '9') return usage();
+                const long c1 = strtol(p, &end, 10);
+                if (*end != ':' || end[1] < '0' || end[1] > '9') return usage();
+                p = end + 1;
+                const long c2 = strtol(p, &end, 10);
+                if (c1 > 0x7FFFFFFF || c2 > 0x7FFFFFFF || pair_cols.size() >= 2 * (size_t)TAMCMC_MODEPDF_MAX_PAIRS) return usage();
+                pair_cols.push_back((int32_t)c1); pair_cols.push_back((int32_t)c2);
+                if (*end == '\0') break;
+                if (*end != ',') return usage();
+                p = end + 1;
+            }
+            if (i + 1 < argc && argv[i + 1][0] >= '0' && argv[i + 1][0] <= '9') {
+                char *end = nullptr;
+                pair_bins = strtol(argv[++i], &end, 10);
+                if (*end != '\0' || pair_bins < 1 || pair_bins > TAMCMC_MODEPDF_MAX_BINS2D) return usage();
+            }
             continue;
         }
         if (a == "--band-ess") {                    // alone, or followed by the lag limit
@@ -409,6 +485,10 @@ int main(int argc, char *argv[])
     if ((modes_ess_lag >= 0 || modes_corr) && !modes) { fprintf(stderr, "chainsummary_hip: --modes-ess and --modes-corr need --modes\n"); return usage(); }
     if (modes_rank_lag >= 0 && !modes) { fprintf(stderr, "chainsummary_hip: --modes-rank needs --modes\n"); return usage(); }
     if (modes_indices && !modes) { fprintf(stderr, "chainsummary_hip: --modes-indices needs --modes\n"); return usage(); }
+    if ((hist_bins != 0 || !hpd_mass.empty() || !pair_cols.empty()) && !modes) {
+        fprintf(stderr, "chainsummary_hip: --modes-hist, --modes-hpd and --modes-pairs need --modes\n");
+        return usage();
+    }
     if (band_lag >= 0 && quant.empty()) { fprintf(stderr, "chainsummary_hip: --band-ess needs --quantiles\n"); return usage(); }
 
     tamcmc_setup *S = nullptr;
@@ -676,6 +756,14 @@ int main(int argc, char *argv[])
     tamcmc_moderank_totals mrt{};                           // --modes-rank
     std::vector<double> r_out;
     std::vector<int32_t> r_cut;
+    std::vector<int64_t> h_cnt, h_below, h_above;           // --modes-hist
+    std::vector<double> h_range;
+    std::vector<int32_t> h_status;
+    std::vector<int64_t> p_k, p_start;                      // --modes-hpd
+    std::vector<double> p_lo, p_hi, p_med;
+    std::vector<int64_t> j_cnt, j_out, j_level;             // --modes-pairs
+    std::vector<double> j_range;
+    std::vector<int32_t> j_status;
     tamcmc_seismic_info sinfo{};                            // --modes-indices
     tamcmc_modetable_totals stt{};
     std::vector<tamcmc_modetable_col> s_col;
@@ -725,6 +813,35 @@ int main(int argc, char *argv[])
             r_out.resize((size_t)TAMCMC_MODERANK_NOUT * nc); r_cut.resize((size_t)TAMCMC_MODERANK_NSERIES * nc);
             rc = tamcmc_moderank_diag(mt, (int32_t)modes_rank_lag, n_cols, nullptr, 0, &mrt, r_out.data(), r_cut.data());
             if (rc != TAMCMC_OK) return mfail("tamcmc_moderank_diag");
+        }
+        if (hist_bins != 0) {
+            if (mtt.n_used < 1) return fail("--modes-hist needs at least 1 accepted sample");
+            h_cnt.resize(nc * (size_t)hist_bins); h_below.resize(nc); h_above.resize(nc); h_range.resize(2 * nc); h_status.resize(nc);
+            rc = tamcmc_modepdf_hist(mt, (int32_t)hist_bins, n_cols, nullptr, nullptr, nullptr, h_cnt.data(), h_below.data(), h_above.data(),
+                                     h_range.data(), h_status.data());
+            if (rc != TAMCMC_OK) return mfail("tamcmc_modepdf_hist");
+        }
+        if (!hpd_mass.empty()) {
+            if (mtt.n_used < 4) return fail("--modes-hpd needs at least 4 accepted samples");
+            const size_t nm = hpd_mass.size();
+            const double half = 0.5;
+            p_k.resize(nm); p_start.resize(nm * nc); p_lo.resize(nm * nc); p_hi.resize(nm * nc); p_med.resize(nc);
+            rc = tamcmc_modepdf_hpd(mt, (int32_t)nm, hpd_mass.data(), n_cols, nullptr, 0, p_k.data(), p_start.data(), p_lo.data(), p_hi.data());
+            if (rc != TAMCMC_OK) return mfail("tamcmc_modepdf_hpd");
+            rc = tamcmc_modetable_quantiles(mt, 1, &half, nullptr, p_med.data());
+            if (rc != TAMCMC_OK) return mfail("tamcmc_modetable_quantiles");
+        }
+        if (!pair_cols.empty()) {
+            if (mtt.n_used < 1) return fail("--modes-pairs needs at least 1 accepted sample");
+            for (const int32_t c : pair_cols)
+                if (c >= n_cols) return fail("--modes-pairs: column " + std::to_string(c) + " of a table of " + std::to_string(n_cols) + " columns");
+            const size_t np = pair_cols.size() / 2, cells = (size_t)pair_bins * (size_t)pair_bins;
+            const double levels[2] = {0.68, 0.95};
+            j_cnt.resize(np * cells); j_out.resize(np); j_level.resize(2 * np); j_status.resize(np); j_range.resize(4 * np);
+            rc = tamcmc_modepdf_hist2d(mt, (int32_t)pair_bins, (int32_t)np, pair_cols.data(), nullptr, nullptr, 2, levels, j_cnt.data(), j_out.data(),
+                                       j_level.data(), j_status.data());
+            if (rc != TAMCMC_OK) return mfail("tamcmc_modepdf_hist2d");
+            for (size_t k = 0; k < 2 * np; k++) { j_range[2 * k] = m_min[(size_t)pair_cols[k]]; j_range[2 * k + 1] = m_max[(size_t)pair_cols[k]]; }
         }
         tamcmc_modetable_destroy(mt);
         mt = nullptr;
@@ -1052,6 +1169,67 @@ int main(int argc, char *argv[])
                 fprintf(orank, "\n");
             }
             fclose(orank);
+        }
+        auto pdf_open = [&](const std::string &name) {
+            FILE *f = fopen(name.c_str(), "w");
+            if (!f) return f;
+            fprintf(f, "# chainsummary_hip (%s)\n", tamcmc_version());
+            fprintf(f, "# n_used= %lld  n_rejected= %lld  n_cols= %lld  n_mult= %lld\n", (long long)mtt.n_used, (long long)mtt.n_rejected,
+                    (long long)mtt.n_cols, (long long)mtt.n_mult);
+            return f;
+        };
+        if (hist_bins != 0) {
+            const std::string hist_file = modes_file + ".hist";
+            FILE *oh = pdf_open(hist_file);
+            if (!oh) return fail("unable to open the output file " + hist_file);
+            fprintf(oh, "# n_bins= %ld\n", hist_bins);
+            for (size_t k = 0; k < m_col.size(); k++) {
+                const tamcmc_modetable_col &c = m_col[k];
+                const double lo = h_range[2 * k], hi = h_range[2 * k + 1];
+                fprintf(oh, "# col %zu %s %d %d %d %d %d\n", k, kind_name[c.kind], (int)c.mult, (int)c.order, (int)c.l, (int)c.m, (int)c.param_index);
+                fprintf(oh, "# range= %.17g %.17g  status= %d\n", lo, hi, (int)h_status[k]);
+                fprintf(oh, "# below= %lld  above= %lld\n", (long long)h_below[k], (long long)h_above[k]);
+                for (long b = 0; b < hist_bins; b++)     // the plot edge of tamcmc_accel_pdf.h: lo + (hi - lo) * (b / n_bins)
+                    fprintf(oh, "%.17g %lld\n", lo + (hi - lo) * ((double)b / (double)hist_bins), (long long)h_cnt[k * (size_t)hist_bins + (size_t)b]);
+                fprintf(oh, "%.17g\n", hi);
+            }
+            fclose(oh);
+        }
+        if (!hpd_mass.empty()) {
+            const std::string hpd_file = modes_file + ".hpd";
+            FILE *op = pdf_open(hpd_file);
+            if (!op) return fail("unable to open the output file " + hpd_file);
+            const size_t nm = hpd_mass.size(), nc = m_col.size();
+            fprintf(op, "# mass= %s\n# k=", hpd_text.c_str());
+            for (size_t m = 0; m < nm; m++) fprintf(op, " %lld", (long long)p_k[m]);
+            fprintf(op, "\n# col kind mult order l m param_index median");
+            for (size_t m = 0; m < nm; m++) fprintf(op, " k%.6g lo%.6g hi%.6g", hpd_mass[m], hpd_mass[m], hpd_mass[m]);
+            fprintf(op, "\n");
+            for (size_t k = 0; k < nc; k++) {
+                const tamcmc_modetable_col &c = m_col[k];
+                fprintf(op, "%zu %s %d %d %d %d %d %.17g", k, kind_name[c.kind], (int)c.mult, (int)c.order, (int)c.l, (int)c.m, (int)c.param_index, p_med[k]);
+                for (size_t m = 0; m < nm; m++) fprintf(op, " %lld %.17g %.17g", (long long)p_k[m], p_lo[m * nc + k], p_hi[m * nc + k]);
+                fprintf(op, "\n");
+            }
+            fclose(op);
+        }
+        if (!pair_cols.empty()) {
+            const std::string pairs_file = modes_file + ".pairs";
+            FILE *oj = pdf_open(pairs_file);
+            if (!oj) return fail("unable to open the output file " + pairs_file);
+            const size_t np = pair_cols.size() / 2, nb = (size_t)pair_bins;
+            fprintf(oj, "# n_bins= %ld\n", pair_bins);
+            for (size_t p = 0; p < np; p++) {
+                fprintf(oj, "# pair %d %d\n", (int)pair_cols[2 * p], (int)pair_cols[2 * p + 1]);
+                fprintf(oj, "# range= %.17g %.17g %.17g %.17g  status= %d\n", j_range[4 * p], j_range[4 * p + 1], j_range[4 * p + 2], j_range[4 * p + 3],
+                        (int)j_status[p]);
+                fprintf(oj, "# outside= %lld  level68= %lld  level95= %lld\n", (long long)j_out[p], (long long)j_level[p], (long long)j_level[np + p]);
+                for (size_t a = 0; a < nb; a++) {
+                    for (size_t b = 0; b < nb; b++) fprintf(oj, b ? " %lld" : "%lld", (long long)j_cnt[(p * nb + a) * nb + b]);
+                    fprintf(oj, "\n");
+                }
+            }
+            fclose(oj);
         }
         if (modes_indices) {
             static const char *const index_name[] = {"dnu_fit", "epsilon", "numax", "dnu_nl", "d2nu", "d02", "d13", "d01", "d10", "r02", "r01", "r13", "r10"};

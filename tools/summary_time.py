@@ -67,6 +67,12 @@ Prints one JSON line:
   p_moderank_*              with --modes and --modes-rank L: the rank-normalised diagnostics of that table's columns -- the summed
                             kernel time of a rank_diag call (sort twice, transform, mean, lag, finish per chunk), the call's wall
                             time, and the same statements on one host thread (tools/moderank_host_time.cpp, std::sort)
+  r_modepdf_*               with --modes and --modes-pdf: the marginal posteriors of that table's columns -- the hist call at 50 classes
+                            on all columns and on the integer window-edge columns alone, the hpd call at masses 0.68 and 0.95 and at
+                            mass 1 (one window start: the sort launch by itself), the hist2d call over the
+                            (width, height) pair of every multiplet at 32 classes: kernel time and wall time of each, beside the
+                            table's own derive and fold kernels and the same statements on one host thread
+                            (tools/modepdf_host_time.cpp, std::sort)
   o_modediag_*              with --modes and --modes-ess L and / or --modes-cov: the diagnostics of that table's columns
                             (ModeTable.ess / ModeTable.cov) on the rows it holds: per call the kernels alone from the object's HIP
                             events (ModeTable.diag_kernel_time: lag and finish kernels of an ess call together, the covariance
@@ -634,6 +640,55 @@ def moderank_leg(a, w, P):
     return out
 
 
+def modepdf_leg(a, w, P):
+    """(r) histograms, shortest intervals and pair densities of the mode table's columns: per call the summed kernel time
+    (ModeTable.pdf_kernel_time) and the wall time, the share of the sort launches in the hpd call, and the serial statements on
+    one host thread (tools/modepdf_host_time.cpp)."""
+    import subprocess
+    import tempfile
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    out = {}
+    with tamcmc_amd.Accel(2, w["plength"], w["x"], np.ones(a.nx)) as acc:
+        with tamcmc_amd.ModeTable(acc, a.samples) as mt:
+            mt.push(P)
+            table_ms, table_launches = mt.kernel_time()
+            n, n_cols = mt.result()["n_used"], mt.n_cols
+            cols = mt.columns()
+            K = tamcmc_amd.ModeTable.KINDS
+            wcol = {int(c["mult"]): k for k, c in enumerate(cols) if K[c["kind"]] == "width"}
+            hcol = {int(c["mult"]): k for k, c in enumerate(cols) if K[c["kind"]] == "height"}
+            pairs = np.array([[wcol[m], hcol[m]] for m in sorted(wcol)], dtype=np.int32)
+            edge = [k for k, c in enumerate(cols) if K[c["kind"]] in ("window_lo", "window_hi")]
+            calls = (("hist", lambda: mt.hist(50)), ("hist_edges", lambda: mt.hist(50, edge)), ("hpd", lambda: mt.hpd([0.68, 0.95])),
+                     ("hpd_sort", lambda: mt.hpd([1.0])),          # k = n: the window kernel has one start, the rest is the sort launch
+                     ("hist2d", lambda: mt.hist2d(pairs, 32, mass=(0.68, 0.95))))
+            for name, fn in calls:
+                ker, call = [], []
+                for k in range(a.warmup + a.steps):
+                    ms0, l0 = mt.pdf_kernel_time()
+                    t0 = time.perf_counter()
+                    fn()                                         # synchronous
+                    t1 = time.perf_counter()
+                    if k >= a.warmup:
+                        ker.append(mt.pdf_kernel_time()[0] - ms0); call.append((t1 - t0) * 1e3)
+                    launches = mt.pdf_kernel_time()[1] - l0
+                out.update({f"r_modepdf_{name}_kernels_ms": float(np.median(ker)), f"r_modepdf_{name}_kernels_spread_ms": [min(ker), max(ker)],
+                            f"r_modepdf_{name}_call_ms": float(np.median(call)), f"r_modepdf_{name}_call_spread_ms": [min(call), max(call)],
+                            f"r_modepdf_{name}_launches": launches})
+            ms0 = mt.rank_kernel_time()[0]
+            mt.rank_diag(1)
+            out.update(r_modepdf_cols=n_cols, r_modepdf_n=n, r_modepdf_pairs=len(pairs), r_modepdf_edge_cols=len(edge),
+                       r_modepdf_table_kernels_ms=table_ms, r_modepdf_table_launches=table_launches,
+                       r_modepdf_rank_diag_kernels_ms=mt.rank_kernel_time()[0] - ms0)
+    with tempfile.TemporaryDirectory() as tmp:
+        exe = os.path.join(tmp, "modepdf_host_time")
+        subprocess.run(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-I", os.path.join(root, "tamcmc-c-_amd", "csrc"),
+                        os.path.join(root, "tools", "modepdf_host_time.cpp"), "-o", exe], check=True)
+        host = json.loads(subprocess.run([exe, str(n), str(n_cols), str(len(pairs))], check=True, capture_output=True, text=True).stdout)
+    out.update({"r_modepdf_" + k: v for k, v in host.items() if k != "host_sink"})
+    return out
+
+
 def bandess_leg(a, w, y, P):
     """(k) the fold pass beside the band ESS pass of the same rows, and the kernels' own times."""
     out = {}
@@ -722,12 +777,14 @@ def main():
     ap.add_argument("--modes-rank", type=int, default=-1, help="L: with --modes, the rank-normalised diagnostics of the table's columns (0: the library's lag limit)")
     ap.add_argument("--modes-indices", action="store_true", help="with --modes, the seismic indices: the indices kernel beside derive and fold, the "
                     "quantile, ess and rank_diag calls on the enlarged table beside the base table")
+    ap.add_argument("--modes-pdf", action="store_true", help="with --modes, the histograms, shortest intervals and pair densities of the "
+                    "table's columns beside derive and fold and beside one host thread")
     ap.add_argument("--scan-null", type=int, default=0, help="R: replicates per run of the scan's Monte-Carlo null (widths of --scan)")
     a = ap.parse_args()
     if a.steps < 1 or a.warmup < 0 or a.samples < 1 or a.samples_b < 2 or a.scan_null < 0:
         ap.error("--steps >= 1, --warmup >= 0, --samples >= 1, --samples-b >= 2, --scan-null >= 0")
-    if (a.modes_ess >= 0 or a.modes_cov or a.modes_rank >= 0 or a.modes_indices) and not a.modes:
-        ap.error("--modes-ess, --modes-cov, --modes-rank and --modes-indices need --modes")
+    if (a.modes_ess >= 0 or a.modes_cov or a.modes_rank >= 0 or a.modes_indices or a.modes_pdf) and not a.modes:
+        ap.error("--modes-ess, --modes-cov, --modes-rank, --modes-indices and --modes-pdf need --modes")
     if a.scan_null:
         out = dict(tool="summary_time", Nx=a.nx, steps=a.steps, warmup=a.warmup, version=tamcmc_amd.capi.version())
         out.update(scan_null_leg(a))
@@ -737,7 +794,7 @@ def main():
     P = synth.chain_params(w, a.samples)
     if a.modes:
         out = dict(tool="summary_time", Nx=a.nx, samples=a.samples, steps=a.steps, warmup=a.warmup, version=tamcmc_amd.capi.version())
-        out.update(seismic_leg(a, w, P) if a.modes_indices else moderank_leg(a, w, P) if a.modes_rank >= 0 else modediag_leg(a, w, P) if a.modes_ess >= 0 or a.modes_cov else modetable_leg(a, w, P))
+        out.update(modepdf_leg(a, w, P) if a.modes_pdf else seismic_leg(a, w, P) if a.modes_indices else moderank_leg(a, w, P) if a.modes_rank >= 0 else modediag_leg(a, w, P) if a.modes_ess >= 0 or a.modes_cov else modetable_leg(a, w, P))
         print(json.dumps(out))
         return
     with tamcmc_amd.Accel(2, w["plength"], w["x"], np.ones(a.nx)) as acc:
