@@ -70,7 +70,12 @@ typedef struct tamcmc_ctx tamcmc_ctx;
 #define TAMCMC_CHAIN_OK            0
 #define TAMCMC_CHAIN_NAN           1  /* logL is NaN: legal, means "reject" (MALA.cpp:475,507-509).  Also where a
                                          width over- or underflows (AppWidth with an absurd exponent): the reference's
-                                         formula stays finite there and loses the move by ~1e4 in logL -- same decision */
+                                         formula stays finite there and loses the move by ~1e4 in logL -- same decision.
+                                         The kernels overflow before the width itself does: a multiplet's components are
+                                         summed over a common denominator, a product of 2 l + 1 factors of the order
+                                         Gamma^2, so a Gamma beyond about 2e51 (l = 1), 1e31 (l = 2), 1e22 (l = 3) or
+                                         1.34e154 (l = 0) gives this code where the reference's model is finite (id 10
+                                         with a width reference frequency of 1e-6: Gamma = 3e37 ... 9e37)              */
 #define TAMCMC_CHAIN_EMPTY_WINDOW  2  /* a truncation window is empty: the reference would exit(EXIT_FAILURE),
                                          build_lorentzian.cpp:428-443; logL is set to NaN                      */
 #define TAMCMC_CHAIN_INTERNAL      3  /* internal consistency check of the tile balancer failed (never expected);
@@ -806,7 +811,11 @@ int tamcmc_scan_null_destroy(tamcmc_scan_null *h);
  * device for all 11 ids that have modes -- and their statistics over the rows pushed: count, mean, standard deviation,
  * minimum, maximum, exact quantiles.  The spectrum plays no part.
  *   Columns, a function of the context's layout alone (tamcmc_modetable_column describes each):
- *     chain level, first:   inclination (degrees, 0 where the model has none), eta, a3, asymmetry
+ *     chain level, first:   inclination (degrees), eta, a3, asymmetry.  The inclination is the one the m-height ratios are
+ *       derived from: ids 2, 9, 10, 11 atan(p4 / p3) of the sqrt(a1) cos i, sqrt(a1) sin i pair, a value in [-90, 90] --
+ *       the quotient's sign decides, not the quadrant of the pair (p3 = 0 gives +-90, p4 = 0 gives 0, both 0 a NaN);
+ *       ids 3, 6, 7, 8 the inclination entry as given, bit for bit, never reduced (150 stays 150, -20 stays -20);
+ *       ids 12, 13, 14, which have none, +0.
  *     per multiplet j = 0 ... n_mult - 1, in the chain's table order, l its degree:
  *       freq, width, height (= sum of the h_m, added in the order m = -l ... l), amplitude (= sqrt((pi height) width), the
  *       reference's H = A^2 / (pi Gamma)), splitting (exactly 0 for l = 0), window_lo, window_hi (the truncation window
@@ -817,9 +826,16 @@ int tamcmc_scan_null_destroy(tamcmc_scan_null *h);
  *     multiplet; m = 0 except on nu_m and h_m columns; param_index = the params index of the mode frequency on freq
  *     columns (the column equals that entry bit for bit), -1 elsewhere.
  *   Status of a sample: the largest status of its multiplets (an empty truncation window: TAMCMC_CHAIN_EMPTY_WINDOW), else
- *     TAMCMC_CHAIN_NAN when any of its columns is a NaN, else TAMCMC_CHAIN_OK -- the code tamcmc_eval_batch gives a row whose
- *     noise parameters are healthy.  A sample whose status is not OK, or whose entry of `skip` is not 0, enters neither the
- *     statistics nor the table, and is counted in n_rejected.
+ *     TAMCMC_CHAIN_NAN when any of its columns is a NaN or the square of a width is infinite (Gamma > 1.34e154: the AppWidth
+ *     width of id 9 with an exponent out of range), else TAMCMC_CHAIN_OK -- the code tamcmc_eval_batch gives a row whose
+ *     noise parameters are healthy, with one exception, "finite columns, overflowing sum": a row whose columns are all
+ *     finite and describe a finite model, but which has a width so large that the eval kernels' sum over the components of
+ *     a multiplet overflows -- they multiply 2 l + 1 factors of the order Gamma^2, so from a Gamma near 2e51 for l = 1,
+ *     1e31 for l = 2 and 1e22 for l = 3 (the AppWidth v2 width of id 10 with a reference frequency of 1e-6 is 3e37 ... 9e37;
+ *     the AppWidth v1 width of id 9 with an exponent of 2600 where its largest value stays below 1.34e154).
+ *     tamcmc_eval_batch gives such a row TAMCMC_CHAIN_NAN, the table TAMCMC_CHAIN_OK: the row is what the reference's
+ *     formulas give, and the model rebuilt from it is the reference's.  A sample whose status is not OK, or whose entry of
+ *     `skip` is not 0, enters neither the statistics nor the table, and is counted in n_rejected.
  *   create       max_samples >= 0 rows of the table are kept on the device for the quantiles: 8 max_samples n_cols bytes,
  *                plus 8 B (Nparams + n_cols + 1) bytes for a block of B = min(4096, 2^23 / n_cols) samples and
  *                128 n_cols + 64 bytes of state; TAMCMC_E_NOMEM when that fails.  max_samples = 0: statistics only.  Refused

@@ -6,7 +6,9 @@
 //              These are the device functions of tamcmc_derive.h that the setup and backward kernels call, compiled here
 //              as there without floating-point contraction: the window indices come out of the same non-fused operations.
 //              Status: the maximum of the multiplets' status (an empty window: TAMCMC_CHAIN_EMPTY_WINDOW), else
-//              TAMCMC_CHAIN_NAN when any column is a NaN.
+//              TAMCMC_CHAIN_NAN when any column is a NaN or the square of a width is infinite (an AppWidth exponent out of
+//              range, Gamma = exp(364): every column is finite, but the setup kernel's Gamma^2 is not and the eval kernels'
+//              Lorentzian is inf / inf).
 //   fold       one thread per column walks the block's accepted samples in push order: Welford mean and sum of squared
 //              deviations, minimum, maximum (tm_mt_fold_one), and appends the value to the column-major table.  Nothing
 //              is shared between threads, so no result bit depends on the block size or on how the samples were pushed.
@@ -25,7 +27,7 @@ __global__ __launch_bounds__(TM_MT_THREADS) void tamcmc_modetable_derive_kernel(
 {
     extern __shared__ double s_p[];          // this sample's params row
     __shared__ TmChain C;
-    __shared__ int s_status[2];              // maximum of the multiplets' status; any column a NaN
+    __shared__ int s_status[2];              // maximum of the multiplets' status; any column a NaN or a width^2 infinite
     const TmLayout &L = a.L;
     const int lane = threadIdx.x, sample = blockIdx.x;
     if (sample >= a.B) return;
@@ -59,6 +61,7 @@ __global__ __launch_bounds__(TM_MT_THREADS) void tamcmc_modetable_derive_kernel(
         o[0] = M.f; o[1] = M.W; o[2] = height; o[3] = amp; o[4] = split;
         o[5] = (double)M.imin; o[6] = (double)M.imax;
         nan = nan || !(M.f == M.f) || !(M.W == M.W) || !(height == height) || !(amp == amp) || !(split == split);
+        nan = nan || M.W * M.W == __builtin_inf();     // the g2 of the setup kernel
 #pragma unroll
         for (int k = 0; k < TM_MAXM; k++) {
             if (k < M.ncomp) {

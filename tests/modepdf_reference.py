@@ -76,7 +76,7 @@ def hpd(V, mass):
     for j in range(ns):
         s = sorted_column(V[:, j])
         for m, km in enumerate(k):
-            with np.errstate(invalid="ignore"):
+            with np.errstate(invalid="ignore", over="ignore"):
                 w = s[km - 1:] - s[:n - km + 1]
             i = 0 if np.all(np.isnan(w)) else int(np.nanargmin(w))     # (argmin returns the first index of the minimum)
             start[m, j], lo[m, j], hi[m, j] = i, s[i], s[i + km - 1]

@@ -86,6 +86,11 @@ def reconstruct(model_case, plength, x, params, row, cols=None):
         nu = row[c0 + 7:c0 + 7 + nc].astype(LD)
         h = row[c0 + 7 + nc:c0 + 7 + 2 * nc].astype(LD)
         d = xs[None, :] - nu[:, None]
+        if G == 0:
+            # a width of exactly 0: the limit the oracle's quotient takes, h / (1 + inf) = 0 in every bin off the component
+            # and h / (1 + 0 / 0) = NaN in a bin exactly on it; nothing for the sensitivity to weigh
+            R[lo:hi] += np.where((d == 0).any(axis=0), LD(np.nan), LD(0))
+            continue
         Lz = 1 / (1 + 4 * d * d / (G * G))
         hL = h[:, None] * Lz
         core = hL.sum(axis=0)
@@ -130,3 +135,25 @@ def q_lm(l, m):
 
 def variant_of(model_case):
     return 1 if model_case in (6, 7, 8) else 2 if model_case in (13, 14) else 0
+
+
+def fold(rows):
+    """float64 restatement of the table's fold (tm_mt_fold_one, serial per column in push order, never contracted) and of
+    the host's finish: dict of mean, sd, min, max of the columns of rows (n, n_cols).
+      d = v - mean; mean += d / n; M2 += d * (v - mean); min / max keep the earlier of two equal values (so the zero that came
+      first, with its sign); sd = sqrt(M2 / (n - 1)), NaN for n < 2."""
+    rows = np.asarray(rows, dtype=np.float64)
+    n, nc = rows.shape
+    mean, M2 = np.zeros(nc), np.zeros(nc)
+    mn, mx = rows[0].copy(), rows[0].copy()
+    with np.errstate(all="ignore"):
+        for t in range(n):
+            v = rows[t]
+            d = v - mean
+            mean = mean + d / np.float64(t + 1)
+            M2 = M2 + d * (v - mean)
+            if t > 0:
+                mn = np.where(v < mn, v, mn)
+                mx = np.where(v > mx, v, mx)
+        sd = np.sqrt(M2 / np.float64(n - 1)) if n >= 2 else np.full(nc, np.nan)
+    return dict(mean=mean, sd=sd, min=mn, max=mx)

@@ -59,3 +59,32 @@ def kernel_usage(make_target):
                          r"LDS Size \[bytes/block\]: (\d+)", txt, flags=re.S):
         usage[m.group(1)] = tuple(int(m.group(k)) for k in (2, 3, 4, 5))
     return usage
+
+
+# The reference's .model files that come without a spectrum, and the reader each is written for
+REF_MODEL_FILES = [("kplr008379927_kasoc-psd_slc_v2_1000.model", "io_MS_Global"), ("00088.0.model", "io_MS_Global"),
+                   ("02194.0.model", "io_MS_Global"), ("kplr008379927_kasoc-psd_slc_v2_1000_local-v2.model", "io_local")]
+
+
+def chains_around(s, n, seed=3, scale=0.3):
+    """n parameter rows: the file's initial guesses, then Gaussian steps of `scale` x the initial proposal errors."""
+    rng = np.random.default_rng(seed)
+    P = np.tile(s.inputs, (n, 1))
+    P[1:, s.index_to_relax] += scale * s.err * rng.standard_normal((n - 1, s.Nvars))
+    return P
+
+
+def load_on_flat_spectrum(name, reader, tmp_path, step=0.02):
+    """The Setup of the reference's .model file `name` (first slice) read by `reader`, on a grid of `step` that covers the
+    slice with a flat spectrum y = 1 standing in for the data the file comes without."""
+    from tamcmc_amd.setup_io import Setup, model_file_slices
+    path = os.path.join(G, name)
+    lo, hi = model_file_slices(path)[0]
+    x = np.arange(lo - 5 * step, hi + 5 * step, step)
+    d = os.path.join(str(tmp_path), "flat.data")
+    with open(d, "w") as f:
+        f.write("# flat\n! frequency power\n* (microHz) (ppm^2/microHz)\n" + "".join("%.8f 1.0\n" % v for v in x))
+    s = Setup(CFG)
+    s.set("Modeling", "prior_fct_name", reader)
+    s.load(path, d, 0)
+    return s

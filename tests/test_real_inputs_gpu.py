@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 import gradcheck
+from support import REF_MODEL_FILES, chains_around, load_on_flat_spectrum
 from tamcmc_amd import sampler as S
 from tamcmc_amd.setup_io import Setup, model_file_slices
 
@@ -19,14 +20,6 @@ TF_MODEL = os.path.join(G, "TF_3443483_local-v3.model")
 TF_DATA = os.path.join(G, "TF_3443483_local-v3.data")
 RTOL_LOGL = 1e-10          # north-star tolerance
 RTOL_MODEL = 1e-12
-
-
-def chains_around(s, n, seed=3, scale=0.3):
-    """n parameter rows: the file's initial guesses, then Gaussian steps of `scale` x the initial proposal errors."""
-    rng = np.random.default_rng(seed)
-    P = np.tile(s.inputs, (n, 1))
-    P[1:, s.index_to_relax] += scale * s.err * rng.standard_normal((n - 1, s.Nvars))
-    return P
 
 
 def check_against_oracle(accel_mod, orc, s, P, T, grad=True):
@@ -76,22 +69,11 @@ def test_gradient_on_the_reference_spectrum(accel_mod, orc):
         assert np.allclose(g[m], fd, rtol=0, atol=2e-5 * scale), (m, np.max(np.abs(g[m] - fd)) / scale)
 
 
-@pytest.mark.parametrize("name,reader", [("kplr008379927_kasoc-psd_slc_v2_1000.model", "io_MS_Global"),
-                                         ("00088.0.model", "io_MS_Global"), ("02194.0.model", "io_MS_Global"),
-                                         ("kplr008379927_kasoc-psd_slc_v2_1000_local-v2.model", "io_local")])
+@pytest.mark.parametrize("name,reader", REF_MODEL_FILES)
 def test_reference_model_files_on_synthetic_spectra(accel_mod, orc, tmp_path, name, reader):
     """The other .model files of the reference come without their spectra: a chi^2_2 realisation of the file's own
     initial model stands in for the data."""
-    path = os.path.join(G, name)
-    lo, hi = model_file_slices(path)[0]
-    step = 0.02
-    x = np.arange(lo - 5 * step, hi + 5 * step, step)
-    d = str(tmp_path / "flat.data")
-    with open(d, "w") as f:
-        f.write("# flat\n! frequency power\n* (microHz) (ppm^2/microHz)\n" + "".join("%.8f 1.0\n" % v for v in x))
-    s = Setup(CFG)
-    s.set("Modeling", "prior_fct_name", reader)
-    s.load(path, d, 0)
+    s = load_on_flat_spectrum(name, reader, tmp_path)
     with accel_mod.Accel(s.model_case, s.plength, s.x, np.ones(s.Nx)) as a0:
         m_true, st = a0.model_explicit(s.inputs)
     assert st == 0 and np.all(m_true > 0)

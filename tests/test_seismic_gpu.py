@@ -30,7 +30,6 @@ import modetable_reference as MR
 import seismic_reference as SR
 import workloads as W
 from support import LD, bits
-from tamcmc_amd import synth
 
 pytestmark = pytest.mark.gpu
 
@@ -45,22 +44,7 @@ GLOBAL = [(lmax, Nmax) for lmax in range(4) for Nmax in (3, 4, 5)] + [(3, 12), (
 LAYOUTS = [("g%d-%d" % c) for c in GLOBAL] + ["local"]
 
 
-def local_layout(Nfl=(4, 3, 4, 2), dnu=14.0, eps=1.3, d0=0.15, n0=6):
-    """id 11 with Nfl modes per degree on the asymptotic pattern (workloads._local_layout's params row: heights, frequencies,
-    6 splitting entries, widths, N0, inclination, trunc_c, do_amp)."""
-    Nx = 3000
-    F = [dnu * (n0 + k + l / 2.0 + eps) - l * (l + 1) * d0 for l in range(4) for k in range(Nfl[l])]
-    nm = len(F)
-    H = [12.0 - 0.5 * j for j in range(nm)]
-    G = [0.15 + 0.005 * j for j in range(nm)]
-    a1, inc = 0.4, math.radians(60.0)
-    split = [a1, 0.0, 0.0, math.sqrt(a1) * math.cos(inc), math.sqrt(a1) * math.sin(inc), 0.0]
-    p = np.array(H + F + split + G + [0.8, 60.0, 20.0, 0.0])
-    relax = np.concatenate([np.ones(2 * nm, dtype=np.int32), [0, 0, 0, 1, 1, 0], np.ones(nm, dtype=np.int32), [1, 0, 0, 0]]).astype(np.int32)
-    pl = np.array([nm, 0] + list(Nfl) + [6, nm, 1, 1, 2], dtype=np.int32)
-    assert p.size == int(pl.sum()) == relax.size
-    return dict(model_case=11, plength=pl, params_true=p, x=synth.grid(Nx, 94.30, 81.2 / Nx), index_to_relax=np.flatnonzero(relax).astype(np.int32),
-                relax=relax)
+local_layout = W.local_asymptotic
 
 
 def layout(name):

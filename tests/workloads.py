@@ -333,6 +333,27 @@ def _local_layout(mid, noise_white=0.8, asym=0.0, trunc_c=20.0, do_amp=False, Nx
                 relax=relax.astype(np.int32))
 
 
+def local_asymptotic(Nfl=(4, 3, 4, 2), dnu=14.0, eps=1.3, d0=0.15, n0=6, asym=0.0, do_amp=False):
+    """id 11 with Nfl modes per degree on the asymptotic pattern nu = dnu (n + l / 2 + eps) - l (l + 1) d0: a local layout with
+    enough radial modes for the seismic indices (_local_layout's params row: heights, frequencies, 6 splitting entries, widths,
+    N0, inclination, trunc_c, do_amp)."""
+    Nx = 3000
+    F = [dnu * (n0 + k + l / 2.0 + eps) - l * (l + 1) * d0 for l in range(4) for k in range(Nfl[l])]
+    nm = len(F)
+    H = [12.0 - 0.5 * j for j in range(nm)]
+    G = [0.15 + 0.005 * j for j in range(nm)]
+    if do_amp:
+        H = [h * math.pi * g for h, g in zip(H, G)]
+    a1, inc = 0.4, math.radians(60.0)
+    split = [a1, 0.0, 0.0, math.sqrt(a1) * math.cos(inc), math.sqrt(a1) * math.sin(inc), asym]
+    p = np.array(H + F + split + G + [0.8, 60.0, 20.0, 1.0 if do_amp else 0.0])
+    relax = np.concatenate([np.ones(2 * nm, dtype=np.int32), [0, 0, 0, 1, 1, 0], np.ones(nm, dtype=np.int32), [1, 0, 0, 0]]).astype(np.int32)
+    pl = np.array([nm, 0] + list(Nfl) + [6, nm, 1, 1, 2], dtype=np.int32)
+    assert p.size == int(pl.sum()) == relax.size
+    return dict(model_case=11, plength=pl, params_true=p, x=synth.grid(Nx, 94.30, 81.2 / Nx), index_to_relax=np.flatnonzero(relax).astype(np.int32),
+                relax=relax)
+
+
 def poly_cells(w, params=None):
     """Number of cells (8 * 512 bins) of one chain whose Harvey background the device evaluates as a Taylor polynomial,
     and the number of cells.  Mirrors the rule of tamcmc_setup_body.h (every active profile h: |p_h| * span <= 0.04 and
