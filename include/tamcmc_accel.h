@@ -1122,4 +1122,7 @@ const char *tamcmc_version(void);
 /* Marginal histograms, shortest (HPD) intervals and pair densities of the mode table's columns: the tamcmc_modepdf_* entry
  * points, in a header of their own. */
 #include "tamcmc_accel_pdf.h"
+/* The comparison of several fits of one spectrum from their pointwise LOO values (elpd differences, Bayesian bootstrap,
+ * pseudo-BMA and stacking weights): the tamcmc_compare_* entry points, in a header of their own. */
+#include "tamcmc_accel_compare.h"
 #endif /* TAMCMC_ACCEL_H */

@@ -15,7 +15,7 @@ Contents (only what the hot path needs):
   synth.py         synthetic spectra / chain parameters of SURVEY.md section 8d
 """
 from . import capi, synth, model_def, shard, sampler, setup_io, outputs, sharded  # noqa: F401
-from .capi import Accel, AccelError, Group, Summary, ScanNull, ModeTable, load_library, library_path  # noqa: F401
+from .capi import Accel, AccelError, Group, Summary, ScanNull, Compare, ModeTable, load_library, library_path  # noqa: F401
 from .model_def import ModelDef, Data  # noqa: F401
 
-__all__ = ["capi", "synth", "model_def", "Accel", "AccelError", "Group", "Summary", "ScanNull", "ModeTable", "load_library", "library_path", "ModelDef", "Data"]
+__all__ = ["capi", "synth", "model_def", "Accel", "AccelError", "Group", "Summary", "ScanNull", "Compare", "ModeTable", "load_library", "library_path", "ModelDef", "Data"]

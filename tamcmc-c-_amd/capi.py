@@ -56,6 +56,24 @@ SEISMIC_EXPORTS = ["tamcmc_modetable_indices_enable", "tamcmc_modetable_indices_
 # what include/tamcmc_accel_pdf.h declares (tamcmc_accel.h includes it)
 PDF_EXPORTS = ["tamcmc_modepdf_hist", "tamcmc_modepdf_hpd", "tamcmc_modepdf_hist2d", "tamcmc_modepdf_kernel_time"]
 MODEPDF_MAX_BINS, MODEPDF_MAX_BINS2D, MODEPDF_MAX_PAIRS, MODEPDF_MAX_MASS, MODEPDF_RANGE = 4096, 128, 1024, 8, 1
+# what include/tamcmc_accel_compare.h declares (tamcmc_accel.h includes it)
+COMPARE_EXPORTS = ["tamcmc_compare_create", "tamcmc_compare_info", "tamcmc_compare_diff", "tamcmc_compare_bootstrap",
+                   "tamcmc_compare_replicates", "tamcmc_compare_z", "tamcmc_compare_prob", "tamcmc_compare_interval",
+                   "tamcmc_compare_weights", "tamcmc_compare_stacking", "tamcmc_compare_stacking_cadence", "tamcmc_compare_variates",
+                   "tamcmc_compare_profile", "tamcmc_compare_kernel_time", "tamcmc_compare_destroy"]
+COMPARE_MAX_FITS, COMPARE_MAX_REPLICATES, COMPARE_TILE, COMPARE_STACK_TILE = 8, 1 << 24, 2048, 4096
+COMPARE_METHODS = {"pseudo_bma": 0, "pseudo_bma_plus": 1, "stacking": 2}
+
+
+class CompareTotals(C.Structure):
+    """tamcmc_compare_totals"""
+    _fields_ = [("n_included", C.c_int64), ("n_excluded", C.c_int64), ("n_better", C.c_int64), ("n_worse", C.c_int64),
+                ("n_k_high", C.c_int64), ("elpd_diff", C.c_double), ("se_diff", C.c_double), ("diff_k_high", C.c_double)]
+
+
+class CompareStackingInfo(C.Structure):
+    """tamcmc_compare_stacking_info"""
+    _fields_ = [("iterations", C.c_int64), ("converged", C.c_int32), ("table", C.c_int32), ("gap", C.c_double), ("f", C.c_double)]
 
 
 class SummaryTotals(C.Structure):
@@ -318,7 +336,22 @@ def load_library():
     lib.tamcmc_modepdf_hpd.argtypes = [vp, C.c_int32, dp, C.c_int32, ip, C.c_int64, lp, lp, dp, dp]
     lib.tamcmc_modepdf_hist2d.argtypes = [vp, C.c_int32, C.c_int32, ip, dp, dp, C.c_int32, dp, lp, lp, lp, ip]
     lib.tamcmc_modepdf_kernel_time.argtypes = [vp, dp, lp]
-    for name in EXPORTS + SEISMIC_EXPORTS + PDF_EXPORTS:
+    lib.tamcmc_compare_create.argtypes = [C.POINTER(vp), C.c_int, C.c_int32, C.c_int64, dp, dp, C.c_double, C.c_uint64, C.c_int64]
+    lib.tamcmc_compare_info.argtypes = [vp, lp, lp]
+    lib.tamcmc_compare_diff.argtypes = [vp, C.c_int32, C.c_int32, C.POINTER(CompareTotals)]
+    lib.tamcmc_compare_bootstrap.argtypes = [vp, C.c_int64, C.c_int64]
+    lib.tamcmc_compare_replicates.argtypes = [vp, lp]
+    lib.tamcmc_compare_z.argtypes = [vp, C.c_int32, dp]
+    lib.tamcmc_compare_prob.argtypes = [vp, C.c_int32, C.c_int32, lp, lp]
+    lib.tamcmc_compare_interval.argtypes = [vp, C.c_int32, C.c_int32, C.c_double, dp]
+    lib.tamcmc_compare_weights.argtypes = [vp, C.c_int32, dp]
+    lib.tamcmc_compare_stacking.argtypes = [vp, C.c_double, C.c_int64, C.c_int64, dp, C.POINTER(CompareStackingInfo)]
+    lib.tamcmc_compare_stacking_cadence.argtypes = [vp, C.c_int32]
+    lib.tamcmc_compare_variates.argtypes = [vp, C.c_int64, dp]
+    lib.tamcmc_compare_profile.argtypes = [vp, C.c_int]
+    lib.tamcmc_compare_kernel_time.argtypes = [vp, C.c_int32, dp, lp]
+    lib.tamcmc_compare_destroy.argtypes = [vp]
+    for name in EXPORTS + SEISMIC_EXPORTS + PDF_EXPORTS + COMPARE_EXPORTS:
         fn = getattr(lib, name)
         if fn.restype is not C.c_char_p:
             fn.restype = C.c_int
@@ -1236,6 +1269,133 @@ class ScanNull:
     def close(self):
         if getattr(self, "_h", None) is not None and self._h.value:
             self._check(self._lib.tamcmc_scan_null_destroy(self._h), "tamcmc_scan_null_destroy")
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
+class Compare:
+    """Comparison of K fits of one spectrum from their pointwise log predictive values (tamcmc_accel_compare.h,
+    tamcmc_compare_*): elpd differences with their standard error, a Bayesian bootstrap of the differences on the device,
+    pseudo-BMA, pseudo-BMA+ and stacking weights.  elpd is (K, N): row k the elpd_loo (or elpd_lwo, or lppd - var_l) of fit k
+    per unit; pareto_k likewise or None; scale 1 for chi(2,2p), 0.5 for chi_square.  Units where any fit is not finite are
+    excluded.  Fit 0 is the reference fit of the bootstrap.  Bound to a device and to no Accel or chain."""
+
+    MAX_FITS = COMPARE_MAX_FITS
+    MAX_REPLICATES = COMPARE_MAX_REPLICATES
+    TILE = COMPARE_TILE
+    STACK_TILE = COMPARE_STACK_TILE
+    TOTALS = ("n_included", "n_excluded", "n_better", "n_worse", "n_k_high", "elpd_diff", "se_diff", "diff_k_high")
+
+    def __init__(self, elpd, pareto_k=None, scale=1.0, seed=0, first_replicate=0, device_id=0):
+        self._lib = load_library()
+        self._h = C.c_void_p()
+        e = np.ascontiguousarray(elpd, dtype=np.float64)
+        if e.ndim != 2:
+            raise ValueError("elpd must be (K, N)")
+        kh = _c64(pareto_k, e.shape) if pareto_k is not None else None
+        self.K, self.N = int(e.shape[0]), int(e.shape[1])
+        self.scale = float(scale)
+        self._check(self._lib.tamcmc_compare_create(C.byref(self._h), int(device_id), self.K, self.N, _dptr(e), _dptr(kh), self.scale,
+                                                    int(seed), int(first_replicate)), "tamcmc_compare_create")
+        inc, exc = C.c_int64(0), C.c_int64(0)
+        self._check(self._lib.tamcmc_compare_info(self._h, C.byref(inc), C.byref(exc)), "tamcmc_compare_info")
+        self.n_included, self.n_excluded = int(inc.value), int(exc.value)
+
+    _check = Accel._check
+
+    @classmethod
+    def from_loo(cls, *results, **kw):
+        """From what Summary.loo (keys elpd_loo, pareto_k) or Summary.window_loo (elpd_lwo, pareto_k) returned, one dict per
+        fit, all of one kind and one length."""
+        key = "elpd_loo" if all("elpd_loo" in r for r in results) else "elpd_lwo"
+        elpd = np.stack([np.asarray(r[key], dtype=np.float64) for r in results])
+        kh = np.stack([np.asarray(r["pareto_k"], dtype=np.float64) for r in results]) if all("pareto_k" in r for r in results) else None
+        return cls(elpd, kh, **kw)
+
+    def diff(self, a, b):
+        """dict of the pair (a, b): d_i = elpd[a][i] - elpd[b][i]; elpd_diff, se_diff, n_better, n_worse, n_k_high,
+        diff_k_high, n_included, n_excluded."""
+        t = CompareTotals()
+        self._check(self._lib.tamcmc_compare_diff(self._h, int(a), int(b), C.byref(t)), "tamcmc_compare_diff")
+        return {k: (int(getattr(t, k)) if k.startswith("n_") else float(getattr(t, k))) for k in self.TOTALS}
+
+    def bootstrap(self, R, scratch_bytes=0):
+        """Appends R replicates of the Bayesian bootstrap (synchronous); returns the number of replicates done."""
+        self._check(self._lib.tamcmc_compare_bootstrap(self._h, int(R), int(scratch_bytes)), "tamcmc_compare_bootstrap")
+        return self.replicates
+
+    @property
+    def replicates(self):
+        R = C.c_int64(0)
+        self._check(self._lib.tamcmc_compare_replicates(self._h, C.byref(R)), "tamcmc_compare_replicates")
+        return int(R.value)
+
+    def z(self, k):
+        """z_rk of fit k over the replicates done (zeros for k = 0)."""
+        out = np.empty(self.replicates)
+        self._check(self._lib.tamcmc_compare_z(self._h, int(k), _dptr(out)), "tamcmc_compare_z")
+        return out
+
+    def prob(self, a, b):
+        """(n_greater, n_equal, R): the counts of z_a > z_b and z_a == z_b over the R replicates."""
+        gt, eq = C.c_int64(0), C.c_int64(0)
+        self._check(self._lib.tamcmc_compare_prob(self._h, int(a), int(b), C.byref(gt), C.byref(eq)), "tamcmc_compare_prob")
+        return int(gt.value), int(eq.value), self.replicates
+
+    def interval(self, a, b, q):
+        """The order statistic of z_a - z_b at rank ceil(q R) - 1."""
+        v = C.c_double(0.0)
+        self._check(self._lib.tamcmc_compare_interval(self._h, int(a), int(b), float(q), C.byref(v)), "tamcmc_compare_interval")
+        return v.value
+
+    def weights(self, method="pseudo_bma_plus"):
+        """K weights: "pseudo_bma", "pseudo_bma_plus" (after bootstrap) or "stacking" (what the last stacking() returned)."""
+        w = np.empty(self.K)
+        self._check(self._lib.tamcmc_compare_weights(self._h, COMPARE_METHODS[method] if isinstance(method, str) else int(method), _dptr(w)),
+                    "tamcmc_compare_weights")
+        return w
+
+    def stacking(self, tol=1e-8, max_iter=100000, scratch_bytes=0, cadence=None):
+        """Stacking weights by the EM fixed point: dict of w, iterations, converged, gap, f, table.  cadence (iterations
+        between two looks of the host at the device's state) changes no bit of it."""
+        if cadence is not None:
+            self._check(self._lib.tamcmc_compare_stacking_cadence(self._h, int(cadence)), "tamcmc_compare_stacking_cadence")
+        w = np.empty(self.K)
+        info = CompareStackingInfo()
+        self._check(self._lib.tamcmc_compare_stacking(self._h, float(tol), int(max_iter), int(scratch_bytes), _dptr(w), C.byref(info)),
+                    "tamcmc_compare_stacking")
+        return dict(w=w, iterations=int(info.iterations), converged=int(info.converged), gap=info.gap, f=info.f, table=int(info.table))
+
+    def variates(self, r):
+        """The N variates of replicate r, generated on the device."""
+        e = np.empty(self.N)
+        self._check(self._lib.tamcmc_compare_variates(self._h, int(r), _dptr(e)), "tamcmc_compare_variates")
+        return e
+
+    def profile(self, enable=True):
+        self._check(self._lib.tamcmc_compare_profile(self._h, int(enable)), "tamcmc_compare_profile")
+
+    def kernel_time(self, which=0):
+        """(summed milliseconds, launches) since profile(True): which = 0 the bootstrap's chunks, 1 the stacking's launches."""
+        ms = C.c_double(0.0)
+        n = C.c_int64(0)
+        self._check(self._lib.tamcmc_compare_kernel_time(self._h, int(which), C.byref(ms), C.byref(n)), "tamcmc_compare_kernel_time")
+        return ms.value, n.value
+
+    def close(self):
+        if getattr(self, "_h", None) is not None and self._h.value:
+            self._check(self._lib.tamcmc_compare_destroy(self._h), "tamcmc_compare_destroy")
             self._h = C.c_void_p()
 
     def __del__(self):

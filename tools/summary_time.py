@@ -73,6 +73,13 @@ Prints one JSON line:
                             (width, height) pair of every multiplet at 32 classes: kernel time and wall time of each, beside the
                             table's own derive and fold kernels and the same statements on one host thread
                             (tools/modepdf_host_time.cpp, std::sort)
+  s_compare_*               with --compare K,R (and --nx N): the comparison of K fits (tamcmc_amd.Compare) over N units of pseudo-random
+                            pointwise values, no chain and no context: R replicates of the Bayesian bootstrap after a warm-up
+                            call -- wall seconds and, from HIP events around every chunk, kernel seconds per replicate, and
+                            the variates per second (R N' / kernel time) -- then the stacking fit (tol 1e-8, at most 2000
+                            iterations) with and without the table of P: iterations, wall time, kernel time in total and per
+                            iteration; beside them the header's serial statements on one host thread
+                            (tools/compare_host_time.cpp, built with g++ when the leg runs).  Only this leg runs.
   o_modediag_*              with --modes and --modes-ess L and / or --modes-cov: the diagnostics of that table's columns
                             (ModeTable.ess / ModeTable.cov) on the rows it holds: per call the kernels alone from the object's HIP
                             events (ModeTable.diag_kernel_time: lag and finish kernels of an ess call together, the covariance
@@ -267,6 +274,51 @@ def scan_null_leg(a):
                    j_scan_null_joint_line=[null.line(k, 0, 0.01, True) for k in range(len(widths))] if R >= 99 else None,
                    j_scan_null_width_line=[null.line(k, 0, 0.01, False) for k in range(len(widths))] if R >= 99 else None,
                    j_scan_null_default_line=[float(np.log(0.01 * W / a.nx)) for W in widths])
+    return out
+
+
+def compare_leg(a):
+    """(s) the comparison of fits: the bootstrap per replicate, the stacking per iteration, and one host thread."""
+    import subprocess
+    import tempfile
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    K, R = (int(t) for t in a.compare.split(","))
+    N = a.nx
+    rng = np.random.default_rng(20261021)
+    elpd = rng.normal(-3.0, 1.0, N)[None, :] + 0.3 * rng.standard_t(5, (K, N)) + 0.02 * np.arange(K)[:, None]
+    out = dict(s_compare_K=K, s_compare_R=R, s_compare_N=N)
+    with tamcmc_amd.Compare(elpd, seed=12345) as cmp:
+        cmp.bootstrap(min(R, 256))                          # warm-up: code objects, the chunk's buffers
+        cmp.profile(True)
+        t0 = time.perf_counter()
+        cmp.bootstrap(R)                                    # synchronous
+        wall = time.perf_counter() - t0
+        ms, chunks = cmp.kernel_time(0)
+        out.update(s_compare_bootstrap_wall_s_per_replicate=wall / R, s_compare_bootstrap_kernel_s_per_replicate=ms * 1e-3 / R,
+                   s_compare_bootstrap_chunks=chunks, s_compare_variates_per_s=float(R) * cmp.n_included / (ms * 1e-3),
+                   s_compare_prob=cmp.prob(1, 0)[0] / cmp.replicates, s_compare_weights_bma_plus=cmp.weights("pseudo_bma_plus").tolist())
+        cmp.stacking(1e-8, 20)                              # warm-up
+        for tag, scratch in (("table", 0), ("no_table", 1)):
+            cmp.profile(True)
+            t0 = time.perf_counter()
+            st = cmp.stacking(1e-8, 2000, scratch_bytes=scratch)
+            wall = time.perf_counter() - t0
+            ms, launches = cmp.kernel_time(1)
+            out.update({f"s_compare_stack_{tag}_iterations": st["iterations"], f"s_compare_stack_{tag}_converged": st["converged"],
+                        f"s_compare_stack_{tag}_wall_s": wall, f"s_compare_stack_{tag}_kernel_s": ms * 1e-3,
+                        f"s_compare_stack_{tag}_kernel_s_per_iteration": ms * 1e-3 / st["iterations"],
+                        f"s_compare_stack_{tag}_launch_groups": launches})
+        out.update(s_compare_stack_gap=st["gap"], s_compare_stack_w=st["w"].tolist())
+        cmp.profile(False)
+    with tempfile.TemporaryDirectory() as tmp:
+        exe = os.path.join(tmp, "compare_host_time")
+        subprocess.run(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-I", os.path.join(root, "tamcmc-c-_amd", "csrc"),
+                        os.path.join(root, "tools", "compare_host_time.cpp"), "-o", exe], check=True)
+        host = json.loads(subprocess.run([exe, str(N), str(K), str(4 if N > 1000000 else 16), "3"], check=True, capture_output=True, text=True).stdout)
+    out.update(s_compare_host_bootstrap_s_per_replicate=host["host_bootstrap_ms_per_replicate"] * 1e-3,
+               s_compare_host_stack_s_per_iteration=host["host_stack_ms_per_iteration"] * 1e-3,
+               s_compare_host_over_bootstrap_kernel=host["host_bootstrap_ms_per_replicate"] * 1e-3 / out["s_compare_bootstrap_kernel_s_per_replicate"],
+               s_compare_host_over_stack_kernel=host["host_stack_ms_per_iteration"] * 1e-3 / out["s_compare_stack_table_kernel_s_per_iteration"])
     return out
 
 
@@ -780,7 +832,13 @@ def main():
     ap.add_argument("--modes-pdf", action="store_true", help="with --modes, the histograms, shortest intervals and pair densities of the "
                     "table's columns beside derive and fold and beside one host thread")
     ap.add_argument("--scan-null", type=int, default=0, help="R: replicates per run of the scan's Monte-Carlo null (widths of --scan)")
+    ap.add_argument("--compare", default="", help="K,R: the comparison of K fits over --nx units, R bootstrap replicates, and the stacking fit")
     a = ap.parse_args()
+    if a.compare:
+        out = dict(tool="summary_time", version=tamcmc_amd.capi.version())
+        out.update(compare_leg(a))
+        print(json.dumps(out))
+        return
     if a.steps < 1 or a.warmup < 0 or a.samples < 1 or a.samples_b < 2 or a.scan_null < 0:
         ap.error("--steps >= 1, --warmup >= 0, --samples >= 1, --samples-b >= 2, --scan-null >= 0")
     if (a.modes_ess >= 0 or a.modes_cov or a.modes_rank >= 0 or a.modes_indices or a.modes_pdf) and not a.modes:
