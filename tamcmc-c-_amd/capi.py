@@ -374,7 +374,52 @@ def _c64(a, shape=None):
     return a
 
 
-class Accel:
+class _Handle:
+    """What the classes that own one handle of the library share.  A subclass names the attribute that holds its handle (a
+    C.c_void_p, set before the create call) in _HANDLE and the library's destroy function in _DESTROY; _lib is the loaded
+    library.  close() keeps the handle when the library refuses to destroy it; where _DESTROY_CHECKED is False the refusal
+    is not looked at."""
+
+    _HANDLE = None
+    _DESTROY = None
+    _DESTROY_CHECKED = True
+
+    def _check(self, rc, where):
+        if rc != OK:
+            detail = self._lib.tamcmc_strerror(rc).decode()
+            if rc == E_HIP:
+                detail += " | " + self._lib.tamcmc_last_hip_error().decode()
+            raise AccelError(rc, where, detail)
+
+    def close(self):
+        h = getattr(self, self._HANDLE, None)
+        if h is not None and h.value:
+            rc = getattr(self._lib, self._DESTROY)(h)
+            if self._DESTROY_CHECKED:
+                self._check(rc, self._DESTROY)
+            setattr(self, self._HANDLE, C.c_void_p())
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def _kernel_time(self, fn_name, *args):
+        """(summed milliseconds, count) from the library's fn_name(handle, *args, &ms, &count)."""
+        ms = C.c_double(0.0)
+        n = C.c_int64(0)
+        self._check(getattr(self._lib, fn_name)(getattr(self, self._HANDLE), *args, C.byref(ms), C.byref(n)), fn_name)
+        return ms.value, n.value
+
+
+class Accel(_Handle):
     """One context = one star (x, y[, sigma_y]) on one GPU, for one model / likelihood id."""
 
     def __init__(self, model_case, plength, x, y, sigma_y=None, likelihood_case=0, likelihood_p=1.0, device_id=0):
@@ -395,31 +440,8 @@ class Accel:
                                          _dptr(sig))
         self._check(rc, "tamcmc_ctx_create")
 
-    # -- plumbing -------------------------------------------------------------------------------
-    def _check(self, rc, where):
-        if rc != OK:
-            detail = self._lib.tamcmc_strerror(rc).decode()
-            if rc == E_HIP:
-                detail += " | " + self._lib.tamcmc_last_hip_error().decode()
-            raise AccelError(rc, where, detail)
-
-    def close(self):
-        if getattr(self, "_ctx", None) is not None and self._ctx.value:
-            # refused (and the context kept) while a fit group holds it: close the Group first
-            self._check(self._lib.tamcmc_ctx_destroy(self._ctx), "tamcmc_ctx_destroy")
-            self._ctx = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
+    # close() is refused (and the context kept) while a fit group holds it: close the Group first
+    _HANDLE, _DESTROY = "_ctx", "tamcmc_ctx_destroy"
 
     # -- API ------------------------------------------------------------------------------------
     def set_vars(self, index_to_relax):
@@ -533,10 +555,7 @@ class Accel:
         self._check(self._lib.tamcmc_ctx_profile(self._ctx, int(enable)), "tamcmc_ctx_profile")
 
     def kernel_time(self):
-        ms = C.c_double(0.0)
-        n = C.c_int64(0)
-        self._check(self._lib.tamcmc_ctx_kernel_time(self._ctx, C.byref(ms), C.byref(n)), "tamcmc_ctx_kernel_time")
-        return ms.value, n.value
+        return self._kernel_time("tamcmc_ctx_kernel_time")
 
     def clock_probe_begin(self, milliseconds):
         self._check(self._lib.tamcmc_ctx_clock_probe_begin(self._ctx, float(milliseconds)), "tamcmc_ctx_clock_probe_begin")
@@ -556,7 +575,7 @@ class Accel:
                     tiles_grad=g[0].value, bins_per_tile_grad=g[1].value)
 
 
-class Group:
+class Group(_Handle):
     """A fit group (tamcmc_accel.h, tamcmc_group_*): the likelihood batches of several Accel contexts -- different grids,
     model ids, layouts -- in one call.  Every chain's result equals its member's own eval_batch bit for bit.  The group
     keeps references to its members; a member cannot be closed while the group is open."""
@@ -569,7 +588,8 @@ class Group:
         self._check(self._lib.tamcmc_group_create(C.byref(self._g), len(self.members), arr), "tamcmc_group_create")
         self.Nparams = np.array([a.Nparams for a in self.members], dtype=np.int32)
 
-    _check = Accel._check
+    _HANDLE, _DESTROY = "_g", "tamcmc_group_destroy"
+    _DESTROY_CHECKED = False
 
     def _counts(self, P_list, T_list):
         if len(P_list) != len(self.members) or len(T_list) != len(self.members):
@@ -639,25 +659,8 @@ class Group:
     def synchronize(self):
         self._check(self._lib.tamcmc_group_synchronize(self._g), "tamcmc_group_synchronize")
 
-    def close(self):
-        if getattr(self, "_g", None) is not None and self._g.value:
-            self._lib.tamcmc_group_destroy(self._g)
-            self._g = C.c_void_p()
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-
-class Summary:
+class Summary(_Handle):
     """Posterior summaries of a stored chain (tamcmc_accel.h, tamcmc_summary_*): per-bin running statistics of the model
     and of the pointwise log-likelihood over the parameter rows pushed so far, kept on the device.  Results do not depend,
     bit for bit, on block_chains or on how the rows are split over pushes.  quantiles() gives the exact per-bin quantiles
@@ -690,7 +693,7 @@ class Summary:
             self.close()
             raise
 
-    _check = Accel._check
+    _HANDLE, _DESTROY = "_s", "tamcmc_summary_destroy"
 
     def push(self, params):
         """params: (n, Nparams) rows.  Returns (logL, status) of these rows at T = 1."""
@@ -733,10 +736,7 @@ class Summary:
 
     def kernel_time(self):
         """(summed milliseconds, launches) of the fold kernel since profile(True)."""
-        ms = C.c_double(0.0)
-        n = C.c_int64(0)
-        self._check(self._lib.tamcmc_summary_kernel_time(self._s, C.byref(ms), C.byref(n)), "tamcmc_summary_kernel_time")
-        return ms.value, n.value
+        return self._kernel_time("tamcmc_summary_kernel_time")
 
     # ---- quantiles: exact per-bin order statistics of the model over the accepted samples, a few bits per pass ----
     MAX_QUANTILES = 8
@@ -863,11 +863,7 @@ class Summary:
 
     def loo_pit_kernel_time(self):
         """(summed milliseconds, launches) of the PIT kernel since profile(True)."""
-        ms = C.c_double(0.0)
-        n = C.c_int64(0)
-        self._check(self._lib.tamcmc_summary_loo_pit_kernel_time(self._s, C.byref(ms), C.byref(n)),
-                    "tamcmc_summary_loo_pit_kernel_time")
-        return ms.value, n.value
+        return self._kernel_time("tamcmc_summary_loo_pit_kernel_time")
 
     # ---- posterior predictive check: PIT and both log tail probabilities per bin, beside every fold pass ----
     PREDICTIVE_MAX_P = 64
@@ -893,11 +889,7 @@ class Summary:
 
     def predictive_kernel_time(self):
         """(summed milliseconds, launches) of the predictive kernel since profile(True); kernel_time() stays the fold kernel's."""
-        ms = C.c_double(0.0)
-        n = C.c_int64(0)
-        self._check(self._lib.tamcmc_summary_predictive_kernel_time(self._s, C.byref(ms), C.byref(n)),
-                    "tamcmc_summary_predictive_kernel_time")
-        return ms.value, n.value
+        return self._kernel_time("tamcmc_summary_predictive_kernel_time")
 
     # ---- windowed predictive check: the same over disjoint windows of W bins, the first one `first` bins long ----
     WINDOW_MAX_BINS = 512
@@ -932,11 +924,7 @@ class Summary:
 
     def window_kernel_time(self):
         """(summed milliseconds, blocks) of the window kernels since profile(True); kernel_time() stays the fold kernel's."""
-        ms = C.c_double(0.0)
-        n = C.c_int64(0)
-        self._check(self._lib.tamcmc_summary_window_kernel_time(self._s, C.byref(ms), C.byref(n)),
-                    "tamcmc_summary_window_kernel_time")
-        return ms.value, n.value
+        return self._kernel_time("tamcmc_summary_window_kernel_time")
 
     # ---- window-LOO: PSIS-LOO and LOO-PIT with a window of bins left out, the windows of the windowed check ----
     WLOO_ARRAYS = ("elpd_lwo", "pareto_k", "cutoff")
@@ -988,11 +976,7 @@ class Summary:
 
     def wloo_pit_kernel_time(self):
         """(summed milliseconds, blocks) of the sub-mode's sums, tails and PIT kernels since profile(True)."""
-        ms = C.c_double(0.0)
-        n = C.c_int64(0)
-        self._check(self._lib.tamcmc_summary_wloo_pit_kernel_time(self._s, C.byref(ms), C.byref(n)),
-                    "tamcmc_summary_wloo_pit_kernel_time")
-        return ms.value, n.value
+        return self._kernel_time("tamcmc_summary_wloo_pit_kernel_time")
 
     def wloo_end(self):
         self._check(self._lib.tamcmc_summary_wloo_end(self._s), "tamcmc_summary_wloo_end")
@@ -1062,11 +1046,7 @@ class Summary:
 
     def scan_kernel_time(self):
         """(summed milliseconds, blocks) of the scan kernels since profile(True); kernel_time() stays the fold kernel's."""
-        ms = C.c_double(0.0)
-        n = C.c_int64(0)
-        self._check(self._lib.tamcmc_summary_scan_kernel_time(self._s, C.byref(ms), C.byref(n)),
-                    "tamcmc_summary_scan_kernel_time")
-        return ms.value, n.value
+        return self._kernel_time("tamcmc_summary_scan_kernel_time")
 
     # ---- effective sample size, MCSE and split R-hat per bin, one more pass over the same rows in the same order ----
     ESS_MAX_LAG = 1023
@@ -1175,25 +1155,8 @@ class Summary:
         r["tail_ess"] = np.minimum(r["ess"][lo], r["ess"][hi])              # (np.minimum propagates NaN)
         return r
 
-    def close(self):
-        if getattr(self, "_s", None) is not None and self._s.value:
-            self._check(self._lib.tamcmc_summary_destroy(self._s), "tamcmc_summary_destroy")
-            self._s = C.c_void_p()
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-
-class ScanNull:
+class ScanNull(_Handle):
     """Monte-Carlo null of the sliding-window scan (tamcmc_accel.h, tamcmc_scan_null_*): the law of the scan's extremes over
     every position of every width under a correctly specified model, simulated on the device, and the lines and p-values
     counted off it.  Bound to a device and to no Accel or chain: it depends on (likelihood_case, p, Nx, widths) alone.
@@ -1213,7 +1176,7 @@ class ScanNull:
         self._check(self._lib.tamcmc_scan_null_create(C.byref(self._h), int(device_id), int(likelihood_case), float(p), self.Nx, int(W.size),
                                                       _iptr(W) if W.size else None, int(seed), int(first_replicate)), "tamcmc_scan_null_create")
 
-    _check = Accel._check
+    _HANDLE, _DESTROY = "_h", "tamcmc_scan_null_destroy"
 
     def run(self, n):
         """Appends n replicates (synchronous); returns the number of replicates done."""
@@ -1261,30 +1224,10 @@ class ScanNull:
 
     def kernel_time(self):
         """(summed milliseconds, chunks) of the kernels since profile(True)."""
-        ms = C.c_double(0.0)
-        n = C.c_int64(0)
-        self._check(self._lib.tamcmc_scan_null_kernel_time(self._h, C.byref(ms), C.byref(n)), "tamcmc_scan_null_kernel_time")
-        return ms.value, n.value
-
-    def close(self):
-        if getattr(self, "_h", None) is not None and self._h.value:
-            self._check(self._lib.tamcmc_scan_null_destroy(self._h), "tamcmc_scan_null_destroy")
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
+        return self._kernel_time("tamcmc_scan_null_kernel_time")
 
 
-class Compare:
+class Compare(_Handle):
     """Comparison of K fits of one spectrum from their pointwise log predictive values (tamcmc_accel_compare.h,
     tamcmc_compare_*): elpd differences with their standard error, a Bayesian bootstrap of the differences on the device,
     pseudo-BMA, pseudo-BMA+ and stacking weights.  elpd is (K, N): row k the elpd_loo (or elpd_lwo, or lppd - var_l) of fit k
@@ -1312,7 +1255,7 @@ class Compare:
         self._check(self._lib.tamcmc_compare_info(self._h, C.byref(inc), C.byref(exc)), "tamcmc_compare_info")
         self.n_included, self.n_excluded = int(inc.value), int(exc.value)
 
-    _check = Accel._check
+    _HANDLE, _DESTROY = "_h", "tamcmc_compare_destroy"
 
     @classmethod
     def from_loo(cls, *results, **kw):
@@ -1388,30 +1331,10 @@ class Compare:
 
     def kernel_time(self, which=0):
         """(summed milliseconds, launches) since profile(True): which = 0 the bootstrap's chunks, 1 the stacking's launches."""
-        ms = C.c_double(0.0)
-        n = C.c_int64(0)
-        self._check(self._lib.tamcmc_compare_kernel_time(self._h, int(which), C.byref(ms), C.byref(n)), "tamcmc_compare_kernel_time")
-        return ms.value, n.value
-
-    def close(self):
-        if getattr(self, "_h", None) is not None and self._h.value:
-            self._check(self._lib.tamcmc_compare_destroy(self._h), "tamcmc_compare_destroy")
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
+        return self._kernel_time("tamcmc_compare_kernel_time", int(which))
 
 
-class ModeTable:
+class ModeTable(_Handle):
     """The posterior mode table (tamcmc_accel.h, tamcmc_modetable_*): per params row the derived quantities of every
     multiplet and of the chain -- frequency, width, height, amplitude, splitting, truncation window, component frequencies
     and heights; inclination, eta, a3, asymmetry -- produced on the device by the derivation the kernels use, and their
@@ -1434,7 +1357,7 @@ class ModeTable:
         self.n_cols, self.n_mult = int(nc.value), int(nm.value)
         self.max_samples = int(max_samples)
 
-    _check = Accel._check
+    _HANDLE, _DESTROY = "_mt", "tamcmc_modetable_destroy"
 
     def columns(self):
         """Structured array (kind, mult, order, l, m, param_index) of the n_cols columns; KINDS[kind] is the kind's name."""
@@ -1502,10 +1425,7 @@ class ModeTable:
 
     def kernel_time(self):
         """(summed milliseconds, launches) of the derive and fold kernels since the object was created or reset."""
-        ms = C.c_double(0.0)
-        n = C.c_int64(0)
-        self._check(self._lib.tamcmc_modetable_kernel_time(self._mt, C.byref(ms), C.byref(n)), "tamcmc_modetable_kernel_time")
-        return ms.value, n.value
+        return self._kernel_time("tamcmc_modetable_kernel_time")
 
     def enable_indices(self, ref_params):
         """Appends the seismic indices (tamcmc_modetable_indices_enable) as further columns: the plan is fixed from the
@@ -1542,10 +1462,7 @@ class ModeTable:
 
     def seismic_kernel_time(self):
         """(summed milliseconds, launches) of the indices kernel since the object was created or reset."""
-        ms = C.c_double(0.0)
-        n = C.c_int64(0)
-        self._check(self._lib.tamcmc_seismic_kernel_time(self._mt, C.byref(ms), C.byref(n)), "tamcmc_seismic_kernel_time")
-        return ms.value, n.value
+        return self._kernel_time("tamcmc_seismic_kernel_time")
 
     DIAG_ARRAYS = ("ess", "tau", "mcse", "rhat")
 
@@ -1570,14 +1487,17 @@ class ModeTable:
         self._check(self._lib.tamcmc_modediag_acov(self._mt, _dptr(out)), "tamcmc_modediag_acov")
         return out
 
-    def _between(self, fn, name, cols):
+    def _selection(self, cols):
+        """(n_sel, the columns as the library takes them -- None: the first n_sel --, the columns as a result names them)"""
         if cols is None:
-            n_sel, sel = self.n_cols, None          # (more than 1024 columns: the library refuses)
-        else:
-            sel = np.ascontiguousarray(cols, dtype=np.int32)
-            if sel.ndim != 1:
-                raise ValueError("cols must be a sequence of column indices")
-            n_sel = sel.size
+            return self.n_cols, None, np.arange(self.n_cols, dtype=np.int32)
+        sel = np.ascontiguousarray(cols, dtype=np.int32)
+        if sel.ndim != 1:
+            raise ValueError("cols must be a sequence of column indices")
+        return sel.size, sel, sel.copy()
+
+    def _between(self, fn, name, cols):
+        n_sel, sel, _ = self._selection(cols)       # (None and more than 1024 columns: the library refuses)
         out = np.empty((max(n_sel, 1), max(n_sel, 1)))
         self._check(fn(self._mt, n_sel, _iptr(sel), _dptr(out)), name)
         return out
@@ -1592,10 +1512,7 @@ class ModeTable:
 
     def diag_kernel_time(self):
         """(summed milliseconds, launches) of the lag, finish and covariance kernels since the object was created or reset."""
-        ms = C.c_double(0.0)
-        n = C.c_int64(0)
-        self._check(self._lib.tamcmc_modediag_kernel_time(self._mt, C.byref(ms), C.byref(n)), "tamcmc_modediag_kernel_time")
-        return ms.value, n.value
+        return self._kernel_time("tamcmc_modediag_kernel_time")
 
     def rank_diag(self, max_lag=0, cols=None, scratch_bytes=0):
         """Rank-normalised diagnostics (tamcmc_moderank_diag) of the columns `cols`, in that order (None: all): dict of
@@ -1603,13 +1520,7 @@ class ModeTable:
         the series z, zfold, i05, i95, cols, and the totals n_used, lag, min_ess_bulk, col_min_ess_bulk, min_ess_tail,
         col_min_ess_tail, max_rhat, col_max_rhat, n_truncated, n_constant, n_rhat_high.  The columns are processed in
         chunks that fit scratch_bytes of device memory (0: 256 MiB); no result bit depends on it."""
-        if cols is None:
-            n_sel, sel = self.n_cols, None
-        else:
-            sel = np.ascontiguousarray(cols, dtype=np.int32)
-            if sel.ndim != 1:
-                raise ValueError("cols must be a sequence of column indices")
-            n_sel = sel.size
+        n_sel, sel, cols_out = self._selection(cols)
         arr = np.empty((MODERANK_NOUT, max(n_sel, 1)))
         cut = np.empty((MODERANK_NSERIES, max(n_sel, 1)), dtype=np.int32)
         t = ModeRankTotals()
@@ -1617,7 +1528,7 @@ class ModeTable:
                                                    _dptr(arr), _iptr(cut)), "tamcmc_moderank_diag")
         out = {k: arr[i].copy() for i, k in enumerate(MODERANK_OUT)}
         out["cut"] = cut
-        out["cols"] = np.arange(n_sel, dtype=np.int32) if sel is None else sel.copy()
+        out["cols"] = cols_out
         out.update({k: (float if k.startswith(("min_", "max_")) else int)(getattr(t, k)) for k, _ in ModeRankTotals._fields_})
         self._rank_lag, self._rank_nsel = int(t.lag), n_sel
         return out
@@ -1643,18 +1554,7 @@ class ModeTable:
 
     def rank_kernel_time(self):
         """(summed milliseconds, launches) of the rank diagnostics' kernels since the object was created or reset."""
-        ms = C.c_double(0.0)
-        n = C.c_int64(0)
-        self._check(self._lib.tamcmc_moderank_kernel_time(self._mt, C.byref(ms), C.byref(n)), "tamcmc_moderank_kernel_time")
-        return ms.value, n.value
-
-    def _selection(self, cols):
-        if cols is None:
-            return self.n_cols, None
-        sel = np.ascontiguousarray(cols, dtype=np.int32)
-        if sel.ndim != 1:
-            raise ValueError("cols must be a sequence of column indices")
-        return sel.size, sel
+        return self._kernel_time("tamcmc_moderank_kernel_time")
 
     @staticmethod
     def _range(lo, hi, m):
@@ -1673,7 +1573,7 @@ class ModeTable:
         classes over lo ... hi (n_sel doubles each; None: the column's min and max): dict of counts (n_sel, bins), below,
         above (n_sel) int64, range (n_sel, 2), status (n_sel int32; 1: a default range that is not finite, every count 0)
         and cols.  The class rule is that of tamcmc_accel_pdf.h; hist_edges() gives the edges for a plot."""
-        n_sel, sel = self._selection(cols)
+        n_sel, sel, cols_out = self._selection(cols)
         m, nb = max(n_sel, 1), max(int(bins), 1)
         lo, hi = self._range(lo, hi, n_sel)
         counts = np.zeros((m, nb), dtype=np.int64)
@@ -1683,8 +1583,7 @@ class ModeTable:
         self._check(self._lib.tamcmc_modepdf_hist(self._mt, int(bins), n_sel, _iptr(sel), _dptr(lo), _dptr(hi), counts.ctypes.data_as(l64),
                                                   below.ctypes.data_as(l64), above.ctypes.data_as(l64), _dptr(rng), _iptr(status)),
                     "tamcmc_modepdf_hist")
-        return dict(counts=counts, below=below, above=above, range=rng, status=status,
-                    cols=np.arange(n_sel, dtype=np.int32) if sel is None else sel.copy())
+        return dict(counts=counts, below=below, above=above, range=rng, status=status, cols=cols_out)
 
     @staticmethod
     def hist_edges(range, bins):
@@ -1702,15 +1601,14 @@ class ModeTable:
         mass = _c64(np.atleast_1d(mass))
         if mass.ndim != 1:
             raise ValueError("mass must be a sequence of probabilities")
-        n_sel, sel = self._selection(cols)
+        n_sel, sel, cols_out = self._selection(cols)
         nm, m = max(mass.size, 1), max(n_sel, 1)
         k, start = np.zeros(nm, dtype=np.int64), np.zeros((nm, m), dtype=np.int64)
         lo, hi = np.zeros((nm, m)), np.zeros((nm, m))
         l64 = C.POINTER(C.c_int64)
         self._check(self._lib.tamcmc_modepdf_hpd(self._mt, mass.size, _dptr(mass), n_sel, _iptr(sel), int(scratch_bytes), k.ctypes.data_as(l64),
                                                  start.ctypes.data_as(l64), _dptr(lo), _dptr(hi)), "tamcmc_modepdf_hpd")
-        return dict(mass=mass.copy(), k=k[:mass.size], start=start[:mass.size], lo=lo[:mass.size], hi=hi[:mass.size],
-                    cols=np.arange(n_sel, dtype=np.int32) if sel is None else sel.copy())
+        return dict(mass=mass.copy(), k=k[:mass.size], start=start[:mass.size], lo=lo[:mass.size], hi=hi[:mass.size], cols=cols_out)
 
     def hist2d(self, pairs, bins, lo=None, hi=None, mass=()):
         """Pair densities (tamcmc_modepdf_hist2d) of the column pairs `pairs` (n_pairs, 2) in bins x bins classes over
@@ -1736,27 +1634,7 @@ class ModeTable:
     def pdf_kernel_time(self):
         """(summed milliseconds, launches) of the histogram, pair and HPD kernels, hpd's sort launches included, since the
         object was created or reset."""
-        ms = C.c_double(0.0)
-        n = C.c_int64(0)
-        self._check(self._lib.tamcmc_modepdf_kernel_time(self._mt, C.byref(ms), C.byref(n)), "tamcmc_modepdf_kernel_time")
-        return ms.value, n.value
-
-    def close(self):
-        if getattr(self, "_mt", None) is not None and self._mt.value:
-            self._check(self._lib.tamcmc_modetable_destroy(self._mt), "tamcmc_modetable_destroy")
-            self._mt = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
+        return self._kernel_time("tamcmc_modepdf_kernel_time")
 
 
 def device_count():

@@ -13,44 +13,10 @@
 #include "tamcmc_modetable_obj.h"
 #include "tamcmc_modediag.h"
 
-// what can be checked without a device; n_min: the fewest accepted rows the call works on
-static int md_check(const tamcmc_modetable *mt, long long n_min)
-{
-    if (!mt || mt->c->in_flight || mt->c->armed) return TAMCMC_E_INVALID;
-    if (mt->max_samples == 0 || mt->n_used < n_min) return TAMCMC_E_INVALID;
-    return TAMCMC_OK;
-}
-
-static int md_enter(tamcmc_modetable *mt)
-{
-    TM_HIP(hipSetDevice(mt->c->device));
-    TM_HIP(tm_ctx_stream_sync(mt->c));
-    mt->c->enq_seq++;
-    return TAMCMC_OK;
-}
-
-// one launch between the object's two events, waited for; its time goes to the diagnostics' own sum
-template <class F>
-static int md_timed(tamcmc_modetable *mt, const char *what, F &&launch)
-{
-    const hipStream_t stream = mt->c->stream;
-    TM_HIP(hipEventRecord(mt->ev[0], stream));
-    const int hr = launch();
-    if (hr != 0) return tm_launch_failed(what, hr);
-    TM_HIP(hipEventRecord(mt->ev[1], stream));
-    TM_HIP(hipStreamSynchronize(stream));
-    float ms = 0.f;
-    TM_HIP(hipEventElapsedTime(&ms, mt->ev[0], mt->ev[1]));
-    mt->diag_ms += (double)ms;
-    mt->diag_launches++;
-    return TAMCMC_OK;
-}
-
 extern "C" int tamcmc_modediag_ess(tamcmc_modetable *mt, int32_t max_lag, tamcmc_modediag_totals *totals, double *ess, double *tau, double *mcse,
                                    double *rhat, int32_t *cut)
 {
-    int rc = md_check(mt, 4);
-    if (rc != TAMCMC_OK) return rc;
+    if (!tm_mt_ready(mt, 4)) return TAMCMC_E_INVALID;
     if (max_lag < 0 || max_lag > TAMCMC_MODEDIAG_MAX_LAG) return TAMCMC_E_INVALID;
     const long long n = mt->n_used;
     const int L = tme_lag_limit(max_lag, n);
@@ -58,38 +24,30 @@ extern "C" int tamcmc_modediag_ess(tamcmc_modetable *mt, int32_t max_lag, tamcmc
     std::vector<double> fin, m2, a0;
     std::vector<int32_t> cutv;
     try { fin.resize(TM_MD_NFIN * nc); m2.resize(nc); a0.resize(nc); cutv.resize(nc); } catch (const std::bad_alloc &) { return TAMCMC_E_NOMEM; }
-    rc = md_enter(mt);
+    int rc = tm_mt_enter(mt);
     if (rc != TAMCMC_OK) return rc;
     tamcmc_ctx *c = mt->c;
-    if (L + 1 > mt->acc_lags) {
-        double *acc = nullptr;
-        int32_t *dcut = nullptr;
-        if (hipMalloc(&acc, ((size_t)(L + 1) + TM_MD_NFIN) * nc * sizeof(double)) != hipSuccess ||
-            (!mt->d_cut && hipMalloc(&dcut, nc * sizeof(int32_t)) != hipSuccess)) {
-            (void)hipGetLastError();
-            (void)hipFree(acc);
-            return TAMCMC_E_NOMEM;
-        }
-        (void)hipFree(mt->d_acc);
-        mt->d_acc = acc;
-        if (dcut) mt->d_cut = dcut;
-        mt->acc_lags = L + 1;
-    }
-    mt->acov_valid = false;
+    TmMtDiag &D = mt->diag;
+    const size_t acc_bytes = ((size_t)(L + 1) + TM_MD_NFIN) * nc * sizeof(double), cut_bytes = nc * sizeof(int32_t);
+    void *acc = nullptr, *dcut = nullptr;
+    if (D.acc.reserve(acc_bytes, &acc) != TAMCMC_OK || D.cut.reserve(cut_bytes, &dcut) != TAMCMC_OK) { (void)hipFree(acc); return TAMCMC_E_NOMEM; }
+    D.acc.install(acc, acc_bytes);
+    D.cut.install(dcut, cut_bytes);
+    D.acov_valid = false;
     TmMdArgs a{};
     a.table = mt->d_table; a.mean = mt->d_state + (size_t)TM_MT_MEAN * nc;
-    a.acc = mt->d_acc; a.fin = mt->d_acc + (size_t)(L + 1) * nc; a.cut = mt->d_cut;
+    a.acc = (double *)D.acc.d; a.fin = a.acc + (size_t)(L + 1) * nc; a.cut = (int32_t *)D.cut.d;
     a.n = n; a.max_samples = mt->max_samples; a.n_cols = mt->n_cols; a.L = L;
     a.tau_floor = 1.0 / std::log10((double)n);
-    rc = md_timed(mt, "modediag lag", [&] { return tm_launch_modediag_lag(a, c->stream); });
-    if (rc == TAMCMC_OK) rc = md_timed(mt, "modediag finish", [&] { return tm_launch_modediag_finish(a, c->stream); });
-    if (rc != TAMCMC_OK) { (void)hipStreamSynchronize(c->stream); return rc; }
+    rc = tm_mt_timed(mt, D.clock, "modediag lag", [&] { return tm_launch_modediag_lag(a, c->stream); });
+    if (rc == TAMCMC_OK) rc = tm_mt_timed(mt, D.clock, "modediag finish", [&] { return tm_launch_modediag_finish(a, c->stream); });
+    if (rc != TAMCMC_OK) return rc;
     TM_HIP(hipMemcpy(fin.data(), a.fin, fin.size() * sizeof(double), hipMemcpyDeviceToHost));
     TM_HIP(hipMemcpy(cutv.data(), a.cut, nc * sizeof(int32_t), hipMemcpyDeviceToHost));
     TM_HIP(hipMemcpy(a0.data(), a.acc, nc * sizeof(double), hipMemcpyDeviceToHost));
     TM_HIP(hipMemcpy(m2.data(), mt->d_state + (size_t)TM_MT_M2 * nc, nc * sizeof(double), hipMemcpyDeviceToHost));
-    mt->diag_L = L;
-    mt->acov_valid = true;
+    D.L = L;
+    D.acov_valid = true;
     const double dn = (double)n;
     for (size_t i = 0; i < nc; i++) {
         const double sd = std::sqrt(m2[i] / (dn - 1.0));                    // the sd of tamcmc_modetable_result
@@ -110,52 +68,36 @@ extern "C" int tamcmc_modediag_ess(tamcmc_modetable *mt, int32_t max_lag, tamcmc
 
 extern "C" int tamcmc_modediag_acov(tamcmc_modetable *mt, double *acov)
 {
-    int rc = md_check(mt, 4);
+    if (!tm_mt_ready(mt, 4) || !acov || !mt->diag.acov_valid) return TAMCMC_E_INVALID;
+    const int rc = tm_mt_enter(mt);
     if (rc != TAMCMC_OK) return rc;
-    if (!acov || !mt->acov_valid) return TAMCMC_E_INVALID;
-    rc = md_enter(mt);
-    if (rc != TAMCMC_OK) return rc;
-    TM_HIP(hipMemcpy(acov, mt->d_acc, (size_t)(mt->diag_L + 1) * (size_t)mt->n_cols * sizeof(double), hipMemcpyDeviceToHost));
+    TM_HIP(hipMemcpy(acov, mt->diag.acc.d, (size_t)(mt->diag.L + 1) * (size_t)mt->n_cols * sizeof(double), hipMemcpyDeviceToHost));
     return TAMCMC_OK;
 }
 
 // S (n_sel x n_sel sums of products) of the selected columns into out, divided by n - 1
 static int md_cov(tamcmc_modetable *mt, int32_t n_sel, const int32_t *cols, double *out)
 {
-    int rc = md_check(mt, 2);
-    if (rc != TAMCMC_OK) return rc;
-    if (!out || n_sel < 1 || n_sel > mt->n_cols || n_sel > TAMCMC_MODEDIAG_MAX_COLS) return TAMCMC_E_INVALID;
+    if (!tm_mt_ready(mt, 2) || !out) return TAMCMC_E_INVALID;
     std::vector<int32_t> sel;
-    std::vector<char> seen;
-    try { sel.resize((size_t)n_sel); seen.assign((size_t)mt->n_cols, 0); } catch (const std::bad_alloc &) { return TAMCMC_E_NOMEM; }
-    for (int32_t k = 0; k < n_sel; k++) {
-        const int32_t col = cols ? cols[k] : k;
-        if (col < 0 || col >= mt->n_cols || seen[(size_t)col]) return TAMCMC_E_INVALID;
-        seen[(size_t)col] = 1;
-        sel[(size_t)k] = col;
-    }
-    rc = md_enter(mt);
+    int rc = tm_mt_select(mt, n_sel, cols, sel, TAMCMC_MODEDIAG_MAX_COLS);
+    if (rc != TAMCMC_OK) return rc;
+    rc = tm_mt_enter(mt);
     if (rc != TAMCMC_OK) return rc;
     tamcmc_ctx *c = mt->c;
-    const size_t ns = (size_t)n_sel, nc = (size_t)mt->n_cols;
-    if (n_sel > mt->sel_cap) {
-        double *S = nullptr;
-        int32_t *dsel = nullptr;
-        if (hipMalloc(&S, ns * ns * sizeof(double)) != hipSuccess || hipMalloc(&dsel, ns * sizeof(int32_t)) != hipSuccess) {
-            (void)hipGetLastError();
-            (void)hipFree(S);
-            return TAMCMC_E_NOMEM;
-        }
-        (void)hipFree(mt->d_S); (void)hipFree(mt->d_sel);
-        mt->d_S = S; mt->d_sel = dsel; mt->sel_cap = n_sel;
-    }
-    TM_HIP(hipMemcpy(mt->d_sel, sel.data(), ns * sizeof(int32_t), hipMemcpyHostToDevice));
+    TmMtDiag &D = mt->diag;
+    const size_t ns = (size_t)n_sel, nc = (size_t)mt->n_cols, S_bytes = ns * ns * sizeof(double), sel_bytes = ns * sizeof(int32_t);
+    void *S = nullptr, *dsel = nullptr;
+    if (D.S.reserve(S_bytes, &S) != TAMCMC_OK || D.sel.reserve(sel_bytes, &dsel) != TAMCMC_OK) { (void)hipFree(S); return TAMCMC_E_NOMEM; }
+    D.S.install(S, S_bytes);
+    D.sel.install(dsel, sel_bytes);
+    TM_HIP(hipMemcpy(D.sel.d, sel.data(), sel_bytes, hipMemcpyHostToDevice));
     TmMdCovArgs a{};
-    a.table = mt->d_table; a.mean = mt->d_state + (size_t)TM_MT_MEAN * nc; a.sel = mt->d_sel; a.S = mt->d_S;
+    a.table = mt->d_table; a.mean = mt->d_state + (size_t)TM_MT_MEAN * nc; a.sel = (const int32_t *)D.sel.d; a.S = (double *)D.S.d;
     a.n = mt->n_used; a.max_samples = mt->max_samples; a.n_cols = mt->n_cols; a.n_sel = n_sel;
-    rc = md_timed(mt, "modediag cov", [&] { return tm_launch_modediag_cov(a, c->stream); });
-    if (rc != TAMCMC_OK) { (void)hipStreamSynchronize(c->stream); return rc; }
-    TM_HIP(hipMemcpy(out, mt->d_S, ns * ns * sizeof(double), hipMemcpyDeviceToHost));
+    rc = tm_mt_timed(mt, D.clock, "modediag cov", [&] { return tm_launch_modediag_cov(a, c->stream); });
+    if (rc != TAMCMC_OK) return rc;
+    TM_HIP(hipMemcpy(out, D.S.d, S_bytes, hipMemcpyDeviceToHost));
     const double dn1 = (double)(mt->n_used - 1);
     for (size_t k = 0; k < ns * ns; k++) out[k] = out[k] / dn1;
     return TAMCMC_OK;
@@ -178,8 +120,5 @@ extern "C" int tamcmc_modediag_corr(tamcmc_modetable *mt, int32_t n_sel, const i
 
 extern "C" int tamcmc_modediag_kernel_time(tamcmc_modetable *mt, double *total_ms, int64_t *launches)
 {
-    if (!mt || !total_ms || !launches || mt->c->in_flight || mt->c->armed) return TAMCMC_E_INVALID;
-    *total_ms = mt->diag_ms;
-    *launches = mt->diag_launches;
-    return TAMCMC_OK;
+    return tm_mt_idle(mt) ? mt->diag.clock.read(total_ms, launches) : TAMCMC_E_INVALID;
 }

@@ -14,65 +14,17 @@
 #include "tamcmc_modepdf.h"
 #include "tamcmc_accel_pdf.h"
 
-static int pdf_check(const tamcmc_modetable *mt, const long long n_min)
+// The scratch at `bytes` or more, then the entry.  The scratch comes first: a call that cannot have it returns
+// TAMCMC_E_NOMEM with the object, its context's counters included, as it was.
+static int pdf_enter(tamcmc_modetable *mt, const size_t bytes)
 {
-    if (!mt || mt->c->in_flight || mt->c->armed) return TAMCMC_E_INVALID;
-    if (mt->max_samples == 0 || mt->n_used < n_min) return TAMCMC_E_INVALID;
-    return TAMCMC_OK;
-}
-
-// the selection: cols NULL means the first n_sel columns; an index out of range or repeated is refused
-static int pdf_select(const tamcmc_modetable *mt, const int32_t n_sel, const int32_t *cols, std::vector<int32_t> &sel)
-{
-    if (n_sel < 1 || n_sel > mt->n_cols) return TAMCMC_E_INVALID;
-    std::vector<char> seen;
-    try { sel.resize((size_t)n_sel); seen.assign((size_t)mt->n_cols, 0); } catch (const std::bad_alloc &) { return TAMCMC_E_NOMEM; }
-    for (int32_t k = 0; k < n_sel; k++) {
-        const int32_t col = cols ? cols[k] : k;
-        if (col < 0 || col >= mt->n_cols || seen[(size_t)col]) return TAMCMC_E_INVALID;
-        seen[(size_t)col] = 1;
-        sel[(size_t)k] = col;
-    }
-    return TAMCMC_OK;
-}
-
-// the device buffer, at least `bytes`: *grown is what the caller installs with pdf_install once nothing can fail before a launch
-static int pdf_reserve(const tamcmc_modetable *mt, const size_t bytes, void **grown)
-{
-    *grown = nullptr;
-    if (bytes <= mt->pdf_bytes) return TAMCMC_OK;
-    if (hipMalloc(grown, bytes) != hipSuccess) { (void)hipGetLastError(); *grown = nullptr; return TAMCMC_E_NOMEM; }
-    return TAMCMC_OK;
-}
-static void pdf_install(tamcmc_modetable *mt, void *grown, const size_t bytes)
-{
-    if (!grown) return;
-    (void)hipFree(mt->d_pdf);
-    mt->d_pdf = grown;
-    mt->pdf_bytes = bytes;
-}
-
-static int pdf_enter(tamcmc_modetable *mt)
-{
-    TM_HIP(tm_ctx_stream_sync(mt->c));
-    mt->c->enq_seq++;
-    return TAMCMC_OK;
-}
-
-// one launch between the object's two events, waited for; its time goes to this feature's own sum
-template <class F>
-static int pdf_timed(tamcmc_modetable *mt, const char *what, F &&launch)
-{
-    const hipStream_t stream = mt->c->stream;
-    TM_HIP(hipEventRecord(mt->ev[0], stream));
-    const int hr = launch();
-    if (hr != 0) { (void)hipStreamSynchronize(stream); return tm_launch_failed(what, hr); }
-    TM_HIP(hipEventRecord(mt->ev[1], stream));
-    TM_HIP(hipStreamSynchronize(stream));
-    float ms = 0.f;
-    TM_HIP(hipEventElapsedTime(&ms, mt->ev[0], mt->ev[1]));
-    mt->pdf_ms += (double)ms;
-    mt->pdf_launches++;
+    TM_HIP(hipSetDevice(mt->c->device));
+    void *grown = nullptr;
+    int rc = mt->pdf.scratch.reserve(bytes, &grown);
+    if (rc != TAMCMC_OK) return rc;
+    rc = tm_mt_enter(mt);
+    if (rc != TAMCMC_OK) { (void)hipFree(grown); return rc; }
+    mt->pdf.scratch.install(grown, bytes);
     return TAMCMC_OK;
 }
 
@@ -99,11 +51,10 @@ static bool pdf_ranges(const tamcmc_modetable *mt, const size_t m, const int32_t
 extern "C" int tamcmc_modepdf_hist(tamcmc_modetable *mt, int32_t n_bins, int32_t n_sel, const int32_t *cols, const double *lo, const double *hi,
                                    int64_t *counts, int64_t *below, int64_t *above, double *range, int32_t *status)
 {
-    int rc = pdf_check(mt, 1);
-    if (rc != TAMCMC_OK) return rc;
+    if (!tm_mt_ready(mt, 1)) return TAMCMC_E_INVALID;
     if (n_bins < 1 || n_bins > TAMCMC_MODEPDF_MAX_BINS || !counts || !below || !above || (lo == nullptr) != (hi == nullptr)) return TAMCMC_E_INVALID;
     std::vector<int32_t> sel, st;
-    rc = pdf_select(mt, n_sel, cols, sel);
+    int rc = tm_mt_select(mt, n_sel, cols, sel);
     if (rc != TAMCMC_OK) return rc;
     const size_t ns = (size_t)n_sel, nb2 = (size_t)n_bins + 2;
     std::vector<double> state, arg;
@@ -112,18 +63,13 @@ extern "C" int tamcmc_modepdf_hist(tamcmc_modetable *mt, int32_t n_bins, int32_t
     if (lo && !pdf_ranges(mt, ns, sel.data(), lo, hi, n_bins, state, arg.data(), arg.data() + ns, arg.data() + 2 * ns, st.data())) return TAMCMC_E_INVALID;
     // device buffer: lo, hi, s [n_sel] doubles each; counters [n_sel][n_bins + 2]; sel, status [n_sel]
     const size_t bytes = 3 * ns * sizeof(double) + ns * nb2 * sizeof(uint32_t) + 2 * ns * sizeof(int32_t);
-    TM_HIP(hipSetDevice(mt->c->device));
-    void *grown = nullptr;
-    rc = pdf_reserve(mt, bytes, &grown);
+    rc = pdf_enter(mt, bytes);
     if (rc != TAMCMC_OK) return rc;
-    rc = pdf_enter(mt);
-    if (rc != TAMCMC_OK) { (void)hipFree(grown); return rc; }
-    pdf_install(mt, grown, bytes);
     if (!lo) {
         TM_HIP(hipMemcpy(state.data(), mt->d_state, state.size() * sizeof(double), hipMemcpyDeviceToHost));
         (void)pdf_ranges(mt, ns, sel.data(), nullptr, nullptr, n_bins, state, arg.data(), arg.data() + ns, arg.data() + 2 * ns, st.data());
     }
-    double *d_arg = (double *)mt->d_pdf;
+    double *d_arg = (double *)mt->pdf.scratch.d;
     uint32_t *d_cnt = (uint32_t *)(d_arg + 3 * ns);
     int32_t *d_sel = (int32_t *)(d_cnt + ns * nb2);
     TM_HIP(hipMemcpy(d_arg, arg.data(), 3 * ns * sizeof(double), hipMemcpyHostToDevice));
@@ -132,7 +78,7 @@ extern "C" int tamcmc_modepdf_hist(tamcmc_modetable *mt, int32_t n_bins, int32_t
     TmPdfHistArgs a{};
     a.table = mt->d_table; a.sel = d_sel; a.status = d_sel + ns; a.lo = d_arg; a.hi = d_arg + ns; a.s = d_arg + 2 * ns; a.out = d_cnt;
     a.n = mt->n_used; a.max_samples = mt->max_samples; a.n_sel = n_sel; a.n_bins = n_bins;
-    rc = pdf_timed(mt, "modepdf hist", [&] { return tm_launch_modepdf_hist(a, mt->c->stream); });
+    rc = tm_mt_timed(mt, mt->pdf.clock, "modepdf hist", [&] { return tm_launch_modepdf_hist(a, mt->c->stream); });
     if (rc != TAMCMC_OK) return rc;
     TM_HIP(hipMemcpy(cnt.data(), d_cnt, cnt.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
     for (size_t j = 0; j < ns; j++) {
@@ -149,8 +95,7 @@ extern "C" int tamcmc_modepdf_hist2d(tamcmc_modetable *mt, int32_t n_bins, int32
                                      const double *hi, int32_t n_mass, const double *mass, int64_t *counts, int64_t *outside, int64_t *level,
                                      int32_t *status)
 {
-    int rc = pdf_check(mt, 1);
-    if (rc != TAMCMC_OK) return rc;
+    if (!tm_mt_ready(mt, 1)) return TAMCMC_E_INVALID;
     if (n_bins < 1 || n_bins > TAMCMC_MODEPDF_MAX_BINS2D || n_pairs < 1 || n_pairs > TAMCMC_MODEPDF_MAX_PAIRS || !pairs || !counts || !outside ||
         (lo == nullptr) != (hi == nullptr) || n_mass < 0 || n_mass > TAMCMC_MODEPDF_MAX_MASS || (n_mass > 0 && (!mass || !level)))
         return TAMCMC_E_INVALID;
@@ -169,19 +114,14 @@ extern "C" int tamcmc_modepdf_hist2d(tamcmc_modetable *mt, int32_t n_bins, int32
     if (lo && !pdf_ranges(mt, 2 * np, pairs, lo, hi, n_bins, state, arg.data(), arg.data() + 2 * np, arg.data() + 4 * np, st.data())) return TAMCMC_E_INVALID;
     // device buffer: lo, hi, s [n_pairs][2] doubles each; counters [n_pairs][cells + 1]; pairs [n_pairs][2], status [n_pairs]
     const size_t bytes = 6 * np * sizeof(double) + np * (cells + 1) * sizeof(uint32_t) + 3 * np * sizeof(int32_t);
-    TM_HIP(hipSetDevice(mt->c->device));
-    void *grown = nullptr;
-    rc = pdf_reserve(mt, bytes, &grown);
+    int rc = pdf_enter(mt, bytes);
     if (rc != TAMCMC_OK) return rc;
-    rc = pdf_enter(mt);
-    if (rc != TAMCMC_OK) { (void)hipFree(grown); return rc; }
-    pdf_install(mt, grown, bytes);
     if (!lo) {
         TM_HIP(hipMemcpy(state.data(), mt->d_state, state.size() * sizeof(double), hipMemcpyDeviceToHost));
         (void)pdf_ranges(mt, 2 * np, pairs, nullptr, nullptr, n_bins, state, arg.data(), arg.data() + 2 * np, arg.data() + 4 * np, st.data());
     }
     for (size_t p = 0; p < np; p++) pst[p] = (st[2 * p] || st[2 * p + 1]) ? TM_PDF_RANGE : 0;
-    double *d_arg = (double *)mt->d_pdf;
+    double *d_arg = (double *)mt->pdf.scratch.d;
     uint32_t *d_cnt = (uint32_t *)(d_arg + 6 * np);
     int32_t *d_pairs = (int32_t *)(d_cnt + np * (cells + 1));
     TM_HIP(hipMemcpy(d_arg, arg.data(), 6 * np * sizeof(double), hipMemcpyHostToDevice));
@@ -190,7 +130,7 @@ extern "C" int tamcmc_modepdf_hist2d(tamcmc_modetable *mt, int32_t n_bins, int32
     TmPdfPairArgs a{};
     a.table = mt->d_table; a.pairs = d_pairs; a.status = d_pairs + 2 * np; a.lo = d_arg; a.hi = d_arg + 2 * np; a.s = d_arg + 4 * np; a.out = d_cnt;
     a.n = mt->n_used; a.max_samples = mt->max_samples; a.n_pairs = n_pairs; a.n_bins = n_bins;
-    rc = pdf_timed(mt, "modepdf pair", [&] { return tm_launch_modepdf_pair(a, mt->c->stream); });
+    rc = tm_mt_timed(mt, mt->pdf.clock, "modepdf pair", [&] { return tm_launch_modepdf_pair(a, mt->c->stream); });
     if (rc != TAMCMC_OK) return rc;
     TM_HIP(hipMemcpy(cnt.data(), d_cnt, cnt.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
     for (size_t p = 0; p < np; p++) {
@@ -211,13 +151,12 @@ extern "C" int tamcmc_modepdf_hist2d(tamcmc_modetable *mt, int32_t n_bins, int32
 extern "C" int tamcmc_modepdf_hpd(tamcmc_modetable *mt, int32_t n_mass, const double *mass, int32_t n_sel, const int32_t *cols,
                                   int64_t scratch_bytes, int64_t *k, int64_t *start, double *lo, double *hi)
 {
-    int rc = pdf_check(mt, 4);
-    if (rc != TAMCMC_OK) return rc;
+    if (!tm_mt_ready(mt, 4)) return TAMCMC_E_INVALID;
     if (n_mass < 1 || n_mass > TAMCMC_MODEPDF_MAX_MASS || !mass || scratch_bytes < 0 || !start || !lo || !hi) return TAMCMC_E_INVALID;
     for (int32_t m = 0; m < n_mass; m++)
         if (!tmp_mass_ok(mass[m])) return TAMCMC_E_INVALID;
     std::vector<int32_t> sel;
-    rc = pdf_select(mt, n_sel, cols, sel);
+    int rc = tm_mt_select(mt, n_sel, cols, sel);
     if (rc != TAMCMC_OK) return rc;
     const long long n = mt->n_used, P = tmr_padded(n);
     long long kk[TM_PDF_MAX_MASS] = {};
@@ -225,23 +164,14 @@ extern "C" int tamcmc_modepdf_hpd(tamcmc_modetable *mt, int32_t n_mass, const do
     // chunks of w columns: w * tmp_hpd_col_bytes and the window lengths fit the scratch; at least one column
     const size_t ns = (size_t)n_sel, nm = (size_t)n_mass, per = tmp_hpd_col_bytes(P, n_mass), fixed = TM_PDF_MAX_MASS * sizeof(long long);
     const size_t budget = scratch_bytes ? (size_t)scratch_bytes : (size_t)TM_PDF_DEFAULT_SCRATCH;
-    size_t wmax = budget > fixed ? (budget - fixed) / per : 0;
-    if (wmax < 1) wmax = 1;
-    if (wmax > ns) wmax = ns;
-    if (wmax > 65535) wmax = 65535;
-    const int w = (int)wmax;
+    const int w = tm_mt_chunk_width(budget, fixed, per, ns, 65535);
     std::vector<double> res;
     try { res.resize(3 * nm * (size_t)w); } catch (const std::bad_alloc &) { return TAMCMC_E_NOMEM; }
     const size_t bytes = fixed + (size_t)w * per;
-    TM_HIP(hipSetDevice(mt->c->device));
-    void *grown = nullptr;
-    rc = pdf_reserve(mt, bytes, &grown);
+    rc = pdf_enter(mt, bytes);
     if (rc != TAMCMC_OK) return rc;
-    rc = pdf_enter(mt);
-    if (rc != TAMCMC_OK) { (void)hipFree(grown); return rc; }
-    pdf_install(mt, grown, bytes);
     // the 8-byte arrays first: k [TM_PDF_MAX_MASS], keys [w][P], start, lo, hi [n_mass][w] each, then sel [w]
-    long long *d_k = (long long *)mt->d_pdf;
+    long long *d_k = (long long *)mt->pdf.scratch.d;
     uint64_t *d_keys = (uint64_t *)(d_k + TM_PDF_MAX_MASS);
     long long *d_start = (long long *)(d_keys + (size_t)w * (size_t)P);
     double *d_lo = (double *)(d_start + nm * (size_t)w), *d_hi = d_lo + nm * (size_t)w;
@@ -250,15 +180,12 @@ extern "C" int tamcmc_modepdf_hpd(tamcmc_modetable *mt, int32_t n_mass, const do
     for (size_t k0 = 0; k0 < ns; k0 += (size_t)w) {
         const int wc = ns - k0 < (size_t)w ? (int)(ns - k0) : w;
         TM_HIP(hipMemcpy(d_sel, sel.data() + k0, (size_t)wc * sizeof(int32_t), hipMemcpyHostToDevice));
-        TmMrArgs r{};                                        // the sort kernel reads table, sel, n, max_samples, P, w and writes keys
-        r.table = mt->d_table; r.sel = d_sel; r.keys = d_keys; r.n = n; r.max_samples = mt->max_samples; r.P = P;
-        r.r05 = (long long)tmq_rank(0.05, (int64_t)n); r.r95 = (long long)tmq_rank(0.95, (int64_t)n);
-        r.w = wc;
-        rc = pdf_timed(mt, "modepdf sort", [&] { return tm_launch_moderank_sort(r, 0, mt->c->stream); });
+        const TmMrArgs r = tmr_sort_args(mt->d_table, d_sel, d_keys, n, mt->max_samples, P, wc);
+        rc = tm_mt_timed(mt, mt->pdf.clock, "modepdf sort", [&] { return tm_launch_moderank_sort(r, 0, mt->c->stream); });
         if (rc != TAMCMC_OK) return rc;
         TmPdfHpdArgs a{};
         a.keys = d_keys; a.k = d_k; a.start = d_start; a.lo = d_lo; a.hi = d_hi; a.n = n; a.P = P; a.w = wc; a.n_mass = n_mass;
-        rc = pdf_timed(mt, "modepdf hpd", [&] { return tm_launch_modepdf_hpd(a, mt->c->stream); });
+        rc = tm_mt_timed(mt, mt->pdf.clock, "modepdf hpd", [&] { return tm_launch_modepdf_hpd(a, mt->c->stream); });
         if (rc != TAMCMC_OK) return rc;
         // start, lo, hi lie one behind the other, [n_mass][wc] each with the chunk's own width
         const size_t m1 = nm * (size_t)wc;
@@ -280,8 +207,5 @@ extern "C" int tamcmc_modepdf_hpd(tamcmc_modetable *mt, int32_t n_mass, const do
 
 extern "C" int tamcmc_modepdf_kernel_time(tamcmc_modetable *mt, double *total_ms, int64_t *launches)
 {
-    if (!mt || !total_ms || !launches || mt->c->in_flight || mt->c->armed) return TAMCMC_E_INVALID;
-    *total_ms = mt->pdf_ms;
-    *launches = mt->pdf_launches;
-    return TAMCMC_OK;
+    return tm_mt_idle(mt) ? mt->pdf.clock.read(total_ms, launches) : TAMCMC_E_INVALID;
 }

@@ -226,6 +226,16 @@ struct TmMrArgs {
     long long r05, r95;           // tmq_rank(0.05, n), tmq_rank(0.95, n), formed on the host
     int32_t w, pad;
 };
+// what the sort kernel reads (table, sel, n, max_samples, P, w) and writes (keys), and the two ranks every launch checks; the
+// transform and mean kernels' arrays are left NULL
+inline TmMrArgs tmr_sort_args(const double *table, const int32_t *sel, uint64_t *keys, const long long n, const long long max_samples,
+                              const long long P, const int w)
+{
+    TmMrArgs a{};
+    a.table = table; a.sel = sel; a.keys = keys; a.n = n; a.max_samples = max_samples; a.P = P; a.w = w;
+    a.r05 = (long long)tmq_rank(0.05, (int64_t)n); a.r95 = (long long)tmq_rank(0.95, (int64_t)n);
+    return a;
+}
 
 int tm_launch_moderank_sort(const TmMrArgs &a, int fold, void *stream);      // each returns a hipError_t
 int tm_launch_moderank_transform(const TmMrArgs &a, void *stream);

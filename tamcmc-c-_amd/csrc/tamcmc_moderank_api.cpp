@@ -13,38 +13,6 @@
 #include "tamcmc_modetable_obj.h"
 #include "tamcmc_moderank.h"
 
-static int mr_check(const tamcmc_modetable *mt)
-{
-    if (!mt || mt->c->in_flight || mt->c->armed) return TAMCMC_E_INVALID;
-    if (mt->max_samples == 0 || mt->n_used < 4) return TAMCMC_E_INVALID;
-    return TAMCMC_OK;
-}
-
-static int mr_enter(tamcmc_modetable *mt)
-{
-    TM_HIP(hipSetDevice(mt->c->device));
-    TM_HIP(tm_ctx_stream_sync(mt->c));
-    mt->c->enq_seq++;
-    return TAMCMC_OK;
-}
-
-// one launch between the object's two events, waited for; its time goes to the rank diagnostics' own sum
-template <class F>
-static int mr_timed(tamcmc_modetable *mt, const char *what, F &&launch)
-{
-    const hipStream_t stream = mt->c->stream;
-    TM_HIP(hipEventRecord(mt->ev[0], stream));
-    const int hr = launch();
-    if (hr != 0) return tm_launch_failed(what, hr);
-    TM_HIP(hipEventRecord(mt->ev[1], stream));
-    TM_HIP(hipStreamSynchronize(stream));
-    float ms = 0.f;
-    TM_HIP(hipEventElapsedTime(&ms, mt->ev[0], mt->ev[1]));
-    mt->rk_ms += (double)ms;
-    mt->rk_launches++;
-    return TAMCMC_OK;
-}
-
 // a chunk's buffers inside one allocation of w * tmr_col_bytes(n, L) bytes: the 8-byte arrays first
 struct MrChunk {
     TmMrArgs r{};
@@ -62,82 +30,64 @@ static MrChunk mr_carve(const tamcmc_modetable *mt, void *base, const int w, con
     double *medq = fin + (size_t)TM_MD_NFIN * ns;
     int32_t *cut = (int32_t *)(medq + 3 * (size_t)w);
     int32_t *sel = cut + ns;
-    k.r.table = mt->d_table; k.r.sel = sel; k.r.keys = keys; k.r.series = series; k.r.mean = mean; k.r.medq = medq; k.r.rank2 = rank2;
-    k.r.n = n; k.r.max_samples = mt->max_samples; k.r.P = (long long)P;
-    k.r.r05 = (long long)tmq_rank(0.05, (int64_t)n); k.r.r95 = (long long)tmq_rank(0.95, (int64_t)n);
-    k.r.w = w;
+    k.r = tmr_sort_args(mt->d_table, sel, keys, n, mt->max_samples, (long long)P, w);
+    k.r.series = series; k.r.mean = mean; k.r.medq = medq; k.r.rank2 = rank2;
     k.d.table = series; k.d.mean = mean; k.d.acc = acc; k.d.fin = fin; k.d.cut = cut;
     k.d.n = n; k.d.max_samples = n; k.d.n_cols = (int32_t)ns; k.d.L = L;
     k.d.tau_floor = 1.0 / std::log10((double)n);
     return k;
 }
 
-// the chunk's columns to the device, then every kernel of the chunk
-static int mr_run(tamcmc_modetable *mt, const MrChunk &k, const int32_t *sel)
+// the chunk's columns to the device, then the kernels that form its series and, with `lags`, those of their lag products
+static int mr_run(tamcmc_modetable *mt, const MrChunk &k, const int32_t *sel, const bool lags)
 {
     tamcmc_ctx *c = mt->c;
+    TmMtClock &clock = mt->rank.clock;
     TM_HIP(hipMemcpy((void *)k.r.sel, sel, (size_t)k.r.w * sizeof(int32_t), hipMemcpyHostToDevice));
-    int rc = mr_timed(mt, "moderank sort", [&] { return tm_launch_moderank_sort(k.r, 0, c->stream); });
-    if (rc == TAMCMC_OK) rc = mr_timed(mt, "moderank sort (folded)", [&] { return tm_launch_moderank_sort(k.r, 1, c->stream); });
-    if (rc == TAMCMC_OK) rc = mr_timed(mt, "moderank transform", [&] { return tm_launch_moderank_transform(k.r, c->stream); });
-    if (rc == TAMCMC_OK) rc = mr_timed(mt, "moderank mean", [&] { return tm_launch_moderank_mean(k.r, c->stream); });
-    if (rc == TAMCMC_OK) rc = mr_timed(mt, "moderank lag", [&] { return tm_launch_modediag_lag(k.d, c->stream); });
-    if (rc == TAMCMC_OK) rc = mr_timed(mt, "moderank finish", [&] { return tm_launch_modediag_finish(k.d, c->stream); });
-    if (rc != TAMCMC_OK) (void)hipStreamSynchronize(c->stream);
+    int rc = tm_mt_timed(mt, clock, "moderank sort", [&] { return tm_launch_moderank_sort(k.r, 0, c->stream); });
+    if (rc == TAMCMC_OK) rc = tm_mt_timed(mt, clock, "moderank sort (folded)", [&] { return tm_launch_moderank_sort(k.r, 1, c->stream); });
+    if (rc == TAMCMC_OK) rc = tm_mt_timed(mt, clock, "moderank transform", [&] { return tm_launch_moderank_transform(k.r, c->stream); });
+    if (rc == TAMCMC_OK) rc = tm_mt_timed(mt, clock, "moderank mean", [&] { return tm_launch_moderank_mean(k.r, c->stream); });
+    if (rc == TAMCMC_OK && lags) rc = tm_mt_timed(mt, clock, "moderank lag", [&] { return tm_launch_modediag_lag(k.d, c->stream); });
+    if (rc == TAMCMC_OK && lags) rc = tm_mt_timed(mt, clock, "moderank finish", [&] { return tm_launch_modediag_finish(k.d, c->stream); });
     return rc;
 }
 
 extern "C" int tamcmc_moderank_diag(tamcmc_modetable *mt, int32_t max_lag, int32_t n_sel, const int32_t *cols, int64_t scratch_bytes,
                                     tamcmc_moderank_totals *totals, double *out, int32_t *cut)
 {
-    int rc = mr_check(mt);
-    if (rc != TAMCMC_OK) return rc;
-    if (max_lag < 0 || max_lag > TAMCMC_MODEDIAG_MAX_LAG || n_sel < 1 || n_sel > mt->n_cols || scratch_bytes < 0) return TAMCMC_E_INVALID;
+    if (!tm_mt_ready(mt, 4)) return TAMCMC_E_INVALID;
+    if (max_lag < 0 || max_lag > TAMCMC_MODEDIAG_MAX_LAG || scratch_bytes < 0) return TAMCMC_E_INVALID;
     const long long n = mt->n_used;
     const int L = tme_lag_limit(max_lag, n);
     const size_t ns = (size_t)n_sel, S = TM_MR_NSERIES, nl = (size_t)(L + 1);
     std::vector<int32_t> sel, cutv, cc;
-    std::vector<char> seen;
     std::vector<double> fin, acov, chunk_acc;
-    try { sel.resize(ns); seen.assign((size_t)mt->n_cols, 0); } catch (const std::bad_alloc &) { return TAMCMC_E_NOMEM; }
-    for (int32_t k = 0; k < n_sel; k++) {
-        const int32_t col = cols ? cols[k] : k;
-        if (col < 0 || col >= mt->n_cols || seen[(size_t)col]) return TAMCMC_E_INVALID;
-        seen[(size_t)col] = 1;
-        sel[(size_t)k] = col;
-    }
+    int rc = tm_mt_select(mt, n_sel, cols, sel);
+    if (rc != TAMCMC_OK) return rc;
     const size_t per = tmr_col_bytes(n, L);
     const size_t budget = scratch_bytes ? (size_t)scratch_bytes : (size_t)TM_MR_DEFAULT_SCRATCH;
-    size_t wmax = budget / per;
-    if (wmax < 1) wmax = 1;
-    if (wmax > ns) wmax = ns;
-    if (wmax > 16383) wmax = 16383;                  // (4 w series are the lag kernel's grid.x, w the transform kernel's grid.y)
-    int w = (int)wmax;
+    int w = tm_mt_chunk_width(budget, 0, per, ns, 16383);   // (4 w series are the lag kernel's grid.x, w the transform kernel's grid.y)
     try {
         cutv.resize(S * ns); fin.resize((size_t)TM_MD_NFIN * S * ns); acov.resize(S * nl * ns);
         chunk_acc.resize(S * (size_t)w * (nl + TM_MD_NFIN)); cc.resize(S * (size_t)w);
     } catch (const std::bad_alloc &) { return TAMCMC_E_NOMEM; }
     // the scratch first: a call that cannot have it returns with the object, its context's counters included, as it was
     TM_HIP(hipSetDevice(mt->c->device));
+    TmMtRank &R = mt->rank;
     void *grown = nullptr;
-    if ((size_t)w * per > mt->rk_bytes && hipMalloc(&grown, (size_t)w * per) != hipSuccess) {
-        (void)hipGetLastError();
-        grown = nullptr;
-        if (per > mt->rk_bytes && hipMalloc(&grown, per) != hipSuccess) { (void)hipGetLastError(); return TAMCMC_E_NOMEM; }
-        w = grown ? 1 : (int)(mt->rk_bytes / per);   // one column at a time, or what the scratch at hand holds
+    if (R.scratch.reserve((size_t)w * per, &grown) != TAMCMC_OK) {
+        if (R.scratch.reserve(per, &grown) != TAMCMC_OK) return TAMCMC_E_NOMEM;
+        w = grown ? 1 : (int)(R.scratch.bytes / per);   // one column at a time, or what the scratch at hand holds
     }
-    rc = mr_enter(mt);
+    rc = tm_mt_enter(mt);
     if (rc != TAMCMC_OK) { (void)hipFree(grown); return rc; }
-    if (grown) {
-        (void)hipFree(mt->d_rk);
-        mt->d_rk = grown;
-        mt->rk_bytes = (size_t)w * per;
-    }
-    mt->rk_valid = false;
+    R.scratch.install(grown, (size_t)w * per);
+    R.valid = false;
     for (size_t k0 = 0; k0 < ns; k0 += (size_t)w) {
         const int wc = ns - k0 < (size_t)w ? (int)(ns - k0) : w;
-        const MrChunk k = mr_carve(mt, mt->d_rk, wc, n, L, nullptr);
-        rc = mr_run(mt, k, sel.data() + k0);
+        const MrChunk k = mr_carve(mt, R.scratch.d, wc, n, L, nullptr);
+        rc = mr_run(mt, k, sel.data() + k0, true);
         if (rc != TAMCMC_OK) return rc;
         const size_t cs = S * (size_t)wc;                                   // the chunk's series: TM_MR_NSERIES c + s
         TM_HIP(hipMemcpy(chunk_acc.data(), k.d.acc, (nl + TM_MD_NFIN) * cs * sizeof(double), hipMemcpyDeviceToHost));   // acc, then fin behind it
@@ -150,8 +100,8 @@ extern "C" int tamcmc_moderank_diag(tamcmc_modetable *mt, int32_t max_lag, int32
         for (size_t c = 0; c < (size_t)wc; c++)
             for (size_t s = 0; s < S; s++) cutv[s * ns + k0 + c] = cc[S * c + s];
     }
-    mt->rk_acov.swap(acov);
-    mt->rk_L = L; mt->rk_nsel = n_sel; mt->rk_valid = true;
+    R.acov.swap(acov);
+    R.L = L; R.nsel = n_sel; R.valid = true;
     auto F = [&](int f, int s, size_t k) { return fin[((size_t)f * S + (size_t)s) * ns + k]; };
     std::vector<double> eb, et, rh, a0;
     try { eb.resize(ns); et.resize(ns); rh.resize(ns); a0.resize(ns); } catch (const std::bad_alloc &) { return TAMCMC_E_NOMEM; }
@@ -159,7 +109,7 @@ extern "C" int tamcmc_moderank_diag(tamcmc_modetable *mt, int32_t max_lag, int32
         eb[k] = F(TM_MD_ESS, TM_MR_Z, k);
         et[k] = tmr_min_skip(F(TM_MD_ESS, TM_MR_I05, k), F(TM_MD_ESS, TM_MR_I95, k));
         rh[k] = tmr_max_skip(F(TM_MD_RHAT, TM_MR_Z, k), F(TM_MD_RHAT, TM_MR_ZFOLD, k));
-        a0[k] = mt->rk_acov[((size_t)TM_MR_Z * nl) * ns + k];
+        a0[k] = R.acov[((size_t)TM_MR_Z * nl) * ns + k];
         if (out) {
             out[TM_MR_ESS_BULK * ns + k] = eb[k];
             out[TM_MR_ESS_TAIL * ns + k] = et[k];
@@ -184,23 +134,19 @@ extern "C" int tamcmc_moderank_diag(tamcmc_modetable *mt, int32_t max_lag, int32
 
 extern "C" int tamcmc_moderank_acov(tamcmc_modetable *mt, int32_t series, double *acov)
 {
-    const int rc = mr_check(mt);
-    if (rc != TAMCMC_OK) return rc;
-    if (!acov || series < 0 || series >= TM_MR_NSERIES || !mt->rk_valid) return TAMCMC_E_INVALID;
-    const size_t m = (size_t)(mt->rk_L + 1) * (size_t)mt->rk_nsel;
-    std::memcpy(acov, mt->rk_acov.data() + (size_t)series * m, m * sizeof(double));
+    if (!tm_mt_ready(mt, 4) || !acov || series < 0 || series >= TM_MR_NSERIES || !mt->rank.valid) return TAMCMC_E_INVALID;
+    const size_t m = (size_t)(mt->rank.L + 1) * (size_t)mt->rank.nsel;
+    std::memcpy(acov, mt->rank.acov.data() + (size_t)series * m, m * sizeof(double));
     return TAMCMC_OK;
 }
 
 extern "C" int tamcmc_moderank_series(tamcmc_modetable *mt, int32_t col, int64_t *rank2, int64_t *rank2_fold, double *series, double *mean,
                                       double *med_q)
 {
-    int rc = mr_check(mt);
-    if (rc != TAMCMC_OK) return rc;
-    if (col < 0 || col >= mt->n_cols) return TAMCMC_E_INVALID;
+    if (!tm_mt_ready(mt, 4) || col < 0 || col >= mt->n_cols) return TAMCMC_E_INVALID;
     const long long n = mt->n_used;
     const int L = 1;                                                        // (the lag kernels are not run)
-    rc = mr_enter(mt);
+    int rc = tm_mt_enter(mt);
     if (rc != TAMCMC_OK) return rc;
     void *base = nullptr;
     long long *d_rank2 = nullptr;
@@ -212,11 +158,7 @@ extern "C" int tamcmc_moderank_series(tamcmc_modetable *mt, int32_t col, int64_t
     const MrChunk k = mr_carve(mt, base, 1, n, L, d_rank2);
     tamcmc_ctx *c = mt->c;
     auto done = [&](int code) { (void)hipStreamSynchronize(c->stream); (void)hipFree(base); (void)hipFree(d_rank2); return code; };
-    if (hipMemcpy((void *)k.r.sel, &col, sizeof(int32_t), hipMemcpyHostToDevice) != hipSuccess) return done(TAMCMC_E_HIP);
-    rc = mr_timed(mt, "moderank sort", [&] { return tm_launch_moderank_sort(k.r, 0, c->stream); });
-    if (rc == TAMCMC_OK) rc = mr_timed(mt, "moderank sort (folded)", [&] { return tm_launch_moderank_sort(k.r, 1, c->stream); });
-    if (rc == TAMCMC_OK) rc = mr_timed(mt, "moderank transform", [&] { return tm_launch_moderank_transform(k.r, c->stream); });
-    if (rc == TAMCMC_OK) rc = mr_timed(mt, "moderank mean", [&] { return tm_launch_moderank_mean(k.r, c->stream); });
+    rc = mr_run(mt, k, &col, false);
     if (rc != TAMCMC_OK) return done(rc);
     const size_t sn = (size_t)n;
     if ((rank2 && hipMemcpy(rank2, d_rank2, sn * sizeof(int64_t), hipMemcpyDeviceToHost) != hipSuccess) ||
@@ -230,8 +172,5 @@ extern "C" int tamcmc_moderank_series(tamcmc_modetable *mt, int32_t col, int64_t
 
 extern "C" int tamcmc_moderank_kernel_time(tamcmc_modetable *mt, double *total_ms, int64_t *launches)
 {
-    if (!mt || !total_ms || !launches || mt->c->in_flight || mt->c->armed) return TAMCMC_E_INVALID;
-    *total_ms = mt->rk_ms;
-    *launches = mt->rk_launches;
-    return TAMCMC_OK;
+    return tm_mt_idle(mt) ? mt->rank.clock.read(total_ms, launches) : TAMCMC_E_INVALID;
 }

@@ -14,39 +14,11 @@
 
 #include "tamcmc_modetable_obj.h"          // struct tamcmc_modetable
 
-static int mt_enter(tamcmc_modetable *mt)
-{
-    if (!mt || mt->c->in_flight || mt->c->armed) return TAMCMC_E_INVALID;
-    TM_HIP(hipSetDevice(mt->c->device));
-    TM_HIP(tm_ctx_stream_sync(mt->c));
-    return TAMCMC_OK;
-}
-
 static int mt_check(const tamcmc_modetable *mt, int32_t Nsamples, int32_t Nparams, const double *params)
 {
     if (!mt || !params || Nsamples < 1) return TAMCMC_E_INVALID;
     const tamcmc_ctx *c = mt->c;
     if (Nparams != c->L.Nparams || c->in_flight || c->armed) return TAMCMC_E_INVALID;
-    return TAMCMC_OK;
-}
-
-// One launch between the object's two events; its time is added once the stream has been waited for (mt_timed_done).
-template <class F>
-static int mt_timed(tamcmc_modetable *mt, const char *what, F &&launch)
-{
-    const hipStream_t stream = mt->c->stream;
-    TM_HIP(hipEventRecord(mt->ev[0], stream));
-    const int hr = launch();
-    if (hr != 0) return tm_launch_failed(what, hr);
-    TM_HIP(hipEventRecord(mt->ev[1], stream));
-    return TAMCMC_OK;
-}
-static int mt_timed_done(tamcmc_modetable *mt)
-{
-    float ms = 0.f;
-    TM_HIP(hipEventElapsedTime(&ms, mt->ev[0], mt->ev[1]));
-    mt->ms += (double)ms;
-    mt->launches++;
     return TAMCMC_OK;
 }
 
@@ -63,7 +35,7 @@ static int mt_derive_block(tamcmc_modetable *mt, int n, const double *params, bo
     a.L = c->L; a.params = mt->d_params; a.rows = mt->d_rows; a.status = mt->d_status; a.B = n; a.n_cols = mt->n_cols;
     const size_t lds = ((np + 1) & ~(size_t)1) * sizeof(double);
     int rc;
-    if (timed) rc = mt_timed(mt, "modetable derive", [&] { return tm_launch_modetable_derive(a, lds, c->stream); });
+    if (timed) rc = tm_mt_timed_record(mt, mt->ev, "modetable derive", [&] { return tm_launch_modetable_derive(a, lds, c->stream); });
     else {
         const int hr = tm_launch_modetable_derive(a, lds, c->stream);
         rc = hr != 0 ? tm_launch_failed("modetable derive", hr) : TAMCMC_OK;
@@ -74,11 +46,8 @@ static int mt_derive_block(tamcmc_modetable *mt, int n, const double *params, bo
 
 static int mt_clear(tamcmc_modetable *mt)
 {
-    mt->n_used = 0; mt->n_rejected = 0; mt->ms = 0.0; mt->launches = 0;
-    mt->acov_valid = false; mt->diag_ms = 0.0; mt->diag_launches = 0;      // tamcmc_modediag_*
-    mt->rk_valid = false; mt->rk_ms = 0.0; mt->rk_launches = 0;            // tamcmc_moderank_*
-    mt->seis_ms = 0.0; mt->seis_launches = 0;                              // tamcmc_modetable_indices_* (the plan stays)
-    mt->pdf_ms = 0.0; mt->pdf_launches = 0;                                // tamcmc_modepdf_*
+    mt->n_used = 0; mt->n_rejected = 0; mt->clock.clear();
+    mt->diag.clear(); mt->rank.clear(); mt->seis.clear(); mt->pdf.clear();
     TM_HIP(hipMemsetAsync(mt->d_state, 0, mt->state_doubles() * sizeof(double), mt->c->stream));
     return TAMCMC_OK;
 }
@@ -130,11 +99,7 @@ extern "C" int tamcmc_modetable_destroy(tamcmc_modetable *mt)
     if (mt->counted) c->modetables--;
     (void)hipFree(mt->d_params); (void)hipFree(mt->d_rows); (void)hipFree(mt->d_status); (void)hipFree(mt->d_accept);
     (void)hipFree(mt->d_state); (void)hipFree(mt->d_ranks); (void)hipFree(mt->d_table);
-    (void)hipFree(mt->d_acc); (void)hipFree(mt->d_cut); (void)hipFree(mt->d_S); (void)hipFree(mt->d_sel);
-    (void)hipFree(mt->d_rk);
-    (void)hipFree(mt->d_seis_i); (void)hipFree(mt->d_seis_d);
-    (void)hipFree(mt->d_pdf);
-    for (hipEvent_t e : mt->seis_ev) if (e) (void)hipEventDestroy(e);
+    mt->diag.release(); mt->rank.release(); mt->seis.release(); mt->pdf.release();
     for (hipEvent_t e : mt->ev) if (e) (void)hipEventDestroy(e);
     delete mt;
     return TAMCMC_OK;
@@ -142,7 +107,7 @@ extern "C" int tamcmc_modetable_destroy(tamcmc_modetable *mt)
 
 extern "C" int tamcmc_modetable_columns(tamcmc_modetable *mt, int32_t *n_cols, int32_t *n_mult)
 {
-    if (!mt || !n_cols || !n_mult || mt->c->in_flight || mt->c->armed) return TAMCMC_E_INVALID;
+    if (!tm_mt_idle(mt) || !n_cols || !n_mult) return TAMCMC_E_INVALID;
     *n_cols = mt->n_cols;
     *n_mult = mt->c->L.n_mult;
     return TAMCMC_OK;
@@ -150,7 +115,7 @@ extern "C" int tamcmc_modetable_columns(tamcmc_modetable *mt, int32_t *n_cols, i
 
 extern "C" int tamcmc_modetable_column(tamcmc_modetable *mt, int32_t col, tamcmc_modetable_col *out)
 {
-    if (!mt || !out || col < 0 || col >= mt->n_cols || mt->c->in_flight || mt->c->armed) return TAMCMC_E_INVALID;
+    if (!tm_mt_idle(mt) || !out || col < 0 || col >= mt->n_cols) return TAMCMC_E_INVALID;
     const TmMtCol &k = mt->cols[(size_t)col];
     out->kind = k.kind; out->mult = k.mult; out->order = k.order; out->l = k.l; out->m = k.m; out->param_index = k.param_index;
     return TAMCMC_OK;
@@ -186,8 +151,7 @@ extern "C" int tamcmc_modetable_push(tamcmc_modetable *mt, int32_t Nsamples, int
     if (rc != TAMCMC_OK) return rc;
     tamcmc_ctx *c = mt->c;
     TM_HIP(hipSetDevice(c->device));
-    mt->acov_valid = false;              // tamcmc_modediag_acov: the lag products are those of the table before this push
-    mt->rk_valid = false;                // tamcmc_moderank_acov likewise
+    mt->diag.invalidate(); mt->rank.invalidate(); mt->seis.invalidate(); mt->pdf.invalidate();      // what they keep is that of the table before this push
     const size_t np = (size_t)Nparams, ns = mt->state_doubles();
     std::vector<int32_t> st, acc;
     try { st.resize((size_t)Nsamples); acc.resize((size_t)mt->B); } catch (const std::bad_alloc &) { return TAMCMC_E_NOMEM; }
@@ -206,7 +170,7 @@ extern "C" int tamcmc_modetable_push(tamcmc_modetable *mt, int32_t Nsamples, int
         rc = mt_derive_block(mt, n, params + (size_t)k * np, true);
         if (rc != TAMCMC_OK) return undo(rc);
         if (hipMemcpyAsync(st.data() + k, mt->d_status, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
-            hipStreamSynchronize(c->stream) != hipSuccess || mt_timed_done(mt) != TAMCMC_OK ||
+            hipStreamSynchronize(c->stream) != hipSuccess || tm_mt_timed_add(mt->ev, mt->clock) != TAMCMC_OK ||
             (mt->n_index_cols > 0 && tm_seis_timed_done(mt) != TAMCMC_OK))
             return undo(TAMCMC_E_HIP);
         long long take = 0;
@@ -221,9 +185,9 @@ extern "C" int tamcmc_modetable_push(tamcmc_modetable *mt, int32_t Nsamples, int
             TmMtFoldArgs a{};
             a.rows = mt->d_rows; a.accept = mt->d_accept; a.state = mt->d_state; a.table = mt->d_table;
             a.n_before = mt->n_used; a.max_samples = mt->max_samples; a.B = n; a.n_cols = mt->n_cols;
-            rc = mt_timed(mt, "modetable fold", [&] { return tm_launch_modetable_fold(a, c->stream); });
+            rc = tm_mt_timed_record(mt, mt->ev, "modetable fold", [&] { return tm_launch_modetable_fold(a, c->stream); });
             if (rc != TAMCMC_OK) return undo(rc);
-            if (hipStreamSynchronize(c->stream) != hipSuccess || mt_timed_done(mt) != TAMCMC_OK) return undo(TAMCMC_E_HIP);
+            if (hipStreamSynchronize(c->stream) != hipSuccess || tm_mt_timed_add(mt->ev, mt->clock) != TAMCMC_OK) return undo(TAMCMC_E_HIP);
         }
         mt->n_used += take;
         mt->n_rejected += n - take;
@@ -235,7 +199,8 @@ extern "C" int tamcmc_modetable_push(tamcmc_modetable *mt, int32_t Nsamples, int
 
 extern "C" int tamcmc_modetable_result(tamcmc_modetable *mt, tamcmc_modetable_totals *t, double *mean, double *sd, double *mn, double *mx)
 {
-    const int rc = mt_enter(mt);
+    if (!tm_mt_idle(mt)) return TAMCMC_E_INVALID;
+    const int rc = tm_mt_enter(mt);                 // (it enqueues nothing; the count it adds to only makes a fit group order itself once more)
     if (rc != TAMCMC_OK) return rc;
     const size_t nc = (size_t)mt->n_cols;
     std::vector<double> st;
@@ -255,18 +220,17 @@ extern "C" int tamcmc_modetable_result(tamcmc_modetable *mt, tamcmc_modetable_to
 
 extern "C" int tamcmc_modetable_quantiles(tamcmc_modetable *mt, int32_t Nq, const double *q, int64_t *ranks, double *out)
 {
-    if (!mt || !q || !out || Nq < 1 || Nq > TAMCMC_SUMMARY_MAX_QUANTILES) return TAMCMC_E_INVALID;
+    if (!tm_mt_idle(mt) || !q || !out || Nq < 1 || Nq > TAMCMC_SUMMARY_MAX_QUANTILES) return TAMCMC_E_INVALID;
     for (int j = 0; j < Nq; j++)
         if (!(q[j] >= 0.0 && q[j] <= 1.0)) return TAMCMC_E_INVALID;        // (a NaN fails both comparisons)
     if (mt->max_samples < 1 || mt->n_used < 1) return TAMCMC_E_INVALID;
-    const int rc = mt_enter(mt);
+    const int rc = tm_mt_enter(mt);
     if (rc != TAMCMC_OK) return rc;
     tamcmc_ctx *c = mt->c;
     uint64_t rk[TM_Q_MAXQ] = {};
     for (int j = 0; j < Nq; j++) rk[j] = (uint64_t)tmq_rank(q[j], (int64_t)mt->n_used);
     const size_t nc = (size_t)mt->n_cols;
     auto fail = [&](int code) { (void)hipStreamSynchronize(c->stream); return code; };
-    c->enq_seq++;
     if (hipMemcpyAsync(mt->d_ranks, rk, sizeof(rk), hipMemcpyHostToDevice, c->stream) != hipSuccess) return fail(TAMCMC_E_HIP);
     TmMtQuantArgs a{};
     a.table = mt->d_table; a.state = mt->d_state; a.ranks = mt->d_ranks; a.out = mt->d_state + 2 * mt->state_doubles();
@@ -282,16 +246,12 @@ extern "C" int tamcmc_modetable_quantiles(tamcmc_modetable *mt, int32_t Nq, cons
 
 extern "C" int tamcmc_modetable_reset(tamcmc_modetable *mt)
 {
-    const int rc = mt_enter(mt);
-    if (rc != TAMCMC_OK) return rc;
-    mt->c->enq_seq++;
-    return mt_clear(mt);
+    if (!tm_mt_idle(mt)) return TAMCMC_E_INVALID;
+    const int rc = tm_mt_enter(mt);
+    return rc != TAMCMC_OK ? rc : mt_clear(mt);
 }
 
 extern "C" int tamcmc_modetable_kernel_time(tamcmc_modetable *mt, double *total_ms, int64_t *launches)
 {
-    if (!mt || !total_ms || !launches || mt->c->in_flight || mt->c->armed) return TAMCMC_E_INVALID;
-    *total_ms = mt->ms;
-    *launches = mt->launches;
-    return TAMCMC_OK;
+    return tm_mt_idle(mt) ? mt->clock.read(total_ms, launches) : TAMCMC_E_INVALID;
 }

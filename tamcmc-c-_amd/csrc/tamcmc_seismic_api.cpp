@@ -13,44 +13,35 @@
 
 static void seis_info(const tamcmc_modetable *mt, tamcmc_seismic_info *info)
 {
-    const TmSeisPlan &P = mt->plan;
+    const TmSeisPlan &P = mt->seis.plan;
     info->n_base_cols = mt->n_base_cols; info->n_index_cols = mt->n_index_cols; info->n_radial = P.n_radial;
     info->n_unassigned = P.n_unassigned; info->n_base = P.n_base; info->dnu_ref = P.dnu_ref; info->eps_ref = P.eps_ref;
 }
 
 int tm_seis_block(tamcmc_modetable *mt, int n, bool timed)
 {
-    const TmSeisPlan &P = mt->plan;
+    const TmSeisPlan &P = mt->seis.plan;
     const size_t ni = (size_t)P.n_index(), nt = (size_t)P.n_terms();
     TmSeisArgs a{};
     a.rows = mt->d_rows; a.status = mt->d_status;
-    a.first = mt->d_seis_i; a.n_num = a.first + ni + 1; a.src = a.n_num + ni; a.wsrc = a.src + nt;
-    a.coef = mt->d_seis_d; a.offset = a.coef + nt;
+    a.first = mt->seis.d_i; a.n_num = a.first + ni + 1; a.src = a.n_num + ni; a.wsrc = a.src + nt;
+    a.coef = mt->seis.d_d; a.offset = a.coef + nt;
     a.B = n; a.n_cols = mt->n_cols; a.n_base_cols = mt->n_base_cols; a.n_index = mt->n_index_cols;
     const hipStream_t stream = mt->c->stream;
-    if (timed) TM_HIP(hipEventRecord(mt->seis_ev[0], stream));
+    if (timed) return tm_mt_timed_record(mt, mt->seis.ev, "seismic indices", [&] { return tm_launch_seismic(a, stream); });
     const int hr = tm_launch_seismic(a, stream);
-    if (hr != 0) return tm_launch_failed("seismic indices", hr);
-    if (timed) TM_HIP(hipEventRecord(mt->seis_ev[1], stream));
-    return TAMCMC_OK;
+    return hr != 0 ? tm_launch_failed("seismic indices", hr) : TAMCMC_OK;
 }
 
-int tm_seis_timed_done(tamcmc_modetable *mt)
-{
-    float ms = 0.f;
-    TM_HIP(hipEventElapsedTime(&ms, mt->seis_ev[0], mt->seis_ev[1]));
-    mt->seis_ms += (double)ms;
-    mt->seis_launches++;
-    return TAMCMC_OK;
-}
+int tm_seis_timed_done(tamcmc_modetable *mt) { return tm_mt_timed_add(mt->seis.ev, mt->seis.clock); }
 
 extern "C" int tamcmc_modetable_indices_enable(tamcmc_modetable *mt, int32_t Nparams, const double *ref_params, tamcmc_seismic_info *info)
 {
-    if (!mt || !ref_params || !info) return TAMCMC_E_INVALID;
+    if (!tm_mt_idle(mt) || !ref_params || !info) return TAMCMC_E_INVALID;
     tamcmc_ctx *c = mt->c;
-    if (Nparams != c->L.Nparams || c->in_flight || c->armed) return TAMCMC_E_INVALID;
+    if (Nparams != c->L.Nparams) return TAMCMC_E_INVALID;
     if (mt->n_index_cols > 0 || mt->n_used != 0 || mt->n_rejected != 0) return TAMCMC_E_INVALID;         // once, on an empty table
-    if (mt->d_acc || mt->d_cut || mt->d_S || mt->d_sel || mt->d_rk) return TAMCMC_E_INVALID;               // a diagnostics buffer exists
+    if (mt->diag.sized_by_columns() || mt->rank.sized_by_columns()) return TAMCMC_E_INVALID;               // a diagnostics buffer exists
     const int nb = mt->n_base_cols;
     if (((size_t)nb + 1) * sizeof(double) > TM_SEIS_LDS_MAX) return TAMCMC_E_INVALID;                      // the row does not fit the kernel's LDS
     TM_HIP(hipSetDevice(c->device));
@@ -122,19 +113,19 @@ extern "C" int tamcmc_modetable_indices_enable(tamcmc_modetable *mt, int32_t Npa
     // nothing below fails
     (void)hipFree(mt->d_rows); (void)hipFree(mt->d_state); (void)hipFree(mt->d_table);
     mt->d_rows = rows; mt->d_state = state; mt->d_table = table;
-    mt->d_seis_i = si; mt->d_seis_d = sd;
-    mt->seis_ev[0] = ev[0]; mt->seis_ev[1] = ev[1];
+    mt->seis.d_i = si; mt->seis.d_d = sd;
+    mt->seis.ev[0] = ev[0]; mt->seis.ev[1] = ev[1];
     mt->cols.swap(cols);
-    mt->plan = std::move(P);
+    mt->seis.plan = std::move(P);
     mt->n_index_cols = ni; mt->n_cols = n_cols; mt->B = B;
-    mt->seis_ms = 0.0; mt->seis_launches = 0;
+    mt->seis.clock.clear();
     seis_info(mt, info);
     return TAMCMC_OK;
 }
 
 extern "C" int tamcmc_modetable_indices_info(tamcmc_modetable *mt, tamcmc_seismic_info *info)
 {
-    if (!mt || !info || mt->c->in_flight || mt->c->armed || mt->n_index_cols < 1) return TAMCMC_E_INVALID;
+    if (!tm_mt_idle(mt) || !info || mt->n_index_cols < 1) return TAMCMC_E_INVALID;
     seis_info(mt, info);
     return TAMCMC_OK;
 }
@@ -142,9 +133,9 @@ extern "C" int tamcmc_modetable_indices_info(tamcmc_modetable *mt, tamcmc_seismi
 extern "C" int tamcmc_modetable_index_terms(tamcmc_modetable *mt, int32_t col, int32_t cap, int32_t *n_num, int32_t *n_den,
                                             int32_t *src, int32_t *wsrc, double *coef, double *offset)
 {
-    if (!mt || !n_num || !n_den || mt->c->in_flight || mt->c->armed) return TAMCMC_E_INVALID;
+    if (!tm_mt_idle(mt) || !n_num || !n_den) return TAMCMC_E_INVALID;
     if (col < mt->n_base_cols || col >= mt->n_cols) return TAMCMC_E_INVALID;
-    const TmSeisPlan &P = mt->plan;
+    const TmSeisPlan &P = mt->seis.plan;
     const size_t j = (size_t)(col - mt->n_base_cols);
     const int t0 = P.first[j], t2 = P.first[j + 1];
     *n_num = P.n_num[j];
@@ -157,8 +148,5 @@ extern "C" int tamcmc_modetable_index_terms(tamcmc_modetable *mt, int32_t col, i
 
 extern "C" int tamcmc_seismic_kernel_time(tamcmc_modetable *mt, double *total_ms, int64_t *launches)
 {
-    if (!mt || !total_ms || !launches || mt->c->in_flight || mt->c->armed) return TAMCMC_E_INVALID;
-    *total_ms = mt->seis_ms;
-    *launches = mt->seis_launches;
-    return TAMCMC_OK;
+    return tm_mt_idle(mt) ? mt->seis.clock.read(total_ms, launches) : TAMCMC_E_INVALID;
 }

@@ -68,9 +68,22 @@ def test_symbols_and_signatures(accel_mod):
     mk = open(os.path.join(CSRC, "Makefile")).read()
     assert "tamcmc_modepdf.o tamcmc_modepdf_api.o" in mk and "resource-usage-modepdf:" in mk and "modepdf-core-check:" in mk
     obj = open(os.path.join(CSRC, "tamcmc_modetable_obj.h")).read()
-    assert "tamcmc_modepdf_*" in obj and "d_pdf" in obj
-    api = open(os.path.join(CSRC, "tamcmc_modepdf_api.cpp")).read()
-    assert "d_rk" not in api and "rk_valid" not in api and "acov_valid" not in api
+    assert "tamcmc_modepdf_*" in obj and re.search(r"struct TmMtPdf \{\s*TmMtBuf scratch;", obj) and re.search(r"\bTmMtPdf pdf;", obj)
+    # every feature's file reaches its own member struct of the object and no other's (a field is reached through its member or
+    # through the member's type alone); the table's file reaches the four through their hooks alone
+    owners = {"modediag": "diag", "moderank": "rank", "seismic": "seis", "modepdf": "pdf"}
+    foreign = r"(->|\.)\s*(%s)\b|\bTmMt(%s)\b"
+    for feature, own in owners.items():
+        api = open(os.path.join(CSRC, "tamcmc_%s_api.cpp" % feature)).read()
+        others = [m for m in owners.values() if m != own]
+        if feature == "seismic":                    # indices_enable asks the two whose buffers are sized by n_cols, and nothing else of them
+            api = api.replace("mt->diag.sized_by_columns()", "").replace("mt->rank.sized_by_columns()", "")
+        assert re.search(r"(->|\.)\s*%s\b" % own, api), feature
+        assert not re.search(foreign % ("|".join(others), "|".join(m.capitalize() for m in others)), api), feature
+    api = open(os.path.join(CSRC, "tamcmc_modetable_api.cpp")).read()
+    named = re.findall(r"(?:->|\.)\s*(?:diag|rank|seis|pdf)\b\s*(\.\s*\w+\s*\(\s*\))?", api)
+    assert len(named) == 12 and set(re.sub(r"\s", "", n) for n in named) == {".invalidate()", ".clear()", ".release()"}
+    assert not re.search(r"\bTmMt(Diag|Rank|Seis|Pdf)\b", api) and "acov_valid" not in api and "sized_by_columns" not in api
 
 
 def test_null_handle_is_refused_without_a_device(accel_mod):

@@ -107,6 +107,22 @@ def test_null_handle_is_refused_without_a_device(accel_mod):
     assert ms.value == -1.0 and n.value == -1
 
 
+def test_handle_classes_share_their_plumbing(accel_mod):
+    """The six classes that own a handle take close and the context manager from one base, and the destroy function each
+    of them names is one the loaded library has."""
+    lib, capi = accel_mod.load_library(), accel_mod.capi
+    classes = (capi.Accel, capi.Group, capi.Summary, capi.ScanNull, capi.Compare, capi.ModeTable)
+    bases = {cls.__mro__[1] for cls in classes}
+    assert len(bases) == 1 and bases != {object}
+    base = bases.pop()
+    for cls in classes:
+        for meth in ("_check", "close", "__del__", "__enter__", "__exit__", "_kernel_time"):
+            assert getattr(cls, meth) is getattr(base, meth) and meth not in vars(cls), (cls.__name__, meth)
+        assert isinstance(cls._HANDLE, str) and cls._HANDLE.startswith("_"), cls.__name__
+        assert cls._DESTROY.startswith("tamcmc_") and cls._DESTROY.endswith("_destroy") and hasattr(lib, cls._DESTROY), cls.__name__
+    assert len({cls._DESTROY for cls in classes}) == 6
+
+
 def test_tool_knows_the_option():
     exe = tool()
     r = subprocess.run([exe], capture_output=True, text=True, timeout=60)
